@@ -27,6 +27,46 @@ FS_CFG = dict(n_units=256, n_heads=4, enc_n_layers=4, dec_n_layers=2, dropout=0.
               max_seqlen=500, dec_dim_feedforward=2048, mask_delay=0)     # conf/spk_onl_tfm_enc_dec_nonautoreg.yaml
 PEAK_MFMA_TFLOPS = 2500.0     # dense bf16/f16 MFMA peak (MI355X_MICROARCH.md)
 PEAK_HBM_GBS = 8000.0
+DUMP_BUDGET_BYTES = 60_000_000    # --dump-outputs: array payload of one directory (under 64 MB with the .npy headers)
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES, seed=DUMP_SEED):
+    """--dump-outputs: write {name: tensor} as out_dir/<name>.npy, float64 kept, everything else as float32.  Arrays are
+    viewed as rows (all leading dims flattened, the last dim whole); the budget is handed out smallest array first, and an
+    array that does not fit keeps a fixed sample of its rows (torch.randperm on a generator seeded with `seed`,
+    rows in ascending order), so two builds given the same arguments write the same elements.  Returns the bench-line
+    record {name: {shape, saved_shape, rows_kept, rows}}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    items = []
+    for name, t in arrays.items():
+        t = torch.as_tensor(t).detach()
+        t = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32)
+        rows = t.reshape(-1, t.shape[-1]) if t.dim() > 1 else t.reshape(-1, 1)
+        items.append((rows.numel() * rows.element_size(), name, t, rows))
+    rec, left = {}, budget
+    for i, (nbytes, name, t, rows) in enumerate(sorted(items, key=lambda it: (it[0], it[1]))):
+        row_bytes = max(1, rows.shape[1] * rows.element_size())
+        later = len(items) - i - 1
+        if nbytes <= left - later * budget // (4 * len(items)):     # whole, still leaving every later array a floor
+            keep = rows.shape[0]
+        else:                                                      # an equal share of what is left
+            keep = min(rows.shape[0], max(1, int(left / (later + 1)) // row_bytes))
+        if keep < rows.shape[0]:
+            idx = torch.randperm(rows.shape[0], generator=torch.Generator().manual_seed(seed))[:keep].sort().values
+            arr = rows[idx.to(rows.device)].cpu().numpy()
+        else:
+            arr = t.cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+        left -= arr.nbytes
+        rec[name] = dict(shape=list(t.shape), saved_shape=list(arr.shape), rows_kept=keep, rows=rows.shape[0])
+    return rec
+
+
+def stack_items(tensors):
+    """Per-utterance outputs of model.test -> one array: stacked when the utterances have one length, else concatenated."""
+    return torch.stack(tensors) if len({tuple(t.shape) for t in tensors}) == 1 else torch.cat(tensors)
 
 
 def flops_per_launch(name, shape, T):
@@ -761,7 +801,8 @@ def train_setup(dev, B, T, n_spk, rank=0, flavour="fs"):
     return eng, feats, labels
 
 
-def time_train(dev, B, T, n_spk, steps, warmup, rank=0, fence=None, flavour="fs"):
+def time_train(dev, B, T, n_spk, steps, warmup, rank=0, fence=None, flavour="fs", outputs=None):
+    """`outputs` (a dict): receives what the last timed step returned and the parameters it left, before any further step."""
     eng, feats, labels = train_setup(dev, B, T, n_spk, rank, flavour)
     ilens = [T] * B
     for _ in range(warmup):
@@ -775,6 +816,9 @@ def time_train(dev, B, T, n_spk, steps, warmup, rank=0, fence=None, flavour="fs"
     (fence or torch.cuda.synchronize)()
     dt = time.perf_counter() - t0
     gc.enable()
+    if outputs is not None:
+        outputs.update({k: v.detach().clone() if torch.is_tensor(v) else torch.tensor(float(v), dtype=torch.float64)
+                        for k, v in out.items()}, params=eng.flat.params.detach().clone())
     return eng, dt, float(out["loss"]), feats, labels
 
 
@@ -979,7 +1023,12 @@ def main():
     ap.add_argument("--speakers", type=int, default=4, help="train mode: speakers per mixture (labels get +2 columns)")
     ap.add_argument("--flavour", choices=("fs", "ls"), default="fs",
                     help="train mode: fs = FS-EEND (T=500 chunks), ls = LS-EEND (T=1000 chunks unless --frames is given)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (rank 0; float32 / float64, "
+                         "at most 64 MB: larger outputs as a fixed seeded sample of their rows)")
     args = ap.parse_args()
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs --steps >= 1")
     if args.mode == "train" and args.flavour == "ls" and "--frames" not in " ".join(sys.argv):
         args.frames = 1000                       # data.chunk_size of the LS-EEND yaml
 
@@ -1017,7 +1066,9 @@ def main():
 
     if args.mode == "train":
         from fs_eend_amd.shard import job_throughput
-        eng, dt, loss, feats, labels = time_train(dev, B, T, args.speakers, args.steps, args.warmup, rank, fence, args.flavour)
+        last = {} if args.dump_outputs else None
+        eng, dt, loss, feats, labels = time_train(dev, B, T, args.speakers, args.steps, args.warmup, rank, fence, args.flavour, last)
+        dumped = dump_outputs(args.dump_outputs, last) if args.dump_outputs and rank == 0 else None
         ls = args.flavour == "ls" 
         value = job_throughput(B * T * args.steps, dt, dev)
         dt = world * B * T * args.steps / value
@@ -1037,6 +1088,8 @@ def main():
                           "parallelism": f"dp{world}: one all-reduce of the flat {eng.flat.numel * 4 / 1e6:.1f} MB f32 gradient buffer per step",
                           "launch": "eager ctypes launches"},
                "final_loss": loss, "peak_hbm_bytes": int(torch.cuda.max_memory_allocated(dev))}
+        if dumped is not None:
+            out["dump_outputs"] = dict(dir=args.dump_outputs, seed=DUMP_SEED, arrays=dumped)
         if rank == 0 and world == 1 and not args.no_breakdown:
             # dominant kernel: HIP events around every C-ABI call of 2 extra steps (same stream, same inputs).  N = 1 only: a
             # training step contains the gradient all-reduce, a collective every rank would have to enter
@@ -1088,6 +1141,8 @@ def main():
     def step():
         return model.test(src, ilens, C)
 
+    static_out = None
+
     step()                                       # allocate the workspace, prepare f16 weights
     torch.cuda.synchronize()
     run = step
@@ -1116,9 +1171,16 @@ def main():
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        run()
+        last = run()
     fence()
     dt = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the caller's view of the last timed step: per-utterance logits (T, C), embeddings (T, D), attractors (T, C, D);
+        # a replayed graph rewrites the tensors its capture returned
+        logits, embs, attractors = static_out if graph_used else last
+        dumped = dump_outputs(args.dump_outputs, dict(logits=stack_items(logits), emb=stack_items(embs),
+                                                      attractors=stack_items(attractors)))
     from fs_eend_amd.shard import job_throughput
     value = job_throughput(B * T * args.steps, dt, dev)         # sum of frames / max of time over ranks (RCCL)
     dt = world * B * T * args.steps / value
@@ -1136,6 +1198,8 @@ def main():
                    "launch": "hipGraph replay" if graph_used else "eager ctypes launches"},
         "rtf": dt / args.steps / (B * T * 0.1),
     }
+    if dumped is not None:
+        out["dump_outputs"] = dict(dir=args.dump_outputs, seed=DUMP_SEED, arrays=dumped)
 
     if rank == 0 and not args.no_breakdown:
         gc.collect()

@@ -76,23 +76,17 @@ def test_yaml_ref_loader():
     assert out["log"]["log_dir"] == "./logs/m1/v4" and out["b"] == 3
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/FS-EEND/conf"), reason="needs the reference tree (build container only)")
 def test_loader_reads_the_reference_configs():
-    """Every shipped reference config parses, and the committed tables carry the reference's values."""
-    import glob
-    n = 0
-    for path in glob.glob("/root/reference/*/conf/*.yaml"):
-        cfg = CFG.load(path)
-        assert isinstance(cfg, dict) and "model" in cfg
-        n += 1
-    assert n >= 10
-    ref = CFG.load("/root/reference/FS-EEND/conf/spk_onl_tfm_enc_dec_nonautoreg.yaml")
+    """Every shipped reference config parses, and the committed tables carry the reference's values.  The reference's
+    configs were read with this loader into tests/golden/reference_configs.json (oracle/gen_golden_conf.py)."""
+    ref = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "reference_configs.json")))
+    assert len(ref["configs"]) >= 10
+    assert all("model" in c["sections"] for c in ref["configs"].values())
     mine = CFG.load(CFG.FS_EEND_SIMU)
-    assert ref["model"]["params"] == mine["model"]["params"]
+    assert ref["fs"]["model_params"] == mine["model"]["params"]
     for k in ("max_speakers", "context_recp", "chunk_size", "subsampling", "label_delay", "feat_type"):
-        assert ref["data"][k] == mine["data"][k]
+        assert ref["fs"]["data"][k] == mine["data"][k]
     for k in ("lr", "grad_clip", "warm_steps", "schedule_scale", "batch_size"):
-        assert ref["training"][k] == mine["training"][k]
-    ref = CFG.load("/root/reference/LS-EEND/conf/spk_onl_conformer_retention_enc_dec_nonautoreg.yaml")
+        assert ref["fs"]["training"][k] == mine["training"][k]
     mine = CFG.load(CFG.LS_EEND_SIMU)
-    assert ref["model"]["params"] == mine["model"]["params"]
+    assert ref["ls"]["model_params"] == mine["model"]["params"]

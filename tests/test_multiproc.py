@@ -171,7 +171,23 @@ def test_dropin_import_paths():
         assert out.returncode == 0 and "ok" in out.stdout, out.stderr
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/FS-EEND"), reason="needs the reference tree (build container only)")
+def _reference_like_root(base, flavour, script, model_mod, kept):
+    """A project root laid out like the reference's (namespace packages, no __init__.py): the entry script, the hot-path
+    model module the shims replace, the modules they do not provide, and a train/utils/loss.py with names the shim
+    keeps (standard_loss, batch_pit_loss) next to names it overrides (calc_diarization_error, batch_pit_n_speaker_loss)."""
+    ref = base / flavour
+    files = {script: "", model_mod.replace(".", "/") + ".py": "", "train/utils/loss.py":
+             "def standard_loss(ys, ts, label_delay=0):\n    return None\n\n\n"
+             "def batch_pit_loss(ys, ts, label_delay=0):\n    return None\n\n\n"
+             "def calc_diarization_error(pred, label, label_delay=0):\n    return None\n\n\n"
+             "def batch_pit_n_speaker_loss(ys, ts, n_speakers_list):\n    return None\n"}
+    files.update({n.replace(".", "/") + ".py": "" for n in kept})
+    for rel, text in files.items():
+        (ref / rel).parent.mkdir(parents=True, exist_ok=True)
+        (ref / rel).write_text(text)
+    return str(ref)
+
+
 @pytest.mark.parametrize("flavour,script,model_mod,kept", [
     ("FS-EEND", "streaming_infer_dia.py", "nnet.model.onl_tfm_enc_1dcnn_enc_linear_non_autoreg_pos_enc_l2norm",
      ["train.oln_tfm_enc_dec", "train.oln_tfm_enc_dec_spk_pit", "datasets.diarization_dataset", "datasets.kaldi_data",
@@ -180,11 +196,11 @@ def test_dropin_import_paths():
      "nnet.model.onl_conformer_retention_enc_1dcnn_tfm_retention_enc_linear_non_autoreg_pos_enc_l2norm_emb_loss_mask",
      ["train.oln_tfm_enc_dec", "train.oln_tfm_enc_dec_spk_pit_on_the_fly", "datasets.diarization_dataset_on_the_fly",
       "data_loaders.utils.my_distributed_sampler", "nnet.conformer.attention"])])
-def test_dropin_binds_next_to_the_reference(flavour, script, model_mod, kept):
-    """With the reference's project root present (the launcher's situation): the hot-path modules resolve to THIS
+def test_dropin_binds_next_to_the_reference(tmp_path, flavour, script, model_mod, kept):
+    """With a reference-like project root present (the launcher's situation): the hot-path modules resolve to THIS
     repository, everything the shims do not provide still resolves to the reference's own files, and the modules the
     shims overlay (train/utils/loss.py) expose the reference's names next to the accelerated ones."""
-    ref = f"/root/reference/{flavour}"
+    ref = _reference_like_root(tmp_path, flavour, script, model_mod, kept)
     code = ("import sys, os, importlib.util; sys.dont_write_bytecode = True; sys.path.insert(0, r'%s'); "
             "from fs_eend_amd.dropin import arrange_sys_path; arrange_sys_path(r'%s'); "
             "m = importlib.util.find_spec('%s'); assert m.origin.startswith(r'%s'), m.origin; "
@@ -193,10 +209,8 @@ def test_dropin_binds_next_to_the_reference(flavour, script, model_mod, kept):
             "print('ok')") % (ROOT, os.path.join(ref, script), model_mod, ROOT, kept, ref, ROOT)
     out = _run_py(code)
     assert out.returncode == 0 and "ok" in out.stdout, out.stderr + out.stdout
-    # the overlay: reference definitions + accelerated overrides in one module (torchmetrics is stubbed here only
-    # because this container lacks it; the reference environment has it)
-    code = ("import sys, types; sys.dont_write_bytecode = True; sys.path.insert(0, r'%s'); "
-            "tm = types.ModuleType('torchmetrics'); tm.PermutationInvariantTraining = object; sys.modules['torchmetrics'] = tm; "
+    # the overlay: reference definitions + accelerated overrides in one module
+    code = ("import sys; sys.dont_write_bytecode = True; sys.path.insert(0, r'%s'); "
             "from fs_eend_amd.dropin import arrange_sys_path; arrange_sys_path(r'%s'); "
             "import train.utils.loss as L; import fs_eend_amd.postproc as P, fs_eend_amd.pit as PIT; "
             "assert L._REFERENCE_FILE.startswith(r'%s'), L._REFERENCE_FILE; "
