@@ -252,6 +252,8 @@ int eend_attn_causal_bwd_bf16(const void* Q, const void* Qt, const void* K, cons
                               float* dh_ws, void* dQKV, int ldg, int nseq, int H, int Tp, int mask_delay, int kv_len,
                               int q_len, float scale_log2, float sq, float sk, const eend_dropout* drop, void* stream) {
     if (!dO || !O_f16 || !dOt_ws || !dh_ws || H != 4 || ldo != 256 || ldout != 256) return EEND_EINVAL;
+    // the whole envelope before the row-dot launch: nothing runs for a shape the backward rejects
+    if (nseq <= 0 || Tp <= 0 || (Tp % 64) || kv_len < 1 || kv_len > Tp || q_len < 1 || q_len > Tp) return EEND_EINVAL;
     int rc = eend_launch_attn_rowdot(dO, O_f16, dh_ws, nseq, H, Tp, (hipStream_t)stream);
     if (rc != EEND_OK) return rc;
     AttnBwdParams p;

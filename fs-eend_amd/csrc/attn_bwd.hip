@@ -428,7 +428,7 @@ void heads_transpose_kernel(const unsigned short* __restrict__ in, int ld, unsig
 int eend_launch_attn_bwd(const AttnBwdParams& p, hipStream_t stream) {
     if (!p.Q || !p.K || !p.V || !p.dO || !p.dOt || !p.Lse || !p.Dh || !p.dQKV) return EEND_EINVAL;
     if (p.nseq <= 0 || p.nseq > 65535 || p.H <= 0 || p.Tp <= 0 || (p.Tp % 64) || (p.ldo & 7) || (p.ldg & 3) || p.kv_len <= 0 ||
-        p.kv_len > p.Tp || p.q_len <= 0)
+        p.kv_len > p.Tp || p.q_len <= 0 || p.q_len > p.Tp)
         return EEND_EINVAL;
 #ifndef EEND_ATTN_BWD_TWO_KERNELS                       // (study build: the round-2 two-kernel form at every size)
     if (eend_attn_bwd_fused_ok(p, false)) return eend_launch_attn_bwd_fused(p, false, stream);

@@ -527,7 +527,9 @@ int eend_launch_inproj_attn_pack(const void* W, void* out, hipStream_t stream) {
 
 // p.W = the packed weights (eend_launch_inproj_attn_pack)
 int eend_launch_inproj_attn_stream(const InprojAttnParams& p, hipStream_t stream) {
-    if (p.Tp <= 0 || p.Tp > TP || (p.Tp & 63) || (p.ldo & 7) || (p.ldx & 7) || p.H != 4 || p.nseq <= 0 || !p.X || !p.W || !p.bias || !p.O) return EEND_EINVAL;
+    if (p.Tp <= 0 || p.Tp > TP || (p.Tp & 63) || (p.ldo & 7) || (p.ldx & 7) || p.H != 4 || p.nseq <= 0 || !p.X || !p.W || !p.bias || !p.O ||
+        p.kv_len < 1 || p.kv_len > p.Tp)
+        return EEND_EINVAL;
     static EendOncePerDevice attr_once;
     static EendOncePerDevice attr_once_full;
     if (!eend_set_dynamic_lds(attr_once, (const void*)inproj_attn_stream_kernel<false, false, false>, SMEM)) return EEND_ELAUNCH;
@@ -545,7 +547,7 @@ int eend_launch_inproj_attn_stream(const InprojAttnParams& p, hipStream_t stream
 // training forward (Tp = 64 m <= 512): p.Qh / p.Kh / p.Vh bf16 head rows and p.lse [nseq][4][Tp] out, p.drop on the probabilities
 int eend_launch_inproj_attn_train(const InprojAttnParams& p, hipStream_t stream) {
     if (p.Tp <= 0 || p.Tp > TP || (p.Tp & 63) || (p.ldo & 7) || (p.ldx & 7) || p.H != 4 || p.nseq <= 0 || !p.X || !p.W || !p.bias || !p.O || !p.Qh || !p.Kh ||
-        !p.Vh || !p.lse || p.kv_len < 1 || (long)p.nseq * 4 * p.Tp >= (1L << 31))
+        !p.Vh || !p.lse || p.kv_len < 1 || p.kv_len > p.Tp || (long)p.nseq * 4 * p.Tp >= (1L << 31))
         return EEND_EINVAL;
     static EendOncePerDevice attr_once;
     static EendOncePerDevice attr_once_full;

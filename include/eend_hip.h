@@ -452,7 +452,7 @@ int eend_spk_attn_f16(const void* qkv, void* O_f16, int B, int C, int Tp, int H,
  * the X rows of the 64 tokens whose queries it runs in registers, the head's 96 KB of weights arrive by LDS-DMA, Q, K and V never
  * reach HBM.  eend_inproj_attn_pack_f16 re-orders W_in f16 [768][256] (= in_proj_weight with the q rows pre-multiplied by
  * 1/sqrt(64) * log2(e)) into eend_inproj_attn_packed_elems() f16 elements, once per parameter version.  mask: key j visible to
- * query i iff j - i <= mask_delay and j < kv_len.  Equivalent to eend_inproj_heads_bf16 followed by
+ * query i iff j - i <= mask_delay and j < kv_len (1 <= kv_len <= Tp, EEND_EINVAL otherwise).  Equivalent to eend_inproj_heads_bf16 followed by
  * eend_attn_causal_bf16(scale = ln 2), which is what the caller uses for other chunk lengths (EEND_EINVAL here).  The key bias
  * is not applied (it cancels in the softmax); b_in is the [768] in_proj_bias, q part pre-scaled. */
 int eend_inproj_attn_packed_elems(void);
@@ -643,7 +643,8 @@ int eend_attn_causal_lse_bf16(const void* Q, const void* K, const void* Vt, void
  * the forward output; dQKV bf16 [nseq*Tp][ldg] receives dQ | dK | dV at columns 0 / 256 / 512 (+ h*64).
  * dOt_ws (bf16, nseq*Tp*256) and dh_ws (f32, nseq*H*Tp) are scratch.  scale_log2 as given to the forward
  * (its `scale` * log2 e); sq / sk: factors applied to dQ / dK (for the pre-scaled-q convention of
- * eend_attn_causal_bf16: scale_log2 = 1, sq = 1/sqrt(dh), sk = ln 2).  `drop`: the forward's spec; O_f16 is the
+ * eend_attn_causal_bf16: scale_log2 = 1, sq = 1/sqrt(dh), sk = ln 2).  1 <= kv_len, q_len <= Tp (EEND_EINVAL otherwise, before any
+ * launch).  `drop`: the forward's spec; O_f16 is the
  * forward output (computed from the dropped probabilities), which keeps D_i = <dO_i, O_i> valid. */
 int eend_attn_causal_bwd_bf16(const void* Q, const void* Qt, const void* K, const void* Kt, const void* V,
                               const void* dO, int ldo, const void* O_f16, int ldout, const float* lse, void* dOt_ws,
