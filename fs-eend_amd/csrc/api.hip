@@ -286,6 +286,27 @@ int eend_encoder_input_f16(const float* const* x_ptrs, const int* lens, float pa
     return eend_launch_encin(p, (hipStream_t)stream);
 }
 
+int eend_dec_stream_elems(int F) { return F >= 64 && F % 64 == 0 && F <= 2048 ? (int)eend_dec_stream_nelems(F) : 0; }
+
+int eend_dec_stream_ok(int C, int Tp) { return eend_dec_stream_supported(C, Tp); }
+
+int eend_dec_stream_pack_f16(const void* Wo1, const void* W_in, const void* Wo2, const void* W1, const void* W2, void* stream_out, int F,
+                             void* stream) {
+    return eend_launch_dec_stream_pack(Wo1, W_in, Wo2, W1, W2, stream_out, F, (hipStream_t)stream);
+}
+
+int eend_attnout_spk_ffn_stream_f16(const void* A, int lda, const void* wstream, const float* bo1, const void* res_f16, const float* g11,
+                                    const float* be11, float eps11, const float* b_in, const float* bo2, const float* g21, const float* be21,
+                                    float eps21, const float* b1, const float* b2, const float* g22, const float* be22, float eps22,
+                                    void* out_f16, int B, int C, int Tp, int F, float scale, void* stream) {
+    DecStreamParams p;
+    memset(&p, 0, sizeof(p));
+    p.A = A; p.lda = lda; p.wstream = wstream; p.bo1 = bo1; p.g11 = g11; p.be11 = be11; p.eps11 = eps11; p.res16 = res_f16; p.bin = b_in;
+    p.bo2 = bo2; p.g21 = g21; p.be21 = be21; p.eps21 = eps21; p.b1 = b1; p.b2 = b2; p.g22 = g22; p.be22 = be22; p.eps22 = eps22;
+    p.out16 = out_f16; p.B = B; p.C = C; p.Tp = Tp; p.F = F; p.scale = scale;
+    return eend_launch_dec_stream(p, (hipStream_t)stream);
+}
+
 int eend_spk_stream_elems(void) { return (int)eend_spk_stream_nelems(); }
 
 int eend_spk_stream_ok(int C, int Tp) { return eend_spk_stream_supported(C, Tp); }

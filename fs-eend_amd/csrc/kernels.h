@@ -333,6 +333,35 @@ long eend_spk_stream_nelems();
 int eend_spk_stream_supported(int C, int Tp);
 int eend_launch_spk_stream_pack(const void* Wo, const void* Win, void* out, hipStream_t stream);
 int eend_launch_spk_stream(const SpkStreamParams& p, hipStream_t stream);
+// dec_stream.hip: the whole FS decoder layer behind the time-axis attention (attnout_spk_stream + attnout_ffn_stream) in one launch
+struct DecStreamParams {
+    const void* A;        // time-axis attention output f16 [B*C*Tp][lda], row = (b*C + c)*Tp + t
+    int lda;
+    const void* wstream;  // eend_dec_stream_pack_f16 output
+    const float* bo1;     // out-projection 1 bias, LayerNorm11 affine
+    const float* g11;
+    const float* be11;
+    float eps11;
+    const void* res16;    // residual f16 [B*C*Tp][256]
+    const float* bin;     // [768] speaker-axis in-projection bias (q, k, v)
+    const float* bo2;     // out-projection 2 bias, LayerNorm21 affine
+    const float* g21;
+    const float* be21;
+    float eps21;
+    const float* b1;      // [F]
+    const float* b2;      // [256]
+    const float* g22;     // LayerNorm22 affine
+    const float* be22;
+    float eps22;
+    void* out16;          // layer output f16 [B*C*Tp][256] (may be res16)
+    int B, C, Tp, F;
+    float scale;          // 1/sqrt(dh)
+};
+long eend_dec_stream_nelems(int F);
+int eend_dec_stream_supported(int C, int Tp);
+int eend_launch_dec_stream_pack(const void* Wo1, const void* Win, const void* Wo2, const void* W1, const void* W2, void* out, int F,
+                                hipStream_t stream);
+int eend_launch_dec_stream(const DecStreamParams& p, hipStream_t stream);
 // convert_rows.hip: the decoder input fan-out as a store-shaped kernel (weights stationary)
 int eend_launch_convert_fanout_rows(const void* E, const void* W1, const float* pc, float* out32, void* out16, int B, int Tp, int C,
                                     hipStream_t stream);

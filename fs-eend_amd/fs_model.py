@@ -29,6 +29,7 @@ _H_SUPPORTED = 4
 # their questions are answered in profiles/OPTIMISATION_LOG.md):
 #   encoder input      encin.hip (320 < in_size <= 384)              | gather + BatchNorm + linear_res_ln
 #   time-axis MHA      attn_stream.hip (Tp <= 512, packed weights)   | in-projection + attn.hip (longer chunks)
+#   decoder layer      dec_stream.hip (C = 3 / 6, F % 64 == 0, F <= 2048: head and tail in one launch) | the two launches below
 #   layer head         spk_stream.hip (C <= 12: the limit of every speaker-axis kernel)
 #   layer tail         ffn_stream.hip (F % 64 == 0)                  | attnout_ffn_fused_res16 (ffn.hip)
 #   look-ahead conv    conv_stream.hip (256 channels)                | implicit-GEMM epilogue (gemm.hip)
@@ -286,6 +287,8 @@ class OnlineTransformerDADiarization(nn.Module):
             if ops.stream_ok(L["w1"].shape[0]):
                 L["ws"] = ops.ffn_stream_pack(L["out2_w"], L["w1"], L["w2"])
             L["ws1"] = ops.spk_stream_pack(L["out1_w"], L["in2_w"])
+            if ops.stream_ok(L["w1"].shape[0]):
+                L["wsd"] = ops.dec_stream_pack(L["out1_w"], L["in2_w"], L["out2_w"], L["w1"], L["w2"])
             L["in1_wp"] = ops.inproj_attn_pack(L["in1_w"])
         P["dec.layers"] = dl
         self._prep, self._prep_key = P, key
@@ -397,6 +400,11 @@ class OnlineTransformerDADiarization(nn.Module):
             # speaker-axis kernels take, C <= 12).  It takes no T_valid: the slab's padded frames [T, Tp) are computed too (finite
             # don't-care rows, masked as keys and dropped by the head) -- 2.4 % of the rows at T = 500 / Tp = 512; a per-tile T_valid test
             # would cost the kernel its tile-uniform control flow
+            if "wsd" in L and ops.dec_stream_ok(C, Tp):
+                # ... and the rest of the layer in the same launch: x1 and O never leave the chip (dec_stream.hip)
+                ops.attnout_spk_ffn_stream(o16, L["wsd"], L["out1_b"], ws.a16, L["g11"], L["be11"], L["eps11"], L["in2_b"], L["out2_b"],
+                                           L["g21"], L["be21"], L["eps21"], L["b1"], L["b2"], L["g22"], L["be22"], L["eps22"], ws.a16, B, C, Tp)
+                continue
             ops.attnout_spk_stream(o16, L["ws1"], L["out1_b"], ws.a16, L["g11"], L["be11"], L["eps11"], ws.a16, L["in2_b"], o16, B, C, Tp)
             if "ws" in L:
                 ops.attnout_ffn_stream(o16, L["ws"], L["out2_b"], None, ws.a16, L["g21"], L["be21"], L["eps21"], L["b1"], L["b2"],

@@ -59,6 +59,11 @@ PROTOTYPES = {
     "eend_spk_stream_pack_f16": [_vp, _vp, _vp, _vp],
     "eend_attnout_spk_stream_f16": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _i, _i, _i, _f, _vp],
     "eend_attnout_spk_stream_res32_f16": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _i, _i, _i, _f, _vp],
+    "eend_dec_stream_elems": [_i],
+    "eend_dec_stream_ok": [_i, _i],
+    "eend_dec_stream_pack_f16": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp],
+    "eend_attnout_spk_ffn_stream_f16": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i,
+                                        _i, _f, _vp],
     "eend_ffn_stream_max_rows": [_i],
     "eend_debug_ffn_stream_set": [_i, _l],
     "eend_attnout_ffn_stream_f16": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _f, _vp, _vp, _i, _i, _vp],

@@ -424,6 +424,46 @@ def attnout_spk_stream_res32(a16, wstream, bo, res32, g1, be1, eps1, x32, b_in, 
                                                    _p(b_in), _p(out16), B, C, Tp, 0.125, _stream()), "eend_attnout_spk_stream_res32_f16")
 
 
+def dec_stream_pack(wo1, win, wo2, w1, w2):
+    """Pack Wo1, in_proj_weight [768][256], Wo2 [256][256], W1 [F][256], W2 [256][F] (f16) into the weight stream of attnout_spk_ffn_stream."""
+    L = _lib.load()
+    for n, t in (("wo1", wo1), ("win", win), ("wo2", wo2), ("w1", w1), ("w2", w2)):
+        _chk(t, F16, n)
+    Fh = w1.shape[0]
+    n = L.eend_dec_stream_elems(Fh)
+    if (wo1.shape != (256, 256) or win.shape != (768, 256) or wo2.shape != (256, 256) or w1.shape[1] != 256 or w2.shape != (256, Fh)
+            or n <= 0 or not all(t.is_contiguous() for t in (wo1, win, wo2, w1, w2))):
+        raise _lib.EendHipError("dec_stream_pack: expected contiguous Wo1 / Wo2 [256][256], W_in [768][256], W1 [F][256], W2 [256][F], "
+                                "F a multiple of 64 up to 2048")
+    out = torch.empty(n, dtype=F16, device=wo1.device)
+    _lib.check(L.eend_dec_stream_pack_f16(_p(wo1), _p(win), _p(wo2), _p(w1), _p(w2), _p(out), Fh, _stream()), "eend_dec_stream_pack_f16")
+    return out
+
+
+def dec_stream_ok(C, Tp):
+    return bool(_lib.load().eend_dec_stream_ok(int(C), int(Tp)))
+
+
+def attnout_spk_ffn_stream(a16, wstream, bo1, res16, g11, be11, eps11, b_in, bo2, g21, be21, eps21, b1, b2, g22, be22, eps22, out16,
+                           B, C, Tp):
+    """attnout_spk_stream followed by attnout_ffn_stream (res16 form) in one launch, x1 and O kept on chip:
+    out16 = the decoder layer's output rows.  out16 may be res16."""
+    L = _lib.load()
+    _chk(a16, F16, "a16"); _chk(wstream, F16, "wstream"); _chk(res16, F16, "res16"); _chk(out16, F16, "out16")
+    for n, t in (("bo1", bo1), ("g11", g11), ("be11", be11), ("b_in", b_in), ("bo2", bo2), ("g21", g21), ("be21", be21), ("b1", b1),
+                 ("b2", b2), ("g22", g22), ("be22", be22)):
+        _chk(t, F32, n)
+    M = B * C * Tp
+    Fh = b1.numel()
+    if a16.shape != (M, 256) or res16.shape != (M, 256) or out16.shape != (M, 256) or b_in.numel() != 768:
+        raise _lib.EendHipError("attnout_spk_ffn_stream: shape mismatch")
+    if wstream.numel() != L.eend_dec_stream_elems(Fh):
+        raise _lib.EendHipError("attnout_spk_ffn_stream: weight stream has the wrong size")
+    _lib.check(L.eend_attnout_spk_ffn_stream_f16(_p(a16), a16.stride(0), _p(wstream), _p(bo1), _p(res16), _p(g11), _p(be11), eps11,
+                                                 _p(b_in), _p(bo2), _p(g21), _p(be21), eps21, _p(b1), _p(b2), _p(g22), _p(be22), eps22,
+                                                 _p(out16), B, C, Tp, Fh, 0.125, _stream()), "eend_attnout_spk_ffn_stream_f16")
+
+
 def spk_attn(qkv16, o16, B, C, Tp, H):
     L = _lib.load()
     _chk(qkv16, F16, "qkv16"); _chk(o16, F16, "o16")

@@ -251,6 +251,23 @@ int eend_attnout_spk_stream_f16(const void* A, int lda, const void* wstream, con
 int eend_attnout_spk_stream_res32_f16(const void* A, int lda, const void* wstream, const float* bo, const float* res_f32,
                                       const float* g1, const float* be1, float eps1, float* x_f32, const float* b_in, void* O_f16,
                                       int B, int C, int Tp, float scale, void* stream);
+/* The whole FS decoder layer behind the time-axis attention in one launch on one packed weight stream (dec_stream.hip):
+ *   x1  = LayerNorm11(A Wo1^T + bo1 + res),   O = MHA over the C slots of (x1 W_in^T + b_in),
+ *   x   = LayerNorm21(O Wo2^T + bo2 + x1),    out = LayerNorm22(ReLU(x W1^T + b1) W2^T + b2 + x)
+ * i.e. eend_attnout_spk_stream_f16 followed by eend_attnout_ffn_stream_f16 with x1 and O kept on chip (x1 rounded to f16 as there; the
+ * Wo2 sum runs in another order, so rows may differ from the pair's in the last f16 bit).  f16 rows (b*C + c)*Tp + t of 256 features,
+ * out_f16 may be res_f16.  Supported where eend_dec_stream_ok(C, Tp) != 0 and F is a multiple of 64
+ * in [64, 2048]; other shapes return EEND_EINVAL before any launch.  eend_dec_stream_ok admits C = 3 and C = 6 only (the tilings whose
+ * instantiations keep inside the register file; other slot counts use the two launches).  eend_dec_stream_pack_f16 re-orders Wo1, W_in [768][256], Wo2,
+ * W1 [F][256] and W2 [256][F] (f16) into the stream (eend_dec_stream_elems(F) f16 elements; 0 for an unsupported F). */
+int eend_dec_stream_elems(int F);
+int eend_dec_stream_ok(int C, int Tp);
+int eend_dec_stream_pack_f16(const void* Wo1, const void* W_in, const void* Wo2, const void* W1, const void* W2, void* stream_out, int F,
+                             void* stream);
+int eend_attnout_spk_ffn_stream_f16(const void* A, int lda, const void* wstream, const float* bo1, const void* res_f16, const float* g11,
+                                    const float* be11, float eps11, const float* b_in, const float* bo2, const float* g21, const float* be21,
+                                    float eps21, const float* b1, const float* b2, const float* g22, const float* be22, float eps22,
+                                    void* out_f16, int B, int C, int Tp, int F, float scale, void* stream);
 
 
 /* Embedding-consistency loss (FS model :46-57; LS model :92-113): mean over (b,i,j) of
