@@ -14,16 +14,10 @@
 // lengths take eend_inproj_heads_bf16 + eend_attn_causal_bf16.
 #include "common.h"
 #include "kernels.h"
+#include "wstream.h"
 #include <stdlib.h>
-#include <type_traits>
-#include <utility>
 
 namespace {
-
-template <class F, int... I>
-__device__ __forceinline__ void sfor_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, class F>
-__device__ __forceinline__ void sfor(F&& f) { sfor_impl(f, std::make_integer_sequence<int, N>{}); }
 
 constexpr int KB = 64;
 constexpr int TILE = KB * 128;            // one [64][64] bf16 tile
@@ -36,9 +30,7 @@ constexpr int NITEM = 6;                  // Q (features 0-31, 32-63), K, K, V, 
 constexpr int L_K = 0, L_V = NT * TILE, L_X = 2 * NT * TILE;
 constexpr int SMEM = L_X + NW * OSTG;     // 160 KB
 
-typedef __attribute__((address_space(3))) char lds_char;
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 DEV int swap23(int r) { return (r & 0x13) | ((r & 4) << 1) | ((r & 8) >> 1); }
 
@@ -236,7 +228,7 @@ void inproj_attn_stream_kernel(const InprojAttnParams p) {
                 }
             }
             // this wave's pieces of item n have landed (its X rows are older): the younger requests are 2 (5 - n) pieces
-            __builtin_amdgcn_s_waitcnt(0x0F70 | (2 * (NITEM - 1 - n)));
+            wait_vm<2 * (NITEM - 1 - n)>();
             __builtin_amdgcn_s_barrier();
             AS_STAMP(1 + n);
             relaunder();

@@ -1,6 +1,6 @@
 // Look-ahead Conv1d(256 -> 256, ktaps, padding) + bias + L2 normalisation on a packed weight stream (round 4): the operator of
 // eend_conv1d_l2norm_f16 (FS model :38-41 / LS model :80-87; frames >= ilens[seq] read as zero) with the decomposition of
-// ffn_stream.hip instead of the generic implicit GEMM (119 us for 81 GFLOP = 0.27 of the f16 peak):
+// ffn_stream.hip (its weight ring shared through wstream.h) instead of the generic implicit GEMM (119 us for 81 GFLOP = 0.27 of the f16 peak):
 //   * one workgroup per CU, one wave per SIMD; a tile = 128 consecutive frames of one sequence; a wave owns 64 of them and 128 of the
 //     256 output features (128 accumulator registers): per 16-KB weight item a wave reads 8 weight and 4 input fragments for 32 MFMAs,
 //     48 KB of LDS reads per item for the workgroup (with 32 frames x 256 features per wave it was 72 KB and LDS-read-bound);
@@ -13,24 +13,14 @@
 //     half rows (256 / 512 contiguous bytes) leave through a staging tile as full 128-byte lines.
 #include "common.h"
 #include "kernels.h"
-#include <type_traits>
-#include <utility>
+#include "wstream.h"
 
 namespace {
-
-template <class F, int... I>
-__device__ __forceinline__ void sfor_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, class F>
-__device__ __forceinline__ void sfor(F&& f) { sfor_impl(f, std::make_integer_sequence<int, N>{}); }
-template <int V> using IC = std::integral_constant<int, V>;
-
-typedef __attribute__((address_space(3))) char lds_char;
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int NR = 4;                // token fragments per wave (64 rows)
 constexpr int NF = 8;                // feature fragments per wave (128 features)
 constexpr int TM = 128, WM = 64;     // rows per tile / per wave
-constexpr int SLOT = 16384;          // one stream item: 16 fragments of 1 KB = the weights of one (tap, 32-channel block)
+constexpr int SLOT = STREAM_ITEM;    // one stream item: 16 fragments of 1 KB = the weights of one (tap, 32-channel block)
 constexpr int NSLOT = 5;
 constexpr int MAXTAPS = 24;
 constexpr int XROWS = TM + MAXTAPS;  // staged input rows (halo included), 512 B each
@@ -58,7 +48,6 @@ __global__ void conv_stream_pack_kernel(const _Float16* __restrict__ Wr, _Float1
 
 __global__ __launch_bounds__(256, 1)
 void conv_stream_kernel(const ConvStreamParams p) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
     const int S = p.ktaps * 8;                            // stream items per tile
     const int TPS = (p.Tp + TM - 1) / TM;                 // tiles per sequence
     const int ntiles = p.nseq * TPS;
@@ -70,18 +59,8 @@ void conv_stream_kernel(const ConvStreamParams p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     int frow = lane & 15, g = lane >> 4;
 
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)p.wstream, 0, S * SLOT, 0x00020000);
-    int nxt = 0, slot = 0;
-    auto dma_piece = [&](int sd, auto I) __attribute__((always_inline)) {
-        constexpr int i = decltype(I)::value;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_char*)(smem + L_RING + sd * SLOT + wave * 4096 + i * 1024), 16, lane * 16 + wave * 4096,
-                                                 nxt * SLOT + i * 1024, 0, 0);
-    };
-    auto dma_advance = [&]() __attribute__((always_inline)) { nxt = nxt + 1 == S ? 0 : nxt + 1; };
-    sfor<NSLOT - 1>([&](auto IT) __attribute__((always_inline)) {
-        sfor<4>([&](auto I) __attribute__((always_inline)) { dma_piece(decltype(IT)::value, I); });
-        dma_advance();
-    });
+    WeightRing<NSLOT, L_RING> ring(p.wstream, S, wave, lane);
+    ring.prime();
     float* vb = (float*)(smem + L_VEC);
     vb[tid] = p.bias[tid];
 
@@ -106,6 +85,7 @@ void conv_stream_kernel(const ConvStreamParams p) {
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         asm volatile("" : "+v"(tid));
         lane = tid & 63; frow = lane & 15; g = lane >> 4;
+        ring.set_lane(lane);
         const int seq = __builtin_amdgcn_readfirstlane(tile / TPS), t0 = (tile - seq * TPS) * TM;
         // every wave is done with the staging region (input rows of the previous tile, then its output staging)
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -133,14 +113,14 @@ void conv_stream_kernel(const ConvStreamParams p) {
             // this wave's pieces of the NEXT item have landed (2 younger items x 4 pieces may stay in flight) -- so behind the barrier
             // every wave's have, and its first fragments can be requested under this item's last MFMAs
             if (q > 0) {
-                __builtin_amdgcn_s_waitcnt(0x0F70 | INFL);
+                wait_vm<INFL>();
                 __builtin_amdgcn_s_barrier();
             }
             // accumulators pinned to the accumulator file, the fragment rotation to the vector file, once per item: left alone the
             // compiler renames them around the loop (124 v_accvgpr_mov per item, each waiting for the MFMA that wrote its source)
-            const char* wc = smem + L_RING + slot * SLOT + nh * (NF * 1024) + lane * 16;
-            const char* wn = smem + L_RING + (slot + 1 == NSLOT ? 0 : slot + 1) * SLOT + nh * (NF * 1024) + lane * 16;
-            const int sd = slot == 0 ? NSLOT - 1 : slot - 1;
+            const char* wc = smem + L_RING + ring.slot * SLOT + nh * (NF * 1024) + lane * 16;
+            const char* wn = smem + L_RING + ring.next_slot() * SLOT + nh * (NF * 1024) + lane * 16;
+            const int sd = ring.refill_slot();
             if (cold) {
                 sfor<PD>([&](auto Q) __attribute__((always_inline)) { wf[decltype(Q)::value % NB] = *(const f16x8*)(wc + decltype(Q)::value * 1024); });
                 cold = false;
@@ -152,14 +132,14 @@ void conv_stream_kernel(const ConvStreamParams p) {
                 for (int j = 0; j < NR; ++j) acc[pi][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w, xf[j], acc[pi][j], 0, 0, 0);
                 if constexpr (pi + PD < NF) wf[(pi + PD) % NB] = *(const f16x8*)(wc + (pi + PD) * 1024);
                 else wf[(pi + PD) % NB] = *(const f16x8*)(wn + (pi + PD - NF) * 1024);
-                if constexpr (pi < 4) dma_piece(sd, IC<pi>{});
+                if constexpr (pi < 4) ring.piece<pi>(sd);
                 if constexpr (pi == 2) { if (q + 1 < S) read_x(q + 1, xn); }
                 __builtin_amdgcn_sched_barrier(0);
             });
 #pragma unroll
             for (int j = 0; j < NR; ++j) xf[j] = xn[j];
-            dma_advance();
-            slot = slot + 1 == NSLOT ? 0 : slot + 1;
+            ring.advance();
+            ring.rotate();
         }
         // every wave has read its last input fragments: the staging region becomes the output staging
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -242,10 +222,5 @@ int eend_launch_conv_stream(const ConvStreamParams& p, hipStream_t stream) {
     if (!p.X || !p.wstream || !p.bias || !p.ilens || !p.out32 || !p.out16 || p.nseq <= 0 || p.Tp <= 0 || !eend_conv_stream_supported(256, p.ktaps, p.pad) ||
         (long)p.Tp * 512 >= (1L << 31))
         return EEND_EINVAL;
-    static EendOncePerDevice attr_once;
-    if (!eend_set_dynamic_lds(attr_once, (const void*)conv_stream_kernel, SMEM)) return EEND_ELAUNCH;
-    const int ncu = eend_cu_count();
-    const int ntiles = p.nseq * ((p.Tp + TM - 1) / TM);
-    hipLaunchKernelGGL(conv_stream_kernel, dim3(ntiles < ncu ? ntiles : ncu), dim3(256), SMEM, stream, p);
-    return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
+    return stream_launch<conv_stream_kernel>(p, SMEM, p.nseq * ((p.Tp + TM - 1) / TM), eend_cu_count(), stream);
 }

@@ -21,23 +21,12 @@
 // Shipped for C = 3 and 6 only (eend_dec_stream_supported).
 #include "common.h"
 #include "kernels.h"
-#include <type_traits>
-#include <utility>
+#include "wstream.h"
 
 namespace {
 
-template <class F, int... I>
-__device__ __forceinline__ void sfor_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, class F>
-__device__ __forceinline__ void sfor(F&& f) { sfor_impl(f, std::make_integer_sequence<int, N>{}); }
-template <int V> using IC = std::integral_constant<int, V>;
-
-typedef __attribute__((address_space(3))) char lds_char;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
 constexpr int NJ = 3;                    // token fragments per wave (48 rows)
-constexpr int SLOT = 16384;              // one stream item: 16 fragments of 1 KB
+constexpr int SLOT = STREAM_ITEM;        // one stream item: 16 fragments of 1 KB
 constexpr int NSLOT = 8;
 constexpr int STAGE = NSLOT * SLOT;      // 4 x 2 KB wave-private output staging (4 rows x 512 B)
 constexpr int VECS = STAGE + 4 * 2048;   // 11 per-feature f32 vectors (see V_*)
@@ -63,42 +52,16 @@ __global__ void dec_stream_pack_kernel(const _Float16* __restrict__ Wo1, const _
     for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
         const int item = (int)(t >> 10), w = (int)(t & 1023);
         const int pfrag = w >> 6, l = w & 63, f = l & 15, g = l >> 4;
-        const int n = (f >> 2) * 64 + pfrag * 4 + (f & 3);
         _Float16 v[8];
-        if (item < 8) {
-            const int kc = item >> 1, sl = item & 1;
-            const _Float16* src = Wo1 + (size_t)n * 256 + kc * 64 + sl * 32 + g * 8;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = src[e];
-        } else if (item < NSPK) {
-            const int q = item - 8, h = q / 6, tt = (q % 6) >> 1, u = q & 1;
-            const int s_ = pfrag >> 1, hf = pfrag & 1;
-            const _Float16* src = Win + (size_t)(tt * 256 + h * 64 + (f >> 2) * 16 + (u * 2 + hf) * 4 + (f & 3)) * 256 + g * 64 + 8 * s_;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = src[e];
-        } else if (item < NHEAD) {
-            const int h = (item - NSPK) >> 1, u = (item - NSPK) & 1;
-            const _Float16* src = Wo2 + (size_t)n * 256 + h * 64 + g * 16 + u * 8;
+        if (item < NHEAD) {
+            const _Float16* src;
+            if (item < 8) src = Wo1 + pack_wo_off(item >> 1, item & 1, pfrag, f, g);
+            else if (item < NSPK) src = Win + pack_win_off(item - 8, pfrag, f, g);
+            else src = Wo2 + (size_t)((f >> 2) * 64 + pfrag * 4 + (f & 3)) * 256 + ((item - NSPK) >> 1) * 64 + g * 16 + ((item - NSPK) & 1) * 8;
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] = src[e];
         } else {
-            const int q = item - NHEAD;                  // 0: W1h(0); 2k-1: W1h(k); 2k: W2h(k-1); 2U-1: W2h(U-1)
-            bool is_w1;
-            int k;
-            if (q == 0) { is_w1 = true; k = 0; }
-            else if (q == 2 * U - 1) { is_w1 = false; k = U - 1; }
-            else if (q & 1) { is_w1 = true; k = (q + 1) >> 1; }
-            else { is_w1 = false; k = (q >> 1) - 1; }
-            if (is_w1) {
-                const int s_ = pfrag >> 1, hf = pfrag & 1;
-                const _Float16* src = W1 + (size_t)(k * 32 + hf * 16 + f) * 256 + g * 64 + 8 * s_;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = src[e];
-            } else {
-                const _Float16* src = W2 + (size_t)n * F + k * 32 + g * 4;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = src[(e >> 2) * 16 + (e & 3)];
-            }
+            pack_ffn_frag(W1, W2, F, item - NHEAD, pfrag, f, g, true, v);
         }
         _Float16* dst = out + t * 8;
 #pragma unroll
@@ -121,7 +84,6 @@ void dec_stream_kernel(const DecStreamParams p) {
     constexpr int R = 16 / G, C = 3 * R;
     constexpr bool FULL = CC == C;
     static_assert(CC >= 1 && CC <= C, "slot count beyond the positions of this tiling");
-    extern __shared__ __attribute__((aligned(16))) char smem[];
     const int TPB = p.Tp / (4 * G);                       // tiles per utterance
     const int ntiles = p.B * TPB;
     const int M = p.B * CC * p.Tp;
@@ -135,26 +97,12 @@ void dec_stream_kernel(const DecStreamParams p) {
     int frow = lane & 15, g = lane >> 4;
     int fo = g * 64;
 
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)p.wstream, 0, S * SLOT, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, (M - 1) * p.lda * 2 + 512, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsR = __builtin_amdgcn_make_buffer_rsrc((void*)p.res16, 0, M * 512, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsO = __builtin_amdgcn_make_buffer_rsrc(p.out16, 0, M * 512, 0x00020000);
     auto bload = [&](const __amdgpu_buffer_rsrc_t& r, int off) __attribute__((always_inline)) { return __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0); };
-    int dvo = lane * 16 + wave * 4096;
-    int nxt = 0;
-    int slot = 0;
-
-    auto dma_piece = [&](int sd, auto I) __attribute__((always_inline)) {
-        constexpr int i = decltype(I)::value;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_char*)(smem + sd * SLOT + wave * 4096 + i * 1024), 16, dvo,
-                                                 nxt * SLOT + i * 1024, 0, 0);
-    };
-    auto dma_advance = [&]() __attribute__((always_inline)) { nxt = nxt + 1 == S ? 0 : nxt + 1; };
-
-    sfor<NSLOT - 1>([&](auto IT) __attribute__((always_inline)) {
-        sfor<4>([&](auto I) __attribute__((always_inline)) { dma_piece(decltype(IT)::value, I); });
-        dma_advance();
-    });
+    WeightRing<NSLOT> ring(p.wstream, S, wave, lane);
+    ring.prime();
 
     float* vecs = (float*)(smem + VECS);
     float* b1l = (float*)(smem + B1L);
@@ -205,7 +153,7 @@ void dec_stream_kernel(const DecStreamParams p) {
         for (int e = 0; e < 8; ++e) r8[j][e] = __builtin_bit_cast(f16x8, bload(rsR, off + e * 16));
     };
 
-    __builtin_amdgcn_s_waitcnt(0x0070 | ((4 * (NSLOT - 2)) & 15) | (((4 * (NSLOT - 2)) >> 4) << 14));   // item 0 has landed; lgkmcnt(0)
+    wait_vm_lgkm0<4 * (NSLOT - 2)>();                       // item 0 has landed; lgkmcnt(0)
     __builtin_amdgcn_s_barrier();
     sfor<NJ>([&](auto J) __attribute__((always_inline)) { load_in_frags(blockIdx.x, J); });
 
@@ -227,12 +175,11 @@ void dec_stream_kernel(const DecStreamParams p) {
                     f16x8 (&hbo)[NJ]) __attribute__((always_inline)) {
         constexpr int kind = decltype(KIND)::value, src = decltype(SRCc)::value, vw = INFL + decltype(VWXc)::value;
         constexpr bool conv = decltype(CONVc)::value, cold = decltype(COLDc)::value, pfn = decltype(PFNc)::value;
-        static_assert(vw <= 63, "vmcnt is a 6-bit field");
-        __builtin_amdgcn_s_waitcnt(0x0F70 | (vw & 15) | ((vw >> 4) << 14));
+        wait_vm<vw>();
         __builtin_amdgcn_s_barrier();
-        const char* wc = wl + slot * SLOT;
-        const char* wn = wl + ((slot + 1) & (NSLOT - 1)) * SLOT;
-        const int sd = (slot + NSLOT - 1) & (NSLOT - 1);
+        const char* wc = wl + ring.slot * SLOT;
+        const char* wn = wl + ring.next_slot() * SLOT;
+        const int sd = ring.refill_slot();
         if constexpr (cold) {
             sfor<PD>([&](auto Q) __attribute__((always_inline)) {
                 wf[decltype(Q)::value % NB] = *(const f16x8*)(wc + decltype(Q)::value * 1024);
@@ -273,13 +220,13 @@ void dec_stream_kernel(const DecStreamParams p) {
                 }
                 if constexpr (pi + PD < 16) wf[(pi + PD) % NB] = *(const f16x8*)(wc + (pi + PD) * 1024);
                 else if constexpr (pfn) wf[(pi + PD) % NB] = *(const f16x8*)(wn + (pi + PD - 16) * 1024);
-                if constexpr (pi < 4) dma_piece(sd, IC<pi>{});
+                if constexpr (pi < 4) ring.piece<pi>(sd);
                 if constexpr (kind == 4 && conv && pi >= 2 && pi < 2 + 4 * NJ && !(pi & 1)) conv_part(IC<(pi - 2) / 2>{}, hbo);
             });
             __builtin_amdgcn_sched_barrier(0);
         });
-        dma_advance();
-        slot = (slot + 1) & (NSLOT - 1);
+        ring.advance();
+        ring.rotate();
     };
     auto pin_acc = [&]() __attribute__((always_inline)) {
 #pragma unroll
@@ -294,7 +241,7 @@ void dec_stream_kernel(const DecStreamParams p) {
         auto relaunder = [&]() __attribute__((always_inline)) {
             asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
             frow = lane & 15; g = lane >> 4; fo = g * 64;
-            dvo = lane * 16 + wave * 4096;
+            ring.set_lane(lane);
             wl = smem + lane * 16;
         };
         relaunder();
@@ -578,13 +525,7 @@ void dec_stream_kernel(const DecStreamParams p) {
 
 template <int G, int CC>
 int launch(const DecStreamParams& p, hipStream_t stream) {
-    static EendOncePerDevice attr_once;
-    auto kern = dec_stream_kernel<G, CC>;
-    if (!eend_set_dynamic_lds(attr_once, (const void*)kern, SMEM)) return EEND_ELAUNCH;
-    const int ncu = eend_cu_count();
-    const int ntiles = p.B * (p.Tp / (4 * G));
-    hipLaunchKernelGGL(kern, dim3(ntiles < ncu ? ntiles : ncu), dim3(256), SMEM, stream, p);
-    return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
+    return stream_launch<dec_stream_kernel<G, CC>>(p, SMEM, p.B * (p.Tp / (4 * G)), eend_cu_count(), stream);
 }
 
 constexpr int frames_per_wave(int C) { return C <= 3 ? 16 : C <= 6 ? 8 : 4; }
@@ -604,11 +545,8 @@ int eend_dec_stream_supported(int C, int Tp) {
 int eend_launch_dec_stream_pack(const void* Wo1, const void* Win, const void* Wo2, const void* W1, const void* W2, void* out, int F,
                                 hipStream_t stream) {
     if (!Wo1 || !Win || !Wo2 || !W1 || !W2 || !out || F < 64 || F > MAXF || (F % 64) != 0) return EEND_EINVAL;
-    const long total = eend_dec_stream_nelems(F) / 8;
-    const int blocks = (int)((total + 255) / 256);
-    hipLaunchKernelGGL(dec_stream_pack_kernel, dim3(blocks < 4096 ? blocks : 4096), dim3(256), 0, stream, (const _Float16*)Wo1,
-                       (const _Float16*)Win, (const _Float16*)Wo2, (const _Float16*)W1, (const _Float16*)W2, (_Float16*)out, F);
-    return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
+    return stream_pack_launch(dec_stream_pack_kernel, eend_dec_stream_nelems(F) / 8, stream, (const _Float16*)Wo1, (const _Float16*)Win,
+                              (const _Float16*)Wo2, (const _Float16*)W1, (const _Float16*)W2, (_Float16*)out, F);
 }
 
 int eend_launch_dec_stream(const DecStreamParams& p, hipStream_t stream) {

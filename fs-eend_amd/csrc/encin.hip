@@ -16,18 +16,9 @@
 // 16-byte aligned utterance pointers; anything else returns EEND_EINVAL and the caller keeps the two-launch path.
 #include "common.h"
 #include "kernels.h"
-#include <type_traits>
-#include <utility>
+#include "wstream.h"
 
 namespace {
-
-template <class F, int... I>
-__device__ __forceinline__ void sfor_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, class F>
-__device__ __forceinline__ void sfor(F&& f) { sfor_impl(f, std::make_integer_sequence<int, N>{}); }
-
-typedef __attribute__((address_space(3))) char lds_char;
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int ROWS = 16;                  // frames per tile (one MFMA token fragment)
 constexpr int NBUF = 5;                   // staging buffers: the tile being computed + 4 in flight (the stream is latency-bound otherwise)

@@ -20,13 +20,12 @@
 // lane owns 4 consecutive output features of one token (8-byte Hs writes, lane-local LayerNorm partials).
 #include "common.h"
 #include "kernels.h"
+#include "wstream.h"
 #include <type_traits>
 #include <utility>
 #include <cstdlib>
 
 namespace {
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 template <class F, int... I>
 __device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
@@ -277,7 +276,6 @@ __device__ __forceinline__ void ffn_epilogue_acc(const FfnParams& p, f32x4 (&acc
 //     permuting the per-lane SOURCE address (8 rows x 128 B per instruction; every global row is
 //     still read as one full 128-B line).  The barrier's vmcnt(0) is the completion wait; b1 is
 //     fetched one chunk ahead so no ordinary load result is consumed while a DMA is in flight.
-typedef __attribute__((address_space(3))) char lds_char;
 typedef __attribute__((address_space(1))) const char glb_char;
 
 constexpr int V2_W1 = 0;                       // 2 x 32 KB
@@ -321,7 +319,7 @@ void ffn_fused_kernel(const FfnParams p) {
     if (tile != (int)blockIdx.x) {
         // every wave is done reading the LN scratch at the start of LDS before the weight DMA lands there
         // (raw barrier: __syncthreads() would also wait for the previous tile's global stores)
-        __builtin_amdgcn_s_waitcnt(0xc07f);                  // lgkmcnt(0), vmcnt/expcnt untouched
+        wait_lgkm0();
         __builtin_amdgcn_s_barrier();
     }
     // The thread index is laundered per tile so that everything derived from it (LDS addresses, DMA

@@ -22,8 +22,7 @@
 //     the Hs exchange on top), which was its measured bound.
 #include "common.h"
 #include "kernels.h"
-#include <type_traits>
-#include <utility>
+#include "wstream.h"
 #include <cstdlib>
 
 #include <atomic>
@@ -44,18 +43,8 @@ extern "C" int eend_debug_ffn_stream_set(int tile_fragments, long max_rows_per_l
 
 namespace {
 
-template <class F, int... I>
-__device__ __forceinline__ void sfor_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, class F>
-__device__ __forceinline__ void sfor(F&& f) { sfor_impl(f, std::make_integer_sequence<int, N>{}); }
-template <int V> using IC = std::integral_constant<int, V>;
-
-typedef __attribute__((address_space(3))) char lds_char;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
 // rows per wave = 16 NJ (NJ token fragments), rows per tile (workgroup) = 64 NJ; NJ = 3 for large M, 2 when that fills more CUs
-constexpr int SLOT = 16384;        // one stream item: 16 fragments of 1 KB
+constexpr int SLOT = STREAM_ITEM;  // one stream item: 16 fragments of 1 KB
 constexpr int NSLOT = 8;
 constexpr int STAGE = NSLOT * SLOT;    // 4 x 4 KB wave-private output staging (8 rows x 512 B)
 constexpr int VECS = STAGE + 4 * 4096; // 6 per-feature f32 vectors
@@ -85,32 +74,11 @@ __global__ void ffn_stream_pack_kernel(const _Float16* __restrict__ Wo, const _F
         const int pfrag = w >> 6, l = w & 63, f = l & 15, g = l >> 4;
         _Float16 v[8];
         if (item < nWo) {
-            const int kc = (item & 7) >> 1, sl = item & 1, i = pfrag;
-            const int n = (f >> 2) * 64 + i * 4 + (f & 3);
-            const _Float16* src = (item < 8 ? Wo : Wo_lo) + (size_t)n * 256 + kc * 64 + sl * 32 + g * 8;
+            const _Float16* src = (item < 8 ? Wo : Wo_lo) + pack_wo_off((item & 7) >> 1, item & 1, pfrag, f, g);
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] = src[e];
         } else {
-            const int q = item - nWo;                    // 0: W1h(0); 2k-1: W1h(k); 2k: W2h(k-1); 2U-1: W2h(U-1)
-            bool is_w1;
-            int k;
-            if (q == 0) { is_w1 = true; k = 0; }
-            else if (q == 2 * U - 1) { is_w1 = false; k = U - 1; }
-            else if (q & 1) { is_w1 = true; k = (q + 1) >> 1; }
-            else { is_w1 = false; k = (q >> 1) - 1; }
-            if (is_w1) {
-                const int s_ = pfrag >> 1, hf = pfrag & 1;
-                const int k0 = k_permuted ? g * 64 + 8 * s_ : s_ * 32 + g * 8;
-                const _Float16* src = W1 + (size_t)(k * 32 + hf * 16 + f) * 256 + k0;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = src[e];
-            } else {
-                const int i = pfrag;
-                const int n = (f >> 2) * 64 + i * 4 + (f & 3);
-                const _Float16* src = W2 + (size_t)n * F + k * 32 + g * 4;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = src[(e >> 2) * 16 + (e & 3)];
-            }
+            pack_ffn_frag(W1, W2, F, item - nWo, pfrag, f, g, k_permuted, v);
         }
         _Float16* dst = out + t * 8;
 #pragma unroll
@@ -141,7 +109,6 @@ void ffn_stream_kernel(const FfnStreamParams p) {
     // the INFL pieces in between plus the epilogue's own f16 row stores (8 per token fragment) and, where they are issued in or
     // behind the epilogue, the next tile's input-row loads (8 per fragment)
     constexpr int LOOSE = INFL + 8 * NJ;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
     const int U = p.F >> 5;                               // half-chunks of 32 hidden units
     const int S = (PRE ? (LO ? 16 : 8) : 0) + 2 * U;      // stream items per tile
     const int ntiles = (p.M + TM - 1) / TM;
@@ -155,7 +122,6 @@ void ffn_stream_kernel(const FfnStreamParams p) {
     int frow = lane & 15, g = lane >> 4;
     int fo = g * 64;                                      // this lane's features: fo + i*4 + r
 
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)p.wstream, 0, S * SLOT, 0x00020000);
     // Rows move through raw buffer resources: 32-bit offsets instead of 64-bit pointers (fewer address registers), and the
     // hardware drops / zero-fills accesses beyond the last row -- no clamps, no per-row branches in the epilogue.
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, (p.M - 1) * p.lda * 2 + 512, 0x00020000);
@@ -165,26 +131,11 @@ void ffn_stream_kernel(const FfnStreamParams p) {
     const __amdgpu_buffer_rsrc_t rsO32 = __builtin_amdgcn_make_buffer_rsrc((void*)p.out32, 0, p.out32 ? p.M * 1024 : 0, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsO16L = __builtin_amdgcn_make_buffer_rsrc(p.out16lo, 0, LO && p.out16lo ? p.M * 512 : 0, 0x00020000);
     auto bload = [&](const __amdgpu_buffer_rsrc_t& r, int off) __attribute__((always_inline)) { return __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0); };
-    int dvo = lane * 16 + wave * 4096;                    // this wave moves pieces wave*4 .. wave*4+3 of every item
-    int nxt = 0;                                          // next stream item to request (0 .. S-1)
-    int slot = 0;                                         // ring slot of the item being consumed
 #ifdef EEND_FS_TRACE
     int tix = -1;
 #endif
-
-    // piece i of stream item nxt -> ring slot sd
-    auto dma_piece = [&](int sd, auto I) __attribute__((always_inline)) {
-        constexpr int i = decltype(I)::value;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_char*)(smem + sd * SLOT + wave * 4096 + i * 1024), 16, dvo,
-                                                 nxt * SLOT + i * 1024, 0, 0);
-    };
-    auto dma_advance = [&]() __attribute__((always_inline)) { nxt = nxt + 1 == S ? 0 : nxt + 1; };
-
-    // prime the ring: items 0 .. NSLOT-2
-    sfor<NSLOT - 1>([&](auto IT) __attribute__((always_inline)) {
-        sfor<4>([&](auto I) __attribute__((always_inline)) { dma_piece(decltype(IT)::value, I); });
-        dma_advance();
-    });
+    WeightRing<NSLOT> ring(p.wstream, S, wave, lane);
+    ring.prime();
 
     // per-feature vectors and b1 live in LDS: the only VMEM traffic of the FFN loop is the weight stream
     float* vecs = (float*)(smem + VECS);                  // [6][256]: bo, g1, be1, b2, gamma, beta
@@ -217,7 +168,7 @@ void ffn_stream_kernel(const FfnStreamParams p) {
     };
 
     // first fragments of slot 0 (legal once every wave's pieces of item 0 have landed); vectors visible
-    __builtin_amdgcn_s_waitcnt(0x0070 | ((4 * (NSLOT - 2)) & 15) | (((4 * (NSLOT - 2)) >> 4) << 14));   // item 0 of this wave has landed; lgkmcnt(0)
+    wait_vm_lgkm0<4 * (NSLOT - 2)>();                       // item 0 of this wave has landed; lgkmcnt(0)
     __builtin_amdgcn_s_barrier();
     // RES16: the residual rows of token fragment 0 travel with the tile's input rows, those of fragments 1 and 2 are requested
     // once the first six k-steps' input fragments are dead (before the 7th out-projection item)
@@ -254,12 +205,12 @@ void ffn_stream_kernel(const FfnStreamParams p) {
         constexpr bool conv = decltype(CONVc)::value;
         constexpr bool cold = decltype(COLDc)::value;    // the previous item did not request this item's first fragments
         constexpr bool pfn = decltype(PFNc)::value;      // request the next item's first fragments (not in front of a VALU phase)
-        if (loose) __builtin_amdgcn_s_waitcnt(0x0F70 | (LOOSE & 15) | ((LOOSE >> 4) << 14));
-        else __builtin_amdgcn_s_waitcnt(0x0F70 | (vw & 15) | ((vw >> 4) << 14));
+        if (loose) wait_vm<LOOSE>();
+        else wait_vm<vw>();
         __builtin_amdgcn_s_barrier();
-        const char* wc = wl + slot * SLOT;
-        const char* wn = wl + ((slot + 1) & (NSLOT - 1)) * SLOT;
-        const int sd = (slot + NSLOT - 1) & (NSLOT - 1);
+        const char* wc = wl + ring.slot * SLOT;
+        const char* wn = wl + ring.next_slot() * SLOT;
+        const int sd = ring.refill_slot();
         if constexpr (cold) {
             sfor<PD>([&](auto Q) __attribute__((always_inline)) {
                 wf[decltype(Q)::value % NB] = *(const f16x8*)(wc + decltype(Q)::value * 1024);
@@ -297,14 +248,14 @@ void ffn_stream_kernel(const FfnStreamParams p) {
                 if constexpr (pi + PD < 16) wf[(pi + PD) % NB] = *(const f16x8*)(wc + (pi + PD) * 1024);
                 else if constexpr (pfn) wf[(pi + PD) % NB] = *(const f16x8*)(wn + (pi + PD - 16) * 1024);
                 // the 4 DMA pieces of the item NSLOT-1 ahead, on fragments 0 .. 3
-                if constexpr (pi < 4) dma_piece(sd, IC<pi>{});
+                if constexpr (pi < 4) ring.piece<pi>(sd);
                 // activation of the half-chunk held in h (6 fragment parts) on fragments 2, 4, ..., 12
                 if constexpr (kind == 2 && conv && pi >= 2 && pi < 2 + 4 * NJ && !(pi & 1)) conv_part(IC<(pi - 2) / 2>{}, hbo);
             });
             __builtin_amdgcn_sched_barrier(0);
         });
-        dma_advance();
-        slot = (slot + 1) & (NSLOT - 1);
+        ring.advance();
+        ring.rotate();
     };
     // the accumulators sit in the accumulator half of the register file whenever matrix work is about to run on them
     auto pin_acc = [&](int where) __attribute__((always_inline)) {
@@ -326,7 +277,7 @@ void ffn_stream_kernel(const FfnStreamParams p) {
         auto relaunder = [&]() __attribute__((always_inline)) {
             asm volatile("" : "+v"(tid));
             lane = tid & 63; frow = lane & 15; g = lane >> 4; fo = g * 64;
-            dvo = lane * 16 + wave * 4096;
+            ring.set_lane(lane);
             wl = smem + lane * 16;
         };
         relaunder();
@@ -583,26 +534,13 @@ void ffn_stream_kernel(const FfnStreamParams p) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // no LDS-DMA may outlive the workgroup
 }
 
-template <int MODE, int ACT, int EPI, bool RES16, int NJ, bool LO = false>
-int launch_nj(const FfnStreamParams& p, int ncu, hipStream_t stream) {
-    static EendOncePerDevice attr_once;
-    auto kern = ffn_stream_kernel<MODE, ACT, EPI, RES16, NJ, LO>;
-    if (!eend_set_dynamic_lds(attr_once, (const void*)kern, SMEM)) return EEND_ELAUNCH;
-    const int ntiles = (p.M + 64 * NJ - 1) / (64 * NJ);
-    hipLaunchKernelGGL(kern, dim3(ntiles < ncu ? ntiles : ncu), dim3(256), SMEM, stream, p);
-    return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
-}
-
 template <int MODE, int ACT, int EPI, bool RES16, bool LO = false>
 int launch(const FfnStreamParams& p, hipStream_t stream) {
     const int ncu = eend_cu_count();
-    // 192-row tiles reuse every weight fragment for three MFMAs; when they leave CUs idle in the only (or last of few) rounds,
-    // 128-row tiles finish earlier: compare rounds x rows-per-tile (the time of a tile is close to linear in its rows).
-    const long t3 = (p.M + 191) / 192, t2 = (p.M + 127) / 128;
-    const long c3 = ((t3 + ncu - 1) / ncu) * (3 * 10 + 9), c2 = ((t2 + ncu - 1) / ncu) * (2 * 10 + 9);     // per-tile cost model: rows + fixed part
     const int forced = g_debug_nj.load(std::memory_order_relaxed);              // tests only (eend_debug_ffn_stream_set)
-    const int nj = forced ? forced : (c2 < c3 ? 2 : 3);
-    return nj == 2 ? launch_nj<MODE, ACT, EPI, RES16, 2, LO>(p, ncu, stream) : launch_nj<MODE, ACT, EPI, RES16, 3, LO>(p, ncu, stream);
+    const int nj = forced ? forced : stream_pick_nj(p.M, ncu);
+    return nj == 2 ? stream_launch<ffn_stream_kernel<MODE, ACT, EPI, RES16, 2, LO>>(p, SMEM, (p.M + 127) / 128, ncu, stream)
+                   : stream_launch<ffn_stream_kernel<MODE, ACT, EPI, RES16, 3, LO>>(p, SMEM, (p.M + 191) / 192, ncu, stream);
 }
 
 }  // namespace
@@ -619,11 +557,8 @@ long eend_ffn_stream_nelems(int F, int with_wo) { return (long)((with_wo == 2 ? 
 int eend_launch_ffn_stream_pack(const void* Wo, const void* Wo_lo, const void* W1, const void* W2, void* out, int F, int k_permuted,
                                 hipStream_t stream) {
     if (!W1 || !W2 || !out || F < 64 || (F % 64) != 0 || (Wo_lo && !Wo)) return EEND_EINVAL;
-    const long total = eend_ffn_stream_nelems(F, Wo ? (Wo_lo ? 2 : 1) : 0) / 8;
-    const int blocks = (int)((total + 255) / 256);
-    hipLaunchKernelGGL(ffn_stream_pack_kernel, dim3(blocks < 4096 ? blocks : 4096), dim3(256), 0, stream, (const _Float16*)Wo, (const _Float16*)Wo_lo,
-                       (const _Float16*)W1, (const _Float16*)W2, (_Float16*)out, F, k_permuted);
-    return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
+    return stream_pack_launch(ffn_stream_pack_kernel, eend_ffn_stream_nelems(F, Wo ? (Wo_lo ? 2 : 1) : 0) / 8, stream, (const _Float16*)Wo,
+                              (const _Float16*)Wo_lo, (const _Float16*)W1, (const _Float16*)W2, (_Float16*)out, F, k_permuted);
 }
 
 int eend_launch_ffn_stream(const FfnStreamParams& p, int mode, int act, int epi, hipStream_t stream) {

@@ -11,7 +11,7 @@
 //
 // Same operators as ffn.hip MODE 3 / 4 (which stay as the shape fallback) in the decomposition of ffn_stream.hip: one 256-thread workgroup
 // per CU, one wave per SIMD owning 16 NJ token rows end to end, accumulators for all 256 output features in registers, hidden units never
-// in LDS, weights flowing through an 8-slot LDS-DMA ring with one barrier per 16-KB item.  What differs from the inference kernel:
+// in LDS, weights flowing through an 8-slot LDS-DMA ring with one barrier per 16-KB item (wstream.h).  What differs from the inference kernel:
 //   * the hidden-unit order inside a 32-unit half-chunk is chosen so that a lane's 8 units are CONSECUTIVE (unit = 32 k + 8 g + e): the
 //     activation / gradient rows leave (and the saved activations arrive) as one 16-byte buffer access per lane and token fragment,
 //     straight from / to the registers that are the second GEMM's B operand.  The stream is packed accordingly
@@ -28,22 +28,11 @@
 //     account for them (two of the last three converting items' accesses are assumed younger than the awaited pieces: conservative by one).
 #include "common.h"
 #include "kernels.h"
-#include <type_traits>
-#include <utility>
+#include "wstream.h"
 
 namespace {
 
-template <class F, int... I>
-__device__ __forceinline__ void sfor_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, class F>
-__device__ __forceinline__ void sfor(F&& f) { sfor_impl(f, std::make_integer_sequence<int, N>{}); }
-template <int V> using IC = std::integral_constant<int, V>;
-
-typedef __attribute__((address_space(3))) char lds_char;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-constexpr int SLOT = 16384;            // one stream item: 16 fragments of 1 KB
+constexpr int SLOT = STREAM_ITEM;      // one stream item: 16 fragments of 1 KB
 constexpr int NSLOT = 8;
 constexpr int STAGE = NSLOT * SLOT;    // 4 x 4 KB wave-private output staging (8 rows x 512 B)
 constexpr int VECS = STAGE + 4 * 4096; // b2, gamma, beta
@@ -68,10 +57,7 @@ __global__ void ffn_train_stream_pack_kernel(const unsigned short* __restrict__ 
         const int pfrag = w >> 6, l = w & 63, f = l & 15, g = l >> 4;
         bool is_w1;
         int k;
-        if (q == 0) { is_w1 = true; k = 0; }
-        else if (q == 2 * U - 1) { is_w1 = false; k = U - 1; }
-        else if (q & 1) { is_w1 = true; k = (q + 1) >> 1; }
-        else { is_w1 = false; k = (q >> 1) - 1; }
+        ffn_item_of(q, U, is_w1, k);
         const unsigned short* src;
         if (is_w1) {
             const int s_ = pfrag >> 1, hf = pfrag & 1;
@@ -85,9 +71,6 @@ __global__ void ffn_train_stream_pack_kernel(const unsigned short* __restrict__ 
 }
 
 DEV bool keep_of(const DropSpec d, unsigned rowbase, unsigned col) {       // drop_keep(d, row, col) with rowbase = row * golden
-#ifdef FTS_NOHASH
-    return (rowbase + col) != d.seed;
-#endif
     return drop_mix((rowbase + col) ^ d.seed) >= (d.thresh24 << 8);
 }
 
@@ -106,7 +89,6 @@ void ffn_train_stream_kernel(const FfnTrainStreamParams p) {
     constexpr int LAST2 = STEADY + 8 * NJ < 63 ? STEADY + 8 * NJ : 63;
     constexpr int LAST1 = LAST2 + (FWD ? 16 : 0) < 63 ? LAST2 + (FWD ? 16 : 0) : 63;
     enum { VW_STEADY = 0, VW_LOOSE = 1, VW_LAST2 = 2, VW_LAST1 = 3 };
-    extern __shared__ __attribute__((aligned(16))) char smem[];
     const int U = p.F >> 5;
     const int S = 2 * U;
     const int ntiles = (p.M + TM - 1) / TM;
@@ -118,7 +100,6 @@ void ffn_train_stream_kernel(const FfnTrainStreamParams p) {
     int frow = lane & 15, g = lane >> 4;
     int fo = g * 64;
 
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)p.wstream, 0, S * SLOT, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)p.X, 0, (p.M - 1) * p.ldx * 2 + 512, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsR32 = __builtin_amdgcn_make_buffer_rsrc((void*)p.res, 0, p.M * 1024, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsO32 = __builtin_amdgcn_make_buffer_rsrc((void*)p.out32, 0, p.M * 1024, 0x00020000);
@@ -129,21 +110,8 @@ void ffn_train_stream_kernel(const FfnTrainStreamParams p) {
     const __amdgpu_buffer_rsrc_t rsH = __builtin_amdgcn_make_buffer_rsrc(p.hid, 0, hid_bytes, 0x00020000);                   // TR 1: written; TR 2: the mask
     const __amdgpu_buffer_rsrc_t rsDH = __builtin_amdgcn_make_buffer_rsrc(p.dH, 0, FWD ? 0u : hid_bytes, 0x00020000);
     auto bload = [&](const __amdgpu_buffer_rsrc_t& r, int off) __attribute__((always_inline)) { return __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0); };
-    int dvo = lane * 16 + wave * 4096;
-    int nxt = 0;
-    int slot = 0;
-
-    auto dma_piece = [&](int sd, auto I) __attribute__((always_inline)) {
-        constexpr int i = decltype(I)::value;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_char*)(smem + sd * SLOT + wave * 4096 + i * 1024), 16, dvo,
-                                                 nxt * SLOT + i * 1024, 0, 0);
-    };
-    auto dma_advance = [&]() __attribute__((always_inline)) { nxt = nxt + 1 == S ? 0 : nxt + 1; };
-
-    sfor<NSLOT - 1>([&](auto IT) __attribute__((always_inline)) {
-        sfor<4>([&](auto I) __attribute__((always_inline)) { dma_piece(decltype(IT)::value, I); });
-        dma_advance();
-    });
+    WeightRing<NSLOT> ring(p.wstream, S, wave, lane);
+    ring.prime();
 
     float* vecs = (float*)(smem + VECS);                  // [3][256]: b2, gamma, beta
     float* b1l = (float*)(smem + B1L);
@@ -180,7 +148,7 @@ void ffn_train_stream_kernel(const FfnTrainStreamParams p) {
         }
     };
 
-    __builtin_amdgcn_s_waitcnt(0x0070 | ((4 * (NSLOT - 2)) & 15) | (((4 * (NSLOT - 2)) >> 4) << 14));   // item 0 of this wave has landed; lgkmcnt(0)
+    wait_vm_lgkm0<4 * (NSLOT - 2)>();                       // item 0 of this wave has landed; lgkmcnt(0)
     __builtin_amdgcn_s_barrier();
     if (blockIdx.x < ntiles) sfor<NJ>([&](auto J) __attribute__((always_inline)) { load_in_frags(blockIdx.x, J); });
 
@@ -209,12 +177,8 @@ void ffn_train_stream_kernel(const FfnTrainStreamParams p) {
             }
         }
         if constexpr (hf == 1) {
-#ifndef FTS_NOSTORE
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, hbo[j]), FWD ? rsH : rsDH, (int)(hoff[j] + (unsigned)kc * 1024u), 0, 0);
-#endif
-#ifndef FTS_NOMASK
             load_mask(PAR, IC<j>{}, kc + 2);
-#endif
         }
     };
 
@@ -226,21 +190,16 @@ void ffn_train_stream_kernel(const FfnTrainStreamParams p) {
         constexpr bool conv = decltype(CONVc)::value;
         constexpr bool cold = decltype(COLDc)::value;
         constexpr bool pfn = decltype(PFNc)::value;
-        // vmcnt is a 6-bit field split over bits 3:0 and 15:14; the count is wave-uniform
-#ifdef FTS_WAIT63
-        vw = 99;
-#endif
-        switch (vw) {
-            case 99: __builtin_amdgcn_s_waitcnt(0x0F70 | (63 & 15) | ((63 >> 4) << 14)); break;      // (timing study only: not a valid wait)
-            case VW_LOOSE: __builtin_amdgcn_s_waitcnt(0x0F70 | (LOOSE & 15) | ((LOOSE >> 4) << 14)); break;
-            case VW_LAST2: __builtin_amdgcn_s_waitcnt(0x0F70 | (LAST2 & 15) | ((LAST2 >> 4) << 14)); break;
-            case VW_LAST1: __builtin_amdgcn_s_waitcnt(0x0F70 | (LAST1 & 15) | ((LAST1 >> 4) << 14)); break;
-            default: __builtin_amdgcn_s_waitcnt(0x0F70 | (STEADY & 15) | ((STEADY >> 4) << 14)); break;
+        switch (vw) {                                    // (wave-uniform; s_waitcnt takes an immediate)
+            case VW_LOOSE: wait_vm<LOOSE>(); break;
+            case VW_LAST2: wait_vm<LAST2>(); break;
+            case VW_LAST1: wait_vm<LAST1>(); break;
+            default: wait_vm<STEADY>(); break;
         }
         __builtin_amdgcn_s_barrier();
-        const char* wc = wl + slot * SLOT;
-        const char* wn = wl + ((slot + 1) & (NSLOT - 1)) * SLOT;
-        const int sd = (slot + NSLOT - 1) & (NSLOT - 1);
+        const char* wc = wl + ring.slot * SLOT;
+        const char* wn = wl + ring.next_slot() * SLOT;
+        const int sd = ring.refill_slot();
         if constexpr (cold) {
             sfor<PD>([&](auto Q) __attribute__((always_inline)) {
                 wf[decltype(Q)::value % NB] = *(const T8*)(wc + decltype(Q)::value * 1024);
@@ -284,15 +243,15 @@ void ffn_train_stream_kernel(const FfnTrainStreamParams p) {
                 }
                 if constexpr (pi + PD < 16) wf[(pi + PD) % NB] = *(const T8*)(wc + (pi + PD) * 1024);
                 else if constexpr (pfn) wf[(pi + PD) % NB] = *(const T8*)(wn + (pi + PD - 16) * 1024);
-                if constexpr (pi < 4) dma_piece(sd, IC<pi>{});
+                if constexpr (pi < 4) ring.piece<pi>(sd);
                 // conversion of the half-chunk held in h (2 NJ parts) on fragments 4, 6, ...: behind the item's DMA pieces
                 if constexpr (kind == 2 && conv && pi >= 4 && pi < 4 + 4 * NJ && !(pi & 1)) conv_part(IC<(pi - 4) / 2>{}, PARc, hbo, kc);
 
             });
             __builtin_amdgcn_sched_barrier(0);
         });
-        dma_advance();
-        slot = (slot + 1) & (NSLOT - 1);
+        ring.advance();
+        ring.rotate();
     };
     auto pin_acc = [&]() __attribute__((always_inline)) {
 #pragma unroll
@@ -305,7 +264,7 @@ void ffn_train_stream_kernel(const FfnTrainStreamParams p) {
         auto relaunder = [&]() __attribute__((always_inline)) {
             asm volatile("" : "+v"(tid));
             lane = tid & 63; frow = lane & 15; g = lane >> 4; fo = g * 64;
-            dvo = lane * 16 + wave * 4096;
+            ring.set_lane(lane);
             wl = smem + lane * 16;
         };
         relaunder();
@@ -470,22 +429,11 @@ void ffn_train_stream_kernel(const FfnTrainStreamParams p) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // no LDS-DMA may outlive the workgroup
 }
 
-template <int TR, bool DROP, int NJ>
-int launch_nj(const FfnTrainStreamParams& p, int ncu, hipStream_t stream) {
-    static EendOncePerDevice attr_once;
-    auto kern = ffn_train_stream_kernel<TR, DROP, NJ>;
-    if (!eend_set_dynamic_lds(attr_once, (const void*)kern, SMEM)) return EEND_ELAUNCH;
-    const int ntiles = (p.M + 64 * NJ - 1) / (64 * NJ);
-    hipLaunchKernelGGL(kern, dim3(ntiles < ncu ? ntiles : ncu), dim3(256), SMEM, stream, p);
-    return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
-}
-
 template <int TR, bool DROP>
 int launch(const FfnTrainStreamParams& p, hipStream_t stream) {
     const int ncu = eend_cu_count();
-    const long t3 = (p.M + 191) / 192, t2 = (p.M + 127) / 128;
-    const long c3 = ((t3 + ncu - 1) / ncu) * (3 * 10 + 9), c2 = ((t2 + ncu - 1) / ncu) * (2 * 10 + 9);     // rounds x (rows + fixed part), as ffn_stream.hip
-    return c2 < c3 ? launch_nj<TR, DROP, 2>(p, ncu, stream) : launch_nj<TR, DROP, 3>(p, ncu, stream);
+    return stream_pick_nj(p.M, ncu) == 2 ? stream_launch<ffn_train_stream_kernel<TR, DROP, 2>>(p, SMEM, (p.M + 127) / 128, ncu, stream)
+                                         : stream_launch<ffn_train_stream_kernel<TR, DROP, 3>>(p, SMEM, (p.M + 191) / 192, ncu, stream);
 }
 
 }  // namespace
@@ -494,11 +442,8 @@ long eend_ffn_train_stream_nelems(int F) { return (long)(2 * (F / 32)) * (SLOT /
 
 int eend_launch_ffn_train_stream_pack(const void* W1, const void* W2, void* out, int F, hipStream_t stream) {
     if (!W1 || !W2 || !out || F < 64 || (F % 64) != 0 || F > MAXF || (((size_t)W1 | (size_t)W2 | (size_t)out) & 15)) return EEND_EINVAL;
-    const long total = eend_ffn_train_stream_nelems(F) / 8;
-    const int blocks = (int)((total + 255) / 256);
-    hipLaunchKernelGGL(ffn_train_stream_pack_kernel, dim3(blocks < 4096 ? blocks : 4096), dim3(256), 0, stream, (const unsigned short*)W1,
-                       (const unsigned short*)W2, (unsigned short*)out, F);
-    return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
+    return stream_pack_launch(ffn_train_stream_pack_kernel, eend_ffn_train_stream_nelems(F) / 8, stream, (const unsigned short*)W1,
+                              (const unsigned short*)W2, (unsigned short*)out, F);
 }
 
 // rows one launch can take: 32-bit buffer offsets into hid / dH ([M][F] 16-bit) and into the f32 rows, with the input-row prefetch running

@@ -13,21 +13,11 @@
 // passes per 16 rows with their loads exposed, and the accumulators spilling.  Not kept; the caller runs the two launches.)
 #include "common.h"
 #include "kernels.h"
-#include <type_traits>
-#include <utility>
+#include "wstream.h"
 
 namespace {
 
-template <class F, int... I>
-__device__ __forceinline__ void sfor_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, class F>
-__device__ __forceinline__ void sfor(F&& f) { sfor_impl(f, std::make_integer_sequence<int, N>{}); }
-template <int V> using IC = std::integral_constant<int, V>;
-
-typedef __attribute__((address_space(3))) char lds_char;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int SLOT = 16384;            // one stream item: 16 fragments of 1 KB = 256 output features x 32 k
+constexpr int SLOT = STREAM_ITEM;      // one stream item: 16 fragments of 1 KB = 256 output features x 32 k
 constexpr int NSLOT = 8;
 constexpr int STAGE = NSLOT * SLOT;    // 4 x 4 KB wave-private output staging (8 rows x 512 B)
 constexpr int SMEM = STAGE + 4 * 4096; // 147456
@@ -52,7 +42,6 @@ __global__ __launch_bounds__(256, 1)
 void gemm_acc_stream_kernel(const GemmAccStreamParams p) {
     constexpr int TM = 64 * NJ, WM = 16 * NJ;
     constexpr int STEADY = INFL + 5 * NJ;          // + the operand-row loads of the last five items (every item issues NJ of them)
-    extern __shared__ __attribute__((aligned(16))) char smem[];
     const int S = p.K >> 5;
     const int ntiles = (p.M + TM - 1) / TM;
 
@@ -63,23 +52,11 @@ void gemm_acc_stream_kernel(const GemmAccStreamParams p) {
     int frow = lane & 15, g = lane >> 4;
     int fo = g * 64;
 
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)p.wstream, 0, S * SLOT, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, (p.M - 1) * p.lda * 2 + p.K * 2, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsG = __builtin_amdgcn_make_buffer_rsrc((void*)p.g, 0, p.M * 1024, 0x00020000);
     auto bload = [&](const __amdgpu_buffer_rsrc_t& r, int off) __attribute__((always_inline)) { return __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0); };
-    int dvo = lane * 16 + wave * 4096;
-    int nxt = 0;
-    int slot = 0;
-    auto dma_piece = [&](int sd, auto I) __attribute__((always_inline)) {
-        constexpr int i = decltype(I)::value;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_char*)(smem + sd * SLOT + wave * 4096 + i * 1024), 16, dvo,
-                                                 nxt * SLOT + i * 1024, 0, 0);
-    };
-    auto dma_advance = [&]() __attribute__((always_inline)) { nxt = nxt + 1 == S ? 0 : nxt + 1; };
-    sfor<NSLOT - 1>([&](auto IT) __attribute__((always_inline)) {
-        sfor<4>([&](auto I) __attribute__((always_inline)) { dma_piece(decltype(IT)::value, I); });
-        dma_advance();
-    });
+    WeightRing<NSLOT> ring(p.wstream, S, wave, lane);
+    ring.prime();
 
     const char* wl = smem + lane * 16;
     bf16x8 wf[NB];
@@ -87,7 +64,7 @@ void gemm_acc_stream_kernel(const GemmAccStreamParams p) {
     bf16x8 hq[PA][NJ];                                   // operand-row fragments of the next PA items
     int aoff[NJ];                                        // byte offset of this lane's 16 bytes of item 0, per token fragment
 
-    __builtin_amdgcn_s_waitcnt(0x0070 | ((4 * (NSLOT - 2)) & 15) | (((4 * (NSLOT - 2)) >> 4) << 14));   // item 0 of this wave has landed; lgkmcnt(0)
+    wait_vm_lgkm0<4 * (NSLOT - 2)>();                    // item 0 of this wave has landed; lgkmcnt(0)
     __builtin_amdgcn_s_barrier();
     sfor<PD>([&](auto Q) __attribute__((always_inline)) { wf[decltype(Q)::value % NB] = *(const bf16x8*)(wl + decltype(Q)::value * 1024); });
 
@@ -106,7 +83,7 @@ void gemm_acc_stream_kernel(const GemmAccStreamParams p) {
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         asm volatile("" : "+v"(tid));
         lane = tid & 63; frow = lane & 15; g = lane >> 4; fo = g * 64;
-        dvo = lane * 16 + wave * 4096;
+        ring.set_lane(lane);
         wl = smem + lane * 16;
         // ---- accumulators: the gradient stream's rows (rows beyond M read as zeros and are dropped at the end).  (Starting from zero and
         //      adding the rows in the epilogue, their loads under the last item, measured the same and costs 64 registers + VALU work on
@@ -128,12 +105,12 @@ void gemm_acc_stream_kernel(const GemmAccStreamParams p) {
                 const int k = k0 + u;
                 // the item's barrier: this wave's pieces of the NEXT item have landed.  Younger accesses of this wave: INFL DMA pieces and,
                 // from the sixth item of a tile on, the NJ operand-row loads of each of the last five items (counting fewer is the safe side)
-                if (k < 5) __builtin_amdgcn_s_waitcnt(0x0F70 | (INFL & 15) | ((INFL >> 4) << 14));
-                else __builtin_amdgcn_s_waitcnt(0x0F70 | (STEADY & 15) | ((STEADY >> 4) << 14));
+                if (k < 5) wait_vm<INFL>();
+                else wait_vm<STEADY>();
                 __builtin_amdgcn_s_barrier();
-                const char* wc = wl + slot * SLOT;
-                const char* wn = wl + ((slot + 1) & (NSLOT - 1)) * SLOT;
-                const int sd = (slot + NSLOT - 1) & (NSLOT - 1);
+                const char* wc = wl + ring.slot * SLOT;
+                const char* wn = wl + ring.next_slot() * SLOT;
+                const int sd = ring.refill_slot();
                 sfor<8>([&](auto P2) __attribute__((always_inline)) {
                     sfor<2>([&](auto PH) __attribute__((always_inline)) {
                         constexpr int pi = decltype(P2)::value * 2 + decltype(PH)::value;
@@ -142,12 +119,12 @@ void gemm_acc_stream_kernel(const GemmAccStreamParams p) {
                         for (int j = 0; j < NJ; ++j) acc[pi][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, hq[u][j], acc[pi][j], 0, 0, 0);
                         if constexpr (pi + PD < 16) wf[(pi + PD) % NB] = *(const bf16x8*)(wc + (pi + PD) * 1024);
                         else wf[(pi + PD) % NB] = *(const bf16x8*)(wn + (pi + PD - 16) * 1024);
-                        if constexpr (pi < 4) dma_piece(sd, IC<pi>{});
+                        if constexpr (pi < 4) ring.piece<pi>(sd);
                     });
                     __builtin_amdgcn_sched_barrier(0);
                 });
-                dma_advance();
-                slot = (slot + 1) & (NSLOT - 1);
+                ring.advance();
+                ring.rotate();
                 // the rows of item k + PA take the registers this item has just used (past the last item: a repeat of it, so that every
                 // item issues the same number of accesses)
                 load_a(U, k + PA < S ? k + PA : S - 1);
@@ -186,27 +163,13 @@ void gemm_acc_stream_kernel(const GemmAccStreamParams p) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // no LDS-DMA may outlive the workgroup
 }
 
-template <int NJ>
-int launch_nj(const GemmAccStreamParams& p, int ncu, hipStream_t stream) {
-    static EendOncePerDevice attr_once;
-    auto kern = gemm_acc_stream_kernel<NJ>;
-    if (!eend_set_dynamic_lds(attr_once, (const void*)kern, SMEM)) return EEND_ELAUNCH;
-    const int ntiles = (p.M + 64 * NJ - 1) / (64 * NJ);
-    hipLaunchKernelGGL(kern, dim3(ntiles < ncu ? ntiles : ncu), dim3(256), SMEM, stream, p);
-    return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
-}
-
 }  // namespace
 
 long eend_gemm_acc_stream_nelems(int K) { return (K < 256 || (K % 128) != 0 || K > MAXK) ? 0 : (long)(K / 32) * (SLOT / 2); }
 
 int eend_launch_gemm_acc_stream_pack(const void* Wt, int ldw, void* out, int K, hipStream_t stream) {
     if (!Wt || !out || eend_gemm_acc_stream_nelems(K) == 0 || ldw < K || (ldw & 7) || (((size_t)Wt | (size_t)out) & 15)) return EEND_EINVAL;
-    const long total = eend_gemm_acc_stream_nelems(K) / 8;
-    const int blocks = (int)((total + 255) / 256);
-    hipLaunchKernelGGL(gemm_acc_stream_pack_kernel, dim3(blocks < 4096 ? blocks : 4096), dim3(256), 0, stream, (const unsigned short*)Wt, ldw,
-                       (unsigned short*)out, K);
-    return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
+    return stream_pack_launch(gemm_acc_stream_pack_kernel, eend_gemm_acc_stream_nelems(K) / 8, stream, (const unsigned short*)Wt, ldw, (unsigned short*)out, K);
 }
 
 // rows one launch takes: 32-bit buffer offsets into A and the f32 rows
@@ -218,7 +181,6 @@ bool eend_gemm_acc_stream_fits(int M, int K, int lda) {
 int eend_launch_gemm_acc_stream(const GemmAccStreamParams& p, hipStream_t stream) {
     if (!eend_gemm_acc_stream_fits(p.M, p.K, p.lda) || !p.A || !p.wstream || !p.g || (((size_t)p.A | (size_t)p.wstream | (size_t)p.g) & 15)) return EEND_EINVAL;
     const int ncu = eend_cu_count();
-    const long t3 = (p.M + 191) / 192, t2 = (p.M + 127) / 128;
-    const long c3 = ((t3 + ncu - 1) / ncu) * (3 * 10 + 9), c2 = ((t2 + ncu - 1) / ncu) * (2 * 10 + 9);     // rounds x (rows + fixed part), as ffn_stream.hip
-    return c2 < c3 ? launch_nj<2>(p, ncu, stream) : launch_nj<3>(p, ncu, stream);
+    return stream_pick_nj(p.M, ncu) == 2 ? stream_launch<gemm_acc_stream_kernel<2>>(p, SMEM, (p.M + 127) / 128, ncu, stream)
+                                         : stream_launch<gemm_acc_stream_kernel<3>>(p, SMEM, (p.M + 191) / 192, ncu, stream);
 }

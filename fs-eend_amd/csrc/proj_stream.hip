@@ -12,26 +12,15 @@
 // Reference sites: nn.MultiheadAttention in_proj (FS model :147, merge_tfm_encoder.py:379-385), MultiScaleRetention q / k / v / g
 // projections (LS retention.py:146-160).  proj.hip (X tile resident in LDS, two workgroup barriers per 64 features and destination)
 // stays as the general form: [196608, 768]: 189 us there.
-// Study switches (timing only, tools/build_variant.sh; several are not valid kernels): PS_NOSTORE no destination stores, PS_WAIT60 the item
-// barrier waits for (almost) nothing, PS_NOBARRIER no item barrier, PS_NODMA no weight DMA after the prologue.
 #include "common.h"
 #include "kernels.h"
-#include <type_traits>
-#include <utility>
+#include "wstream.h"
 
 namespace {
 
-template <class F, int... I>
-__device__ __forceinline__ void sfor_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, class F>
-__device__ __forceinline__ void sfor(F&& f) { sfor_impl(f, std::make_integer_sequence<int, N>{}); }
-template <int V> using IC = std::integral_constant<int, V>;
-
-typedef __attribute__((address_space(3))) char lds_char;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
-constexpr int SLOT = 16384;            // one stream item: 16 fragments of 1 KB = 32 output features x 256 inputs
+constexpr int SLOT = STREAM_ITEM;      // one stream item: 16 fragments of 1 KB = 32 output features x 256 inputs
 constexpr int NSLOT = 8;
 constexpr int BIASL = NSLOT * SLOT;    // bias table, up to 1024 features
 constexpr int MAXN = 1024;
@@ -77,21 +66,20 @@ DEV u32x2 pack4(const f32x4 a, bool bf) {
     return __builtin_bit_cast(u32x2, o);
 }
 
-// vmcnt is a 6-bit field split over bits 3:0 and 15:14; lgkmcnt untouched (0xF at 11:8), expcnt 7
-DEV void wait_vm(int n) {
-#define PS_W(v) case v: __builtin_amdgcn_s_waitcnt(0x0F70 | ((v) & 15) | (((v) >> 4) << 14)); break;
+// vmcnt(n >> 2) for a run-time count n: s_waitcnt takes an immediate
+DEV void wait_vm_table(int n) {
     switch (n >> 2) {
+#define PS_W(v) case v: wait_vm<v>(); break;
         PS_W(5) PS_W(6) PS_W(7) PS_W(8) PS_W(9) PS_W(10) PS_W(11) PS_W(12) PS_W(13) PS_W(14)
-        default: __builtin_amdgcn_s_waitcnt(0x0F70 | (60 & 15) | ((60 >> 4) << 14)); break;
-    }
 #undef PS_W
+        default: wait_vm<60>(); break;
+    }
 }
-// (the cases above wait for 4 * (n >> 2) <= n outstanding accesses: never more than asked for)
-static_assert(INFL == 20, "wait_vm's first case");
+// (the cases above wait for n >> 2 outstanding accesses, the default for 60: never more than asked for)
+static_assert(INFL == 20, "wait_vm_table's first case");
 
 __global__ __launch_bounds__(256, 1)
 void proj_stream_kernel(const ProjStreamParams p) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
     const int S = p.N >> 5;
     const int ntiles = (p.M + TM - 1) / TM;
 
@@ -101,21 +89,9 @@ void proj_stream_kernel(const ProjStreamParams p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     int frow = lane & 15, g = lane >> 4;
 
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)p.wstream, 0, S * SLOT, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)p.X, 0, (p.M - 1) * p.ldx * 2 + 512, 0x00020000);
-    int dvo = lane * 16 + wave * 4096;
-    int nxt = 0;
-    int slot = 0;
-    auto dma_piece = [&](int sd, auto I) __attribute__((always_inline)) {
-        constexpr int i = decltype(I)::value;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_char*)(smem + sd * SLOT + wave * 4096 + i * 1024), 16, dvo,
-                                                 nxt * SLOT + i * 1024, 0, 0);
-    };
-    auto dma_advance = [&]() __attribute__((always_inline)) { nxt = nxt + 1 == S ? 0 : nxt + 1; };
-    sfor<NSLOT - 1>([&](auto IT) __attribute__((always_inline)) {
-        sfor<4>([&](auto I) __attribute__((always_inline)) { dma_piece(decltype(IT)::value, I); });
-        dma_advance();
-    });
+    WeightRing<NSLOT> ring(p.wstream, S, wave, lane);
+    ring.prime();
     float* bl = (float*)(smem + BIASL);
     for (int i = tid; i < p.N; i += 256) bl[i] = p.bias[i];
 
@@ -131,7 +107,7 @@ void proj_stream_kernel(const ProjStreamParams p) {
         }
     };
 
-    __builtin_amdgcn_s_waitcnt(0x0070 | ((4 * (NSLOT - 2)) & 15) | (((4 * (NSLOT - 2)) >> 4) << 14));   // item 0 of this wave has landed; lgkmcnt(0)
+    wait_vm_lgkm0<4 * (NSLOT - 2)>();                    // item 0 of this wave has landed; lgkmcnt(0)
     __builtin_amdgcn_s_barrier();
     if ((int)blockIdx.x < ntiles) load_rows(blockIdx.x, xf);
     sfor<PD>([&](auto Q) __attribute__((always_inline)) { wf[decltype(Q)::value % NB] = *(const f16x8*)(wl + decltype(Q)::value * 1024); });
@@ -144,7 +120,7 @@ void proj_stream_kernel(const ProjStreamParams p) {
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         asm volatile("" : "+v"(tid));
         lane = tid & 63; frow = lane & 15; g = lane >> 4;
-        dvo = lane * 16 + wave * 4096;
+        ring.set_lane(lane);
         wl = smem + lane * 16;
         const int row0 = tile * TM + wave * WM;                       // the wave's 64 rows: inside one sequence (Tp is a multiple of 64)
         const int seq = row0 / p.Tp, t0 = row0 - seq * p.Tp;
@@ -156,18 +132,13 @@ void proj_stream_kernel(const ProjStreamParams p) {
             const bool has_n = kind_a != 0 || has_b;
             // ---- the item's barrier: this wave's pieces of the NEXT item have landed (its first fragments are prefetched below)
             int extra = (q == 3 || q == 4) ? 8 * NJ : 0;             // the next tile's rows, requested in front of item 3
-            int allow = INFL + e1 + e2 + e3 + e4 + e5 + extra;
-#ifdef PS_WAIT60
-            allow = 63;
-#endif
-            wait_vm(allow < 63 ? allow : 63);
-#ifndef PS_NOBARRIER
+            const int allow = INFL + e1 + e2 + e3 + e4 + e5 + extra;
+            wait_vm_table(allow < 63 ? allow : 63);
             __builtin_amdgcn_s_barrier();
-#endif
             if (q == 2) load_rows(tile + (int)gridDim.x, xn);         // rows beyond M read as zeros
-            const char* wc = wl + slot * SLOT;
-            const char* wn = wl + ((slot + 1) & (NSLOT - 1)) * SLOT;
-            const int sd = (slot + NSLOT - 1) & (NSLOT - 1);
+            const char* wc = wl + ring.slot * SLOT;
+            const char* wn = wl + ring.next_slot() * SLOT;
+            const int sd = ring.refill_slot();
 
             f32x4 h[2][NJ], ht[2][NJ];
             auto run = [&](auto HN, auto HT) __attribute__((always_inline)) {
@@ -195,9 +166,7 @@ void proj_stream_kernel(const ProjStreamParams p) {
                         }
                         if constexpr (pi + PD < 16) wf[(pi + PD) % NB] = *(const f16x8*)(wc + (pi + PD) * 1024);
                         else wf[(pi + PD) % NB] = *(const f16x8*)(wn + (pi + PD - 16) * 1024);
-#ifndef PS_NODMA
-                        if constexpr (pi < 4) dma_piece(sd, IC<pi>{});
-#endif
+                        if constexpr (pi < 4) ring.piece<pi>(sd);
                     });
                     __builtin_amdgcn_sched_barrier(0);
                 });
@@ -205,16 +174,12 @@ void proj_stream_kernel(const ProjStreamParams p) {
             if (has_n && has_t) run(std::true_type{}, std::true_type{});
             else if (has_t) run(std::false_type{}, std::true_type{});
             else run(std::true_type{}, std::false_type{});
-            dma_advance();
-            slot = (slot + 1) & (NSLOT - 1);
+            ring.advance();
+            ring.rotate();
 
             // ---- the item's 64 rows x 32 features leave from the accumulators
             int issued = 0;
-#ifdef PS_NOSTORE
-            if (row0 < 0) {
-#else
             if (row0 < p.M) {
-#endif
                 if (kind_a != 0) {
                     const bool bf = p.bf_a[grp] != 0;
                     if (kind_a == 1) {                                // row-major [M][ld]: 16 bytes per lane and token
@@ -269,10 +234,7 @@ long eend_proj_stream_nelems(int N) { return (N <= 0 || (N % 256) != 0 || N > MA
 
 int eend_launch_proj_stream_pack(const void* W, void* out, int N, hipStream_t stream) {
     if (!W || !out || eend_proj_stream_nelems(N) == 0 || (((size_t)W | (size_t)out) & 15)) return EEND_EINVAL;
-    const long total = eend_proj_stream_nelems(N) / 8;
-    const int blocks = (int)((total + 255) / 256);
-    hipLaunchKernelGGL(proj_stream_pack_kernel, dim3(blocks < 4096 ? blocks : 4096), dim3(256), 0, stream, (const unsigned short*)W, (unsigned short*)out, N);
-    return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
+    return stream_pack_launch(proj_stream_pack_kernel, eend_proj_stream_nelems(N) / 8, stream, (const unsigned short*)W, (unsigned short*)out, N);
 }
 
 // shapes one launch takes: 32-bit buffer offsets with the row prefetch running one grid of tiles past the end; head / transposed
@@ -293,10 +255,5 @@ bool eend_proj_stream_fits(const ProjStreamParams& p) {
 
 int eend_launch_proj_stream(const ProjStreamParams& p, hipStream_t stream) {
     if (!eend_proj_stream_fits(p)) return EEND_EINVAL;
-    static EendOncePerDevice attr_once;
-    if (!eend_set_dynamic_lds(attr_once, (const void*)proj_stream_kernel, SMEM)) return EEND_ELAUNCH;
-    const int ncu = eend_cu_count();
-    const int ntiles = (p.M + TM - 1) / TM;
-    hipLaunchKernelGGL(proj_stream_kernel, dim3(ntiles < ncu ? ntiles : ncu), dim3(256), SMEM, stream, p);
-    return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
+    return stream_launch<proj_stream_kernel>(p, SMEM, (p.M + TM - 1) / TM, eend_cu_count(), stream);
 }

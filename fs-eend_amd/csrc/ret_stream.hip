@@ -28,17 +28,10 @@
 // term.  K, V, G, the probabilities and the state stay as before (f16 operands, f32 accumulation, hi/lo state).
 #include "common.h"
 #include "kernels.h"
+#include "wstream.h"
 #include <stdlib.h>
-#include <type_traits>
-#include <utility>
 
 namespace {
-
-template <class F, int... I>
-__device__ __forceinline__ void sfor_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, class F>
-__device__ __forceinline__ void sfor(F&& f) { sfor_impl(f, std::make_integer_sequence<int, N>{}); }
-template <int V> using IC = std::integral_constant<int, V>;
 
 constexpr int KB = 64;
 constexpr int TILE = KB * 128;            // one [64][64] f16 tile
@@ -50,9 +43,7 @@ enum { I_Q0H = 0, I_Q1H = 1, I_Q0L = 2, I_Q1L = 3, I_G0 = 4, I_G1 = 5, I_K0 = 6,
 constexpr int L_K = 0, L_V = 8 * TILE, L_X = 16 * TILE;
 constexpr int SMEM = L_X + NW * OSTG;     // 160 KB
 
-typedef __attribute__((address_space(3))) char lds_char;
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 DEV int swap23(int r) { return (r & 0x13) | ((r & 4) << 1) | ((r & 8) >> 1); }
 
@@ -255,9 +246,9 @@ void ret_stream_kernel(const RetStreamParams p) {
 
     f16x8 xq[2][8], xo[2][8];
     // the xq rows are older than everything issued in this item
-    if (KV_ONLY) __builtin_amdgcn_s_waitcnt(0x0F70 | (28 & 15) | ((28 >> 4) << 14));                     // xo 16 + biases 4 + DMA 8
-    else if (has_lo) __builtin_amdgcn_s_waitcnt(0x0F70 | (32 & 15) | ((32 >> 4) << 14));                 // bv 4 + xlo 16 + DMA 12
-    else __builtin_amdgcn_s_waitcnt(0x0F70 | (16 & 15) | ((16 >> 4) << 14));                             // bv 4 + DMA 12
+    if (KV_ONLY) wait_vm<28>();                     // xo 16 + biases 4 + DMA 8
+    else if (has_lo) wait_vm<32>();                 // bv 4 + xlo 16 + DMA 12
+    else wait_vm<16>();                             // bv 4 + DMA 12
     to_frags(xq_r, xq);
     RS_STAMP(2);
 
@@ -300,17 +291,17 @@ void ret_stream_kernel(const RetStreamParams p) {
     auto wait_barrier = [&](int younger) __attribute__((always_inline)) {
         // this wave's pieces of the item have landed (`younger` operations may stay in flight); then every wave's
         switch (younger) {      // s_waitcnt takes an immediate
-            case 0: __builtin_amdgcn_s_waitcnt(0x0F70 | 0); break;
-            case 2: __builtin_amdgcn_s_waitcnt(0x0F70 | 2); break;
-            case 4: __builtin_amdgcn_s_waitcnt(0x0F70 | 4); break;
-            case 6: __builtin_amdgcn_s_waitcnt(0x0F70 | 6); break;
-            case 10: __builtin_amdgcn_s_waitcnt(0x0F70 | 10); break;
-            case 12: __builtin_amdgcn_s_waitcnt(0x0F70 | 12); break;
-            case 20: __builtin_amdgcn_s_waitcnt(0x0F70 | (20 & 15) | ((20 >> 4) << 14)); break;
-            case 22: __builtin_amdgcn_s_waitcnt(0x0F70 | (22 & 15) | ((22 >> 4) << 14)); break;
-            case 26: __builtin_amdgcn_s_waitcnt(0x0F70 | (26 & 15) | ((26 >> 4) << 14)); break;
-            case 28: __builtin_amdgcn_s_waitcnt(0x0F70 | (28 & 15) | ((28 >> 4) << 14)); break;
-            default: __builtin_amdgcn_s_waitcnt(0x0F70 | 0); break;
+            case 0: wait_vm<0>(); break;
+            case 2: wait_vm<2>(); break;
+            case 4: wait_vm<4>(); break;
+            case 6: wait_vm<6>(); break;
+            case 10: wait_vm<10>(); break;
+            case 12: wait_vm<12>(); break;
+            case 20: wait_vm<20>(); break;
+            case 22: wait_vm<22>(); break;
+            case 26: wait_vm<26>(); break;
+            case 28: wait_vm<28>(); break;
+            default: wait_vm<0>(); break;
         }
         __builtin_amdgcn_s_barrier();
     };
@@ -319,7 +310,7 @@ void ret_stream_kernel(const RetStreamParams p) {
     if constexpr (!KV_ONLY) {
         // ================================================================== Q (three products), G
         f16x8 xl[2][8];
-        __builtin_amdgcn_s_waitcnt(0x0F70 | 12);         // the xlo rows have landed (12 DMA pieces are younger)
+        wait_vm<12>();         // the xlo rows have landed (12 DMA pieces are younger)
         to_frags(xl_r, xl);
         RS_STAMP(3);
         // Two accumulator sets in rotation: while an item accumulates into one, the epilogue of the item before it (pack q / swish g /
@@ -442,7 +433,7 @@ void ret_stream_kernel(const RetStreamParams p) {
             // the lower half's frames 32 w .. of this wave: requested only now (their 64 registers are not free earlier)
             u32x4 xo_r[2][8];
             request_rows(p.X, seq, f0 + to0, xo_r);
-            __builtin_amdgcn_s_waitcnt(0x0F70 | 0);
+            wait_vm<0>();
             RS_STAMP(12);
             to_frags_half(xo_r, xo);                     // wave-private 4-KB tiles in K rows 0 .. 255 (not yet written)
             RS_STAMP(13);
@@ -463,7 +454,7 @@ void ret_stream_kernel(const RetStreamParams p) {
         RS_STAMP(14);
     } else {
         // pass 1: fragments 2, 3 = the chunk's upper half (biases 4 + DMA 8 are younger)
-        __builtin_amdgcn_s_waitcnt(0x0F70 | 12);
+        wait_vm<12>();
         to_frags(xo_r1, xo);
     }
 

@@ -5,8 +5,8 @@
 // Replaces eend_linear_res16_ln_f16 + eend_spk_qkv_attn_f16 on the hot path for every slot count C <= 12 (3 / 6 / 12 fill the tiling
 // exactly; the others leave phantom slot positions that are masked and never stored).
 //
-// Same machinery as ffn_stream.hip (one wave per SIMD, 48 token rows per wave, weight fragments streamed by LDS-DMA through an
-// 8-slot ring, one barrier per 16-KB item, LayerNorm output == next GEMM's B operand), with two differences:
+// Same machinery as ffn_stream.hip, shared through wstream.h (one wave per SIMD, 48 token rows per wave, weight fragments streamed by
+// LDS-DMA through an 8-slot ring, one barrier per 16-KB item, LayerNorm output == next GEMM's B operand), with two differences:
 //   * a wave's 48 rows are the C slots of 48/C consecutive frames (row = (b*C + c)*Tp + t), token index = c*G + t', so every
 //     frame's slots sit in ONE wave: in the MFMA output layout (lane = token column, 4 rows per 16-lane group) the keys and
 //     values of the other slots of a lane's frame are in the same lane (other token fragment) or a fixed rotation away inside
@@ -17,22 +17,12 @@
 // The key bias is dropped: q . b_k is the same for every key of a query and cancels in the softmax.
 #include "common.h"
 #include "kernels.h"
-#include <type_traits>
-#include <utility>
+#include "wstream.h"
 
 namespace {
 
-template <class F, int... I>
-__device__ __forceinline__ void sfor_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, class F>
-__device__ __forceinline__ void sfor(F&& f) { sfor_impl(f, std::make_integer_sequence<int, N>{}); }
-template <int V> using IC = std::integral_constant<int, V>;
-
-typedef __attribute__((address_space(3))) char lds_char;
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
 constexpr int NJ = 3;                // token fragments per wave (48 rows)
-constexpr int SLOT = 16384;          // one stream item: 16 fragments of 1 KB
+constexpr int SLOT = STREAM_ITEM;    // one stream item: 16 fragments of 1 KB
 constexpr int NSLOT = 8;
 constexpr int STAGE = NSLOT * SLOT;  // 4 x 4 KB wave-private output staging
 constexpr int VECS = STAGE + 4 * 4096;   // f32 vectors: bo, g1, be1 (3 x 256), bin (768)
@@ -52,15 +42,7 @@ __global__ void spk_stream_pack_kernel(const _Float16* __restrict__ Wo, const _F
     for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
         const int item = (int)(t >> 10), w = (int)(t & 1023);
         const int pfrag = w >> 6, l = w & 63, f = l & 15, g = l >> 4;
-        const _Float16* src;
-        if (item < 8) {
-            const int kc = item >> 1, sl = item & 1;
-            src = Wo + (size_t)((f >> 2) * 64 + pfrag * 4 + (f & 3)) * 256 + kc * 64 + sl * 32 + g * 8;
-        } else {
-            const int q = item - 8, h = q / 6, tt = (q % 6) >> 1, u = q & 1;
-            const int s_ = pfrag >> 1, hf = pfrag & 1;
-            src = Win + (size_t)(tt * 256 + h * 64 + (f >> 2) * 16 + (u * 2 + hf) * 4 + (f & 3)) * 256 + g * 64 + 8 * s_;
-        }
+        const _Float16* src = item < 8 ? Wo + pack_wo_off(item >> 1, item & 1, pfrag, f, g) : Win + pack_win_off(item - 8, pfrag, f, g);
         _Float16* dst = out + t * 8;
 #pragma unroll
         for (int e = 0; e < 8; ++e) dst[e] = src[e];
@@ -100,7 +82,6 @@ void spk_stream_kernel(const SpkStreamParams p) {
     constexpr int R = 16 / G, C = 3 * R;
     constexpr bool FULL = CC == C;
     static_assert(CC >= 1 && CC <= C, "slot count beyond the positions of this tiling");
-    extern __shared__ __attribute__((aligned(16))) char smem[];
     const int TPB = p.Tp / (4 * G);                       // tiles per utterance
     const int ntiles = p.B * TPB;
 
@@ -111,22 +92,8 @@ void spk_stream_kernel(const SpkStreamParams p) {
     int frow = lane & 15, g = lane >> 4;
     int fo = g * 64;
 
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)p.wstream, 0, NITEMS * SLOT, 0x00020000);
-    int dvo = lane * 16 + wave * 4096;
-    int nxt = 0;
-    int slot = 0;
-
-    auto dma_piece = [&](int sd, auto I) __attribute__((always_inline)) {
-        constexpr int i = decltype(I)::value;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_char*)(smem + sd * SLOT + wave * 4096 + i * 1024), 16, dvo,
-                                                 nxt * SLOT + i * 1024, 0, 0);
-    };
-    auto dma_advance = [&]() __attribute__((always_inline)) { nxt = nxt + 1 == NITEMS ? 0 : nxt + 1; };
-
-    sfor<NSLOT - 1>([&](auto IT) __attribute__((always_inline)) {
-        sfor<4>([&](auto I) __attribute__((always_inline)) { dma_piece(decltype(IT)::value, I); });
-        dma_advance();
-    });
+    WeightRing<NSLOT> ring(p.wstream, NITEMS, wave, lane);
+    ring.prime();
 
     float* vecs = (float*)(smem + VECS);                  // [0..767]: bo, g1, be1; [768..1535]: bin (q, k, v)
     {
@@ -180,7 +147,7 @@ void spk_stream_kernel(const SpkStreamParams p) {
         }
     };
 
-    __builtin_amdgcn_s_waitcnt(0x0070 | ((4 * (NSLOT - 2)) & 15) | (((4 * (NSLOT - 2)) >> 4) << 14));   // item 0 has landed; lgkmcnt(0)
+    wait_vm_lgkm0<4 * (NSLOT - 2)>();                       // item 0 has landed; lgkmcnt(0)
     __builtin_amdgcn_s_barrier();
     if (blockIdx.x < ntiles) sfor<NJ>([&](auto J) __attribute__((always_inline)) { load_in_frags(blockIdx.x, J); });
 
@@ -191,12 +158,11 @@ void spk_stream_kernel(const SpkStreamParams p) {
     auto step = [&](auto KIND, auto SRCc, auto COLDc, auto PFNc, auto VWXc) __attribute__((always_inline)) {
         constexpr int kind = decltype(KIND)::value, src = decltype(SRCc)::value, vw = INFL + decltype(VWXc)::value;
         constexpr bool cold = decltype(COLDc)::value, pfn = decltype(PFNc)::value;
-        static_assert(vw <= 63, "vmcnt is a 6-bit field");
-        __builtin_amdgcn_s_waitcnt(0x0F70 | (vw & 15) | ((vw >> 4) << 14));
+        wait_vm<vw>();
         __builtin_amdgcn_s_barrier();
-        const char* wc = wl + slot * SLOT;
-        const char* wn = wl + ((slot + 1) & (NSLOT - 1)) * SLOT;
-        const int sd = (slot + NSLOT - 1) & (NSLOT - 1);
+        const char* wc = wl + ring.slot * SLOT;
+        const char* wn = wl + ring.next_slot() * SLOT;
+        const int sd = ring.refill_slot();
         if constexpr (cold) {
             sfor<PD>([&](auto Q) __attribute__((always_inline)) {
                 wf[decltype(Q)::value % NB] = *(const f16x8*)(wc + decltype(Q)::value * 1024);
@@ -217,12 +183,12 @@ void spk_stream_kernel(const SpkStreamParams p) {
                 }
                 if constexpr (pi + PD < 16) wf[(pi + PD) % NB] = *(const f16x8*)(wc + (pi + PD) * 1024);
                 else if constexpr (pfn) wf[(pi + PD) % NB] = *(const f16x8*)(wn + (pi + PD - 16) * 1024);
-                if constexpr (pi < 4) dma_piece(sd, IC<pi>{});
+                if constexpr (pi < 4) ring.piece<pi>(sd);
             });
             __builtin_amdgcn_sched_barrier(0);
         });
-        dma_advance();
-        slot = (slot + 1) & (NSLOT - 1);
+        ring.advance();
+        ring.rotate();
     };
 
     char* st = smem + STAGE + wave * 4096;
@@ -232,7 +198,7 @@ void spk_stream_kernel(const SpkStreamParams p) {
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         asm volatile("" : "+v"(tid));
         lane = tid & 63; frow = lane & 15; g = lane >> 4; fo = g * 64;
-        dvo = lane * 16 + wave * 4096;
+        ring.set_lane(lane);
         wl = smem + lane * 16;
         st = smem + STAGE + wave * 4096;
         const int ntile = tile + (int)gridDim.x;
@@ -534,13 +500,7 @@ void spk_stream_kernel(const SpkStreamParams p) {
 
 template <int G, int CC, bool R32>
 int launch(const SpkStreamParams& p, hipStream_t stream) {
-    static EendOncePerDevice attr_once;
-    auto kern = spk_stream_kernel<G, CC, R32>;
-    if (!eend_set_dynamic_lds(attr_once, (const void*)kern, SMEM)) return EEND_ELAUNCH;
-    const int ncu = eend_cu_count();
-    const int ntiles = p.B * (p.Tp / (4 * G));
-    hipLaunchKernelGGL(kern, dim3(ntiles < ncu ? ntiles : ncu), dim3(256), SMEM, stream, p);
-    return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
+    return stream_launch<spk_stream_kernel<G, CC, R32>>(p, SMEM, p.B * (p.Tp / (4 * G)), eend_cu_count(), stream);
 }
 
 constexpr int frames_per_wave(int C) { return C <= 3 ? 16 : C <= 6 ? 8 : 4; }
@@ -557,10 +517,7 @@ long eend_spk_stream_nelems() { return (long)NITEMS * (SLOT / 2); }
 
 int eend_launch_spk_stream_pack(const void* Wo, const void* Win, void* out, hipStream_t stream) {
     if (!Wo || !Win || !out) return EEND_EINVAL;
-    const long total = eend_spk_stream_nelems() / 8;
-    hipLaunchKernelGGL(spk_stream_pack_kernel, dim3((int)((total + 255) / 256)), dim3(256), 0, stream, (const _Float16*)Wo,
-                       (const _Float16*)Win, (_Float16*)out);
-    return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
+    return stream_pack_launch(spk_stream_pack_kernel, eend_spk_stream_nelems() / 8, stream, (const _Float16*)Wo, (const _Float16*)Win, (_Float16*)out);
 }
 
 int eend_spk_stream_supported(int C, int Tp) {

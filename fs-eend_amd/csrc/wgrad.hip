@@ -34,11 +34,11 @@
 // frame t + tap - pad of the same sequence, zero outside [0, ilen) -- an out-of-bounds source offset per lane.
 #include "train_common.h"
 #include "kernels.h"
+#include "wstream.h"
 #include <type_traits>
 
 namespace {
 
-typedef __attribute__((address_space(3))) char lds_char;
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
@@ -287,7 +287,7 @@ void wgrad_tr_kernel(const WgradParams p) {
     typedef std::integral_constant<int, 1> K1;
 #pragma unroll
     for (int s = 0; s < TR_NST - 1; ++s) issue(s);
-    __builtin_amdgcn_s_waitcnt(0x0F70 | (4 * (TR_NST - 2)));           // this wave's pieces of stage 0 (two younger stages in flight)
+    wait_vm<4 * (TR_NST - 2)>();           // this wave's pieces of stage 0 (two younger stages in flight)
     __builtin_amdgcn_s_barrier();
     request(K0{}, 0u);
     int buf = 0;
@@ -299,7 +299,7 @@ void wgrad_tr_kernel(const WgradParams p) {
         __builtin_amdgcn_sched_barrier(0);
         // this wave's pieces of stage st + 1 have landed (one younger stage may stay in flight); behind the barrier every wave's
         // have, and every wave has its last fragments of stage st - 1 in registers: that buffer takes stage st + 3
-        __builtin_amdgcn_s_waitcnt(0x0F70 | (4 * (TR_NST - 3)));
+        wait_vm<4 * (TR_NST - 3)>();
         __builtin_amdgcn_s_barrier();
         issue(buf == 0 ? TR_NST - 1 : buf - 1);
         request(K0{}, (unsigned)(nb * STB));                           // (beyond the last stage: zero rows, never consumed)

@@ -1,5 +1,5 @@
 """Same-box timing of attnout_spk_stream against the two launches it replaces (linear_res16_ln + linear + spk_attn) at the
-FS model.test decoder shape (B=64, C=6, Tp=512).  Usage: python tools/ab_spk_stream.py [reps]"""
+FS model.test decoder shape (B=64, C=6, Tp=512; other slot counts C keep B*C = 384).  Usage: python tools/ab_spk_stream.py [reps] [C]"""
 import importlib, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -11,7 +11,8 @@ ops = importlib.import_module("fs-eend_amd.ops")
 
 def main():
     reps = int(sys.argv[1]) if len(sys.argv) > 1 else 20
-    B, C, Tp = 64, 6, 512
+    C = int(sys.argv[2]) if len(sys.argv) > 2 else 6
+    B, Tp = 384 // C, 512
     M = B * C * Tp
     dev = "cuda"
     g = torch.Generator(device="cpu").manual_seed(0)
