@@ -651,6 +651,23 @@ int eend_window_push_f16(void* win_f16, const float* x, const int* mode_dev, int
     return eend_launch_window_push(win_f16, x, mode_dev, S, k, D, (hipStream_t)stream);
 }
 
+int eend_retention_step_ragged_f32(const float* qkvg_f32, float* kv_state, const int* len_dev, const int* mask_dev, int rows_per_seq,
+                                   void* out_f16, float* out_f32, int N, int H, float gn_eps, void* stream) {
+    return eend_launch_ret_step_ragged(qkvg_f32, kv_state, len_dev, mask_dev, rows_per_seq, out_f16, out_f32, N, H, gn_eps,
+                                       (hipStream_t)stream);
+}
+
+int eend_dwconv_step_ragged_f16(const void* x_f16, float* cache, const int* len_dev, const int* mask_dev, const float* w,
+                                const float* bn_weight, const float* bn_bias, const float* bn_mean, const float* bn_var, float eps,
+                                void* out_f16, int B, int D, int k, void* stream) {
+    return eend_launch_dwconv_step_ragged(x_f16, cache, len_dev, mask_dev, w, bn_weight, bn_bias, bn_mean, bn_var, eps, out_f16, B, D, k,
+                                          (hipStream_t)stream);
+}
+
+int eend_window_push_f32(float* win_f32, const float* x, const int* mode_dev, int S, int k, int D, void* stream) {
+    return eend_launch_window_push_f32(win_f32, x, mode_dev, S, k, D, (hipStream_t)stream);
+}
+
 int eend_retention_step_f16(const void* qkvg, float* kv_state, const float* scale_in, float* scale_out,
                             void* out_f16, int N, int H, float gn_eps, void* stream) {
     if (!qkvg || !kv_state || !scale_in || !scale_out || !out_f16) return EEND_EINVAL;

@@ -212,6 +212,13 @@ int eend_launch_attn_decode_ragged(const void* qkv, void* Kc, void* Vc, void* ou
                                    int rows_per_seq, const int* len, const int* mask, float scale, hipStream_t stream);
 int eend_launch_counter_add_masked(int* len, const int* mask, int S, hipStream_t stream);
 int eend_launch_window_push(void* win16, const float* x, const int* mode, int S, int k, int D, hipStream_t stream);
+// ls_multi.hip: the per-slot state touches of the multi-stream LS frame step
+int eend_launch_ret_step_ragged(const float* qkvg, float* kv, const int* len, const int* mask, int rows_per_seq, void* out16, float* out32,
+                                int N, int H, float eps, hipStream_t stream);
+int eend_launch_dwconv_step_ragged(const void* x16, float* cache, const int* len, const int* mask, const float* w, const float* bn_w,
+                                   const float* bn_b, const float* bn_mean, const float* bn_var, float eps, void* out16, int B, int D,
+                                   int k, hipStream_t stream);
+int eend_launch_window_push_f32(float* win, const float* x, const int* mode, int S, int k, int D, hipStream_t stream);
 int eend_launch_gather_bn_cast_pad(const float* const* x_ptrs, const int* lens, float pad_value, const float* bn_w,
                                    const float* bn_b, const float* bn_mean, const float* bn_var, float eps, void* out16,
                                    int B, int T, int Tp, int Fin, int Fpad, int apply_bn, hipStream_t stream);

@@ -692,6 +692,52 @@ def window_push(win16, x32, mode_i32):
     _lib.check(L.eend_window_push_f16(_p(win16), _p(x32), _p(mode_i32), S, win16.shape[1] // D, D, _stream()), "eend_window_push_f16")
 
 
+def retention_step_ragged(qkvg32, kv_state, len_dev, mask_dev, rows_per_seq, N, H, gn_eps=1e-6, out16=None, out32=None):
+    """retention_step_f32 over slots at different positions: row n belongs to sequence n // rows_per_seq, whose scale is its own
+    length len_dev[s] (int32; 0 = empty state, never read).  mask_dev[s] == 0 leaves the state untouched and zeroes the output
+    rows.  The lengths are not advanced (counter_add_masked)."""
+    L = _lib.load()
+    _chk(qkvg32, F32, "qkvg32"); _chk(kv_state, F32, "kv_state"); _chk(out16, F16, "out16"); _chk(out32, F32, "out32")
+    _chk(len_dev, torch.int32, "len_dev"); _chk(mask_dev, torch.int32, "mask_dev")
+    if out16 is None and out32 is None:
+        raise _lib.EendHipError("retention_step_ragged: out16 and / or out32")
+    if rows_per_seq <= 0 or N % rows_per_seq or len_dev.numel() < N // rows_per_seq or mask_dev.numel() < N // rows_per_seq:
+        raise _lib.EendHipError("retention_step_ragged: one length and one mask per sequence of rows_per_seq rows")
+    D = H * 64
+    if (kv_state.numel() < N * H * 64 * 64 or qkvg32.numel() < N * 4 * D or (out16 is not None and out16.numel() < N * D)
+            or (out32 is not None and out32.numel() < N * D)):
+        raise _lib.EendHipError("retention_step_ragged: shape mismatch")
+    _lib.check(L.eend_retention_step_ragged_f32(_p(qkvg32), _p(kv_state), _p(len_dev), _p(mask_dev), rows_per_seq, _p(out16), _p(out32),
+                                                N, H, gn_eps, _stream()), "eend_retention_step_ragged_f32")
+
+
+def dwconv_step_ragged(x16, cache, len_dev, mask_dev, w, bn, out16, eps=1e-5):
+    """dwconv_step per slot: mask_dev[b] != 0 shifts slot b's cache f32 (B, D, k-1) in place (len_dev[b] == 0: the cache is read
+    as zeros), mask_dev[b] == 0 leaves it as it is and zeroes the output row."""
+    L = _lib.load()
+    _chk(x16, F16, "x16"); _chk(cache, F32, "cache"); _chk(w, F32, "w"); _chk(out16, F16, "out16")
+    _chk(len_dev, torch.int32, "len_dev"); _chk(mask_dev, torch.int32, "mask_dev")
+    for t in bn:
+        _chk(t, F32, "bn")
+    B, D = x16.shape
+    k = w.shape[1]
+    if (cache.shape != (B, D, k - 1) or out16.shape != (B, D) or w.shape[0] != D or len_dev.numel() < B or mask_dev.numel() < B
+            or any(t.numel() < D for t in bn)):
+        raise _lib.EendHipError("dwconv_step_ragged: shape mismatch")
+    _lib.check(L.eend_dwconv_step_ragged_f16(_p(x16), _p(cache), _p(len_dev), _p(mask_dev), _p(w), _p(bn[0]), _p(bn[1]), _p(bn[2]),
+                                             _p(bn[3]), eps, _p(out16), B, D, k, _stream()), "eend_dwconv_step_ragged_f16")
+
+
+def window_push_f32(win32, x32, mode_i32):
+    """window_push on f32 windows (S, k*D): per slot keep / shift + append x32[s] / shift + append zeros."""
+    L = _lib.load()
+    _chk(win32, F32, "win32"); _chk(x32, F32, "x32"); _chk(mode_i32, torch.int32, "mode")
+    S, D = x32.shape
+    if win32.shape[0] != S or win32.shape[1] % D or mode_i32.numel() < S:
+        raise _lib.EendHipError("window_push_f32: shape mismatch")
+    _lib.check(L.eend_window_push_f32(_p(win32), _p(x32), _p(mode_i32), S, win32.shape[1] // D, D, _stream()), "eend_window_push_f32")
+
+
 _PTR_TABLES = {}
 
 

@@ -426,6 +426,29 @@ int eend_counter_add_masked_i32(int* len_dev, const int* mask_dev, int S, void* 
  * anything else: the slot's window is left as it is. */
 int eend_window_push_f16(void* win_f16, const float* x, const int* mode_dev, int S, int k, int D, void* stream);
 
+/* Many LS-EEND streams in one frame step (LsMultiStreamSession): the state touches of the LS frame step per slot (additive to
+ * ABI version 5).  Row n belongs to sequence s = n / rows_per_seq (1 for encoder rows, C for decoder rows); len_dev / mask_dev
+ * are int32 [S] in device memory, so a captured hipGraph stays valid from frame to frame.
+ *
+ * eend_retention_step_ragged_f32: eend_retention_step_f32 (MultiScaleRetention.recurrent_forward, LS-EEND/nnet/modules/
+ * retention.py:126-144, decay 1, + per-head LayerNorm and swish gate) with each sequence's own scale: the reference keeps one
+ * incremental_state["scale"] per batch (retention.py:141-142), here scale_in = len_dev[s] and scale_out = len_dev[s] + 1, so a
+ * slot at position t is bit-identical to eend_retention_step_f32 with scale_in = t.  len_dev[s] == 0 is an empty state: the
+ * old kv_state rows are not read (whatever a reused slot holds, NaN included, cannot leak).  mask_dev[s] == 0 (or a negative
+ * length): kv_state untouched and not read, output rows zero.  qkvg_f32 [N][4*H*64], kv_state f32 [N][H][64][64], out_f16
+ * and / or out_f32 [N][H*64].  The lengths are not advanced (eend_counter_add_masked_i32). */
+int eend_retention_step_ragged_f32(const float* qkvg_f32, float* kv_state, const int* len_dev, const int* mask_dev, int rows_per_seq,
+                                   void* out_f16, float* out_f32, int N, int H, float gn_eps, void* stream);
+/* eend_dwconv_step_f16 (ConformerConvModule.forward_one_step, conformer/convolution.py:157-163) per slot b < B: mask_dev[b] != 0
+ * shifts the slot's cache f32 [B][D][k-1] in place, with len_dev[b] == 0 reading it as zeros (the zero-initialised conv_caches
+ * of LS-EEND/streaming_infer_dia.py:40-45); mask_dev[b] == 0 leaves the cache as it is and writes a zero output row. */
+int eend_dwconv_step_ragged_f16(const void* x_f16, float* cache, const int* len_dev, const int* mask_dev, const float* w,
+                                const float* bn_weight, const float* bn_bias, const float* bn_mean, const float* bn_var, float eps,
+                                void* out_f16, int B, int D, int k, void* stream);
+/* eend_window_push_f16 on an f32 window win_f32 [S][k*D] (the all-f32 look-ahead window of the LS frame step, LS model
+ * :151-186): mode_dev[s] == 1 shifts and appends x f32 [S][D] row s, == 2 shifts and appends zeros, anything else keeps it. */
+int eend_window_push_f32(float* win_f32, const float* x, const int* mode_dev, int S, int k, int D, void* stream);
+
 /* One frame of MultiScaleRetention.recurrent_forward (retention.py:126-144, decay 1) + per-head
  * LayerNorm + swish gate, state updated in place.  qkvg f16 [N][4*H*64] = [q | k*dk^-0.5 | v | g];
  * kv_state f32 [N][H][64][64] in the reference's incremental_state["prev_key_value"] layout;
