@@ -368,6 +368,13 @@ int eend_splice_subsample_f32(const float* Y, int T, int F, int ctx, int sub, fl
     return eend_launch_splice_subsample(Y, T, F, ctx, sub, out, (hipStream_t)stream);
 }
 
+int eend_audio_feed_f32(const long* desc, int n_desc, const long* stft_tiles, int n_stft, const long* splice_tiles, int n_splice,
+                        float* tail, float* ring, double* sums, float* Y, float* out, int mode, int ctx, int sub,
+                        const float* dft, const float* melT, void* stream) {
+    return eend_launch_audio_feed(desc, n_desc, stft_tiles, n_stft, splice_tiles, n_splice, tail, ring, sums, Y, out, mode, ctx, sub,
+                                  dft, melT, (hipStream_t)stream);
+}
+
 int eend_pit_cost_f64(const float* y, const float* labels, int B, int T, int C, double* cost, void* stream) {
     return eend_launch_pit_cost(y, labels, B, T, C, cost, (hipStream_t)stream);
 }

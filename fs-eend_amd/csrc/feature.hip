@@ -28,23 +28,20 @@ constexpr int SM_P = SM_B + KC * NCOL * 4;           // + 23040
 constexpr int SM_M = SM_P + 4 * 16 * PSTR * 4;       // + 34048
 constexpr int SM_BYTES = SM_M + KMEL * MELP * 4;     // + 16896 = 94944
 
-__global__ __launch_bounds__(256)
-void stft_logmel_kernel(const float* __restrict__ y, long len, long first, int n_frames, const float* __restrict__ dft,
-                        const float* __restrict__ melT, float* __restrict__ out) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
+// The per-tile body of both STFT kernels: FB consecutive frames whose samples gather(i), i = 0..XSPAN-1, returns (tap 0 of
+// the tile's first frame is i = 0), written as log-mel rows out[r][23] for r < rows.  Batch and incremental front-ends run
+// exactly this instruction sequence, so their log-mel frames are bit-identical.
+template <class Gather>
+__device__ __forceinline__ void stft_logmel_tile(char* smem, Gather gather, const float* __restrict__ dft,
+                                                 const float* __restrict__ melT, float* __restrict__ out, int rows) {
     float* xs = (float*)(smem + SM_X);
     float* Bs = (float*)(smem + SM_B);
     float* Pw = (float*)(smem + SM_P);
     float* Ms = (float*)(smem + SM_M);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int frow = lane & 15, fk = lane >> 4;
-    const int f0 = blockIdx.x * FB;
-    const long base = first + (long)f0 * HOP;            // sample index of tap 0 of the block's first frame
 
-    for (int i = tid; i < XSPAN; i += 256) {
-        const long idx = base + i;
-        xs[i] = (idx >= 0 && idx < len) ? y[idx] : 0.f;
-    }
+    for (int i = tid; i < XSPAN; i += 256) xs[i] = gather(i);
     for (int i = tid; i < KMEL * MELP; i += 256) Ms[i] = melT[i];
 
     f32x4 acc[18];
@@ -87,11 +84,24 @@ void stft_logmel_kernel(const float* __restrict__ y, long len, long first, int n
         if (m < NMEL) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const int f = f0 + wave * 16 + fk * 4 + r;
-                if (f < n_frames) out[(long)f * NMEL + m] = log10f(__builtin_fmaxf(am[mt][r], 1e-10f));
+                const int f = wave * 16 + fk * 4 + r;
+                if (f < rows) out[(long)f * NMEL + m] = log10f(__builtin_fmaxf(am[mt][r], 1e-10f));
             }
         }
     }
+}
+
+__global__ __launch_bounds__(256)
+void stft_logmel_kernel(const float* __restrict__ y, long len, long first, int n_frames, const float* __restrict__ dft,
+                        const float* __restrict__ melT, float* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int f0 = blockIdx.x * FB;
+    const long base = first + (long)f0 * HOP;            // sample index of tap 0 of the block's first frame
+    auto gather = [=](int i) {
+        const long idx = base + i;
+        return (idx >= 0 && idx < len) ? y[idx] : 0.f;
+    };
+    stft_logmel_tile(smem, gather, dft, melT, out + (long)f0 * NMEL, n_frames - f0);
 }
 
 // Mean normalisations of a (T, F) map, one block per column, the running column sum carried in fp64:
@@ -164,6 +174,118 @@ void splice_subsample_kernel(const float* __restrict__ Y, int T, int F, int ctx,
     out[idx] = (t >= 0 && t < T) ? Y[t * F + m] : 0.f;
 }
 
+
+// ---- incremental front-end: many streams ("slots"), each fed its audio in chunks of any size (eend_audio_feed_f32) ----
+// Per slot the device keeps the sample tail (TAIL floats: samples 80 f - 100 .. of its next log-mel frame f, fewer than 200
+// received), the fp64 column sums of cumulative mean normalisation and a ring of the last normalised log-mel frames that the
+// splice of its next model frame needs.  The host keeps the counters and builds one descriptor per slot named in the call
+// (FEED_* fields) and the two tile tables.  Y is the call's scratch of normalised log-mel rows: a slot's region starts at
+// row ybase with its ring frames rb .. f_before - 1 followed by its new frames f_before .. f_after - 1.
+constexpr int TAIL = 200, RING = 32;
+enum { FEED_CHUNK, FEED_RECV0, FEED_RECV1, FEED_F0, FEED_F1, FEED_RB0, FEED_RB1, FEED_YBASE, FEED_SLOT, FEED_N };
+
+// One block per tile of up to FB new log-mel frames of one slot (tile = {descriptor, first frame, rows}): the samples
+// come from the slot's tail (received before this call) or from its new chunk, zero before 0 and from recv1 on.
+__global__ __launch_bounds__(256)
+void feed_stft_kernel(const long* __restrict__ desc, const long* __restrict__ tiles, const float* __restrict__ tail,
+                      const float* __restrict__ dft, const float* __restrict__ melT, float* __restrict__ Y) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const long* t = tiles + 3 * (long)blockIdx.x;
+    const long* d = desc + FEED_N * t[0];
+    const float* chunk = (const float*)d[FEED_CHUNK];
+    const long recv0 = d[FEED_RECV0], recv1 = d[FEED_RECV1], f_a = t[1];
+    const long tbase = d[FEED_F0] * HOP - 100;                    // sample index of the tail's element 0
+    const float* tl = tail + (long)d[FEED_SLOT] * TAIL;
+    const long base = f_a * HOP - 100;
+    auto gather = [=](int i) {
+        const long idx = base + i;
+        if (idx < 0 || idx >= recv1) return 0.f;
+        if (idx >= recv0) return chunk[idx - recv0];
+        return idx - tbase < TAIL ? tl[idx - tbase] : 0.f;
+    };
+    float* out = Y + (d[FEED_YBASE] + f_a - d[FEED_RB0]) * NMEL;
+    stft_logmel_tile(smem, gather, dft, melT, out, (int)t[2]);
+}
+
+// One block per slot: history rows from the ring, normalisation of the new rows in place (mode 2: out[t] = Y[t] - (Y[0] + .. +
+// Y[t]) / (t + 1), the fp64 sum added strictly in frame order, so the result does not depend on the chunking), then the new
+// ring and tail.  Everything the block overwrites is read before the barrier.
+__global__ __launch_bounds__(256)
+void feed_state_kernel(const long* __restrict__ desc, float* __restrict__ tail, float* __restrict__ ring, double* __restrict__ sums,
+                       float* __restrict__ Y, int mode) {
+    __shared__ float nr[RING * NMEL];
+    const int tid = threadIdx.x;
+    const long* d = desc + FEED_N * (long)blockIdx.x;
+    const float* chunk = (const float*)d[FEED_CHUNK];
+    const long recv0 = d[FEED_RECV0], recv1 = d[FEED_RECV1], f0 = d[FEED_F0], f1 = d[FEED_F1];
+    const long rb0 = d[FEED_RB0], rb1 = d[FEED_RB1], slot = d[FEED_SLOT];
+    float* Ys = Y + d[FEED_YBASE] * NMEL;
+    float* rg = ring + slot * RING * NMEL;
+    float* tl = tail + slot * TAIL;
+    const int hist = (int)(f0 - rb0), n_new = (int)(f1 - f0);
+
+    for (int i = tid; i < hist * NMEL; i += 256) {
+        const float v = rg[i];
+        Ys[i] = v;
+        const long q = rb0 + i / NMEL - rb1;
+        if (q >= 0) nr[q * NMEL + i % NMEL] = v;
+    }
+    float tv = 0.f;
+    if (tid < TAIL) {
+        const long idx = f1 * HOP - 100 + tid, tbase = f0 * HOP - 100;
+        if (idx >= 0 && idx < recv1) tv = idx >= recv0 ? chunk[idx - recv0] : (idx - tbase < TAIL ? tl[idx - tbase] : 0.f);
+    }
+    float* Yn = Ys + (long)hist * NMEL;
+    if (mode == 2) {
+        if (tid < NMEL) {
+            double s = f0 ? sums[slot * NMEL + tid] : 0.0;
+            constexpr int U = 8;
+            for (int i0 = 0; i0 < n_new; i0 += U) {
+                float v[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) v[u] = i0 + u < n_new ? Yn[(long)(i0 + u) * NMEL + tid] : 0.f;
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const int i = i0 + u;
+                    if (i < n_new) {
+                        s += (double)v[u];
+                        const float o = v[u] - (float)(s / (double)(f0 + i + 1));
+                        Yn[(long)i * NMEL + tid] = o;
+                        const long q = f0 + i - rb1;
+                        if (q >= 0) nr[q * NMEL + tid] = o;
+                    }
+                }
+            }
+            sums[slot * NMEL + tid] = s;
+        }
+    } else {
+        const long skip = rb1 > f0 ? (rb1 - f0) * NMEL : 0;        // only the frames that stay in the ring
+        for (long i = skip + tid; i < (long)n_new * NMEL; i += 256) nr[(f0 - rb1) * NMEL + i] = Yn[i];
+    }
+    __syncthreads();
+    for (int i = tid; i < (int)(f1 - rb1) * NMEL; i += 256) rg[i] = nr[i];
+    if (tid < TAIL) tl[tid] = tv;
+}
+
+// One block per tile of up to SPL_ROWS model frames of one slot (tile = {descriptor, first model frame j, rows, output row}):
+// model frame j = frames j sub - ctx .. j sub + ctx side by side, zero outside [0, f_after).
+constexpr int SPL_ROWS = 16;
+__global__ __launch_bounds__(256)
+void feed_splice_kernel(const long* __restrict__ desc, const long* __restrict__ tiles, const float* __restrict__ Y,
+                        float* __restrict__ out, int ctx, int sub) {
+    const long* t = tiles + 4 * (long)blockIdx.x;
+    const long* d = desc + FEED_N * t[0];
+    const long j0 = t[1], f1 = d[FEED_F1], rb = d[FEED_RB0];
+    const int rows = (int)t[2], W = NMEL * (2 * ctx + 1);
+    const float* Ys = Y + d[FEED_YBASE] * NMEL;
+    float* o = out + t[3] * W;
+    for (int i = threadIdx.x; i < rows * W; i += 256) {
+        const int r = i / W, e = i - r * W, c = e / NMEL, m = e - c * NMEL;
+        const long f = (j0 + r) * sub + c - ctx;
+        o[i] = (f >= rb && f < f1) ? Ys[(f - rb) * NMEL + m] : 0.f;
+    }
+}
+
 }  // namespace
 
 int eend_launch_stft_logmel(const float* y, long len, long first, int n_frames, const float* dft, const float* melT, float* out,
@@ -186,5 +308,24 @@ int eend_launch_splice_subsample(const float* Y, int T, int F, int ctx, int sub,
     const int To = (T + sub - 1) / sub;
     const long n = (long)To * F * (2 * ctx + 1);
     hipLaunchKernelGGL(splice_subsample_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, Y, T, F, ctx, sub, To, out);
+    return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
+}
+
+int eend_launch_audio_feed(const long* desc, int n_desc, const long* stft_tiles, int n_stft, const long* splice_tiles, int n_splice,
+                           float* tail, float* ring, double* sums, float* Y, float* out, int mode, int ctx, int sub,
+                           const float* dft, const float* melT, hipStream_t stream) {
+    if (n_desc < 0 || n_stft < 0 || n_splice < 0 || (mode != 0 && mode != 2) || ctx < 0 || ctx > 15 || sub < 1 || sub > 16)
+        return EEND_EINVAL;
+    if (n_desc == 0) return (n_stft || n_splice) ? EEND_EINVAL : EEND_OK;
+    if (!desc || !tail || !ring || !sums || (n_stft && (!stft_tiles || !Y || !dft || !melT)) || (n_splice && (!splice_tiles || !out)))
+        return EEND_EINVAL;
+    if (n_stft) {
+        static EendOncePerDevice attr_once;
+        if (!eend_set_dynamic_lds(attr_once, (const void*)feed_stft_kernel, SM_BYTES)) return EEND_ELAUNCH;
+        hipLaunchKernelGGL(feed_stft_kernel, dim3(n_stft), dim3(256), SM_BYTES, stream, desc, stft_tiles, tail, dft, melT, Y);
+    }
+    hipLaunchKernelGGL(feed_state_kernel, dim3(n_desc), dim3(256), 0, stream, desc, tail, ring, sums, Y, mode);
+    if (n_splice)
+        hipLaunchKernelGGL(feed_splice_kernel, dim3(n_splice), dim3(256), 0, stream, desc, splice_tiles, Y, out, ctx, sub);
     return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
 }

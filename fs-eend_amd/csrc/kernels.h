@@ -103,6 +103,9 @@ int eend_launch_stft_logmel(const float* y, long len, long first, int n_frames, 
                             hipStream_t stream);
 int eend_launch_colnorm(const float* Y, float* out, int T, int F, int mode, hipStream_t stream);
 int eend_launch_splice_subsample(const float* Y, int T, int F, int ctx, int sub, float* out, hipStream_t stream);
+int eend_launch_audio_feed(const long* desc, int n_desc, const long* stft_tiles, int n_stft, const long* splice_tiles, int n_splice,
+                           float* tail, float* ring, double* sums, float* Y, float* out, int mode, int ctx, int sub,
+                           const float* dft, const float* melT, hipStream_t stream);
 
 int eend_launch_pit_cost(const float* y, const float* lab, int B, int T, int C, double* cost, hipStream_t stream);
 int eend_launch_pit_assign(const double* cost, const int* nspk, int B, int C, int* perm, double* loss, hipStream_t stream);

@@ -320,6 +320,20 @@ int eend_feature_meannorm_f32(const float* Y, float* out, int T, int F, int mode
  * zero outside [0, T) (splice + subsample). */
 int eend_splice_subsample_f32(const float* Y, int T, int F, int ctx, int sub, float* out, void* stream);
 
+/* Incremental front-end: many streams ("slots") fed audio in chunks of any size; the log-mel frames are those of
+ * eend_stft_logmel23_f32 (first = -100) bit for bit, normalised (mode 0 = logmel23, 2 = logmel23_cummn with the fp64
+ * running sum added in frame order), spliced (ctx 0..15) and subsampled (sub 1..16) as eend_splice_subsample_f32.
+ * Per-slot device state: tail f32 [slots][200] (samples 80 f - 100 .. of the slot's next log-mel frame f), ring f32
+ * [slots][32][23] (its last normalised frames that later splices read), sums f64 [slots][23].  desc i64 [n_desc][9], one
+ * row per slot in the call: {device address of its new samples, samples received before / after, log-mel frames before /
+ * after, first frame held in the ring before / after, row of that frame in Y, slot}.  stft_tiles i64 [n_stft][3]:
+ * {desc row, first new log-mel frame, frames <= 64}; splice_tiles i64 [n_splice][4]: {desc row, first model frame,
+ * frames <= 16, output row}.  Y f32 scratch [rows][23]: per slot its ring frames then its new frames; out f32
+ * [rows][23 (2 ctx + 1)].  At most three launches; the host owns all counters (see fs-eend_amd/audio_stream.py). */
+int eend_audio_feed_f32(const long* desc, int n_desc, const long* stft_tiles, int n_stft, const long* splice_tiles, int n_splice,
+                        float* tail, float* ring, double* sums, float* Y, float* out, int mode, int ctx, int sub,
+                        const float* dft, const float* melT, void* stream);
+
 /* ---- permutation-invariant label assignment (FS-EEND/train/utils/loss.py:257-327 batch_pit_n_speaker_loss;
  * LS-EEND/train/utils/loss.py:350-379 pit_loss_multispk) ---- */
 
