@@ -250,17 +250,20 @@ class AudioStreamSession:
         y = ses.end([a])                  # the rest of the stream: remaining frames, flush -> {slot: (k, C) logits}
         ses.close(a)
 
+    A `live_rttm.SegmentSession` around either session is served the same way (its segments then follow the audio).
     `push` runs the front-end once for all slots named, then steps the session max(n_s) times, each step pushing the next
     feature frame of every slot that still has one (the other slots pause).  `input_transform` defaults to the reference
     configs': logmel23 for FS-EEND, logmel23_cummn for LS-EEND."""
 
     def __init__(self, session, input_transform=None, context_size: int = 7, subsampling: int = 10):
         from .fs_multistream import FsMultiStreamSession
+        from .live_rttm import SegmentSession
         from .ls_multistream import LsMultiStreamSession
         if input_transform is None:
-            if isinstance(session, FsMultiStreamSession):
+            inner = session.ses if isinstance(session, SegmentSession) else session    # look through the segment wrapper
+            if isinstance(inner, FsMultiStreamSession):
                 input_transform = "logmel23"
-            elif isinstance(session, LsMultiStreamSession):
+            elif isinstance(inner, LsMultiStreamSession):
                 input_transform = "logmel23_cummn"
             else:
                 raise TypeError("AudioStreamSession wraps an FsMultiStreamSession or LsMultiStreamSession")

@@ -350,6 +350,12 @@ int eend_activity_segments_i32(const unsigned char* act, int T, int S, int* chan
     return eend_launch_segments(act, T, S, changes, counts, cap, (hipStream_t)stream);
 }
 
+int eend_segtrack_feed_f32(const long* desc, const int* counts, const int* ends, int n, int ld, int col0, int ntracks, float threshold,
+                           int median, int is_prob, unsigned long long* hist, int* open, int* box, int slots, int cap, void* stream) {
+    return eend_launch_segtrack(desc, counts, ends, n, ld, col0, ntracks, threshold, median, is_prob, hist, open, box, slots, cap,
+                                (hipStream_t)stream);
+}
+
 int eend_der_counters_u64(const float* pred, int ldp, const float* label, int ldl, int T, int C, int label_delay,
                           unsigned long long* counters, void* stream) {
     return eend_launch_der_counters(pred, ldp, label, ldl, T, C, label_delay, counters, (hipStream_t)stream);

@@ -69,21 +69,29 @@ def segments(act):
     return [list(zip(ch[s][0:n[s]:2], ch[s][1:n[s]:2])) for s in range(S)]
 
 
-def make_rttm(rec, pred, frame_shift=80, threshold=0.5, median=11, subsampling=10, sampling_rate=8000):
-    pred = _to_device(pred, "pred")
+RTTM_FMT = "SPEAKER {:s} 1 {:7.2f} {:7.2f} <NA> <NA> {:s} <NA>"
+
+
+def rttm_lines(rec, segs, frame_shift=80, subsampling=10, sampling_rate=8000):
+    """segs: per speaker track, [(start_frame, end_frame), ...] in frame order -> make_rttm's dict {str(spkid): [line, ...]}
+    (speakers without segments are absent).  Shared by make_rttm and the live tracker (live_rttm.py)."""
     rttm = defaultdict(list)
-    fmt = "SPEAKER {:s} 1 {:7.2f} {:7.2f} <NA> <NA> {:s} <NA>"
-    for spkid, segs in enumerate(segments(activity(pred, threshold, median))):
-        if not segs:
+    for spkid, ss in enumerate(segs):
+        if not ss:
             continue
         # the reference formats 0-dim torch tensors computed as int64 * int / int -> float32; the same
         # arithmetic on the whole vector of change points gives the same float32 values
-        se = torch.tensor(segs, dtype=torch.int64)
+        se = torch.tensor(ss, dtype=torch.int64)
         st = (se[:, 0] * frame_shift * subsampling / sampling_rate).tolist()
         du = ((se[:, 1] - se[:, 0]) * frame_shift * subsampling / sampling_rate).tolist()
         name = rec + "_" + str(spkid)
-        rttm[str(spkid)] = [fmt.format(rec, a, b, name) for a, b in zip(st, du)]
+        rttm[str(spkid)] = [RTTM_FMT.format(rec, a, b, name) for a, b in zip(st, du)]
     return rttm
+
+
+def make_rttm(rec, pred, frame_shift=80, threshold=0.5, median=11, subsampling=10, sampling_rate=8000):
+    pred = _to_device(pred, "pred")
+    return rttm_lines(rec, segments(activity(pred, threshold, median)), frame_shift, subsampling, sampling_rate)
 
 
 def der_counters(pred, label, label_delay=0):

@@ -293,6 +293,21 @@ int eend_activity_median_u8(const float* pred, int ld, int T, int S, float thres
 int eend_activity_segments_i32(const unsigned char* act, int T, int S, int* changes, int* counts, int cap,
                                void* stream);
 
+/* Live segments for many streams ("slots"; fs-eend_amd/live_rttm.py, additive to ABI version 5): the incremental form of
+ * eend_activity_median_u8 + eend_activity_segments_i32.  One wave per entry e < n advances slot desc[2e + 1] by counts[e] rows
+ * (device int32; <= 0: none) of a row-major f32 matrix starting at address desc[2e] (desc i64 [n][2], row stride ld floats),
+ * columns col0 .. col0 + ntracks - 1 (1 <= ntracks <= 64, ld >= col0 + ntracks).  Decision: x > threshold with is_prob, else
+ * 1 / (1 + expf(-x)) > threshold (NaN inactive); then the zero-padded median of `median` (odd, 1..63) frames, whose decision of
+ * frame u is final once frame u + median / 2 has arrived.  ends (device int32 [n], may be NULL): != 0 ends the stream after its
+ * rows -- the last median / 2 decisions are finalised with zeros past the end and open segments close at the frame count.
+ * State: hist u64 [slots][64] (last median - 1 raw decisions per track), open i32 [slots][64] (start of the open segment, -1:
+ * none), box i32 [slots][4 + 3 cap] = {frames, count, overflow, 0} then a ring of cap closed segments {track, start, end (exclusive)},
+ * appended by end frame, then track; a full ring sets overflow and drops the segment.  frames == 0 marks an empty stream whose
+ * hist / open words are not read; the host zeroes {frames, count, overflow} to start a stream and {count, overflow} after reading
+ * the ring.  A slot may appear in at most one entry per call. */
+int eend_segtrack_feed_f32(const long* desc, const int* counts, const int* ends, int n, int ld, int col0, int ntracks, float threshold,
+                           int median, int is_prob, unsigned long long* hist, int* open, int* box, int slots, int cap, void* stream);
+
 /* Frame-level DER counters of pre-activations pred f32 [T][ldp] against 0/1 labels f32 [T][ldl], C columns,
  * label_delay as in the reference: counters u64 [8] = speech_scored, speech_miss, speech_falarm,
  * speaker_scored, speaker_miss, speaker_falarm, speaker_error, #(label == decision).  Zeroed by the call. */
