@@ -252,8 +252,9 @@ class AudioStreamSession:
 
     A `live_rttm.SegmentSession` around either session is served the same way (its segments then follow the audio).
     `push` runs the front-end once for all slots named, then steps the session max(n_s) times, each step pushing the next
-    feature frame of every slot that still has one (the other slots pause).  `input_transform` defaults to the reference
-    configs': logmel23 for FS-EEND, logmel23_cummn for LS-EEND."""
+    feature frame of every slot that still has one (the other slots pause).  An FS session built with max_frames > 1 is
+    stepped with step_frames instead, max_frames feature frames per slot and step (and `end` flushes with the last of
+    them).  `input_transform` defaults to the reference configs': logmel23 for FS-EEND, logmel23_cummn for LS-EEND."""
 
     def __init__(self, session, input_transform=None, context_size: int = 7, subsampling: int = 10):
         from .fs_multistream import FsMultiStreamSession
@@ -295,6 +296,20 @@ class AudioStreamSession:
         for k in range(n):
             self._collect(out, self.ses.step(push={s: f[k] for s, f in feats.items() if k < f.shape[0]}))
 
+    def _run_frames(self, feats, out, flush=()):
+        """step_frames in pieces of max_frames; `flush` goes with the last piece (alone when there are no frames)."""
+        m = self.ses.max_frames
+        n = max([f.shape[0] for f in feats.values()] + [0])
+        k = 0
+        while True:
+            last = k + m >= n
+            y = self.ses.step_frames(push={s: f[k:k + m] for s, f in feats.items() if k < f.shape[0]}, flush=flush if last else ())
+            for s, v in y.items():
+                out[s].append(v.reshape(-1, self.C))
+            k += m
+            if last:
+                return
+
     def _result(self, out):
         z = lambda: torch.zeros(0, self.C, dtype=F32, device=self.ses.dev)
         return {s: torch.cat(v) if v else z() for s, v in out.items()}
@@ -312,7 +327,11 @@ class AudioStreamSession:
         self._check_open(waves, "push to")
         feats = self.fe.feed(waves)
         out = {s: [] for s in waves}
-        self._run(feats, out)
+        if getattr(self.ses, "max_frames", 1) > 1:
+            if any(f.shape[0] for f in feats.values()):
+                self._run_frames(feats, out)
+        else:
+            self._run(feats, out)
         return self._result(out)
 
     @torch.no_grad()
@@ -325,6 +344,12 @@ class AudioStreamSession:
             raise SlotError("end(slots, waves): every slot in waves must be among the slots that end")
         feats = self.fe.feed(waves, end=slots)
         out = {s: [] for s in slots}
+        if getattr(self.ses, "max_frames", 1) > 1:
+            self._run_frames(feats, out, flush=slots)
+            while any(self.ses.state(s) == "flushing" for s in slots):
+                for s, v in self.ses.step_frames().items():
+                    out[s].append(v.reshape(-1, self.C))
+            return self._result(out)
         self._run(feats, out)
         self._collect(out, self.ses.step(flush=slots))
         while any(self.ses.state(s) == "flushing" for s in slots):

@@ -664,6 +664,21 @@ int eend_window_push_f16(void* win_f16, const float* x, const int* mode_dev, int
     return eend_launch_window_push(win_f16, x, mode_dev, S, k, D, (hipStream_t)stream);
 }
 
+int eend_attn_chunk_ragged_f16(const void* qkv, void* K_cache, void* V_cache, void* out_f16, float* ws, long ws_floats, int Nseq, int H,
+                               int cap, int nmax, int rows_per_seq, const int* len_dev, const int* cnt_dev, float scale, void* stream) {
+    return eend_launch_attn_chunk_ragged(qkv, K_cache, V_cache, out_f16, ws, ws_floats, Nseq, H, cap, nmax, rows_per_seq, len_dev, cnt_dev,
+                                         scale, (hipStream_t)stream);
+}
+
+int eend_counter_add_count_i32(int* len_dev, const int* cnt_dev, int S, void* stream) {
+    return eend_launch_counter_add_count(len_dev, cnt_dev, S, (hipStream_t)stream);
+}
+
+int eend_window_chunk_f16(void* win_f16, const float* x, void* cols_f16, const int* npush_dev, const int* ndummy_dev, const int* ndec_dev,
+                          int S, int nmax, int k, int D, void* stream) {
+    return eend_launch_window_chunk(win_f16, x, cols_f16, npush_dev, ndummy_dev, ndec_dev, S, nmax, k, D, (hipStream_t)stream);
+}
+
 int eend_retention_step_ragged_f32(const float* qkvg_f32, float* kv_state, const int* len_dev, const int* mask_dev, int rows_per_seq,
                                    void* out_f16, float* out_f32, int N, int H, float gn_eps, void* stream) {
     return eend_launch_ret_step_ragged(qkvg_f32, kv_state, len_dev, mask_dev, rows_per_seq, out_f16, out_f32, N, H, gn_eps,

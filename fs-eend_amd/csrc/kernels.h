@@ -219,6 +219,12 @@ int eend_launch_attn_decode_ragged(const void* qkv, void* Kc, void* Vc, void* ou
                                    int rows_per_seq, const int* len, const int* mask, float scale, hipStream_t stream);
 int eend_launch_counter_add_masked(int* len, const int* mask, int S, hipStream_t stream);
 int eend_launch_window_push(void* win16, const float* x, const int* mode, int S, int k, int D, hipStream_t stream);
+// stream_chunk.hip: the per-slot pieces of the multi-frame FS step (up to nmax frames per slot and step)
+int eend_launch_attn_chunk_ragged(const void* qkv, void* Kc, void* Vc, void* out16, float* part, long part_floats, int Nseq, int H,
+                                  int cap, int nmax, int rows_per_seq, const int* len, const int* cnt, float scale, hipStream_t stream);
+int eend_launch_counter_add_count(int* len, const int* cnt, int S, hipStream_t stream);
+int eend_launch_window_chunk(void* win16, const float* x, void* cols16, const int* npush, const int* ndummy, const int* ndec, int S,
+                             int nmax, int k, int D, hipStream_t stream);
 // ls_multi.hip: the per-slot state touches of the multi-stream LS frame step
 int eend_launch_ret_step_ragged(const float* qkvg, float* kv, const int* len, const int* mask, int rows_per_seq, void* out16, float* out32,
                                 int N, int H, float eps, hipStream_t stream);

@@ -204,20 +204,23 @@ class SegmentTracker:
         self.log.ended(end)
 
     @torch.no_grad()
-    def feed_rows(self, x, counts_dev):
+    def feed_rows(self, x, counts_dev, rows_per_slot=1):
         """The session form: row s of x ((S, C) or (S, 1, C) f32 device tensor, rows contiguous) is slot s's next row when
-        counts_dev[s] (device int32 [S]) is 1.  No host data, one launch; the host does not check slot states here."""
+        counts_dev[s] (device int32 [S]) is 1.  With rows_per_slot = n, x is (S, n, C) and slot s takes its first counts_dev[s]
+        (0..n) rows.  No host data, one launch; the host does not check slot states here."""
         if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != F32 or not x.is_contiguous():
             raise _lib.EendHipError("feed_rows: expected a contiguous f32 GPU tensor")
-        x2 = x.reshape(x.shape[0], -1)
-        if x2.shape[0] != self.S:
-            raise ValueError(f"feed_rows: one row per slot ({self.S}), got {x2.shape[0]}")
+        if not isinstance(rows_per_slot, int) or rows_per_slot < 1:
+            raise ValueError(f"feed_rows: rows_per_slot must be a positive int, got {rows_per_slot!r}")
+        x2 = x.reshape(x.shape[0] * rows_per_slot, -1) if x.shape[0] == self.S else x.reshape(x.shape[0], -1)
+        if x2.shape[0] != self.S * rows_per_slot:
+            raise ValueError(f"feed_rows: {rows_per_slot} row(s) per slot ({self.S}), got {x2.shape[0]}")
         ld = x2.shape[1]
         if ld < self.col0 + self.ntracks:
             raise ValueError(f"rows have {ld} columns, the tracker reads columns {self.col0}..{self.col0 + self.ntracks - 1}")
-        key = (x2.data_ptr(), ld)
+        key = (x2.data_ptr(), ld, rows_per_slot)
         if self._rows is None or self._rows[0] != key:
-            desc = torch.tensor([[key[0] + 4 * ld * s, s] for s in range(self.S)], dtype=I64).to(self.dev)
+            desc = torch.tensor([[key[0] + 4 * rows_per_slot * ld * s, s] for s in range(self.S)], dtype=I64).to(self.dev)
             self._rows = (key, desc)
         self._launch(self._rows[1], counts_dev, None, self.S, ld)
 
@@ -306,6 +309,24 @@ class SegmentSession:
         out = self.ses.step(push=push, flush=flush)
         if out:                                 # a replay happened and modes[2] is this step's decoder-append mask
             self.tracker.feed_rows(self.ses.logits, self.ses.modes[2])
+        done = [s for s in range(self.S) if st[s] == "done" and before[s] != "done"]
+        if done:
+            self.tracker.end(done)
+        return out
+
+    @property
+    def max_frames(self):
+        return getattr(self.ses, "max_frames", 1)
+
+    @torch.no_grad()
+    def step_frames(self, push=None, flush=()):
+        """FsMultiStreamSession.step_frames; the tracker reads each slot's emitted rows of the step's (S, max_frames, C) logits,
+        the decoder frame counts as the per-slot row counts."""
+        st = self.ses.table.state
+        before = list(st)
+        out = self.ses.step_frames(push=push, flush=flush)
+        if out:                                 # a replay happened and counts[3] holds this step's decoder frame counts
+            self.tracker.feed_rows(self.ses.c_logits, self.ses.counts[3], rows_per_slot=self.ses.max_frames)
         done = [s for s in range(self.S) if st[s] == "done" and before[s] != "done"]
         if done:
             self.tracker.end(done)

@@ -710,6 +710,57 @@ def window_push(win16, x32, mode_i32):
     _lib.check(L.eend_window_push_f16(_p(win16), _p(x32), _p(mode_i32), S, win16.shape[1] // D, D, _stream()), "eend_window_push_f16")
 
 
+def attn_chunk_ragged_ws(Nseq, H, cap, nmax):
+    return Nseq * H * ((cap + 511) // 512) * nmax * 66
+
+
+def attn_chunk_ragged(qkv16, k_cache, v_cache, out16, ws, Nseq, H, cap, nmax, rows_per_seq, len_dev, cnt_dev):
+    """Chunk attention over ragged histories: rows q*nmax + j of qkv16 are frames j of sequence q, which belongs to slot
+    q // rows_per_seq with history length len_dev[s] and cnt_dev[s] (0..nmax) new frames (int32).  Frame j < cnt attends over
+    its len cached keys and the chunk's keys 0..j and appends its k / v at row len + j; rows j >= cnt, and every row of a slot
+    with cnt == 0 or len + cnt > cap, are zero and leave the caches alone.  The lengths are not advanced (counter_add_count)."""
+    L = _lib.load()
+    _chk(qkv16, F16, "qkv16"); _chk(k_cache, F16, "k_cache"); _chk(v_cache, F16, "v_cache"); _chk(out16, F16, "out16")
+    _chk(len_dev, torch.int32, "len_dev"); _chk(cnt_dev, torch.int32, "cnt_dev"); _chk(ws, F32, "ws")
+    if not 1 <= nmax <= 64:
+        raise _lib.EendHipError("attn_chunk_ragged: nmax must be in 1..64")
+    if Nseq % rows_per_seq or len_dev.numel() < Nseq // rows_per_seq or cnt_dev.numel() < Nseq // rows_per_seq:
+        raise _lib.EendHipError("attn_chunk_ragged: one length and one count per slot of rows_per_seq sequences")
+    if (k_cache.shape != (Nseq, H, cap, 64) or v_cache.shape != (Nseq, H, cap, 64) or qkv16.shape[0] < Nseq * nmax
+            or qkv16.shape[-1] != 3 * H * 64 or out16.shape[0] < Nseq * nmax or out16.shape[-1] != H * 64):
+        raise _lib.EendHipError("attn_chunk_ragged: shape mismatch")
+    if ws.numel() < attn_chunk_ragged_ws(Nseq, H, cap, nmax):
+        raise _lib.EendHipError("attn_chunk_ragged: workspace too small (attn_chunk_ragged_ws)")
+    _lib.check(L.eend_attn_chunk_ragged_f16(_p(qkv16), _p(k_cache), _p(v_cache), _p(out16), _p(ws), ws.numel(), Nseq, H, cap, nmax,
+                                            rows_per_seq, _p(len_dev), _p(cnt_dev), 1.0 / math.sqrt(64.0), _stream()),
+               "eend_attn_chunk_ragged_f16")
+
+
+def counter_add_count(len_i32, cnt_i32):
+    """len[s] += cnt[s] for every s, in one launch."""
+    L = _lib.load()
+    _chk(len_i32, torch.int32, "len"); _chk(cnt_i32, torch.int32, "cnt")
+    if cnt_i32.numel() < len_i32.numel():
+        raise _lib.EendHipError("counter_add_count: one count per counter")
+    _lib.check(L.eend_counter_add_count_i32(_p(len_i32), _p(cnt_i32), len_i32.numel(), _stream()), "eend_counter_add_count_i32")
+
+
+def window_chunk(win16, x32, cols16, npush_i32, ndummy_i32, ndec_i32, nmax):
+    """Look-ahead windows f16 (S, k*D) over a chunk: slot s takes npush[s] frames x32[s*nmax + j] (f32 (S*nmax, D)) and then
+    ndummy[s] zero frames; cols16 f16 (S*nmax, k*D) gets the ndec[s] emitting windows of the slot, in order, then zero rows."""
+    L = _lib.load()
+    _chk(win16, F16, "win16"); _chk(x32, F32, "x32"); _chk(cols16, F16, "cols16")
+    for t, n in ((npush_i32, "npush"), (ndummy_i32, "ndummy"), (ndec_i32, "ndec")):
+        _chk(t, torch.int32, n)
+    S = win16.shape[0]
+    D = x32.shape[-1]
+    if (nmax < 1 or x32.numel() != S * nmax * D or win16.shape[1] % D or cols16.shape != (S * nmax, win16.shape[1])
+            or min(npush_i32.numel(), ndummy_i32.numel(), ndec_i32.numel()) < S):
+        raise _lib.EendHipError("window_chunk: shape mismatch")
+    _lib.check(L.eend_window_chunk_f16(_p(win16), _p(x32), _p(cols16), _p(npush_i32), _p(ndummy_i32), _p(ndec_i32), S, nmax,
+                                       win16.shape[1] // D, D, _stream()), "eend_window_chunk_f16")
+
+
 def retention_step_ragged(qkvg32, kv_state, len_dev, mask_dev, rows_per_seq, N, H, gn_eps=1e-6, out16=None, out32=None):
     """retention_step_f32 over slots at different positions: row n belongs to sequence n // rows_per_seq, whose scale is its own
     length len_dev[s] (int32; 0 = empty state, never read).  mask_dev[s] == 0 leaves the state untouched and zeroes the output

@@ -455,6 +455,30 @@ int eend_counter_add_masked_i32(int* len_dev, const int* mask_dev, int S, void* 
  * anything else: the slot's window is left as it is. */
 int eend_window_push_f16(void* win_f16, const float* x, const int* mode_dev, int S, int k, int D, void* stream);
 
+/* Many frames per slot in one multi-stream step (FsMultiStreamSession.step_frames; additive to ABI version 5).  Rows follow the
+ * batch forward's (B, C, Tp) slabs with Tp = nmax (1 <= nmax <= 64): row q*nmax + j is frame j of sequence q.
+ *
+ * eend_attn_chunk_ragged_f16: the chunked form of eend_attn_decode_ragged_f16 ("chunked prefill" over ragged K/V histories).
+ * qkv f16 [Nseq*nmax][3*H*64]; sequence q belongs to slot s = q / rows_per_seq (Nseq % rows_per_seq == 0) with history length
+ * len_dev[s] and cnt_dev[s] (0..nmax) new frames.  Query j < cnt sits at position len + j and attends, scale `scale`, over cache
+ * keys [0, len) and the chunk's own keys 0..j; its k / v are appended at row len + j of K_cache / V_cache (f16 [Nseq][H][cap][64])
+ * and no other cache row changes.  Output rows (out f16 [Nseq*nmax][H*64]) with j >= cnt are zero; cnt == 0 or len + cnt > cap
+ * leaves the sequence's caches untouched with all its rows zero.  Cache rows at or beyond len are never read.  As in the decode,
+ * 512-key blocks anchored at key 0 merged in key order make a row depend on its own history and chunk alone.  The lengths are not
+ * advanced (eend_counter_add_count_i32).  ws: f32 scratch of Nseq*H*ceil(cap/512)*nmax*66 floats; the grid is fixed per cap
+ * and nmax, so a captured hipGraph stays valid while the lengths and counts change. */
+int eend_attn_chunk_ragged_f16(const void* qkv, void* K_cache, void* V_cache, void* out_f16, float* ws, long ws_floats, int Nseq, int H,
+                               int cap, int nmax, int rows_per_seq, const int* len_dev, const int* cnt_dev, float scale, void* stream);
+/* len_dev[s] += cnt_dev[s] for s < S, in one launch. */
+int eend_counter_add_count_i32(int* len_dev, const int* cnt_dev, int S, void* stream);
+/* The look-ahead window (as eend_window_push_f16: win f16 [S][k*D]) over a chunk: slot s takes npush_dev[s] frames of x f32
+ * [S*nmax][D] (rows s*nmax + j) and then ndummy_dev[s] zero frames, npush + ndummy <= nmax.  The windows that emit are written as
+ * the Conv1d's f16 im2col rows cols_f16 [S*nmax][k*D]: row s*nmax + i (i < ndec_dev[s] <= npush + ndummy) holds the window after
+ * push npush + ndummy - ndec + i + 1, rows i >= ndec are zero.  The stored window ends exactly as npush + ndummy calls of
+ * eend_window_push_f16 leave it.  Counts out of range leave the slot's window alone with zero rows. */
+int eend_window_chunk_f16(void* win_f16, const float* x, void* cols_f16, const int* npush_dev, const int* ndummy_dev, const int* ndec_dev,
+                          int S, int nmax, int k, int D, void* stream);
+
 /* Many LS-EEND streams in one frame step (LsMultiStreamSession): the state touches of the LS frame step per slot (additive to
  * ABI version 5).  Row n belongs to sequence s = n / rows_per_seq (1 for encoder rows, C for decoder rows); len_dev / mask_dev
  * are int32 [S] in device memory, so a captured hipGraph stays valid from frame to frame.
