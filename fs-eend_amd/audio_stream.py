@@ -22,7 +22,7 @@ import torch
 
 from . import feature
 from . import lib as _lib
-from .fs_multistream import SlotError
+from .multistream import SlotError
 
 F32 = torch.float32
 HOP, WIN_END = 80, 100                   # frame f reads samples 80 f - 100 .. 80 f + 99
@@ -251,24 +251,15 @@ class AudioStreamSession:
         ses.close(a)
 
     A `live_rttm.SegmentSession` around either session is served the same way (its segments then follow the audio).
-    `push` runs the front-end once for all slots named, then steps the session max(n_s) times, each step pushing the next
-    feature frame of every slot that still has one (the other slots pause).  An FS session built with max_frames > 1 is
-    stepped with step_frames instead, max_frames feature frames per slot and step (and `end` flushes with the last of
-    them).  `input_transform` defaults to the reference configs': logmel23 for FS-EEND, logmel23_cummn for LS-EEND."""
+    `push` runs the front-end once for all slots named, then steps the session with step_frames, each step pushing the next
+    max_frames feature frames of every slot that still has some (the other slots pause); `end` flushes with the last of
+    them.  `input_transform` defaults to the session's (the reference configs': logmel23 for FS-EEND, logmel23_cummn for
+    LS-EEND)."""
 
     def __init__(self, session, input_transform=None, context_size: int = 7, subsampling: int = 10):
-        from .fs_multistream import FsMultiStreamSession
-        from .live_rttm import SegmentSession
-        from .ls_multistream import LsMultiStreamSession
-        if input_transform is None:
-            inner = session.ses if isinstance(session, SegmentSession) else session    # look through the segment wrapper
-            if isinstance(inner, FsMultiStreamSession):
-                input_transform = "logmel23"
-            elif isinstance(inner, LsMultiStreamSession):
-                input_transform = "logmel23_cummn"
-            else:
-                raise TypeError("AudioStreamSession wraps an FsMultiStreamSession or LsMultiStreamSession")
         self.ses, self.C = session, session.C
+        if input_transform is None:
+            input_transform = session.input_transform
         self.fe = AudioFrontEnd(session.S, input_transform, context_size, subsampling, device=session.dev)
         in_size = session.m._in_size
         if in_size != self.fe.width:
@@ -289,12 +280,7 @@ class AudioStreamSession:
 
     def _collect(self, out, y):
         for s, v in y.items():
-            out[s].append(v.reshape(1, -1))
-
-    def _run(self, feats, out):
-        n = max([f.shape[0] for f in feats.values()] + [0])
-        for k in range(n):
-            self._collect(out, self.ses.step(push={s: f[k] for s, f in feats.items() if k < f.shape[0]}))
+            out[s].append(v.reshape(-1, self.C))
 
     def _run_frames(self, feats, out, flush=()):
         """step_frames in pieces of max_frames; `flush` goes with the last piece (alone when there are no frames)."""
@@ -303,9 +289,8 @@ class AudioStreamSession:
         k = 0
         while True:
             last = k + m >= n
-            y = self.ses.step_frames(push={s: f[k:k + m] for s, f in feats.items() if k < f.shape[0]}, flush=flush if last else ())
-            for s, v in y.items():
-                out[s].append(v.reshape(-1, self.C))
+            self._collect(out, self.ses.step_frames(push={s: f[k:k + m] for s, f in feats.items() if k < f.shape[0]},
+                                                    flush=flush if last else ()))
             k += m
             if last:
                 return
@@ -327,11 +312,8 @@ class AudioStreamSession:
         self._check_open(waves, "push to")
         feats = self.fe.feed(waves)
         out = {s: [] for s in waves}
-        if getattr(self.ses, "max_frames", 1) > 1:
-            if any(f.shape[0] for f in feats.values()):
-                self._run_frames(feats, out)
-        else:
-            self._run(feats, out)
+        if any(f.shape[0] for f in feats.values()):
+            self._run_frames(feats, out)
         return self._result(out)
 
     @torch.no_grad()
@@ -344,14 +326,7 @@ class AudioStreamSession:
             raise SlotError("end(slots, waves): every slot in waves must be among the slots that end")
         feats = self.fe.feed(waves, end=slots)
         out = {s: [] for s in slots}
-        if getattr(self.ses, "max_frames", 1) > 1:
-            self._run_frames(feats, out, flush=slots)
-            while any(self.ses.state(s) == "flushing" for s in slots):
-                for s, v in self.ses.step_frames().items():
-                    out[s].append(v.reshape(-1, self.C))
-            return self._result(out)
-        self._run(feats, out)
-        self._collect(out, self.ses.step(flush=slots))
+        self._run_frames(feats, out, flush=slots)
         while any(self.ses.state(s) == "flushing" for s in slots):
-            self._collect(out, self.ses.step())
+            self._collect(out, self.ses.step_frames())
         return self._result(out)

@@ -17,7 +17,7 @@ import torch
 
 from . import lib as _lib
 from . import ops
-from .fs_multistream import SlotError
+from .multistream import SlotError
 from .postproc import rttm_lines
 
 F32, I32, I64 = torch.float32, torch.int32, torch.int64
@@ -278,13 +278,14 @@ class SegmentSession:
         ses.poll()                              # {slot: [(spk, start, end), ...]} closed since the last poll
         ses.rttm(a, "rec")                      # make_rttm's lines of the stream so far
 
-    After a step that emitted logits, one tracker launch reads the session's logits rows with its decoder-append mask as the
-    per-slot row counts (no host work); slots that turned done in a step are ended.  tracker_kw go to SegmentTracker
-    (col0 = 1 and ntracks = C - col0 by default)."""
+    After a step that emitted logits, one tracker launch reads the rows the session emitted (`emitted()`: its logits rows
+    with the per-slot emitted row counts on the device, no host work); slots that turned done in a step are ended.
+    tracker_kw go to SegmentTracker (col0 = 1 and ntracks = C - col0 by default)."""
 
     def __init__(self, session, **tracker_kw):
         self.ses = session
         self.S, self.C, self.dev, self.m = session.S, session.C, session.dev, session.m
+        self.max_frames, self.input_transform = session.max_frames, session.input_transform
         kw = dict(tracker_kw)
         col0 = kw.setdefault("col0", 1)
         kw.setdefault("ntracks", self.C - col0)
@@ -302,35 +303,24 @@ class SegmentSession:
     def state(self, s: int) -> str:
         return self.ses.state(s)
 
-    @torch.no_grad()
-    def step(self, push=None, flush=()):
-        st = self.ses.table.state
-        before = list(st)
-        out = self.ses.step(push=push, flush=flush)
-        if out:                                 # a replay happened and modes[2] is this step's decoder-append mask
-            self.tracker.feed_rows(self.ses.logits, self.ses.modes[2])
-        done = [s for s in range(self.S) if st[s] == "done" and before[s] != "done"]
+    def _step(self, step, push, flush):
+        before = [self.ses.state(s) for s in range(self.S)]
+        out = step(push=push, flush=flush)
+        if out:                                 # a replay happened: the tracker reads its emitted rows
+            logits, counts, n = self.ses.emitted()
+            self.tracker.feed_rows(logits, counts, rows_per_slot=n)
+        done = [s for s in range(self.S) if before[s] != "done" and self.ses.state(s) == "done"]
         if done:
             self.tracker.end(done)
         return out
 
-    @property
-    def max_frames(self):
-        return getattr(self.ses, "max_frames", 1)
+    @torch.no_grad()
+    def step(self, push=None, flush=()):
+        return self._step(self.ses.step, push, flush)
 
     @torch.no_grad()
     def step_frames(self, push=None, flush=()):
-        """FsMultiStreamSession.step_frames; the tracker reads each slot's emitted rows of the step's (S, max_frames, C) logits,
-        the decoder frame counts as the per-slot row counts."""
-        st = self.ses.table.state
-        before = list(st)
-        out = self.ses.step_frames(push=push, flush=flush)
-        if out:                                 # a replay happened and counts[3] holds this step's decoder frame counts
-            self.tracker.feed_rows(self.ses.c_logits, self.ses.counts[3], rows_per_slot=self.ses.max_frames)
-        done = [s for s in range(self.S) if st[s] == "done" and before[s] != "done"]
-        if done:
-            self.tracker.end(done)
-        return out
+        return self._step(self.ses.step_frames, push, flush)
 
     def seek(self, s: int, t: int):
         """The session's benchmarking aid (FsMultiStreamSession.seek).  The tracker is not moved: the slot's segment frames keep

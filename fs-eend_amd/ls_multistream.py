@@ -10,18 +10,20 @@ slot's own frame count), the Conformer depthwise-conv cache (`ops.dwconv_step_ra
 LS state is O(1) per stream, so one capture serves the whole session (again only when the weights are refreshed).
 
 The per-frame procedure of one slot is LS-EEND/streaming_infer_dia.py:52-97, as in `LsStreamSession`; the slot bookkeeping is
-FsMultiStreamSession's (`SlotTable`): encoder on push, window push or flush, decoder once the look-ahead is full.
+FsMultiStreamSession's (multistream.py): encoder on push, window push or flush, decoder once the look-ahead is full.
 """
+from types import SimpleNamespace
+
 import torch
 
 from . import ops
-from .fs_multistream import SlotError, SlotPlan, SlotTable  # noqa: F401  (re-exported: the same slot semantics)
 from .lib import EendHipError
+from .multistream import MultiStreamSession
 
 F16, F32, I32 = torch.float16, torch.float32, torch.int32
 
 
-class LsMultiStreamSession:
+class LsMultiStreamSession(MultiStreamSession):
     """S concurrent LS-EEND streams on one `OnlineConformerRetentionDADiarization`, one captured hipGraph per frame step:
 
         encoder : input projection + Conformer-retention blocks, S rows (per-slot retention scale and conv cache)
@@ -36,20 +38,20 @@ class LsMultiStreamSession:
 
     State: retention kv f32 (S, H, 64, 64) per encoder block and (S*C, H, 64, 64) per decoder layer, conv caches f32 (S, D, k-1)
     per block, the window f32 (S, k*D) and two int32 length vectors.  States are never cleared: a length of 0 means "empty" to
-    every kernel that reads them, so a reopened slot computes exactly what a fresh one does."""
+    every kernel that reads them, so a reopened slot computes exactly what a fresh one does.  step_frames takes one frame per
+    slot and step (max_frames = 1)."""
+
+    input_transform = "logmel23_cummn"
 
     def __init__(self, model, slots: int, max_nspks: int = 10, use_graph: bool = True):
         m = model
-        self.m, self.S, self.C, self.use_graph = m, slots, max_nspks, use_graph
         P = m._prepare()
-        dev = m.cnn.weight.device
-        self.dev, self.D, self.H = dev, m.n_units, m._n_heads
-        S, C, D, H = slots, max_nspks, self.D, self.H
-        if C <= 0 or C > 16:
+        if max_nspks <= 0 or max_nspks > 16:
             raise EendHipError("max_nspks must be in 1..16 (the f32 speaker attention of the frame step)")
-        self.k = P["cnn.k"]
-        self.center = self.k // 2
-        self.table = SlotTable(S, self.center)
+        dev = m.cnn.weight.device
+        super().__init__(m, slots, max_nspks, use_graph, P["cnn.k"] // 2, dev)
+        self.D, self.H, self.k = m.n_units, m._n_heads, P["cnn.k"]
+        S, C, D, H = slots, max_nspks, self.D, self.H
         R = S * C
         K1 = m.enc.encoder._conv_kernel_size - 1
         Fmax = max([Bk["w1a32"].shape[0] for Bk in P["blocks"]] + [Ld["w1_32"].shape[0] for Ld in P["dec.layers"]] + [1])
@@ -71,21 +73,13 @@ class LsMultiStreamSession:
         self.len_enc = z(S, dt=I32)
         self.len_dec = z(S, dt=I32)
         self.modes = z(3, S, dt=I32)                                  # [encoder step, window mode, decoder step]
-        self.frames = 0
-        self._graph = None
+        self._rows = {1: SimpleNamespace(Tp=1, x_in=self.x_in, ctl=self.modes, logits=self.logits)}
 
-    def _check_weights(self):
-        """As FsMultiStreamSession._check_weights: the graph holds raw pointers into model._prepare()'s operand copies -- capture
-        again when they were refreshed.  The streaming state lives in the session's own buffers and is kept."""
-        P = self.m._prep
-        if P is None or (self.frames & 255) == 0:
-            P = self.m._prepare()
-        if P is not getattr(self, "_P_captured", None):
-            self._P_captured = P
-            self._graph = None
+    def _clear_window(self, s):
+        self.win32[s].zero_()
 
     # ---- the frame step (eager body; captured once)
-    def _frame(self):
+    def _body(self, r):
         P, H, S, C = self.m._prepare(), self.H, self.S, self.C
         enc_m, win_m, dec_m = self.modes[0], self.modes[1], self.modes[2]
         # encoder, S rows: ls_stream.enc_step's all-f32 form, the retention state and conv cache per slot
@@ -135,65 +129,3 @@ class LsMultiStreamSession:
             ops.linear_res_ln_step_f32(ff32, Ld["w2_32"], Ld["b2"], a32, Ld["g22"], Ld["be22"], a32, Ld["eps22"])
         ops.counter_add_masked(self.len_dec, dec_m)
         ops.head_l2dot(self.e32, a32, self.attr, self.logits, S, 1, 1, C, self.D)
-
-    def _capture(self):
-        self.modes.zero_()                      # warm-up and capture with every mask off: no slot state changes
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):                                    # warm-up: workspaces, operand caches
-            self._frame()
-        torch.cuda.current_stream().wait_stream(s)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            self._frame()
-        self._graph = g
-
-    # ---- public API
-    def open(self) -> int:
-        """Claim a free slot for a new stream: its stream positions start at 0 (empty states) and its window at zeros."""
-        s = self.table.open()
-        self.len_enc[s] = 0
-        self.len_dec[s] = 0
-        self.win32[s].zero_()
-        return s
-
-    def close(self, s: int):
-        self.table.close(s)
-
-    def state(self, s: int) -> str:
-        return self.table.state[s]
-
-    @torch.no_grad()
-    def step(self, push=None, flush=()):
-        """One frame for every slot in use.  push: {slot: features of its next frame ((1,1,in) / (1,in) / (in,))}; flush: slots
-        whose stream ended (each then takes conv_delay zero embeddings, one per step); open slots named in neither pause.
-        -> {slot: logits (1,1,C)} for the slots that emitted a frame (frame t - conv_delay of that stream)."""
-        push = dict(push or {})
-        plan = self.table.plan(push.keys(), flush)
-        if plan.idle:
-            self.table.commit(plan)
-            return {}
-        self._check_weights()
-        if self.use_graph and self._graph is None:
-            self._capture()
-        if push:
-            slots = sorted(push)
-            src = torch.stack([push[s].reshape(-1) for s in slots]).to(device=self.dev, dtype=F32)
-            if slots == list(range(self.S)):
-                self.x_in.copy_(src)
-            else:
-                idx = torch.tensor(slots, dtype=torch.int64, pin_memory=True).to(self.dev, non_blocking=True)
-                self.x_in.index_copy_(0, idx, src)
-        modes = torch.tensor(plan.modes(), dtype=I32, pin_memory=True)   # a fresh pinned block per step (copied asynchronously)
-        self.modes.copy_(modes, non_blocking=True)
-        if self.use_graph:
-            self._graph.replay()
-        else:
-            self._frame()
-        self.table.commit(plan)
-        self.frames += 1
-        emit = plan.emit
-        if not emit:
-            return {}
-        y = self.logits.clone()
-        return {s: y[s:s + 1] for s in emit}

@@ -144,7 +144,7 @@ def test_slot_reused_after_nan_stream(hip_lib, dev, tr):
 
 def test_front_end_errors(hip_lib, dev):
     from fs_eend_amd.audio_stream import AudioFrontEnd
-    from fs_eend_amd.fs_multistream import SlotError
+    from fs_eend_amd.multistream import SlotError
     fe = AudioFrontEnd(2, "logmel23", device=dev)
     with pytest.raises(SlotError):
         fe.feed({0: torch.zeros(100)})                                  # not reset
@@ -263,7 +263,8 @@ def test_ls_audio_session_matches_feature_path(hip_lib, dev):
 
 def test_audio_session_zero_length_and_errors(hip_lib, dev):
     from fs_eend_amd.audio_stream import AudioStreamSession
-    from fs_eend_amd.fs_multistream import FsMultiStreamSession, SlotError
+    from fs_eend_amd.fs_multistream import FsMultiStreamSession
+    from fs_eend_amd.multistream import SlotError
     sm, C = _fs_model(dev)
     ases = AudioStreamSession(FsMultiStreamSession(sm, 2, C, cap=64))
     a = ases.open()

@@ -5,7 +5,7 @@ import random
 import pytest
 
 from fs_eend_amd import audio_stream as A
-from fs_eend_amd.fs_multistream import SlotError
+from fs_eend_amd.multistream import SlotError
 
 LENGTHS = [0, 1, 79, 80, 81, 99, 100, 659, 660, 661, 800, 801, 1600, 8000, 12345]
 SHAPES = [(7, 10), (0, 1), (2, 4), (15, 16)]

@@ -1,15 +1,51 @@
 """Host-only: SlotTable.plan_frames, the bookkeeping of the multi-frame step (FsMultiStreamSession.step_frames) -- emission counts,
 flushing in one or several steps, push plus flush in one call, its errors, and that committing a plan of n frames leaves the
-table exactly as n one-frame plan() / commit() calls do."""
+table exactly as n frames through the one-frame rules do (`_OneFrameSlot`, an independent model of them)."""
 import random
 
 import pytest
 
-from fs_eend_amd.fs_multistream import DONE, FLUSHING, FREE, OPEN, SlotError, SlotTable
+from fs_eend_amd.multistream import DONE, FLUSHING, FREE, OPEN, SlotError, SlotTable
+
+
+KEEP, PUSH, FLUSH = 0, 1, 2
 
 
 def _state(tb, s):
     return (tb.state[s], tb.t[s], tb.n_enc[s], tb.n_dec[s], tb.flush_left[s])
+
+
+class _OneFrameSlot:
+    """One slot under the one-frame rules, written out apart from SlotTable: a frame pushes, starts a flush (its first dummy
+    frame) or, while flushing, takes a dummy frame; it emits logits once the look-ahead of `center` frames is full."""
+
+    def __init__(self, center):
+        self.center = center
+        self.state, self.t, self.n_enc, self.n_dec, self.flush_left = FREE, 0, 0, 0, 0
+
+    def open(self):
+        self.state, self.t, self.n_enc, self.n_dec, self.flush_left = OPEN, 0, 0, 0, 0
+
+    def frame(self, push=False, flush=False):
+        """-> 1 when the frame emitted logits."""
+        if push:
+            win = PUSH
+        elif (flush and self.center > 0) or (self.state == FLUSHING and self.flush_left > 0):
+            win = FLUSH
+        else:
+            win = KEEP
+        dec = 1 if win != KEEP and self.t + 1 >= self.center + 1 else 0
+        if flush:
+            self.state, self.flush_left = FLUSHING, self.center
+        self.n_enc += 1 if push else 0
+        self.n_dec += dec
+        if win != KEEP:
+            self.t += 1
+        if win == FLUSH:
+            self.flush_left -= 1
+        if self.state == FLUSHING and self.flush_left <= 0:
+            self.state = DONE
+        return dec
 
 
 def test_warm_up_emission_counts():
@@ -95,12 +131,12 @@ def test_errors():
 @pytest.mark.parametrize("center", [0, 1, 3, 9])
 @pytest.mark.parametrize("nmax", [1, 2, 4, 16])
 def test_frames_commit_like_one_frame_plans(center, nmax):
-    """Random traffic: after every call, each slot's state equals that of a one-slot table driven through the same frames with
-    plan() / commit(), one frame at a time."""
+    """Random traffic: after every call, each slot's state equals that of a `_OneFrameSlot` driven through the same frames, one
+    frame at a time."""
     rng = random.Random(center * 100 + nmax)
     S = 5
     tb = SlotTable(S, center)
-    ref = [SlotTable(1, center) for _ in range(S)]
+    ref = [_OneFrameSlot(center) for _ in range(S)]
     for _ in range(400):
         if rng.random() < 0.2 and FREE in tb.state:
             s = tb.open()
@@ -115,35 +151,30 @@ def test_frames_commit_like_one_frame_plans(center, nmax):
                     flush.append(s)
             elif tb.state[s] == DONE and rng.random() < 0.5:
                 tb.close(s)
-                ref[s].close(0)
+                ref[s].state = FREE
         p = tb.plan_frames(push, flush, nmax)
         emitted = list(p.dec)
         tb.commit(p)
         for s in range(S):
             r = ref[s]
-            if r.state[0] == FREE:
+            if r.state == FREE:
                 continue
             n = push.get(s, 0)
             dec = 0
             for _ in range(n):                                              # the pushed frames
-                q = r.plan([0])
-                dec += q.dec[0]
-                r.commit(q)
+                dec += r.frame(push=True)
             budget = nmax - n
             if s in flush:                                                  # the flush: its first dummy, if there is room
                 if budget == 0:
-                    r.state[0], r.flush_left[0] = FLUSHING, center          # started, dummies in later steps
+                    r.state, r.flush_left = FLUSHING, center                # started, dummies in later steps
                     if center <= 0:
-                        r.state[0] = DONE
+                        r.state = DONE
                 else:
-                    q = r.plan(flush=[0])
-                    dec += q.dec[0]
-                    r.commit(q)
+                    dec += r.frame(flush=True)
                     budget -= 1 if center > 0 else 0
-            while r.state[0] == FLUSHING and budget > 0:                   # dummies while there is room
-                q = r.plan()
-                dec += q.dec[0]
-                r.commit(q)
+            while r.state == FLUSHING and budget > 0:                      # dummies while there is room
+                dec += r.frame()
                 budget -= 1
+            ref_state = (r.state, r.t, r.n_enc, r.n_dec, r.flush_left)
             assert emitted[s] == dec, (s, emitted[s], dec)
-            assert _state(tb, s) == _state(r, 0), (s, _state(tb, s), _state(r, 0))
+            assert _state(tb, s) == ref_state, (s, _state(tb, s), ref_state)

@@ -1,8 +1,8 @@
-"""CPU: the slot bookkeeping of FsMultiStreamSession (fs_multistream.SlotTable) -- slot lifetimes, the errors on misuse and
+"""CPU: the slot bookkeeping of the multi-stream sessions (multistream.SlotTable) -- slot lifetimes, the errors on misuse and
 the per-slot mode rows the device reads for a frame step.  No GPU, no library calls."""
 import pytest
 
-from fs_eend_amd.fs_multistream import DONE, FLUSHING, FREE, OPEN, SlotError, SlotTable
+from fs_eend_amd.multistream import DONE, FLUSHING, FREE, OPEN, SlotError, SlotTable
 
 KEEP, PUSH, FLUSH = 0, 1, 2
 

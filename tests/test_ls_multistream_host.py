@@ -6,7 +6,7 @@ import ctypes
 import pytest
 import torch
 
-from fs_eend_amd.fs_multistream import DONE, FLUSHING, OPEN, SlotTable
+from fs_eend_amd.multistream import DONE, FLUSHING, OPEN, SlotTable
 
 KEEP, PUSH, FLUSH = 0, 1, 2
 EEND_EINVAL = -1
