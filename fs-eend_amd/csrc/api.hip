@@ -696,6 +696,28 @@ int eend_window_push_f32(float* win_f32, const float* x, const int* mode_dev, in
     return eend_launch_window_push_f32(win_f32, x, mode_dev, S, k, D, (hipStream_t)stream);
 }
 
+int eend_retention_chunk_ragged_f32(const float* qkvg_f32, float* kv_state, const int* len_dev, const int* cnt_dev, int seq_per_slot,
+                                    int nmax, void* out_f16, float* out_f32, int Nseq, int H, float gn_eps, void* stream) {
+    return eend_launch_ret_chunk_ragged(qkvg_f32, kv_state, len_dev, cnt_dev, seq_per_slot, nmax, out_f16, out_f32, Nseq, H, gn_eps,
+                                        (hipStream_t)stream);
+}
+
+int eend_dwconv_chunk_ragged_f16(const void* x_f16, float* cache, const int* len_dev, const int* cnt_dev, int nmax, const float* w,
+                                 const float* bn_weight, const float* bn_bias, const float* bn_mean, const float* bn_var, float eps,
+                                 void* out_f16, int B, int D, int k, void* stream) {
+    return eend_launch_dwconv_chunk_ragged(x_f16, cache, len_dev, cnt_dev, nmax, w, bn_weight, bn_bias, bn_mean, bn_var, eps, out_f16, B, D,
+                                           k, (hipStream_t)stream);
+}
+
+int eend_window_chunk_f32(float* win_f32, const float* x, float* cols_f32, const int* npush_dev, const int* ndummy_dev, const int* ndec_dev,
+                          int S, int nmax, int k, int D, void* stream) {
+    return eend_launch_window_chunk_f32(win_f32, x, cols_f32, npush_dev, ndummy_dev, ndec_dev, S, nmax, k, D, (hipStream_t)stream);
+}
+
+int eend_spk_attn_rows_f32(const float* qkv, float* out_f32, int B, int C, int Tp, float scale, void* stream) {
+    return eend_launch_spk_attn_rows_f32(qkv, out_f32, B, C, Tp, scale, (hipStream_t)stream);
+}
+
 int eend_retention_step_f16(const void* qkvg, float* kv_state, const float* scale_in, float* scale_out,
                             void* out_f16, int N, int H, float gn_eps, void* stream) {
     if (!qkvg || !kv_state || !scale_in || !scale_out || !out_f16) return EEND_EINVAL;

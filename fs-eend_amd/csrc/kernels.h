@@ -232,6 +232,15 @@ int eend_launch_dwconv_step_ragged(const void* x16, float* cache, const int* len
                                    const float* bn_b, const float* bn_mean, const float* bn_var, float eps, void* out16, int B, int D,
                                    int k, hipStream_t stream);
 int eend_launch_window_push_f32(float* win, const float* x, const int* mode, int S, int k, int D, hipStream_t stream);
+// ls_chunk.hip (+ the f32 window of stream_chunk.hip): the same touches over a chunk of up to nmax frames per slot
+int eend_launch_ret_chunk_ragged(const float* qkvg, float* kv, const int* len, const int* cnt, int seq_per_slot, int nmax, void* out16,
+                                 float* out32, int Nseq, int H, float eps, hipStream_t stream);
+int eend_launch_dwconv_chunk_ragged(const void* x16, float* cache, const int* len, const int* cnt, int nmax, const float* w,
+                                    const float* bn_w, const float* bn_b, const float* bn_mean, const float* bn_var, float eps, void* out16,
+                                    int B, int D, int k, hipStream_t stream);
+int eend_launch_window_chunk_f32(float* win, const float* x, float* cols, const int* npush, const int* ndummy, const int* ndec, int S,
+                                 int nmax, int k, int D, hipStream_t stream);
+int eend_launch_spk_attn_rows_f32(const float* qkv, float* out, int B, int C, int Tp, float scale, hipStream_t stream);
 int eend_launch_gather_bn_cast_pad(const float* const* x_ptrs, const int* lens, float pad_value, const float* bn_w,
                                    const float* bn_b, const float* bn_mean, const float* bn_var, float eps, void* out16,
                                    int B, int T, int Tp, int Fin, int Fpad, int apply_bn, hipStream_t stream);

@@ -5,28 +5,9 @@
 // per-slot int32 lengths and masks in device memory decide what each row reads and which state changes.
 #include "common.h"
 #include "kernels.h"
+#include "ls_rows.h"
 
 namespace {
-
-// kv_t[a][:] = kv_{t-1}[a][:] * keep + v[a] k[:] * add in place (FRESH: the old row is taken as zero, not read); -> q . kv_t[a][:]
-template <bool FRESH>
-__device__ __forceinline__ float ret_row_update(float* __restrict__ st, const float* __restrict__ kr, const float* __restrict__ qr,
-                                                float keep, float va) {
-    float o = 0.f;
-#pragma unroll
-    for (int b = 0; b < 64; b += 4) {
-        float4 s = FRESH ? make_float4(0.f, 0.f, 0.f, 0.f) : *(const float4*)(st + b);
-        const float4 kk = *(const float4*)(kr + b);
-        const float4 qq = *(const float4*)(qr + b);
-        s.x = __builtin_fmaf(s.x, keep, va * kk.x);
-        s.y = __builtin_fmaf(s.y, keep, va * kk.y);
-        s.z = __builtin_fmaf(s.z, keep, va * kk.z);
-        s.w = __builtin_fmaf(s.w, keep, va * kk.w);
-        *(float4*)(st + b) = s;
-        o += qq.x * s.x + qq.y * s.y + qq.z * s.z + qq.w * s.w;
-    }
-    return o;
-}
 
 // MultiScaleRetention.recurrent_forward (LS-EEND/nnet/modules/retention.py:126-144, decay 1) + per-head LayerNorm + swish
 // gate on f32 projections, as ret_step_kernel<float> of stream.hip, with the scale taken from the row's own sequence:
@@ -55,24 +36,13 @@ void ret_step_ragged_kernel(const float* __restrict__ qkvg, float* __restrict__ 
         return;
     }
     const float* row = qkvg + (size_t)n * 4 * D;
-    const float ps = (float)t;
-    const float ns = ps + 1.0f;
-    const float keep = (float)__builtin_sqrt((double)ps / (double)ns);
-    const float add = (float)(1.0 / __builtin_sqrt((double)ns));
+    float keep, add;
+    ret_scale_factors(t, keep, add);
     const float va = row[2 * D + h * 64 + lane] * add;
     float* st = kv + ((size_t)idx * 64 + lane) * 64;
     const float o = t == 0 ? ret_row_update<true>(st, row + D + h * 64, row + h * 64, keep, va)
                            : ret_row_update<false>(st, row + D + h * 64, row + h * 64, keep, va);
-    float sum = o;
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) sum = wave_xor_add(sum, m);
-    const float mean = sum * (1.0f / 64.0f);
-    float var = (o - mean) * (o - mean);
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) var = wave_xor_add(var, m);
-    const float y = (o - mean) / __builtin_sqrtf(var * (1.0f / 64.0f) + eps);
-    const float g = row[3 * D + h * 64 + lane];
-    const float r = g / (1.0f + __expf(-g)) * y;
+    const float r = ret_norm_gate(o, row[3 * D + h * 64 + lane], eps);
     if (out) out[(size_t)n * D + h * 64 + lane] = to_f16_sat(r);
     if (out32) out32[(size_t)n * D + h * 64 + lane] = r;
 }
@@ -94,21 +64,9 @@ void dwconv_step_ragged_kernel(const _Float16* __restrict__ x, float* __restrict
         out[i] = (_Float16)0.f;
         return;
     }
-    const bool fresh = t == 0;
-    float* cc = cache + (size_t)i * (k - 1);
-    const float* wc = w + (size_t)c * k;
-    const float xn = (float)x[i];
-    float y = wc[k - 1] * xn;
-    float prev = xn;
-    for (int j = k - 2; j >= 0; --j) {           // walk backwards so the shift can be done in place
-        const float cur = fresh ? 0.f : cc[j];
-        y = __builtin_fmaf(wc[j], cur, y);
-        cc[j] = prev;                            // new_cache[j] = window[j+1]
-        prev = cur;
-    }
     const float sc = bw[c] / __builtin_sqrtf(bv[c] + eps);
-    y = (y - bm[c]) * sc + bb[c];
-    out[i] = to_f16_sat(y / (1.0f + __expf(-y)));
+    const float y = dwconv_frame(cache + (size_t)i * (k - 1), w + (size_t)c * k, (float)x[i], t == 0, k, bm[c], sc, bb[c]);
+    out[i] = to_f16_sat(y);
 }
 
 // The f32 look-ahead window of each slot (f32 [S][k*D], [tap*D + c], oldest tap first): mode 1 shifts it by one frame and

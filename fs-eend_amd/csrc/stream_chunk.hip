@@ -236,13 +236,15 @@ void counter_add_count_kernel(int* __restrict__ len, const int* __restrict__ cnt
     if (s < S) len[s] += cnt[s];
 }
 
-// The look-ahead window over a chunk: slot s takes npush[s] frames x[s*nmax + j] (f32 -> f16) and then ndummy[s] zero frames.
+// The look-ahead window over a chunk: slot s takes npush[s] frames x[s*nmax + j] (f32 -> the window's element type T: f16 for
+// FS-EEND, f32 for the all-f32 LS frame step) and then ndummy[s] zero frames.
 // With z = (the k stored taps, then the npush + ndummy new frames), the window after push m is z[m .. m + k - 1].  Conv
 // input row s*nmax + i (i < ndec[s]) gets the window after push npush + ndummy - ndec + i + 1, rows i >= ndec zeros, and
 // the stored window ends as z[P .. P + k - 1] -- what P calls of window_push_kernel leave.  A thread owns one channel of
 // one slot.  Counts out of range (P > nmax or ndec > P) leave the slot alone with zero rows.
+template <typename T>
 __global__ __launch_bounds__(256)
-void window_chunk_kernel(_Float16* __restrict__ win, const float* __restrict__ x, _Float16* __restrict__ cols,
+void window_chunk_kernel(T* __restrict__ win, const float* __restrict__ x, T* __restrict__ cols,
                          const int* __restrict__ npush, const int* __restrict__ ndummy, const int* __restrict__ ndec,
                          int S, int nmax, int k, int D) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -251,17 +253,17 @@ void window_chunk_kernel(_Float16* __restrict__ win, const float* __restrict__ x
     int np = npush[s], nd = ndummy[s], ne = ndec[s];
     const int P = np + nd;
     if (np < 0 || nd < 0 || ne < 0 || P > nmax || ne > P) np = nd = ne = 0;
-    _Float16* w = win + (size_t)s * k * D + ch;
+    T* w = win + (size_t)s * k * D + ch;
     const float* xs = x + (size_t)s * nmax * D + ch;
-    auto z = [&](int u) -> _Float16 {
+    auto z = [&](int u) -> T {
         if (u < k) return w[(size_t)u * D];
         u -= k;
-        return u < np ? (_Float16)xs[(size_t)u * D] : (_Float16)0.f;
+        return u < np ? (T)xs[(size_t)u * D] : (T)0.f;
     };
     for (int r = 0; r < nmax; ++r) {
-        _Float16* dst = cols + ((size_t)s * nmax + r) * k * D + ch;
+        T* dst = cols + ((size_t)s * nmax + r) * k * D + ch;
         const int m = P - ne + r + 1;
-        for (int tap = 0; tap < k; ++tap) dst[(size_t)tap * D] = r < ne ? z(m + tap) : (_Float16)0.f;
+        for (int tap = 0; tap < k; ++tap) dst[(size_t)tap * D] = r < ne ? z(m + tap) : (T)0.f;
     }
     if (P > 0)
         for (int tap = 0; tap < k; ++tap) w[(size_t)tap * D] = z(P + tap);      // ascending: reads index P + tap >= tap
@@ -299,7 +301,17 @@ int eend_launch_window_chunk(void* win16, const float* x, void* cols16, const in
     if (!win16 || !x || !cols16 || !npush || !ndummy || !ndec || S <= 0 || nmax < 1 || k < 1 || D <= 0 ||
         (long)S * nmax * k * D > 0x7fffffffL)
         return EEND_EINVAL;
-    hipLaunchKernelGGL(window_chunk_kernel, dim3((S * D + 255) / 256), dim3(256), 0, stream, (_Float16*)win16, x, (_Float16*)cols16,
+    hipLaunchKernelGGL(window_chunk_kernel<_Float16>, dim3((S * D + 255) / 256), dim3(256), 0, stream, (_Float16*)win16, x, (_Float16*)cols16,
                        npush, ndummy, ndec, S, nmax, k, D);
+    return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
+}
+
+int eend_launch_window_chunk_f32(float* win, const float* x, float* cols, const int* npush, const int* ndummy, const int* ndec, int S,
+                                 int nmax, int k, int D, hipStream_t stream) {
+    if (!win || !x || !cols || !npush || !ndummy || !ndec || S <= 0 || nmax < 1 || nmax > 64 || k < 1 || D <= 0 ||
+        (long)S * nmax * k * D > 0x7fffffffL)
+        return EEND_EINVAL;
+    hipLaunchKernelGGL(window_chunk_kernel<float>, dim3((S * D + 255) / 256), dim3(256), 0, stream, win, x, cols, npush, ndummy, ndec, S,
+                       nmax, k, D);
     return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
 }

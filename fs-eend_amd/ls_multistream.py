@@ -38,69 +38,99 @@ class LsMultiStreamSession(MultiStreamSession):
 
     State: retention kv f32 (S, H, 64, 64) per encoder block and (S*C, H, 64, 64) per decoder layer, conv caches f32 (S, D, k-1)
     per block, the window f32 (S, k*D) and two int32 length vectors.  States are never cleared: a length of 0 means "empty" to
-    every kernel that reads them, so a reopened slot computes exactly what a fresh one does.  step_frames takes one frame per
-    slot and step (max_frames = 1)."""
+    every kernel that reads them, so a reopened slot computes exactly what a fresh one does.
+
+    With max_frames = n > 1, step_frames runs the same step at Tp = n rows per slot in a second graph: the chunk forms of the
+    three state touches (`ops.retention_chunk_ragged`, `ops.dwconv_chunk_ragged`, `ops.window_chunk_f32`: each slot advances
+    by its own 0..n frames, its state read and written once, bit for bit what n per-frame calls leave) and the decoder over
+    (B = S, C, Tp = n) slabs.  Without it step_frames takes one frame per slot and step."""
 
     input_transform = "logmel23_cummn"
 
-    def __init__(self, model, slots: int, max_nspks: int = 10, use_graph: bool = True):
+    def __init__(self, model, slots: int, max_nspks: int = 10, use_graph: bool = True, max_frames: int = 1):
         m = model
+        if not isinstance(max_frames, int) or isinstance(max_frames, bool) or not 1 <= max_frames <= 64:
+            raise EendHipError("max_frames must be in 1..64")
         P = m._prepare()
         if max_nspks <= 0 or max_nspks > 16:
             raise EendHipError("max_nspks must be in 1..16 (the f32 speaker attention of the frame step)")
         dev = m.cnn.weight.device
         super().__init__(m, slots, max_nspks, use_graph, P["cnn.k"] // 2, dev)
-        self.D, self.H, self.k = m.n_units, m._n_heads, P["cnn.k"]
+        self.max_frames, self.D, self.H, self.k = max_frames, m.n_units, m._n_heads, P["cnn.k"]
         S, C, D, H = slots, max_nspks, self.D, self.H
         R = S * C
         K1 = m.enc.encoder._conv_kernel_size - 1
-        Fmax = max([Bk["w1a32"].shape[0] for Bk in P["blocks"]] + [Ld["w1_32"].shape[0] for Ld in P["dec.layers"]] + [1])
         z = lambda *s_, dt=F32: torch.zeros(*s_, dtype=dt, device=dev)
-        self.x_in = z(S, m._in_size)
-        self.xin32 = z(S, P["Fin_pad"])                               # zero-padded input row of the f32 input projection
-        self.h32, self.h16, self.x16, self.xn32 = z(S, D), z(S, D, dt=F16), z(S, D, dt=F16), z(S, D)    # encoder rows
-        self.o16, self.glu16, self.dw16 = z(S, D, dt=F16), z(S, D, dt=F16), z(S, D, dt=F16)
-        self.q32 = z(R, 4 * D)                                        # retention projections (encoder: the first S rows)
-        self.ff32 = z(R * Fmax)
         self.win32 = z(S, self.k * D)                                 # [tap*D + c], oldest tap first
-        self.y32, self.e32 = z(S, D), z(S, D)
-        self.a32, self.a16, self.o32, self.qkv32 = z(R, D), z(R, D, dt=F16), z(R, D), z(R, 3 * D)    # decoder rows
-        self.attr = z(S, 1, C, D)
-        self.logits = z(S, 1, C)
         self.enc_kv = [z(S, H, 64, 64) for _ in P["blocks"]]
         self.caches = [z(S, D, K1) for _ in P["blocks"]]
         self.dec_kv = [z(R, H, 64, 64) for _ in P["dec.layers"]]
         self.len_enc = z(S, dt=I32)
         self.len_dec = z(S, dt=I32)
-        self.modes = z(3, S, dt=I32)                                  # [encoder step, window mode, decoder step]
-        self._rows = {1: SimpleNamespace(Tp=1, x_in=self.x_in, ctl=self.modes, logits=self.logits)}
+        self._rows = {n: self._alloc_rows(n, P) for n in sorted({1, max_frames})}
+        r = self._rows[1]                                             # the per-frame rows under their long-standing names
+        self.x_in, self.logits, self.modes, self.attr = r.x_in, r.logits, r.ctl, r.attr
+
+    def _alloc_rows(self, n, P):
+        """The rows of a step of Tp = n frames per slot: S*n encoder rows, S*C*n decoder rows (slabs: row (s*C + c)*n + j)."""
+        S, C, D, m = self.S, self.C, self.D, self.m
+        Fmax = max([Bk["w1a32"].shape[0] for Bk in P["blocks"]] + [Ld["w1_32"].shape[0] for Ld in P["dec.layers"]] + [1])
+        z = lambda *s_, dt=F32: torch.zeros(*s_, dtype=dt, device=self.dev)
+        N, R = S * n, S * C * n
+        r = SimpleNamespace(Tp=n)
+        r.x_in = z(S, m._in_size) if n == 1 else z(S, n, m._in_size)
+        r.xin32 = z(N, P["Fin_pad"])                                  # zero-padded input rows of the f32 input projection
+        r.h32, r.h16, r.x16, r.xn32 = z(N, D), z(N, D, dt=F16), z(N, D, dt=F16), z(N, D)    # encoder rows
+        r.o16, r.glu16, r.dw16 = z(N, D, dt=F16), z(N, D, dt=F16), z(N, D, dt=F16)
+        r.q32 = z(R, 4 * D)                                           # retention projections (encoder: the first N rows)
+        r.ff32 = z(R * Fmax)
+        r.cols = self.win32 if n == 1 else z(N, self.k * D)           # the Conv1d's rows: the windows, or the im2col rows of
+        r.y32, r.e32 = z(N, D), z(N, D)                               # a chunk's emitting windows
+        r.a32, r.a16, r.o32, r.qkv32 = z(R, D), z(R, D, dt=F16), z(R, D), z(R, 3 * D)    # decoder rows
+        r.attr = z(S, n, C, D)
+        r.logits = z(S, n, C)
+        r.ctl = z(3 if n == 1 else 4, S, dt=I32)                      # SlotPlan.modes() / counts()
+        return r
 
     def _clear_window(self, s):
         self.win32[s].zero_()
 
-    # ---- the frame step (eager body; captured once)
+    # ---- the step of r.Tp frames per slot (eager body; captured once per row set)
+    def _ret(self, r, q32, kv, lens, ctl, per_slot, Nseq, eps, out16=None, out32=None):
+        """The retention recurrence of Nseq sequences (per_slot of them per slot): the frame step at Tp = 1, else the chunk."""
+        if r.Tp == 1:
+            ops.retention_step_ragged(q32, kv, lens, ctl, per_slot, Nseq, self.H, eps, out16=out16, out32=out32)
+        else:
+            ops.retention_chunk_ragged(q32, kv, lens, ctl, per_slot, Nseq, self.H, r.Tp, eps, out16=out16, out32=out32)
+
     def _body(self, r):
-        P, H, S, C = self.m._prepare(), self.H, self.S, self.C
-        enc_m, win_m, dec_m = self.modes[0], self.modes[1], self.modes[2]
-        # encoder, S rows: ls_stream.enc_step's all-f32 form, the retention state and conv cache per slot
-        h32, h16, x16, xn32 = self.h32, self.h16, self.x16, self.xn32
-        self.xin32[:, :self.x_in.shape[1]].copy_(self.x_in)
-        ops.linear_res_ln_step_f32(self.xin32, P["in.w32"], P["in.b"], None, P["in.g"], P["in.beta"], h32, P["in.eps"], out16=h16)
+        P, H, S, C, n = self.m._prepare(), self.H, self.S, self.C, r.Tp
+        enc_c, dec_c = r.ctl[0], r.ctl[-1]                            # modes at Tp = 1, frame counts above
+        advance = ops.counter_add_masked if n == 1 else ops.counter_add_count
+        # encoder, S*n rows (slot s: rows s*n .. s*n + enc[s] - 1 are its new frames): ls_stream.enc_step's all-f32 form, the
+        # retention state and conv cache per slot
+        N = S * n
+        h32, h16, x16, xn32 = r.h32, r.h16, r.x16, r.xn32
+        r.xin32[:, :self.m._in_size].copy_(r.x_in.view(N, -1))
+        ops.linear_res_ln_step_f32(r.xin32, P["in.w32"], P["in.b"], None, P["in.g"], P["in.beta"], h32, P["in.eps"], out16=h16)
         nb = len(P["blocks"])
-        q32 = self.q32[:S]
+        q32 = r.q32[:N]
         for i, (Bk, kv, cache) in enumerate(zip(P["blocks"], self.enc_kv, self.caches)):
-            ff32 = self.ff32[:S * Bk["w1a32"].shape[0]].view(S, -1)
+            ff32 = r.ff32[:N * Bk["w1a32"].shape[0]].view(N, -1)
             if i == 0:
                 ops.layernorm_rows_f32(h32, Bk["lna"][0], Bk["lna"][1], xn32, Bk["lna"][2])
             ops.linear_step_f32(xn32, Bk["w1a32"], Bk["b1a"], ff32, act=ops.ACT_SWISH)
             ops.linear_res_scale_ln_step_f32(ff32, Bk["w2a32"], Bk["b2a"], h32, Bk["fa"], Bk["lnb"][0], Bk["lnb"][1], h32,
                                              ln_out16=x16, eps=Bk["lnb"][2])
-            ops.retention_proj_step(h32, Bk["lnb"], Bk["wqkvg32"], Bk["bqkvg"], q32, S)
-            ops.retention_step_ragged(q32, kv, self.len_enc, enc_m, 1, S, H, Bk["gn_eps"], out16=self.o16)
-            ops.linear_res_scale_ln16(self.o16, Bk["wo"], Bk["bo"], h32, 1.0, Bk["lnc"][0], Bk["lnc"][1], h32, x16, Bk["lnc"][2])
-            ops.linear_glu(x16, Bk["pw1"], Bk["pb1"], self.glu16)
-            ops.dwconv_step_ragged(self.glu16, cache, self.len_enc, enc_m, Bk["dw"], Bk["bn"], self.dw16, Bk["bn_eps"])
-            ops.linear_res_scale_ln16(self.dw16, Bk["pw2"], Bk["pb2"], h32, 1.0, Bk["lnd"][0], Bk["lnd"][1], h32, x16, Bk["lnd"][2])
+            ops.retention_proj_step(h32, Bk["lnb"], Bk["wqkvg32"], Bk["bqkvg"], q32, N)
+            self._ret(r, q32, kv, self.len_enc, enc_c, 1, S, Bk["gn_eps"], out16=r.o16)
+            ops.linear_res_scale_ln16(r.o16, Bk["wo"], Bk["bo"], h32, 1.0, Bk["lnc"][0], Bk["lnc"][1], h32, x16, Bk["lnc"][2])
+            ops.linear_glu(x16, Bk["pw1"], Bk["pb1"], r.glu16)
+            if n == 1:
+                ops.dwconv_step_ragged(r.glu16, cache, self.len_enc, enc_c, Bk["dw"], Bk["bn"], r.dw16, Bk["bn_eps"])
+            else:
+                ops.dwconv_chunk_ragged(r.glu16, cache, self.len_enc, enc_c, Bk["dw"], Bk["bn"], r.dw16, n, Bk["bn_eps"])
+            ops.linear_res_scale_ln16(r.dw16, Bk["pw2"], Bk["pb2"], h32, 1.0, Bk["lnd"][0], Bk["lnd"][1], h32, x16, Bk["lnd"][2])
             ops.layernorm_rows_f32(h32, Bk["lnd"][0], Bk["lnd"][1], xn32, Bk["lnd"][2])
             ops.linear_step_f32(xn32, Bk["w1b32"], Bk["b1b"], ff32, act=ops.ACT_SWISH)
             ops.linear_res_ln_step_f32(ff32, Bk["w2b32"], Bk["b2b"], h32, Bk["lne"][0], Bk["lne"][1], h32, Bk["lne"][2], alpha=Bk["fb"],
@@ -108,24 +138,34 @@ class LsMultiStreamSession(MultiStreamSession):
             if i + 1 < nb:
                 nx = P["blocks"][i + 1]["lna"]
                 ops.layernorm_rows_f32(h32, nx[0], nx[1], xn32, nx[2])
-        ops.counter_add_masked(self.len_enc, enc_m)
-        # look-ahead window (f32), Conv1d, L2 norm: LsStreamSession._conv per slot
-        ops.window_push_f32(self.win32, h32, win_m)
-        ops.linear_step_f32(self.win32, P["cnn.w32"], P["cnn.b"], self.y32)
-        ops.l2norm_rows_f32(self.y32, self.e32)
-        # decoder, S*C rows: ls_stream.dec_step's all-f32 form, the retention state per slot
-        R = S * C
-        a32, o32 = self.a32, self.o32
-        ops.convert_fanout_step_f32(self.e32, P["convert.w32"], self.m._convert_const(C), a32, self.a16, S, C)
+        advance(self.len_enc, enc_c)
+        # look-ahead window (f32): push / zero frame / keep per slot, or a chunk's pushes then dummies into the im2col rows of
+        # its emitting windows; Conv1d, L2 norm (LsStreamSession._conv per slot)
+        if n == 1:
+            ops.window_push_f32(self.win32, h32, r.ctl[1])
+        else:
+            ops.window_chunk_f32(self.win32, h32, r.cols, r.ctl[1], r.ctl[2], r.ctl[3], n)
+        ops.linear_step_f32(r.cols, P["cnn.w32"], P["cnn.b"], r.y32)
+        ops.l2norm_rows_f32(r.y32, r.e32)
+        # decoder, S*C*n rows in (B = S, C, Tp = n) slabs: ls_stream.dec_step's all-f32 form, the retention state per slot
+        R = S * C * n
+        a32, o32 = r.a32, r.o32
+        if n == 1:
+            ops.convert_fanout_step_f32(r.e32, P["convert.w32"], self.m._convert_const(C), a32, r.a16, S, C)
+        else:
+            ops.convert_fanout_f32(r.e32, P["convert.w32"], self.m._convert_const(C), a32, r.a16, S, n, C)
         for Ld, kv in zip(P["dec.layers"], self.dec_kv):
-            ff32 = self.ff32[:R * Ld["w1_32"].shape[0]].view(R, -1)
-            ops.retention_proj_step(a32, None, Ld["wqkvg32"], Ld["bqkvg"], self.q32, R)
-            ops.retention_step_ragged(self.q32, kv, self.len_dec, dec_m, C, R, H, Ld["gn_eps"], out32=o32)
+            ff32 = r.ff32[:R * Ld["w1_32"].shape[0]].view(R, -1)
+            ops.retention_proj_step(a32, None, Ld["wqkvg32"], Ld["bqkvg"], r.q32, R)
+            self._ret(r, r.q32, kv, self.len_dec, dec_c, C, S * C, Ld["gn_eps"], out32=o32)
             ops.linear_res_ln_step_f32(o32, Ld["out1_w32"], Ld["out1_b"], a32, Ld["g11"], Ld["be11"], a32, Ld["eps11"])
-            ops.linear_step_f32(a32, Ld["in2_w32"], Ld["in2_b"], self.qkv32)
-            ops.spk_attn_step_f32(self.qkv32, o32, S, C)
+            ops.linear_step_f32(a32, Ld["in2_w32"], Ld["in2_b"], r.qkv32)
+            if n == 1:
+                ops.spk_attn_step_f32(r.qkv32, o32, S, C)
+            else:
+                ops.spk_attn_rows_f32(r.qkv32, o32, S, C, n)
             ops.linear_res_ln_step_f32(o32, Ld["out2_w32"], Ld["out2_b"], a32, Ld["g21"], Ld["be21"], a32, Ld["eps21"])
             ops.linear_step_f32(a32, Ld["w1_32"], Ld["b1"], ff32, act=ops.ACT_RELU)
             ops.linear_res_ln_step_f32(ff32, Ld["w2_32"], Ld["b2"], a32, Ld["g22"], Ld["be22"], a32, Ld["eps22"])
-        ops.counter_add_masked(self.len_dec, dec_m)
-        ops.head_l2dot(self.e32, a32, self.attr, self.logits, S, 1, 1, C, self.D)
+        advance(self.len_dec, dec_c)
+        ops.head_l2dot(r.e32, a32, r.attr, r.logits, S, n, n, C, self.D)

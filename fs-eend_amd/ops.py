@@ -807,6 +807,73 @@ def window_push_f32(win32, x32, mode_i32):
     _lib.check(L.eend_window_push_f32(_p(win32), _p(x32), _p(mode_i32), S, win32.shape[1] // D, D, _stream()), "eend_window_push_f32")
 
 
+def retention_chunk_ragged(qkvg32, kv_state, len_dev, cnt_dev, seq_per_slot, Nseq, H, nmax, gn_eps=1e-6, out16=None, out32=None):
+    """retention_step_ragged over a chunk: rows q*nmax + j of qkvg32 are frames j of sequence q, which belongs to slot
+    q // seq_per_slot; the slot takes cnt_dev[s] (0..nmax) frames at position len_dev[s].  The state is read and written once;
+    outputs and state are bit for bit those of cnt successive retention_step_ragged calls.  Rows beyond a slot's count are
+    zero.  The lengths are not advanced (counter_add_count)."""
+    L = _lib.load()
+    _chk(qkvg32, F32, "qkvg32"); _chk(kv_state, F32, "kv_state"); _chk(out16, F16, "out16"); _chk(out32, F32, "out32")
+    _chk(len_dev, torch.int32, "len_dev"); _chk(cnt_dev, torch.int32, "cnt_dev")
+    if out16 is None and out32 is None:
+        raise _lib.EendHipError("retention_chunk_ragged: out16 and / or out32")
+    if not 1 <= nmax <= 64:
+        raise _lib.EendHipError("retention_chunk_ragged: nmax must be in 1..64")
+    if seq_per_slot <= 0 or Nseq <= 0 or Nseq % seq_per_slot or len_dev.numel() < Nseq // seq_per_slot or cnt_dev.numel() < Nseq // seq_per_slot:
+        raise _lib.EendHipError("retention_chunk_ragged: one length and one count per slot of seq_per_slot sequences")
+    D, R = H * 64, Nseq * nmax
+    if (kv_state.numel() < Nseq * H * 64 * 64 or qkvg32.numel() < R * 4 * D or (out16 is not None and out16.numel() < R * D)
+            or (out32 is not None and out32.numel() < R * D)):
+        raise _lib.EendHipError("retention_chunk_ragged: shape mismatch")
+    _lib.check(L.eend_retention_chunk_ragged_f32(_p(qkvg32), _p(kv_state), _p(len_dev), _p(cnt_dev), seq_per_slot, nmax, _p(out16),
+                                                 _p(out32), Nseq, H, gn_eps, _stream()), "eend_retention_chunk_ragged_f32")
+
+
+def dwconv_chunk_ragged(x16, cache, len_dev, cnt_dev, w, bn, out16, nmax, eps=1e-5):
+    """dwconv_step_ragged over a chunk: x16 / out16 (B*nmax, D), slot b's frames are rows b*nmax + j, j < cnt_dev[b]; the cache
+    f32 (B, D, k-1) ends as after cnt one-frame calls (bit-identical, as are the outputs); rows beyond the count are zero."""
+    L = _lib.load()
+    _chk(x16, F16, "x16"); _chk(cache, F32, "cache"); _chk(w, F32, "w"); _chk(out16, F16, "out16")
+    _chk(len_dev, torch.int32, "len_dev"); _chk(cnt_dev, torch.int32, "cnt_dev")
+    for t in bn:
+        _chk(t, F32, "bn")
+    if not 1 <= nmax <= 64:
+        raise _lib.EendHipError("dwconv_chunk_ragged: nmax must be in 1..64")
+    B, D = cache.shape[0], cache.shape[1]
+    k = w.shape[1]
+    if (x16.shape != (B * nmax, D) or cache.shape != (B, D, k - 1) or out16.shape != (B * nmax, D) or w.shape[0] != D
+            or len_dev.numel() < B or cnt_dev.numel() < B or any(t.numel() < D for t in bn)):
+        raise _lib.EendHipError("dwconv_chunk_ragged: shape mismatch")
+    _lib.check(L.eend_dwconv_chunk_ragged_f16(_p(x16), _p(cache), _p(len_dev), _p(cnt_dev), nmax, _p(w), _p(bn[0]), _p(bn[1]), _p(bn[2]),
+                                              _p(bn[3]), eps, _p(out16), B, D, k, _stream()), "eend_dwconv_chunk_ragged_f16")
+
+
+def window_chunk_f32(win32, x32, cols32, npush_i32, ndummy_i32, ndec_i32, nmax):
+    """window_chunk on f32 windows (S, k*D): x32 (S*nmax, D), cols32 (S*nmax, k*D) the im2col rows of the emitting windows,
+    compacted to each slot's first rows; the stored window ends as after the same pushes and dummies through window_push_f32."""
+    L = _lib.load()
+    _chk(win32, F32, "win32"); _chk(x32, F32, "x32"); _chk(cols32, F32, "cols32")
+    for t in (npush_i32, ndummy_i32, ndec_i32):
+        _chk(t, torch.int32, "counts")
+    if not 1 <= nmax <= 64:
+        raise _lib.EendHipError("window_chunk_f32: nmax must be in 1..64")
+    S, D = win32.shape[0], x32.shape[1]
+    if (x32.shape[0] != S * nmax or win32.shape[1] % D or cols32.shape != (S * nmax, win32.shape[1])
+            or any(t.numel() < S for t in (npush_i32, ndummy_i32, ndec_i32))):
+        raise _lib.EendHipError("window_chunk_f32: shape mismatch")
+    _lib.check(L.eend_window_chunk_f32(_p(win32), _p(x32), _p(cols32), _p(npush_i32), _p(ndummy_i32), _p(ndec_i32), S, nmax,
+                                       win32.shape[1] // D, D, _stream()), "eend_window_chunk_f32")
+
+
+def spk_attn_rows_f32(qkv32, out32, B, C, Tp):
+    """spk_attn_step_f32 on decoder slabs: rows (b*C + c)*Tp + t; the C rows of frame (b, t) attend to each other."""
+    L = _lib.load()
+    _chk(qkv32, F32, "qkv32"); _chk(out32, F32, "out32")
+    if B <= 0 or Tp <= 0 or not 1 <= C <= 16 or qkv32.numel() < B * C * Tp * 768 or out32.numel() < B * C * Tp * 256:
+        raise _lib.EendHipError("spk_attn_rows_f32: shape mismatch")
+    _lib.check(L.eend_spk_attn_rows_f32(_p(qkv32), _p(out32), B, C, Tp, 1.0 / math.sqrt(64.0), _stream()), "eend_spk_attn_rows_f32")
+
+
 _PTR_TABLES = {}
 
 

@@ -502,6 +502,30 @@ int eend_dwconv_step_ragged_f16(const void* x_f16, float* cache, const int* len_
  * :151-186): mode_dev[s] == 1 shifts and appends x f32 [S][D] row s, == 2 shifts and appends zeros, anything else keeps it. */
 int eend_window_push_f32(float* win_f32, const float* x, const int* mode_dev, int S, int k, int D, void* stream);
 
+/* Many frames per slot in one LS-EEND multi-stream step (LsMultiStreamSession with max_frames = nmax; additive to ABI version 5).
+ * cnt_dev int32 [S]: the frames slot s takes in this launch (0..nmax; anything else counts as 0); its rows are the first
+ * cnt_dev[s] of its nmax rows, the others are written as zeros.  The lengths are not advanced (eend_counter_add_count_i32).
+ *
+ * eend_retention_chunk_ragged_f32: sequence q < Nseq (slot s = q / seq_per_slot: 1 for the encoder, C for the decoder) owns rows
+ * q*nmax .. q*nmax + nmax - 1 of qkvg_f32 [Nseq*nmax][4*H*64] and of out_f16 and / or out_f32 [Nseq*nmax][H*64]; its first
+ * cnt_dev[s] rows are frames len_dev[s] .. len_dev[s] + cnt - 1.  The state kv_state f32 [Nseq][H][64][64] is read once (not at
+ * all when len_dev[s] == 0) and written once; cnt == 0 leaves it unread and unwritten.  Outputs and final state are bit for bit
+ * those of cnt successive eend_retention_step_ragged_f32 calls (lengths advanced in between).  nmax in 1..64. */
+int eend_retention_chunk_ragged_f32(const float* qkvg_f32, float* kv_state, const int* len_dev, const int* cnt_dev, int seq_per_slot,
+                                    int nmax, void* out_f16, float* out_f32, int Nseq, int H, float gn_eps, void* stream);
+/* eend_dwconv_step_ragged_f16 over a chunk: x_f16 / out_f16 [B*nmax][D], slot b's frames are rows b*nmax + j, j < cnt_dev[b]; the
+ * cache f32 [B][D][k-1] ends as after cnt one-frame calls (bit-identical, outputs too).  nmax in 1..64. */
+int eend_dwconv_chunk_ragged_f16(const void* x_f16, float* cache, const int* len_dev, const int* cnt_dev, int nmax, const float* w,
+                                 const float* bn_weight, const float* bn_bias, const float* bn_mean, const float* bn_var, float eps,
+                                 void* out_f16, int B, int D, int k, void* stream);
+/* eend_window_chunk_f16 on the f32 window of eend_window_push_f32: win_f32 [S][k*D], x f32 [S*nmax][D], im2col rows cols_f32
+ * [S*nmax][k*D]; the stored window ends bit for bit as the same pushes and dummies through eend_window_push_f32.  nmax in 1..64. */
+int eend_window_chunk_f32(float* win_f32, const float* x, float* cols_f32, const int* npush_dev, const int* ndummy_dev, const int* ndec_dev,
+                          int S, int nmax, int k, int D, void* stream);
+/* eend_spk_attn_step_f32 on decoder slabs: qkv f32 [(b*C + c)*Tp + t][768], out_f32 [(b*C + c)*Tp + t][256]; the C rows of frame
+ * (b, t) attend to each other.  C <= 16; Tp = 1 is the layout of eend_spk_attn_step_f32. */
+int eend_spk_attn_rows_f32(const float* qkv, float* out_f32, int B, int C, int Tp, float scale, void* stream);
+
 /* One frame of MultiScaleRetention.recurrent_forward (retention.py:126-144, decay 1) + per-head
  * LayerNorm + swish gate, state updated in place.  qkvg f16 [N][4*H*64] = [q | k*dk^-0.5 | v | g];
  * kv_state f32 [N][H][64][64] in the reference's incremental_state["prev_key_value"] layout;
