@@ -647,18 +647,12 @@ int eend_retention_bwd_bf16(const void* Q, const void* Qt, const void* K, const 
     AttnBwdParams p;
     memset(&p, 0, sizeof(p));
     p.H = H; p.nseq = nseq; p.Tp = Tp; p.ldo = 256; p.ldg = ldq; p.L = L; p.nc = nc;
-    // chunk lengths up to 512: the one-launch backward and the row-major state kernel read no [d][t] copies (Qt / Kt / Vt / ott_ws may be NULL)
-    const bool row_major = eend_attn_bwd_fused_ok(p, true);
-    if (!row_major && (!Qt || !Kt || !Vt || !ott_ws)) return EEND_EINVAL;
+    // the envelope of the training forward (eend_retention_chunk_train_f16: L <= 512, L % 4 == 0) and nseq * nc <= 65535: the one-launch
+    // backward and the row-major state kernel, which read no [d][t] copies (Qt / Kt / Vt / ott_ws are not read and may be NULL)
+    if (!eend_attn_bwd_fused_ok(p, true)) return EEND_EINVAL;
     int rc = eend_launch_ret_gate_gn_bwd(dctx_f32, g_f16, ldg, rhat_f16, rc_in, (__bf16*)dqkvg_bf16 + 768, ldq, ot_ws, nseq, Tp, T_valid, st);
     if (rc != EEND_OK) return rc;
-    if (row_major) {
-        rc = eend_launch_ret_bwd_states_rm(K, V, Q, ot_ws, 256, kv_ws, g_ws, St_ws, nseq, H, Tp, L, nc, st);
-    } else {
-        rc = eend_launch_heads_transpose(ot_ws, 256, ott_ws, nseq, H, Tp, st);
-        if (rc != EEND_OK) return rc;
-        rc = eend_launch_ret_bwd_states(Kt, Vt, Qt, ott_ws, kv_ws, g_ws, St_ws, nseq, H, Tp, L, nc, st);
-    }
+    rc = eend_launch_ret_bwd_states_rm(K, V, Q, ot_ws, 256, kv_ws, g_ws, St_ws, nseq, H, Tp, L, nc, st);
     if (rc != EEND_OK) return rc;
     memset(&p, 0, sizeof(p));
     p.Q = Q; p.Qt = Qt; p.K = K; p.Kt = Kt; p.V = V; p.dO = ot_ws; p.dOt = ott_ws; p.dQKV = dqkvg_bf16;

@@ -29,10 +29,12 @@ constexpr int TILE = KB * 128;       // one [64][64] bf16 tile
 
 DEV int swap23(int r) { return (r & 0x13) | ((r & 4) << 1) | ((r & 8) >> 1); }
 
-// RET: the same two kernels for the LS-EEND retention core (retention.py:146-194 with the detached scales folded into
-// dO = o~ = c_t * d out_t): no softmax -- "dS" is the masked A = o~ V^T itself and "P" the masked S = Q K^T -- the
-// mask is block-diagonal causal over chunks of p.L frames, and the cross-chunk terms come from the 64x64 states of
-// ret_bwd_scan_kernel (retention_bwd.hip):  dQ += o~ Spre^T,  dK += R v,  dV += R^T k.
+// RET = true: NOT INSTANTIATED AND KNOWN WRONG.  It was the two-kernel form of the LS-EEND retention core's backward (dO = o~, no softmax,
+// block-diagonal causal mask over chunks of p.L frames, cross-chunk terms from the states of ret_bwd_scan_kernel).  The retention
+// backward runs in attn_bwd_fused.hip only (eend_launch_ret_bwd below refuses what that kernel does not serve); when this form was
+// last driven through eend_retention_bwd_bf16 (L = 6, 10, 516, 544, 1000) its dq was off by its whole norm, cause not found.  The
+// RET branches below are kept only because removing the parameter touches every line of the attention kernels; do not instantiate
+// them without tests/test_ret_edges.py-style checks.
 template <bool RET>
 __global__ __launch_bounds__(256, 2)
 void attn_bwd_dq_kernel(const AttnBwdParams p) {
@@ -442,24 +444,16 @@ int eend_launch_attn_bwd(const AttnBwdParams& p, hipStream_t stream) {
     return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
 }
 
-// Retention core backward (see the RET note above): p.dO = o~ (bf16 rows), p.dOt its head-transposed copy, p.St the
-// states of ret_bwd_scan_kernel, p.L / p.nc the chunking; only query / key tiles inside the nc * L valid frames run.
+// Retention core backward: p.dO = o~ (bf16 rows), p.St the states of ret_bwd_scan_kernel, p.L / p.nc the chunking (p.Qt / p.Kt / p.dOt
+// are not read).  Always the one-launch kernel of attn_bwd_fused.hip; the rows beyond the nc * L valid frames are zeroed there.
 int eend_launch_ret_bwd(const AttnBwdParams& p, hipStream_t stream) {
     if (!p.Q || !p.K || !p.V || !p.dO || !p.St || !p.dQKV) return EEND_EINVAL;
     if (p.nseq <= 0 || p.nseq > 65535 || p.H <= 0 || p.Tp <= 0 || (p.Tp % 64) || (p.ldo & 7) || (p.ldg & 3) || p.L <= 0 || p.nc <= 0 ||
         (long)p.nc * p.L > p.Tp || p.mask_delay != 0 || p.kv_len != p.nc * p.L || p.q_len != p.nc * p.L)
         return EEND_EINVAL;
-#ifndef EEND_ATTN_BWD_TWO_KERNELS
-    if (eend_attn_bwd_fused_ok(p, true)) return eend_launch_attn_bwd_fused(p, true, stream);
-#endif
-    if (!p.Qt || !p.Kt || !p.dOt) return EEND_EINVAL;   // the two-kernel form reads the [d][t] copies
-    // full-slab grids: the blocks beyond the nc * L valid frames only write the zero rows of dQKV
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<true>, dim3((p.Tp + 127) / 128, p.H, p.nseq), dim3(256), 0, stream, p);
-    if (hipGetLastError() != hipSuccess) return EEND_ELAUNCH;
-    static EendOncePerDevice attr_once;
-    if (!eend_set_dynamic_lds(attr_once, (const void*)attn_bwd_dkv_kernel<true>, 2 * DKV_STAGE)) return EEND_ELAUNCH;
-    hipLaunchKernelGGL(attn_bwd_dkv_kernel<true>, dim3((p.Tp + DKV_NW * 32 - 1) / (DKV_NW * 32), p.H, p.nseq), dim3(DKV_NW * 64), 2 * DKV_STAGE, stream, p);
-    return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
+    // one launch per (sequence, head, chunk) (attn_bwd_fused.hip); chunk lengths it does not serve are refused, as the training forward does
+    if (!eend_attn_bwd_fused_ok(p, true)) return EEND_EINVAL;
+    return eend_launch_attn_bwd_fused(p, true, stream);
 }
 
 int eend_launch_heads_transpose(const void* in, int ld, void* out, int nseq, int H, int Tp, hipStream_t stream) {

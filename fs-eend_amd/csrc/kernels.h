@@ -551,8 +551,6 @@ int eend_launch_attn_bwd(const AttnBwdParams& p, hipStream_t stream);
 bool eend_attn_bwd_fused_ok(const AttnBwdParams& p, bool ret);
 int eend_launch_attn_bwd_fused(const AttnBwdParams& p, bool ret, hipStream_t stream);
 int eend_launch_ret_bwd(const AttnBwdParams& p, hipStream_t stream);
-int eend_launch_ret_bwd_states(const void* Kt, const void* Vt, const void* Qt, const void* dOt, float* kv_ws, float* g_ws, void* St,
-                               int nseq, int H, int Tp, int L, int nc, hipStream_t stream);
 int eend_launch_heads_transpose(const void* in, int ld, void* out, int nseq, int H, int Tp, hipStream_t stream);
 int eend_launch_ret_bwd_states_rm(const void* K, const void* V, const void* Q, const void* dO, int ldo, float* kv_ws, float* g_ws, void* St,
                                   int nseq, int H, int Tp, int L, int nc, hipStream_t stream);

@@ -995,8 +995,9 @@ int eend_retention_chunk_train_f16(const void* Q, const void* K, const void* Kt,
  * intra-chunk on bf16 MFMA tiles, across chunks through 64x64 prefix / suffix states.  Q..Vt: bf16 head layouts of
  * eend_inproj_heads_train_bf16 (k rows pre-scaled by dk^-1/2); dqkvg bf16 [nseq*Tp][ldq]: dq | sk*dk | dv | dg at
  * columns 0 / 256 / 512 / 768.  ot_ws, ott_ws: bf16 scratch [nseq*Tp*256]; kv_ws, g_ws: f32 [nseq*H*nc*4096];
- * St_ws: bf16 [nseq*H*nc*6*4096].  Chunk lengths L <= 512 read only the row-major head layouts (Q, K, V; the transposed
- * fragments come out of the LDS reads): Qt, Kt, Vt and ott_ws may then be NULL, and eend_inproj_heads_train_bf16 need not write them. */
+ * St_ws: bf16 [nseq*H*nc*6*4096].  Envelope: that of eend_retention_chunk_train_f16 (L <= 512, L % 4 == 0) and nseq * nc <= 65535; anything
+ * else is EEND_EINVAL.  Only the row-major head layouts (Q, K, V) are read (the transposed fragments come out of the LDS reads): Qt, Kt,
+ * Vt and ott_ws are ignored and may be NULL, and eend_inproj_heads_train_bf16 need not write them. */
 int eend_retention_bwd_bf16(const void* Q, const void* Qt, const void* K, const void* Kt, const void* V, const void* Vt,
                             const float* dctx_f32, const void* g_f16, int ldg, const void* rhat_f16, const float* rc,
                             void* ot_ws, void* ott_ws, float* kv_ws, float* g_ws, void* St_ws, void* dqkvg_bf16, int ldq,
