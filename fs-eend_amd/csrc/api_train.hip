@@ -261,7 +261,7 @@ int eend_attn_causal_bwd_bf16(const void* Q, const void* Qt, const void* K, cons
     p.Q = Q; p.Qt = Qt; p.K = K; p.Kt = Kt; p.V = V; p.dO = dO; p.dOt = dOt_ws; p.Lse = lse; p.Dh = dh_ws; p.dQKV = dQKV;
     p.nseq = nseq; p.H = H; p.Tp = Tp; p.ldo = ldo; p.ldg = ldg; p.mask_delay = mask_delay; p.kv_len = kv_len; p.q_len = q_len;
     p.scale_log2 = scale_log2; p.sq = sq; p.sk = sk; p.drop = drop_spec(drop);
-    if (!eend_attn_bwd_fused_ok(p, false)) {              // windows beyond 512 frames: the two-kernel form reads dO^T (attn_bwd.hip)
+    if (!eend_attn_bwd_fused_ok(p, false)) {              // windows beyond 512 frames: the two kernels of attn_bwd.hip read dO^T
         rc = eend_launch_heads_transpose(dO, ldo, dOt_ws, nseq, H, Tp, (hipStream_t)stream);
         if (rc != EEND_OK) return rc;
     }
@@ -641,24 +641,22 @@ int eend_retention_bwd_bf16(const void* Q, const void* Qt, const void* K, const 
                             void* ot_ws, void* ott_ws, float* kv_ws, float* g_ws, void* St_ws, void* dqkvg_bf16, int ldq,
                             int nseq, int H, int Tp, int L, int T_valid, float sk, void* stream) {
     if (!Q || !K || !V || !dctx_f32 || !g_f16 || !rhat_f16 || !rc_in || !ot_ws || !kv_ws || !g_ws || !St_ws || !dqkvg_bf16) return EEND_EINVAL;
-    if (H != 4 || L <= 0 || T_valid <= 0 || T_valid > Tp || (T_valid % L) != 0 || ldq < 1024 || (ldq & 7)) return EEND_EINVAL;
+    if (H != 4 || L <= 0 || T_valid <= 0 || T_valid > Tp || (T_valid % L) != 0 || (Tp % 64) || ldq < 1024 || (ldq & 7)) return EEND_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const int nc = T_valid / L;
-    AttnBwdParams p;
+    AttnBwdParams p;                                      // Qt / Kt / Vt / ott_ws are not read (there is no [d][t] form) and may be NULL
     memset(&p, 0, sizeof(p));
-    p.H = H; p.nseq = nseq; p.Tp = Tp; p.ldo = 256; p.ldg = ldq; p.L = L; p.nc = nc;
-    // the envelope of the training forward (eend_retention_chunk_train_f16: L <= 512, L % 4 == 0) and nseq * nc <= 65535: the one-launch
-    // backward and the row-major state kernel, which read no [d][t] copies (Qt / Kt / Vt / ott_ws are not read and may be NULL)
+    p.Q = Q; p.K = K; p.V = V; p.dO = ot_ws; p.dQKV = dqkvg_bf16; p.St = St_ws;
+    p.nseq = nseq; p.H = H; p.Tp = Tp; p.ldo = 256; p.ldg = ldq; p.kv_len = T_valid; p.q_len = T_valid; p.L = L; p.nc = nc;
+    p.sq = 1.0f; p.sk = sk; p.drop = drop_spec(nullptr);
+    // the whole envelope before the first launch: that of the training forward (eend_retention_chunk_train_f16: L <= 512, L % 4 == 0)
+    // and nseq * nc <= 65535
     if (!eend_attn_bwd_fused_ok(p, true)) return EEND_EINVAL;
     int rc = eend_launch_ret_gate_gn_bwd(dctx_f32, g_f16, ldg, rhat_f16, rc_in, (__bf16*)dqkvg_bf16 + 768, ldq, ot_ws, nseq, Tp, T_valid, st);
     if (rc != EEND_OK) return rc;
     rc = eend_launch_ret_bwd_states_rm(K, V, Q, ot_ws, 256, kv_ws, g_ws, St_ws, nseq, H, Tp, L, nc, st);
     if (rc != EEND_OK) return rc;
-    memset(&p, 0, sizeof(p));
-    p.Q = Q; p.Qt = Qt; p.K = K; p.Kt = Kt; p.V = V; p.dO = ot_ws; p.dOt = ott_ws; p.dQKV = dqkvg_bf16;
-    p.nseq = nseq; p.H = H; p.Tp = Tp; p.ldo = 256; p.ldg = ldq; p.mask_delay = 0; p.kv_len = T_valid; p.q_len = T_valid;
-    p.scale_log2 = 0.f; p.sq = 1.0f; p.sk = sk; p.drop = drop_spec(nullptr); p.L = L; p.nc = nc; p.St = St_ws;
-    return eend_launch_ret_bwd(p, st);
+    return eend_launch_attn_bwd_fused(p, true, st);
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // Backward of the causal time-axis attention / of the retention core for windows of up to 512 frames, ONE launch, one 8-wave
-// workgroup per (sequence, head[, chunk]) (round 6; attn_bwd.hip stays as the form for longer windows).
+// workgroup per (sequence, head[, chunk]) (round 6; attn_bwd.hip stays as the attention's form for longer windows; the retention core has this form only).
 //
 //   S2 = (Q K^T) * scale_log2        P = 2^(S2 - L2)  (visible: key <= query + mask_delay, key < kv_len)
 //   dP = dO V^T (o keep * scale)     D_i = <dO_i, O_i>      dS = P o (dP - D)
@@ -409,7 +409,10 @@ bool eend_attn_bwd_fused_ok(const AttnBwdParams& p, bool ret) {
     return p.Tp <= FW && p.nseq <= 65535;
 }
 
+// ret: the retention core's backward -- p.dO = o~ (bf16 rows), p.St the states of ret_bwd_scan_kernel, p.L / p.nc the chunking; the rows
+// beyond the nc * L valid frames are zeroed.  This is the only launcher of the retention backward.
 int eend_launch_attn_bwd_fused(const AttnBwdParams& p, bool ret, hipStream_t stream) {
+    if (!p.Q || !p.K || !p.V || !p.dO || !p.dQKV || (ret ? !p.St : !p.Lse || !p.Dh)) return EEND_EINVAL;
     if (!eend_attn_bwd_fused_ok(p, ret)) return EEND_EINVAL;
     const dim3 grid(p.H, ret ? p.nseq * p.nc : p.nseq);
 #define FUSED_LAUNCH(R, D)                                                                                              \

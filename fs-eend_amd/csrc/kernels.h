@@ -528,12 +528,12 @@ int eend_launch_colsum_partial(const void* Y, int ld, long M, int N, int is_bf16
                                hipStream_t stream);
 int eend_launch_conv_wgrad_unpermute(const float* tmp, float* g, int cout, int cin, int ktaps, hipStream_t stream);
 
-struct AttnBwdParams {        // attn_bwd.hip
-    const void *Q, *Qt;       // bf16 [nseq][H][Tp][64] / [nseq][H][64][Tp]  (Q as the forward kernel saw it)
-    const void *K, *Kt;       // bf16, same two layouts
+struct AttnBwdParams {        // attn_bwd.hip (attention, Tp > 512), attn_bwd_fused.hip (attention up to 512 frames; retention)
+    const void *Q, *Qt;       // bf16 [nseq][H][Tp][64] / [nseq][H][64][Tp]  (Q as the forward kernel saw it); Qt: attn_bwd.hip only
+    const void *K, *Kt;       // bf16, same two layouts; Kt: attn_bwd.hip only
     const void* V;            // bf16 [nseq][H][Tp][64]
     const void* dO;           // bf16 [nseq*Tp][ldo], head h at columns h*64
-    const void* dOt;          // bf16 [nseq][H][64][Tp]
+    const void* dOt;          // bf16 [nseq][H][64][Tp]; attn_bwd.hip only
     const float* Lse;         // f32 [nseq][H][Tp] from the forward (log2 domain)
     const float* Dh;          // f32 [nseq][H][Tp]: <dO_i, O_i> per head
     void* dQKV;               // bf16 [nseq*Tp][ldg]: dQ at column h*64, dK at 256 + h*64, dV at 512 + h*64
@@ -542,15 +542,16 @@ struct AttnBwdParams {        // attn_bwd.hip
     float scale_log2;         // as the forward
     float sq, sk;             // output scales of dQ and dK
     DropSpec drop;            // the forward's probability dropout
-    // retention variant (eend_launch_ret_bwd): chunk length, number of valid chunks, states of ret_bwd_scan_kernel
+    // retention (eend_launch_attn_bwd_fused(p, true)): chunk length, number of valid chunks, states of ret_bwd_scan_kernel
     int L, nc;
     const void* St;           // bf16 [nseq][H][nc][6][64][64]: Spre hi/lo [kd][hd], R hi/lo [kd][hd], R^T hi/lo [hd][kd]
 };
+// causal-attention backward: the one-launch kernel where eend_attn_bwd_fused_ok, else the two kernels of attn_bwd.hip (which read Qt / Kt / dOt)
 int eend_launch_attn_bwd(const AttnBwdParams& p, hipStream_t stream);
-// attn_bwd_fused.hip: windows of up to 512 frames in one launch (Qt / Kt / dOt are not read); the launchers above dispatch to it
+// attn_bwd_fused.hip: windows of up to 512 frames in one launch (Qt / Kt / dOt are not read).  ret = false: attention, reached through
+// eend_launch_attn_bwd; ret = true: the retention core (dO = o~, chunks of p.L frames, p.St), which has no other form
 bool eend_attn_bwd_fused_ok(const AttnBwdParams& p, bool ret);
 int eend_launch_attn_bwd_fused(const AttnBwdParams& p, bool ret, hipStream_t stream);
-int eend_launch_ret_bwd(const AttnBwdParams& p, hipStream_t stream);
 int eend_launch_heads_transpose(const void* in, int ld, void* out, int nseq, int H, int Tp, hipStream_t stream);
 int eend_launch_ret_bwd_states_rm(const void* K, const void* V, const void* Q, const void* dO, int ldo, float* kv_ws, float* g_ws, void* St,
                                   int nseq, int H, int Tp, int L, int nc, hipStream_t stream);

@@ -7,7 +7,7 @@ Reference behaviour reproduced (paths relative to the reference root, LS-EEND/):
   * nnet/conformer/encoder.py:76-113   pre-norm residual blocks: x += 0.5 FFN(LN x); x += Ret(LN x); x += Conv(LN x);
     x += 0.5 FFN(LN x); LN
   * nnet/modules/retention.py:146-228  chunk-recurrent retention; `inner_scale` / `kv_scale` are detached (:163,:180), so
-    the backward is that of a linear attention with a constant per-row factor (csrc/attn_bwd.hip RET, retention_bwd.hip)
+    the backward is that of a linear attention with a constant per-row factor (csrc/attn_bwd_fused.hip RET, retention_bwd.hip)
   * nnet/modules/merge_retnet_layer.py:233-253  decoder layer: retention over time, MHA over speaker slots, ReLU FFN
   * train/oln_tfm_enc_dec_on_the_fly.py:52-92 training_step; train/utils/loss.py:136-142 standard_loss
   * train_dia_simu.py:97-117 Adam(betas (0.9, 0.98), eps 1e-9) x Noam; :159-173 gradient_clip_val, `sync_batchnorm`
@@ -54,11 +54,9 @@ class _RetSave:
     """Saved tensors of one retention module: bf16 head layouts for the backward products, gate pre-activation,
     normalised rows, per-(row, head) 1/sigma * detached scale, and the gated output (out_proj input)."""
 
-    def __init__(self, dev, nseq, Tp, L):
+    def __init__(self, dev, nseq, Tp):
         n = nseq * Tp * D
         self.q, self.k, self.v = (torch.empty(n, dtype=BF16, device=dev) for _ in range(3))
-        # [d][t] copies: only the two-kernel backward of chunk lengths beyond 512 reads them (attn_bwd.hip, retention_bwd.hip)
-        self.qt, self.kt, self.vt = ((torch.empty(n, dtype=BF16, device=dev) for _ in range(3)) if L > 512 else (None, None, None))
         self.g = torch.empty(nseq * Tp, D, dtype=F16, device=dev)
         self.rhat = torch.zeros(nseq * Tp, D, dtype=F16, device=dev)        # rows of skipped padding chunks stay zero
         self.rc = torch.zeros(nseq * Tp, H, dtype=F32, device=dev)
@@ -81,14 +79,14 @@ class _LsBuffers:
         for _ in range(n_enc):
             self.enc.append(dict(
                 lnA=_Site(dev, Me), za=e(Me, F_enc, dt=F16), aa=e(Me, F_enc, dt=F16),
-                lnB=_Site(dev, Me), ret=_RetSave(dev, B, Tp, L),
+                lnB=_Site(dev, Me), ret=_RetSave(dev, B, Tp),
                 lnC=_Site(dev, Me), P=e(Me, 2 * D, dt=F16), c16=e(Me, D, dt=F16), s16=e(Me, D, dt=F16),
                 bn_mean=e(D, dt=F32), bn_var=e(D, dt=F32), bn_n=e(1, dt=F32),
                 lnD=_Site(dev, Me), zb=e(Me, F_enc, dt=F16), ab=e(Me, F_enc, dt=F16),
                 lnE=_Site(dev, Me)))
         self.emb32, self.emb16, self.inv_norm = e(Me, D, dt=F32), e(Me, D, dt=F16), e(Me, dt=F32)
         self.a32, self.a16 = e(Md, D, dt=F32), e(Md, D, dt=F16)
-        self.dec = [dict(ret=_RetSave(dev, B * C, Tp, L), s11=_Site(dev, Md), qkv=e(Md, 3 * D, dt=F16), o2=e(Md, D, dt=F16),
+        self.dec = [dict(ret=_RetSave(dev, B * C, Tp), s11=_Site(dev, Md), qkv=e(Md, 3 * D, dt=F16), o2=e(Md, D, dt=F16),
                          s21=_Site(dev, Md), hid=e(Md, F_dec, dt=F16), s22=_Site(dev, Md)) for _ in range(n_dec)]
         # forward transients (f16 operands of the retention forward kernels)
         self.fq, self.fk, self.fkt, self.fvt = (e(Mx * D, dt=F16) for _ in range(4))
@@ -108,7 +106,6 @@ class _LsBuffers:
         self.dqkvg = e(Mx, 4 * D, dt=BF16)
         self.dqkv16 = e(Md, 3 * D, dt=BF16)
         self.ot = e(Mx * D, dt=BF16)
-        self.ott = e(Mx * D, dt=BF16) if L > 512 else None      # head-transposed o~: the two-kernel backward only
         self.g_ws = e(nseq_max * H * nc * 4096, dt=F32)
         self.st_bwd = e(nseq_max * H * nc * 6 * 4096, dt=BF16)
         self.bn_sums = e(2 * D, dt=F32)
@@ -131,7 +128,7 @@ class LsTrainStep(TrainStepBase):
         if not isinstance(model, OnlineConformerRetentionDADiarization):
             raise TypeError("LsTrainStep drives fs_eend_amd.ls_model.OnlineConformerRetentionDADiarization")
         self.L = int(model.recurrent_chunk_size)
-        if self.L > 512 or self.L % 4:
+        if 512 < self.L or self.L % 4:
             raise NotImplementedError("the training retention kernels keep a chunk on chip: recurrent_chunk_size <= 512, % 4 == 0")
         for name, buf in model.named_buffers():
             if name.endswith(".decay") and bool((buf != 0).any()):
@@ -243,15 +240,15 @@ class LsTrainStep(TrainStepBase):
         ws = self._proj_streams.get(wkey + ".wqkvg")
         groups = [dict(rows=q, kind=2, rows2=sv.q), dict(rows=k, kind=2, rows2=sv.k, heads_t=kt), dict(rows2=sv.v, heads_t=vt),
                   dict(rows=sv.g, kind=1, ld=D)]
-        if ws is not None and sv.qt is None and nseq * Tp >= self.proj_stream_min_rows and ops.proj_stream_ok(x16.stride(0), nseq * Tp, 4 * D, Tp, H, groups):
+        if ws is not None and nseq * Tp >= self.proj_stream_min_rows and ops.proj_stream_ok(x16.stride(0), nseq * Tp, 4 * D, Tp, H, groups):
             # one pass over the rows for the f16 operands of the forward kernel AND the bf16 head rows the backward keeps (proj_stream.hip:
             # [393216, 1024] 526 us against 803 us for the two projections below, [65536, 1024] 101 against 149 us; below about 48 k rows
             # the 256-row tiles leave CUs idle and the two launches win)
             ops.proj_stream(x16, ws, W[wkey + ".bqkvg"], nseq * Tp, 4 * D, Tp, H, groups)
         else:
             ops.retention_proj(x16, W[wkey + ".wqkvg"], W[wkey + ".bqkvg"], q, k, kt, vt, sv.g, nseq, Tp, H)
-            _call("eend_inproj_heads_train_bf16", x16, x16.stride(0), W[wkey + ".wqkvg"], W[wkey + ".bqkvg"], sv.q, sv.qt, sv.k, sv.kt,
-                  sv.v, sv.vt, nseq, Tp, H)
+            _call("eend_inproj_heads_train_bf16", x16, x16.stride(0), W[wkey + ".wqkvg"], W[wkey + ".bqkvg"], sv.q, None, sv.k, None,
+                  sv.v, None, nseq, Tp, H)
         _call("eend_retention_chunk_train_f16", q, k, kt, vt, sv.g, sv.ctx, sv.rhat, sv.rc, bf.st, bf.kv_ws, bf.cscale, bf.sexp, nseq, H,
               Tp, self.L, D, D, 1e-6, Tv)
 
@@ -418,7 +415,7 @@ class LsTrainStep(TrainStepBase):
         # the out-projection's data gradient stays f32: the per-head LayerNorm backward that consumes it cancels its two
         # largest components (mean and the component along rhat), which amplifies any rounding applied before it
         _call("eend_gemm_acc_bf16", ds16, D, W[wkey + ".woT" if wkey[0] == "e" else wkey + ".out1_wT"], D, None, 1.0, dctx, None, M, D)
-        _call("eend_retention_bwd_bf16", sv.q, sv.qt, sv.k, sv.kt, sv.v, sv.vt, dctx, sv.g, D, sv.rhat, sv.rc, bf.ot, bf.ott, bf.kv_ws,
+        _call("eend_retention_bwd_bf16", sv.q, None, sv.k, None, sv.v, None, dctx, sv.g, D, sv.rhat, sv.rc, bf.ot, None, bf.kv_ws,
               bf.g_ws, bf.st_bwd, dq, 4 * D, nseq, H, Tp, self.L, bf.Tv, 0.125)
         projs = ("q_proj", "k_proj", "v_proj", "g_proj")
         offw = [self.flat.offsets[pfx + nm + ".weight"] for nm in projs]
