@@ -316,9 +316,16 @@ int eend_conv1d_dgrad_bf16(const void* dY, const void* Wd, const int* src_lens, 
     return eend_launch_gemm(p, EPI_F32_ROWMASK, (hipStream_t)stream);
 }
 
+// host-only: the plan the entries below would take (the same plan_wgrad call); launches nothing, touches no device memory
+int eend_wgrad_plan(long M, int N, int K, int conv_cin, long ws_floats, int with_bias, int* tile, int* nsplit, long* m_per_split) {
+    if (!tile || !nsplit || !m_per_split || M <= 0 || N <= 0 || K <= 0 || (N % 128) || (K % 128) || conv_cin < 0) return EEND_EINVAL;
+    return plan_wgrad(M, N, K, conv_cin, ws_floats, tile, nsplit, m_per_split, with_bias != 0);
+}
+
 int eend_wgrad_bf16(const void* dY, int lda, const void* X, int ldb, int x_is_f16, long M, int N, int K, float* ws,
                     long ws_floats, float* out, int ld_out, int K_out, float scale, int accumulate, void* stream) {
     if (!dY || !X || !ws || !out || M <= 0 || N <= 0 || K <= 0 || (N % 128) || (K % 128)) return EEND_EINVAL;
+    if (K_out <= 0 || K_out > K || ld_out < K_out) return EEND_EINVAL;      // (before any launch: the reduction would refuse it after the main kernel ran)
     WgradParams p;
     memset(&p, 0, sizeof(p));
     p.A = dY; p.B = X; p.partial = ws; p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb;
@@ -333,6 +340,7 @@ int eend_wgrad_bf16(const void* dY, int lda, const void* X, int ldb, int x_is_f1
 int eend_wgrad_bias_bf16(const void* dY, int lda, const void* X, int ldb, int x_is_f16, long M, int N, int K, float* ws,
                          long ws_floats, float* out, int ld_out, int K_out, float* bias_out, float scale, int accumulate, void* stream) {
     if (!dY || !X || !ws || !out || !bias_out || M <= 0 || N <= 0 || K <= 0 || (N % 128) || (K % 128)) return EEND_EINVAL;
+    if (K_out <= 0 || K_out > K || ld_out < K_out) return EEND_EINVAL;
     WgradParams p;
     memset(&p, 0, sizeof(p));
     p.A = dY; p.B = X; p.partial = ws; p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb;

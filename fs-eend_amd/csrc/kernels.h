@@ -516,7 +516,12 @@ struct WgradParams {          // wgrad.hip: partial[s][n][k] = sum_{m in split s
     int tile;                 // output tile edge: 128 or 256 (N, K, conv_cin multiples of it)
     int b_is_f16;
     int a_blocked, b_blocked; // the operand is stored [M/16][ld/32][16 rows][32 features] (hid / dH of ffn_train_stream.hip; ld = its full row width)
-    // Conv1d weight gradient: B rows of k-tile (tap, c_in block) are read at frame t + tap - conv_pad (zero outside [0, ilen))
+                              // Contract: whole 16-row blocks are read.  The padding rows of the last block (rows >= M) must be finite; they
+                              // meet zero rows of the other operand, so `partial` does not depend on them (only one operand may be blocked
+                              // unless M % 16 == 0).  bias_partial sums A alone: with a_blocked it is the column sum of the M rows only if
+                              // those padding rows are zero or M % 16 == 0 (the trainer takes this path with M % 16 == 0 only).
+    // Conv1d weight gradient: B rows of k-tile (tap, c_in block) are read at frame t + tap - conv_pad (zero outside [0, ilen));
+    // ilens[seq] is trusted to lie in [0, Tp] (not validated on the device)
     int conv, conv_cin, conv_pad, Tp;
     const int* ilens;
 };

@@ -837,6 +837,11 @@ int eend_conv1d_dgrad_bf16(const void* dY, const void* Wd, const int* src_lens, 
  * eend_ffn_train_stream_f16's hid (ldb = its full width F); x_is_f16 & 4: dY is (eend_ffn_bwd_data_stream_bf16's dH, lda = F). */
 int eend_wgrad_bf16(const void* dY, int lda, const void* X, int ldb, int x_is_f16, long M, int N, int K, float* ws,
                     long ws_floats, float* out, int ld_out, int K_out, float scale, int accumulate, void* stream);
+/* Host-only query: the output tile (128 / 256), the number of token splits and the rows per split (a multiple of 64) that
+ * eend_wgrad_bf16 (with_bias = 0), eend_wgrad_bias[_grouped]_bf16 (with_bias = 1) and eend_conv1d_wgrad_bf16 (conv_cin = cin, N = 256,
+ * K = ktaps * cin, M = nseq * Tp; 0 otherwise) take for these arguments on the current device -- the entries call the same planner.
+ * Launches nothing and touches no device memory.  EEND_EINVAL where the entries refuse (N, K % 128, workspace under one split). */
+int eend_wgrad_plan(long M, int N, int K, int conv_cin, long ws_floats, int with_bias, int* tile, int* nsplit, long* m_per_split);
 /* eend_wgrad_bias_bf16 for N / group_rows linear layers that share the input X and whose (weight, bias) gradients sit equally spaced in
  * one buffer (the q / k / v / g projections of a retention module in the flat gradient buffer): rows g * group_rows .. of dY's N columns go
  * to out + g * group_stride (row stride K), their bias gradient to bias_out + g * group_stride.  One pass over X instead of N / group_rows,
@@ -845,10 +850,13 @@ int eend_wgrad_bias_grouped_bf16(const void* dY, int lda, const void* X, int ldb
                                  long ws_floats, float* out, float* bias_out, int group_rows, long group_stride, float scale, void* stream);
 /* The same with the bias gradient on the side: bias_out[n] = scale * sum_m dY[m][n] (+ bias_out if accumulate), accumulated
  * from the dY tiles the kernel stages anyway instead of by a separate pass over dY (eend_colsum_f32).  ws needs
- * nsplit * (N*K + N) floats. */
+ * nsplit * (N*K + N) floats.  A blocked dY (x_is_f16 & 4) is summed by whole 16-row blocks: bias_out is the column sum of the M rows
+ * only if the padding rows of the last block are zero (or M % 16 == 0, which is what the trainer requires); the weight gradient does
+ * not depend on them (they meet rows of X beyond M, which read as zero). */
 int eend_wgrad_bias_bf16(const void* dY, int lda, const void* X, int ldb, int x_is_f16, long M, int N, int K, float* ws,
                          long ws_floats, float* out, int ld_out, int K_out, float* bias_out, float scale, int accumulate, void* stream);
-/* Conv1d weight gradient into the parameter's own (c_out, c_in, k) layout; tmp: f32 [c_out][k*c_in] scratch. */
+/* Conv1d weight gradient into the parameter's own (c_out, c_in, k) layout; tmp: f32 [c_out][k*c_in] scratch.  X frames at or beyond
+ * ilens[seq] count as zero, every dY frame counts; Tp % 64 == 0.  ilens are trusted, not validated on the device: 0 <= ilens[seq] <= Tp. */
 int eend_conv1d_wgrad_bf16(const void* dY, const void* X_f16, const int* ilens, int nseq, int Tp, int cin, int ktaps,
                            int pad, float* ws, long ws_floats, float* tmp, float* out, void* stream);
 /* out[n] (+)= scale * sum_m Y[m][n]   (bias gradients); Y bf16 or f16 [M][ld]. */

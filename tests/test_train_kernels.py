@@ -10,6 +10,8 @@ import pytest
 import torch
 import torch.nn.functional as Fn
 
+from tests.wgrad_edge_ref import from_blocked as _from_blocked, to_blocked as _to_blocked      # the blocked layout of the stream entries
+
 pytestmark = pytest.mark.gpu
 
 F16, BF16, F32, I32 = torch.float16, torch.bfloat16, torch.float32, torch.int32
@@ -74,20 +76,6 @@ def _stream_of(T, dev, a, b, F):
     out = torch.empty(n, dtype=a.dtype, device=dev)
     T._call("eend_ffn_train_stream_pack", a, b, out, F)
     return out
-
-
-def _to_blocked(t, pad=0.0):
-    """row-major [M][F] -> the blocked layout of the stream entries, [ceil(M/16)*16][F] storage (padding rows = pad)."""
-    M, F = t.shape
-    Mp = (M + 15) // 16 * 16
-    tp = torch.full((Mp, F), pad, dtype=t.dtype, device=t.device)
-    tp[:M] = t
-    return tp.view(Mp // 16, 16, F // 32, 32).permute(0, 2, 1, 3).contiguous().view(Mp, F)
-
-
-def _from_blocked(tb, M):
-    Mp, F = tb.shape
-    return tb.view(Mp // 16, F // 32, 16, 32).permute(0, 2, 1, 3).contiguous().view(Mp, F)[:M]
 
 
 def _ffn_train_call(T, dev, impl, x, w1, b1, w2, b2, res, gm, be, o32, o16, hid, xh, rs, M, F, r1, r2):
