@@ -16,6 +16,7 @@ from types import SimpleNamespace
 import torch
 
 from . import ops
+from .fs_stream import dec_layers, enc_layers, front_end
 from .lib import EendHipError
 # the slot model lives in multistream.py; its names stay importable from here for existing callers
 from .multistream import DONE, FLUSHING, FREE, OPEN, MultiStreamSession, SlotError, SlotTable  # noqa: F401
@@ -68,21 +69,27 @@ class FsMultiStreamSession(MultiStreamSession):
         self.cap = 0
         self._alloc_caches(cap, keep=False)
 
-    def _alloc_rows(self, n, P):
-        """The rows of a step of Tp = n frames per slot: S*n encoder rows, S*C*n decoder rows."""
-        S, C, D, m = self.S, self.C, self.D, self.m
-        Fmax = max([l["w1"].shape[0] for l in P["enc"] + P["dec"]] + [1])
-        z = lambda *s_, dt=F16: torch.zeros(*s_, dtype=dt, device=self.dev)
-        N, R = S * n, S * C * n
-        r = SimpleNamespace(Tp=n)
-        r.x_in = z(S, n, m._in_size, dt=F32)
+    def _zeros(self, *shape, dt=F16):
+        return torch.zeros(*shape, dtype=dt, device=self.dev)
+
+    def _alloc_row_set(self, N, P, **own):
+        """What every row set holds: the scratch of N encoder rows and C*N decoder rows."""
+        D, R, z = self.D, self.C * N, self._zeros
+        r = SimpleNamespace(**own)
         r.xin16 = z(N, P["Fin_pad"])
         r.h32, r.h16 = z(N, D, dt=F32), z(N, D)                       # encoder rows; h32 is the window's input
+        r.conv32, r.e32, r.e16 = z(N, D, dt=F32), z(N, D, dt=F32), z(N, D)   # the Conv1d's output, its L2 norm
         r.a32, r.a16 = z(R, D, dt=F32), z(R, D)                       # decoder rows
-        r.qkv, r.o16, r.ff = z(R, 3 * D), z(R, D), z(R * Fmax)
-        r.cols = self.win16 if n == 1 else z(N, self.k * D)           # the Conv1d's rows: the windows, or the im2col rows of
-        r.conv32, r.e32, r.e16 = z(N, D, dt=F32), z(N, D, dt=F32), z(N, D)   # a chunk's emitting windows
-        r.attr = z(S, n, C, D, dt=F32)
+        r.qkv, r.o16, r.ff = z(R, 3 * D), z(R, D), z(R * P["Fmax"])
+        return r
+
+    def _alloc_rows(self, n, P):
+        """The rows of a step of Tp = n frames per slot: S*n encoder rows, S*C*n decoder rows."""
+        S, C, D, z = self.S, self.C, self.D, self._zeros
+        r = self._alloc_row_set(S * n, P, Tp=n)
+        r.x_in = z(S, n, self.m._in_size, dt=F32)
+        r.cols = self.win16 if n == 1 else z(S * n, self.k * D)       # the Conv1d's rows: the windows, or the im2col rows of
+        r.attr = z(S, n, C, D, dt=F32)                                # a chunk's emitting windows
         r.logits = z(S, n, C, dt=F32)
         r.ctl = z(3 if n == 1 else 4, S, dt=I32)                      # SlotPlan.modes() / counts()
         return r
@@ -122,84 +129,56 @@ class FsMultiStreamSession(MultiStreamSession):
         else:
             ops.attn_chunk_ragged(qkv, kc, vc, o16, r.ws, N, self.H, self.cap, r.Tp, per_slot, lens, cnt)
 
+    def _conv_l2(self, cols, conv32, e32, e16):
+        """Conv1d over the window rows `cols`, L2 norm (reference :42-50), and the f16 copy the decoder's fan-out reads."""
+        wr, bias = self.m.cnn._weights()[:2]
+        ops.linear_res_scale(cols, wr, bias, None, 1.0, conv32, None)
+        ops.l2norm_rows_f32(conv32, e32)
+        e16.copy_(e32)
+
     def _body(self, r):
+        """The frame procedure (fs_stream.enc_layers / dec_layers) with the ragged attention `_attn` over every slot's history."""
         P, S, C, D, n = self.m._prepare(), self.S, self.C, self.D, r.Tp
         enc_c, dec_c = r.ctl[0], r.ctl[-1]
         advance = ops.counter_add_masked if n == 1 else ops.counter_add_count
         # encoder, S*n rows (slot s: rows s*n .. s*n + enc[s] - 1 are its new frames)
         N = S * n
-        qkv, o16 = r.qkv[:N], r.o16[:N]
-        ops.bn_cast_pad(r.x_in, P["bn"], r.xin16, n, n, True, P["bn.eps"])
-        ops.linear_res_ln(r.xin16, P["in.w"], P["in.b"], None, P["in.g"], P["in.beta"], r.h32, r.h16, P["in.eps"])
-        for L, (kc, vc) in zip(P["enc"], self.enc_kv):
-            Fi = L["w1"].shape[0]
-            ff = r.ff[:N * Fi].view(N, Fi)
-            ops.linear(r.h16, L["att"][0], L["att"][1], qkv)
-            self._attn(r, qkv, kc, vc, o16, S, 1, self.len_enc, enc_c)
-            ops.linear_res_ln(o16, L["att"][2], L["att"][3], r.h32, L["n1"][0], L["n1"][1], r.h32, r.h16, L["n1"][2])
-            ops.linear(r.h16, L["w1"], L["b1"], ff, relu=True)
-            ops.linear_res_ln(ff, L["w2"], L["b2"], r.h32, L["n2"][0], L["n2"][1], r.h32, r.h16, L["n2"][2])
+        front_end(P, r.x_in, r.xin16, r.h32, r.h16, n)
+        enc_layers(P, r.h32, r.h16, r.qkv[:N], r.o16[:N], r.ff,
+                   lambda i, qkv, o16: self._attn(r, qkv, *self.enc_kv[i], o16, S, 1, self.len_enc, enc_c))
         advance(self.len_enc, enc_c)
-        # look-ahead window (reference :42-50): push / dummy / keep per slot, or a chunk's pushes then dummies into the
-        # im2col rows of its emitting windows; Conv1d, L2 norm
+        # look-ahead window: push / dummy / keep per slot, or a chunk's pushes then dummies into the im2col rows of its
+        # emitting windows
         if n == 1:
             ops.window_push(self.win16, r.h32, r.ctl[1])
         else:
             ops.window_chunk(self.win16, r.h32, r.cols, r.ctl[1], r.ctl[2], r.ctl[3], n)
-        wr, bias = self.m.cnn._weights()[:2]
-        ops.linear_res_scale(r.cols, wr, bias, None, 1.0, r.conv32, None)
-        ops.l2norm_rows_f32(r.conv32, r.e32)
-        r.e16.copy_(r.e32)
+        self._conv_l2(r.cols, r.conv32, r.e32, r.e16)
         # decoder, (B = S, C, Tp = n) slabs
-        R = S * C * n
-        qkv, o16 = r.qkv[:R], r.o16[:R]
         ops.convert_fanout(r.e16, P["convert.w1"], self.m._convert_const(C), r.a32, r.a16, S, n, C)
-        for L, (kc, vc) in zip(P["dec"], self.dec_kv):
-            Fi = L["w1"].shape[0]
-            ff = r.ff[:R * Fi].view(R, Fi)
-            ops.linear(r.a16, L["att"][0], L["att"][1], qkv)
-            self._attn(r, qkv, kc, vc, o16, S * C, C, self.len_dec, dec_c)
-            ops.linear_res_ln(o16, L["att"][2], L["att"][3], r.a32, L["n1"][0], L["n1"][1], r.a32, r.a16, L["n1"][2])
-            ops.linear(r.a16, L["spk"][0], L["spk"][1], qkv)
-            ops.spk_attn(qkv, o16, S, C, n, self.H)
-            ops.linear_res_ln(o16, L["spk"][2], L["spk"][3], r.a32, L["n2"][0], L["n2"][1], r.a32, r.a16, L["n2"][2])
-            ops.linear(r.a16, L["w1"], L["b1"], ff, relu=True)
-            ops.linear_res_ln(ff, L["w2"], L["b2"], r.a32, L["n3"][0], L["n3"][1], r.a32, r.a16, L["n3"][2])
+        dec_layers(P, r.a32, r.a16, r.qkv, r.o16, r.ff,
+                   lambda i, qkv, o16: self._attn(r, qkv, *self.dec_kv[i], o16, S * C, C, self.len_dec, dec_c), S, C, n, self.H)
         advance(self.len_dec, dec_c)
         ops.head_l2dot(r.e32, r.a32, r.attr, r.logits, S, n, n, C, D)
 
     # ---- prefill: one slot taken forward by a backlog of any length (eager, no graph)
     def _alloc_prefill(self, P):
         """The rows of one prefill piece: prefill_rows encoder rows (after the k window taps in z), C * prefill_rows decoder rows."""
-        n, C, D, m = self.prefill_rows, self.C, self.D, self.m
-        Fmax = max([l["w1"].shape[0] for l in P["enc"] + P["dec"]] + [1])
-        z = lambda *s_, dt=F16: torch.zeros(*s_, dtype=dt, device=self.dev)
-        r = SimpleNamespace()
-        r.xin16 = z(n, P["Fin_pad"])
-        r.h32, r.h16 = z(n, D, dt=F32), z(n, D)
+        n, C, D, z = self.prefill_rows, self.C, self.D, self._zeros
+        r = self._alloc_row_set(n, P)
         r.z = z(self.k + n, D)                                        # the slot's k stored taps, then the piece's encoder rows
-        r.conv32, r.e32, r.e16 = z(n, D, dt=F32), z(n, D, dt=F32), z(n, D)
-        r.a32, r.a16 = z(C * n, D, dt=F32), z(C * n, D)
-        r.qkv, r.o16, r.ff = z(C * n, 3 * D), z(C * n, D), z(C * n * Fmax)
         r.attr, r.logits = z(n * C * D, dt=F32), z(n * C, dt=F32)
         return r
 
     def _prefill_piece(self, r, s, x, t_enc, t_dec, ne):
         """Slot s takes the N frames x (1, N, in) f32 at encoder history t_enc; the last ne of the N windows emit, at decoder
-        history t_dec.  -> logits (1, ne, C), a view of the row set.  The body of `_body` with B = 1, the prefill attention over
+        history t_dec.  -> logits (1, ne, C), a view of the row set.  The frame procedure with B = 1, the prefill attention over
         the slot's own cache sequences and the Conv1d reading the emitting windows as overlapping rows of z."""
         P, C, D, k, N = self.m._prepare(), self.C, self.D, self.k, x.shape[1]
-        qkv, o16, h32, h16 = r.qkv[:N], r.o16[:N], r.h32[:N], r.h16[:N]
-        ops.bn_cast_pad(x, P["bn"], r.xin16[:N], N, N, True, P["bn.eps"])
-        ops.linear_res_ln(r.xin16[:N], P["in.w"], P["in.b"], None, P["in.g"], P["in.beta"], h32, h16, P["in.eps"])
-        for L, (kc, vc) in zip(P["enc"], self.enc_kv):
-            Fi = L["w1"].shape[0]
-            ff = r.ff[:N * Fi].view(N, Fi)
-            ops.linear(h16, L["att"][0], L["att"][1], qkv)
-            ops.attn_prefill(qkv, kc, vc, o16, s, 1, self.H, t_enc, N)
-            ops.linear_res_ln(o16, L["att"][2], L["att"][3], h32, L["n1"][0], L["n1"][1], h32, h16, L["n1"][2])
-            ops.linear(h16, L["w1"], L["b1"], ff, relu=True)
-            ops.linear_res_ln(ff, L["w2"], L["b2"], h32, L["n2"][0], L["n2"][1], h32, h16, L["n2"][2])
+        h32, h16 = r.h32[:N], r.h16[:N]
+        front_end(P, x, r.xin16[:N], h32, h16, N)
+        enc_layers(P, h32, h16, r.qkv[:N], r.o16[:N], r.ff,
+                   lambda i, qkv, o16: ops.attn_prefill(qkv, *self.enc_kv[i], o16, s, 1, self.H, t_enc, N))
         # look-ahead window: z = the stored taps, then the new frames; the window after push m is z[m .. m + k - 1]
         r.z[:k].copy_(self.win16[s].view(k, D))
         r.z[k:k + N].copy_(h32)
@@ -207,25 +186,13 @@ class FsMultiStreamSession(MultiStreamSession):
         if not ne:
             return r.logits[:0].view(1, 0, C)
         cols = r.z.as_strided((ne, k * D), (D, 1), r.z.storage_offset() + (N - ne + 1) * D)
-        conv32, e32, e16 = r.conv32[:ne], r.e32[:ne], r.e16[:ne]
-        wr, bias = self.m.cnn._weights()[:2]
-        ops.linear_res_scale(cols, wr, bias, None, 1.0, conv32, None)
-        ops.l2norm_rows_f32(conv32, e32)
-        e16.copy_(e32)
+        e32, e16 = r.e32[:ne], r.e16[:ne]
+        self._conv_l2(cols, r.conv32[:ne], e32, e16)
         R = C * ne
-        qkv, o16, a32, a16 = r.qkv[:R], r.o16[:R], r.a32[:R], r.a16[:R]
+        a32, a16 = r.a32[:R], r.a16[:R]
         ops.convert_fanout(e16, P["convert.w1"], self.m._convert_const(C), a32, a16, 1, ne, C)
-        for L, (kc, vc) in zip(P["dec"], self.dec_kv):
-            Fi = L["w1"].shape[0]
-            ff = r.ff[:R * Fi].view(R, Fi)
-            ops.linear(a16, L["att"][0], L["att"][1], qkv)
-            ops.attn_prefill(qkv, kc, vc, o16, s * C, C, self.H, t_dec, ne)
-            ops.linear_res_ln(o16, L["att"][2], L["att"][3], a32, L["n1"][0], L["n1"][1], a32, a16, L["n1"][2])
-            ops.linear(a16, L["spk"][0], L["spk"][1], qkv)
-            ops.spk_attn(qkv, o16, 1, C, ne, self.H)
-            ops.linear_res_ln(o16, L["spk"][2], L["spk"][3], a32, L["n2"][0], L["n2"][1], a32, a16, L["n2"][2])
-            ops.linear(a16, L["w1"], L["b1"], ff, relu=True)
-            ops.linear_res_ln(ff, L["w2"], L["b2"], a32, L["n3"][0], L["n3"][1], a32, a16, L["n3"][2])
+        dec_layers(P, a32, a16, r.qkv[:R], r.o16[:R], r.ff,
+                   lambda i, qkv, o16: ops.attn_prefill(qkv, *self.dec_kv[i], o16, s * C, C, self.H, t_dec, ne), 1, C, ne, self.H)
         logits = r.logits[:ne * C].view(1, ne, C)
         ops.head_l2dot(e32, a32, r.attr[:ne * C * D].view(1, ne, C, D), logits, 1, ne, ne, C, D)
         return logits

@@ -101,6 +101,54 @@ class _KvCache:
                 setattr(self, name, new)
             self.cap *= 2
 
+    def decode(self, qkv, o16):
+        """The eager model's attention callback: append this frame's K/V, attend over the history."""
+        self.ensure_room()
+        ops.attn_decode(qkv, self.k, self.v, o16, self.N, self.H, self.cap, self.t)
+        self.t += 1
+
+
+# ---------------------------------------------------------------------------------------------
+# the frame procedure of every streaming entry point (FS-EEND/streaming_infer_dia.py:77-95): `test`, FsStreamSession and
+# FsMultiStreamSession's step and prefill.  P is `_prepare()`'s operand dict; x32 / x16 are the N-row f32 residual stream and
+# its f16 copy, updated in place; qkv / o16 are N-row scratch, ff flat scratch of N * P["Fmax"] elements.
+# attn(i, qkv, o16) is the caller's cached attention of layer i: the rows' K/V appended, their context written to o16.
+# ---------------------------------------------------------------------------------------------
+def front_end(P, x, xin16, h32, h16, T):
+    """BatchNorm + cast + pad of x (sequences of T frames), input projection + LayerNorm -> the encoder's rows h32 / h16."""
+    ops.bn_cast_pad(x, P["bn"], xin16, T, T, True, P["bn.eps"])
+    ops.linear_res_ln(xin16, P["in.w"], P["in.b"], None, P["in.g"], P["in.beta"], h32, h16, P["in.eps"])
+
+
+def enc_layers(P, x32, x16, qkv, o16, ff, attn):
+    """The incremental encoder layers: in-projection, cached attention, out-projection + LN, FFN + LN."""
+    N = x32.shape[0]
+    for i, L in enumerate(P["enc"]):
+        Fi = L["w1"].shape[0]
+        f = ff[:N * Fi].view(N, Fi)
+        ops.linear(x16, L["att"][0], L["att"][1], qkv)
+        attn(i, qkv, o16)
+        ops.linear_res_ln(o16, L["att"][2], L["att"][3], x32, L["n1"][0], L["n1"][1], x32, x16, L["n1"][2])
+        ops.linear(x16, L["w1"], L["b1"], f, relu=True)
+        ops.linear_res_ln(f, L["w2"], L["b2"], x32, L["n2"][0], L["n2"][1], x32, x16, L["n2"][2])
+
+
+def dec_layers(P, x32, x16, qkv, o16, ff, attn, B, C, n, H):
+    """The incremental decoder layers on (B, C, n) slabs of attractor rows: the encoder layer's time-axis block, then
+    attention along the speaker axis + LN, then FFN + LN."""
+    N = x32.shape[0]
+    for i, L in enumerate(P["dec"]):
+        Fi = L["w1"].shape[0]
+        f = ff[:N * Fi].view(N, Fi)
+        ops.linear(x16, L["att"][0], L["att"][1], qkv)
+        attn(i, qkv, o16)
+        ops.linear_res_ln(o16, L["att"][2], L["att"][3], x32, L["n1"][0], L["n1"][1], x32, x16, L["n1"][2])
+        ops.linear(x16, L["spk"][0], L["spk"][1], qkv)
+        ops.spk_attn(qkv, o16, B, C, n, H)
+        ops.linear_res_ln(o16, L["spk"][2], L["spk"][3], x32, L["n2"][0], L["n2"][1], x32, x16, L["n2"][2])
+        ops.linear(x16, L["w1"], L["b1"], f, relu=True)
+        ops.linear_res_ln(f, L["w2"], L["b2"], x32, L["n3"][0], L["n3"][1], x32, x16, L["n3"][2])
+
 
 class StreamingTransformerEDADiarization(nn.Module):
     """reference FS-EEND/nnet/model/streaming_tfm_enc_...l2norm.py:9-60."""
@@ -167,6 +215,7 @@ class StreamingTransformerEDADiarization(nn.Module):
         P["dec"] = [dict(att=mha(l.temp_attn.attention), spk=mha(l.spk_attn), w1=_f16(l.linear1.weight),
                          b1=_f32(l.linear1.bias), w2=_f16(l.linear2.weight), b2=_f32(l.linear2.bias),
                          n1=ln(l.norm1), n2=ln(l.norm2), n3=ln(l.norm3)) for l in self.dec.layers]
+        P["Fmax"] = max([l["w1"].shape[0] for l in P["enc"] + P["dec"]] + [1])     # the widest FFN: sizes the ff scratch
         self._prep, self._prep_key, self._pc = P, key, {}
         return P
 
@@ -208,8 +257,7 @@ class StreamingTransformerEDADiarization(nn.Module):
         P = self._prepare()
         dev = self.cnn.conv.weight.device
         D, H, C = self.n_units, self._H, max_nspks
-        Fmax = max([l["w1"].shape[0] for l in P["enc"] + P["dec"]] + [1])
-        sc = self._scratch(max(1, C), dev, Fmax)
+        sc = self._scratch(max(1, C), dev, P["Fmax"])
         if dummy_conv_input:
             emb_t = torch.zeros(1, 1, D, device=dev)                         # reference :42-43
         else:
@@ -218,20 +266,9 @@ class StreamingTransformerEDADiarization(nn.Module):
             if self._enc_kv is None:
                 self._enc_kv = [_KvCache(1, H, dev) for _ in P["enc"]]
             x = x_t.to(device=dev, dtype=F32).reshape(1, 1, -1).contiguous()
-            xin16, h32, h16 = sc["xin16"][:1], sc["h32"][:1], sc["h16"][:1]
-            qkv, o16 = sc["qkv"][:1], sc["o16"][:1]
-            ops.bn_cast_pad(x, P["bn"], xin16, 1, 1, True, P["bn.eps"])
-            ops.linear_res_ln(xin16, P["in.w"], P["in.b"], None, P["in.g"], P["in.beta"], h32, h16, P["in.eps"])
-            for L, kv in zip(P["enc"], self._enc_kv):
-                Fi = L["w1"].shape[0]
-                ff = sc["ff"][:Fi].view(1, Fi)
-                kv.ensure_room()
-                ops.linear(h16, L["att"][0], L["att"][1], qkv)
-                ops.attn_decode(qkv, kv.k, kv.v, o16, 1, H, kv.cap, kv.t)
-                kv.t += 1
-                ops.linear_res_ln(o16, L["att"][2], L["att"][3], h32, L["n1"][0], L["n1"][1], h32, h16, L["n1"][2])
-                ops.linear(h16, L["w1"], L["b1"], ff, relu=True)
-                ops.linear_res_ln(ff, L["w2"], L["b2"], h32, L["n2"][0], L["n2"][1], h32, h16, L["n2"][2])
+            h32, h16 = sc["h32"][:1], sc["h16"][:1]
+            front_end(P, x, sc["xin16"][:1], h32, h16, 1)
+            enc_layers(P, h32, h16, sc["qkv"][:1], sc["o16"][:1], sc["ff"], lambda i, qkv, o16: self._enc_kv[i].decode(qkv, o16))
             emb_t = h32.view(1, 1, D).clone()
 
         emb_t = self.cnn(emb_t.transpose(1, 2))                              # (1,D,1) or None
@@ -243,21 +280,8 @@ class StreamingTransformerEDADiarization(nn.Module):
         if self._dec_kv is None or self._dec_kv[0].N != C:
             self._dec_kv = [_KvCache(C, H, dev) for _ in P["dec"]]
         a32, a16 = sc["a32"][:C], sc["a16"][:C]
-        qkv, o16 = sc["qkv"][:C], sc["o16"][:C]
         ops.convert_fanout(e32.to(F16), P["convert.w1"], self._convert_const(C), a32, a16, 1, 1, C)
-        for L, kv in zip(P["dec"], self._dec_kv):
-            Fi = L["w1"].shape[0]
-            ff = sc["ff"][:C * Fi].view(C, Fi)
-            kv.ensure_room()
-            ops.linear(a16, L["att"][0], L["att"][1], qkv)
-            ops.attn_decode(qkv, kv.k, kv.v, o16, C, H, kv.cap, kv.t)
-            kv.t += 1
-            ops.linear_res_ln(o16, L["att"][2], L["att"][3], a32, L["n1"][0], L["n1"][1], a32, a16, L["n1"][2])
-            ops.linear(a16, L["spk"][0], L["spk"][1], qkv)
-            ops.spk_attn(qkv, o16, 1, C, 1, H)
-            ops.linear_res_ln(o16, L["spk"][2], L["spk"][3], a32, L["n2"][0], L["n2"][1], a32, a16, L["n2"][2])
-            ops.linear(a16, L["w1"], L["b1"], ff, relu=True)
-            ops.linear_res_ln(ff, L["w2"], L["b2"], a32, L["n3"][0], L["n3"][1], a32, a16, L["n3"][2])
+        dec_layers(P, a32, a16, sc["qkv"][:C], sc["o16"][:C], sc["ff"], lambda i, qkv, o16: self._dec_kv[i].decode(qkv, o16), 1, C, 1, H)
         attr = torch.empty(1, 1, C, D, dtype=F32, device=dev)
         y = torch.empty(1, 1, C, dtype=F32, device=dev)
         ops.head_l2dot(e32, a32, attr, y, 1, 1, 1, C, D)
@@ -286,13 +310,12 @@ class FsStreamSession:
         D, H, C = self.D, self.H, max_nspks
         self.k = model.cnn.kernel_size
         self.center = model.cnn.center
-        self.Fmax = max([l["w1"].shape[0] for l in P["enc"] + P["dec"]] + [1])
         e = lambda *s_, dt=F16: torch.zeros(*s_, dtype=dt, device=dev)
         N = max(1, C)
         self.x_in = e(1, 1, model._in_size, dt=F32)
         self.xin16 = e(1, P["Fin_pad"])
         self.h32, self.h16 = e(N, D, dt=F32), e(N, D)
-        self.qkv, self.o16, self.ff = e(N, 3 * D), e(N, D), e(N * self.Fmax)
+        self.qkv, self.o16, self.ff = e(N, 3 * D), e(N, D), e(N * P["Fmax"])
         self.enc_out = e(1, D, dt=F32)
         self.win16 = e(1, self.k * D)                                   # [tap*D + c]: the look-ahead window, oldest tap first
         self._shift = e(1, (self.k - 1) * D)
@@ -331,18 +354,12 @@ class FsStreamSession:
 
     # ---- the three stages (eager bodies; captured once per cache capacity)
     def _enc(self):
-        P, H = self.m._prepare(), self.H
-        h32, h16, qkv, o16 = self.h32[:1], self.h16[:1], self.qkv[:1], self.o16[:1]
-        ops.bn_cast_pad(self.x_in, P["bn"], self.xin16, 1, 1, True, P["bn.eps"])
-        ops.linear_res_ln(self.xin16, P["in.w"], P["in.b"], None, P["in.g"], P["in.beta"], h32, h16, P["in.eps"])
-        for L, (kc, vc) in zip(P["enc"], self.enc_kv):
-            Fi = L["w1"].shape[0]
-            ff = self.ff[:Fi].view(1, Fi)
-            ops.linear(h16, L["att"][0], L["att"][1], qkv)
-            self._decode(qkv, kc, vc, o16, 1, self.t_enc)
-            ops.linear_res_ln(o16, L["att"][2], L["att"][3], h32, L["n1"][0], L["n1"][1], h32, h16, L["n1"][2])
-            ops.linear(h16, L["w1"], L["b1"], ff, relu=True)
-            ops.linear_res_ln(ff, L["w2"], L["b2"], h32, L["n2"][0], L["n2"][1], h32, h16, L["n2"][2])
+        """Encoder stage: the cached attention is `_decode` on the encoder caches at t_enc."""
+        P = self.m._prepare()
+        h32, h16 = self.h32[:1], self.h16[:1]
+        front_end(P, self.x_in, self.xin16, h32, h16, 1)
+        enc_layers(P, h32, h16, self.qkv[:1], self.o16[:1], self.ff,
+                   lambda i, qkv, o16: self._decode(qkv, *self.enc_kv[i], o16, 1, self.t_enc))
         ops.counter_add(self.t_enc, 1)
         self.enc_out.copy_(h32)
 
@@ -363,22 +380,14 @@ class FsStreamSession:
         self.e16.copy_(self.e32)
 
     def _dec(self):
-        P, H, C, D = self.m._prepare(), self.H, self.C, self.D
-        a32, a16, qkv, o16 = self.h32[:C], self.h16[:C], self.qkv[:C], self.o16[:C]
+        """Decoder stage, on the first C rows of the encoder's buffers: `_decode` on the decoder caches at t_dec."""
+        P, C = self.m._prepare(), self.C
+        a32, a16 = self.h32[:C], self.h16[:C]
         ops.convert_fanout(self.e16, P["convert.w1"], self.m._convert_const(C), a32, a16, 1, 1, C)
-        for L, (kc, vc) in zip(P["dec"], self.dec_kv):
-            Fi = L["w1"].shape[0]
-            ff = self.ff[:C * Fi].view(C, Fi)
-            ops.linear(a16, L["att"][0], L["att"][1], qkv)
-            self._decode(qkv, kc, vc, o16, C, self.t_dec)
-            ops.linear_res_ln(o16, L["att"][2], L["att"][3], a32, L["n1"][0], L["n1"][1], a32, a16, L["n1"][2])
-            ops.linear(a16, L["spk"][0], L["spk"][1], qkv)
-            ops.spk_attn(qkv, o16, 1, C, 1, H)
-            ops.linear_res_ln(o16, L["spk"][2], L["spk"][3], a32, L["n2"][0], L["n2"][1], a32, a16, L["n2"][2])
-            ops.linear(a16, L["w1"], L["b1"], ff, relu=True)
-            ops.linear_res_ln(ff, L["w2"], L["b2"], a32, L["n3"][0], L["n3"][1], a32, a16, L["n3"][2])
+        dec_layers(P, a32, a16, self.qkv[:C], self.o16[:C], self.ff,
+                   lambda i, qkv, o16: self._decode(qkv, *self.dec_kv[i], o16, C, self.t_dec), 1, C, 1, self.H)
         ops.counter_add(self.t_dec, 1)
-        ops.head_l2dot(self.e32, a32, self.attr, self.logits, 1, 1, 1, C, D)
+        ops.head_l2dot(self.e32, a32, self.attr, self.logits, 1, 1, 1, C, self.D)
 
     def _capture(self):
         keep = [t_.clone() for t_ in (self.t_enc, self.t_dec, self.win16, self.enc_out, self.x_in)]

@@ -3,9 +3,9 @@ advanced by one graph replay per frame.
 
 `LsStreamSession(batch=S)` (ls_stream.py) runs S streams in lockstep: one retention scale for the whole batch, one reset for
 all.  Here every buffer has S rows on the encoder side and S*C on the decoder side, every stage computes all rows every frame
-with the all-f32 frame step of `ls_stream.enc_step` / `dec_step`, and the three state touches of that step take their stream
-position from per-slot int32 lengths in device memory: the retention recurrence (`ops.retention_step_ragged`, scale = the
-slot's own frame count), the Conformer depthwise-conv cache (`ops.dwconv_step_ragged`) and the f32 look-ahead window
+with the all-f32 frame step of ls_stream.py (`enc_step` / `dec_step` run it too), and the three state touches of that step take
+their stream position from per-slot int32 lengths in device memory: the retention recurrence (`ops.retention_step_ragged`,
+scale = the slot's own frame count), the Conformer depthwise-conv cache (`ops.dwconv_step_ragged`) and the f32 look-ahead window
 (`ops.window_push_f32`).  A per-slot mode vector, written with one copy before each replay, decides which state changes.
 LS state is O(1) per stream, so one capture serves the whole session (again only when the weights are refreshed).
 
@@ -18,6 +18,7 @@ import torch
 
 from . import ops
 from .lib import EendHipError
+from .ls_stream import f32_blocks, f32_dec_layers, f32_input
 from .multistream import MultiStreamSession
 
 F16, F32, I32 = torch.float16, torch.float32, torch.int32
@@ -104,68 +105,37 @@ class LsMultiStreamSession(MultiStreamSession):
             ops.retention_chunk_ragged(q32, kv, lens, ctl, per_slot, Nseq, self.H, r.Tp, eps, out16=out16, out32=out32)
 
     def _body(self, r):
-        P, H, S, C, n = self.m._prepare(), self.H, self.S, self.C, r.Tp
+        """ls_stream's all-f32 frame step with the retention state, conv cache and look-ahead window per slot."""
+        P, S, C, n = self.m._prepare(), self.S, self.C, r.Tp
         enc_c, dec_c = r.ctl[0], r.ctl[-1]                            # modes at Tp = 1, frame counts above
         advance = ops.counter_add_masked if n == 1 else ops.counter_add_count
-        # encoder, S*n rows (slot s: rows s*n .. s*n + enc[s] - 1 are its new frames): ls_stream.enc_step's all-f32 form, the
-        # retention state and conv cache per slot
+        # encoder, S*n rows (slot s: rows s*n .. s*n + enc[s] - 1 are its new frames)
         N = S * n
-        h32, h16, x16, xn32 = r.h32, r.h16, r.x16, r.xn32
-        r.xin32[:, :self.m._in_size].copy_(r.x_in.view(N, -1))
-        ops.linear_res_ln_step_f32(r.xin32, P["in.w32"], P["in.b"], None, P["in.g"], P["in.beta"], h32, P["in.eps"], out16=h16)
-        nb = len(P["blocks"])
-        q32 = r.q32[:N]
-        for i, (Bk, kv, cache) in enumerate(zip(P["blocks"], self.enc_kv, self.caches)):
-            ff32 = r.ff32[:N * Bk["w1a32"].shape[0]].view(N, -1)
-            if i == 0:
-                ops.layernorm_rows_f32(h32, Bk["lna"][0], Bk["lna"][1], xn32, Bk["lna"][2])
-            ops.linear_step_f32(xn32, Bk["w1a32"], Bk["b1a"], ff32, act=ops.ACT_SWISH)
-            ops.linear_res_scale_ln_step_f32(ff32, Bk["w2a32"], Bk["b2a"], h32, Bk["fa"], Bk["lnb"][0], Bk["lnb"][1], h32,
-                                             ln_out16=x16, eps=Bk["lnb"][2])
-            ops.retention_proj_step(h32, Bk["lnb"], Bk["wqkvg32"], Bk["bqkvg"], q32, N)
-            self._ret(r, q32, kv, self.len_enc, enc_c, 1, S, Bk["gn_eps"], out16=r.o16)
-            ops.linear_res_scale_ln16(r.o16, Bk["wo"], Bk["bo"], h32, 1.0, Bk["lnc"][0], Bk["lnc"][1], h32, x16, Bk["lnc"][2])
-            ops.linear_glu(x16, Bk["pw1"], Bk["pb1"], r.glu16)
+
+        def dwconv(i, Bk, glu16, dw16):
             if n == 1:
-                ops.dwconv_step_ragged(r.glu16, cache, self.len_enc, enc_c, Bk["dw"], Bk["bn"], r.dw16, Bk["bn_eps"])
+                ops.dwconv_step_ragged(glu16, self.caches[i], self.len_enc, enc_c, Bk["dw"], Bk["bn"], dw16, Bk["bn_eps"])
             else:
-                ops.dwconv_chunk_ragged(r.glu16, cache, self.len_enc, enc_c, Bk["dw"], Bk["bn"], r.dw16, n, Bk["bn_eps"])
-            ops.linear_res_scale_ln16(r.dw16, Bk["pw2"], Bk["pb2"], h32, 1.0, Bk["lnd"][0], Bk["lnd"][1], h32, x16, Bk["lnd"][2])
-            ops.layernorm_rows_f32(h32, Bk["lnd"][0], Bk["lnd"][1], xn32, Bk["lnd"][2])
-            ops.linear_step_f32(xn32, Bk["w1b32"], Bk["b1b"], ff32, act=ops.ACT_SWISH)
-            ops.linear_res_ln_step_f32(ff32, Bk["w2b32"], Bk["b2b"], h32, Bk["lne"][0], Bk["lne"][1], h32, Bk["lne"][2], alpha=Bk["fb"],
-                                       out16=h16)
-            if i + 1 < nb:
-                nx = P["blocks"][i + 1]["lna"]
-                ops.layernorm_rows_f32(h32, nx[0], nx[1], xn32, nx[2])
+                ops.dwconv_chunk_ragged(glu16, self.caches[i], self.len_enc, enc_c, Bk["dw"], Bk["bn"], dw16, n, Bk["bn_eps"])
+
+        ret = lambda i, Bk, q32, **out: self._ret(r, q32, self.enc_kv[i], self.len_enc, enc_c, 1, S, Bk["gn_eps"], **out)
+        f32_input(P, r.x_in.view(N, -1), r.xin32, r.h32, r.h16)
+        f32_blocks(P, r.h32, r.h16, r.x16, r.xn32, r.q32[:N], r.o16, r.glu16, r.dw16, r.ff32, ret, dwconv)
         advance(self.len_enc, enc_c)
         # look-ahead window (f32): push / zero frame / keep per slot, or a chunk's pushes then dummies into the im2col rows of
         # its emitting windows; Conv1d, L2 norm (LsStreamSession._conv per slot)
         if n == 1:
-            ops.window_push_f32(self.win32, h32, r.ctl[1])
+            ops.window_push_f32(self.win32, r.h32, r.ctl[1])
         else:
-            ops.window_chunk_f32(self.win32, h32, r.cols, r.ctl[1], r.ctl[2], r.ctl[3], n)
+            ops.window_chunk_f32(self.win32, r.h32, r.cols, r.ctl[1], r.ctl[2], r.ctl[3], n)
         ops.linear_step_f32(r.cols, P["cnn.w32"], P["cnn.b"], r.y32)
         ops.l2norm_rows_f32(r.y32, r.e32)
-        # decoder, S*C*n rows in (B = S, C, Tp = n) slabs: ls_stream.dec_step's all-f32 form, the retention state per slot
-        R = S * C * n
-        a32, o32 = r.a32, r.o32
+        # decoder, S*C*n rows in (B = S, C, Tp = n) slabs
         if n == 1:
-            ops.convert_fanout_step_f32(r.e32, P["convert.w32"], self.m._convert_const(C), a32, r.a16, S, C)
+            ops.convert_fanout_step_f32(r.e32, P["convert.w32"], self.m._convert_const(C), r.a32, r.a16, S, C)
         else:
-            ops.convert_fanout_f32(r.e32, P["convert.w32"], self.m._convert_const(C), a32, r.a16, S, n, C)
-        for Ld, kv in zip(P["dec.layers"], self.dec_kv):
-            ff32 = r.ff32[:R * Ld["w1_32"].shape[0]].view(R, -1)
-            ops.retention_proj_step(a32, None, Ld["wqkvg32"], Ld["bqkvg"], r.q32, R)
-            self._ret(r, r.q32, kv, self.len_dec, dec_c, C, S * C, Ld["gn_eps"], out32=o32)
-            ops.linear_res_ln_step_f32(o32, Ld["out1_w32"], Ld["out1_b"], a32, Ld["g11"], Ld["be11"], a32, Ld["eps11"])
-            ops.linear_step_f32(a32, Ld["in2_w32"], Ld["in2_b"], r.qkv32)
-            if n == 1:
-                ops.spk_attn_step_f32(r.qkv32, o32, S, C)
-            else:
-                ops.spk_attn_rows_f32(r.qkv32, o32, S, C, n)
-            ops.linear_res_ln_step_f32(o32, Ld["out2_w32"], Ld["out2_b"], a32, Ld["g21"], Ld["be21"], a32, Ld["eps21"])
-            ops.linear_step_f32(a32, Ld["w1_32"], Ld["b1"], ff32, act=ops.ACT_RELU)
-            ops.linear_res_ln_step_f32(ff32, Ld["w2_32"], Ld["b2"], a32, Ld["g22"], Ld["be22"], a32, Ld["eps22"])
+            ops.convert_fanout_f32(r.e32, P["convert.w32"], self.m._convert_const(C), r.a32, r.a16, S, n, C)
+        ret = lambda i, Ld, q32, **out: self._ret(r, q32, self.dec_kv[i], self.len_dec, dec_c, C, S * C, Ld["gn_eps"], **out)
+        f32_dec_layers(P, r.a32, r.q32, r.o32, r.qkv32, r.ff32, ret, S, C, n)
         advance(self.len_dec, dec_c)
-        ops.head_l2dot(r.e32, a32, r.attr, r.logits, S, n, n, C, self.D)
+        ops.head_l2dot(r.e32, r.a32, r.attr, r.logits, S, n, n, C, self.D)

@@ -41,25 +41,93 @@ F32_PROJ = os.environ.get("EEND_STREAM_RET_F32", "1") != "0"      # f32 retentio
 DEC_F32 = os.environ.get("EEND_STREAM_DEC_F32", "1") != "0"       # all-f32 decoder frame step when a frame has <= 16 rows
 
 
+def _ret_update(step, qkvg, Wd, state, N, H, o16, **out):
+    """The recurrence `step` (ops.retention_step / retention_step_f32) on the driver's state dict, then the new scale."""
+    kv, s_in, s_out = _ret_state(state, N, H, o16.device)
+    step(qkvg, kv, s_in, s_out, o16, N, H, Wd["gn_eps"], **out)
+    if state.get("_static"):
+        s_in.copy_(s_out)             # graph-captured sessions: fixed buffers, the new scale is copied back (4 floats)
+    else:
+        state["scale"], state["_scale_next"] = s_out, s_in            # ping-pong
+
+
 def _ret_step(x16, x32, ln, Wd, state, N, H, scratch, out32=None):
     """One frame of MultiScaleRetention (retention.py:126-144) on N rows.  The q / k / v / g projections run in full f32 from
     the f32 residual stream (x32, through LayerNorm `ln` where the block is pre-norm): the recurrence amplifies their
     rounding with the stream position (see csrc/stream.hip ret_proj_step_kernel)."""
     o16 = scratch["o16"][:N]
-    kv, s_in, s_out = _ret_state(state, N, H, x16.device)
     if F32_PROJ:
         q32 = scratch["qkvg32"][:N]
         ops.retention_proj_step(x32, ln, Wd["wqkvg32"], Wd["bqkvg"], q32, N)
-        ops.retention_step_f32(q32, kv, s_in, s_out, o16, N, H, Wd["gn_eps"], out32=out32)
+        _ret_update(ops.retention_step_f32, q32, Wd, state, N, H, o16, out32=out32)
     else:
         qkvg = scratch["qkvg"][:N]
         ops.linear(x16, Wd["wqkvg"], Wd["bqkvg"], qkvg)
-        ops.retention_step(qkvg, kv, s_in, s_out, o16, N, H, Wd["gn_eps"])
-    if state.get("_static"):
-        s_in.copy_(s_out)             # graph-captured sessions: fixed buffers, the new scale is copied back (4 floats)
-    else:
-        state["scale"], state["_scale_next"] = s_out, s_in            # ping-pong
+        _ret_update(ops.retention_step, qkvg, Wd, state, N, H, o16)
     return o16
+
+
+def _ret_f32(states, N, H, o16):
+    """The eager frame steps' retention callback: the f32 recurrence on the driver's state dicts (scale as _ret_update)."""
+    return lambda i, Wd, q32, out16=None, out32=None: _ret_update(ops.retention_step_f32, q32, Wd, states[i], N, H, o16, out32=out32)
+
+
+# ---------------------------------------------------------------------------------------------
+# the all-f32 frame step (f32 activations and weights, DESIGN 9a), shared by enc_step / dec_step and LsMultiStreamSession.
+# The callers differ in the state touches alone: ret(i, Wd, q32, out16= / out32=) is the retention recurrence of layer i
+# (operands Wd) on the projections q32, dwconv(i, Bk, glu16, dw16) the depthwise-conv cache step of block i.  The decoder rows
+# are (B, C, n) slabs.  Row buffers hold N rows; ff32 is flat scratch of N * (the widest FFN) elements.
+# ---------------------------------------------------------------------------------------------
+def f32_input(P, x, xin32, h32, h16):
+    """The input projection in f32: the raw log-mel features are O(10), so their f16 rounding is the largest single operand
+    error of the encoder step (5e-4 on the worst logit of the one-hour stream, emulated on the oracle)."""
+    xin32[:, :x.shape[-1]].copy_(x)
+    ops.linear_res_ln_step_f32(xin32, P["in.w32"], P["in.b"], None, P["in.g"], P["in.beta"], h32, P["in.eps"], out16=h16)
+
+
+def f32_blocks(P, h32, h16, x16, xn32, q32, o16, glu16, dw16, ff32, ret, dwconv):
+    """The Conformer-retention blocks (conformer/encoder.py:223-228) with the two half-step FFNs of every block in f32, weights
+    included.  xn32 is LN(x) in f32, the FFN input: the first block's `lna` before its FFN, the next block's at the end."""
+    N, blocks = h32.shape[0], P["blocks"]
+    for i, Bk in enumerate(blocks):
+        ff = ff32[:N * Bk["w1a32"].shape[0]].view(N, -1)
+        if i == 0:
+            ops.layernorm_rows_f32(h32, Bk["lna"][0], Bk["lna"][1], xn32, Bk["lna"][2])
+        ops.linear_step_f32(xn32, Bk["w1a32"], Bk["b1a"], ff, act=ops.ACT_SWISH)
+        ops.linear_res_scale_ln_step_f32(ff, Bk["w2a32"], Bk["b2a"], h32, Bk["fa"], Bk["lnb"][0], Bk["lnb"][1], h32,
+                                         ln_out16=x16, eps=Bk["lnb"][2])
+        ops.retention_proj_step(h32, Bk["lnb"], Bk["wqkvg32"], Bk["bqkvg"], q32, N)
+        ret(i, Bk, q32, out16=o16)
+        ops.linear_res_scale_ln16(o16, Bk["wo"], Bk["bo"], h32, 1.0, Bk["lnc"][0], Bk["lnc"][1], h32, x16, Bk["lnc"][2])
+        ops.linear_glu(x16, Bk["pw1"], Bk["pb1"], glu16)
+        dwconv(i, Bk, glu16, dw16)
+        ops.linear_res_scale_ln16(dw16, Bk["pw2"], Bk["pb2"], h32, 1.0, Bk["lnd"][0], Bk["lnd"][1], h32, x16, Bk["lnd"][2])
+        ops.layernorm_rows_f32(h32, Bk["lnd"][0], Bk["lnd"][1], xn32, Bk["lnd"][2])
+        ops.linear_step_f32(xn32, Bk["w1b32"], Bk["b1b"], ff, act=ops.ACT_SWISH)
+        ops.linear_res_ln_step_f32(ff, Bk["w2b32"], Bk["b2b"], h32, Bk["lne"][0], Bk["lne"][1], h32, Bk["lne"][2], alpha=Bk["fb"],
+                                   out16=h16)
+        if i + 1 < len(blocks):
+            nx = blocks[i + 1]["lna"]
+            ops.layernorm_rows_f32(h32, nx[0], nx[1], xn32, nx[2])
+
+
+def f32_dec_layers(P, a32, q32, o32, qkv32, ff32, ret, B, C, n):
+    """The attractor decoder layers (LS model :235-243) wholly in f32, weights included: the f16 operand rounding of the linears
+    in front of the retention's per-head LayerNorm was the heavy tail of the one-hour stream."""
+    N = a32.shape[0]
+    for i, Ld in enumerate(P["dec.layers"]):
+        ff = ff32[:N * Ld["w1_32"].shape[0]].view(N, -1)
+        ops.retention_proj_step(a32, None, Ld["wqkvg32"], Ld["bqkvg"], q32, N)
+        ret(i, Ld, q32, out32=o32)
+        ops.linear_res_ln_step_f32(o32, Ld["out1_w32"], Ld["out1_b"], a32, Ld["g11"], Ld["be11"], a32, Ld["eps11"])
+        ops.linear_step_f32(a32, Ld["in2_w32"], Ld["in2_b"], qkv32)
+        if n == 1:
+            ops.spk_attn_step_f32(qkv32, o32, B, C)
+        else:
+            ops.spk_attn_rows_f32(qkv32, o32, B, C, n)
+        ops.linear_res_ln_step_f32(o32, Ld["out2_w32"], Ld["out2_b"], a32, Ld["g21"], Ld["be21"], a32, Ld["eps21"])
+        ops.linear_step_f32(a32, Ld["w1_32"], Ld["b1"], ff, act=ops.ACT_RELU)
+        ops.linear_res_ln_step_f32(ff, Ld["w2_32"], Ld["b2"], a32, Ld["g22"], Ld["be22"], a32, Ld["eps22"])
 
 
 def _scratch(owner, key, N, D, F):
@@ -90,51 +158,34 @@ def enc_step(owner, x_t, t, ret_states, conv_caches):
     F = P["blocks"][0]["w1a"].shape[0] if P["blocks"] else 0
     sc = _scratch(owner, "enc", B, D, F)
     xin16, h32, h16, x16 = sc["xin16"][:B], sc["h32"][:B], sc["h16"][:B], sc["x16"][:B]
-    if F32_PROJ and DEC_F32 and B <= ops.STEP_F32_MAX_ROWS:
-        # the input projection in f32: the raw log-mel features are O(10), so their f16 rounding is the largest single operand
-        # error of the encoder step (5e-4 on the worst logit of the one-hour stream, emulated on the oracle)
-        xin32 = sc["xin32"][:B]
-        xin32[:, :x.shape[-1]].copy_(x.view(B, -1))
-        ops.linear_res_ln_step_f32(xin32, P["in.w32"], P["in.b"], None, P["in.g"], P["in.beta"], h32, P["in.eps"], out16=h16)
-    else:
-        ops.bn_cast_pad(x, None, xin16, 1, 1, False)
-        ops.linear_res_ln(xin16, P["in.w"], P["in.b"], None, P["in.g"], P["in.beta"], h32, h16, P["in.eps"])
-    nb = len(P["blocks"])
-    f32_ffn = F32_PROJ and DEC_F32 and B <= ops.STEP_F32_MAX_ROWS     # the two half-step FFNs of every block in f32 (weights included)
-    xn32 = sc["o32"][:B] if f32_ffn else None                          # LN(x) in f32: the FFN input
-    for i, Bk in enumerate(P["blocks"]):
-        Fi = Bk["w1a"].shape[0]
-        if f32_ffn:
-            ff32 = sc["ff32"][:B * Fi].view(B, Fi)
-            if i == 0:
-                ops.layernorm_rows_f32(h32, Bk["lna"][0], Bk["lna"][1], xn32, Bk["lna"][2])
-            ops.linear_step_f32(xn32, Bk["w1a32"], Bk["b1a"], ff32, act=ops.ACT_SWISH)
-            ops.linear_res_scale_ln_step_f32(ff32, Bk["w2a32"], Bk["b2a"], h32, Bk["fa"], Bk["lnb"][0], Bk["lnb"][1], h32,
-                                             ln_out16=x16, eps=Bk["lnb"][2])
-        else:
-            if i == 0:
-                ops.layernorm_f16(h32, Bk["lna"][0], Bk["lna"][1], x16, Bk["lna"][2])
-            ff = sc["ff16"][:B * Fi].view(B, Fi)
-            ops.linear(x16, Bk["w1a"], Bk["b1a"], ff, act=ops.ACT_SWISH)
-            ops.linear_res_scale_ln16(ff, Bk["w2a"], Bk["b2a"], h32, Bk["fa"], Bk["lnb"][0], Bk["lnb"][1], h32, x16, Bk["lnb"][2])
-        o16 = _ret_step(x16, h32, Bk["lnb"], Bk, ret_states[i], B, H, sc)
-        ops.linear_res_scale_ln16(o16, Bk["wo"], Bk["bo"], h32, 1.0, Bk["lnc"][0], Bk["lnc"][1], h32, x16, Bk["lnc"][2])
-        glu, dw = sc["glu16"][:B], sc["dw16"][:B]
-        ops.linear_glu(x16, Bk["pw1"], Bk["pb1"], glu)
+    glu, dw = sc["glu16"][:B], sc["dw16"][:B]
+
+    def dwconv(i, Bk, glu, dw):
         cache = conv_caches[i]
         if cache.dtype != F32 or not cache.is_contiguous() or cache.device != dev:
             raise EendHipError("conv cache must be a contiguous f32 GPU tensor (B, D, k-1)")
         ops.dwconv_step(glu, cache, Bk["dw"], Bk["bn"], dw, Bk["bn_eps"])      # cache shifted in place
+
+    if F32_PROJ and DEC_F32 and B <= ops.STEP_F32_MAX_ROWS:               # the all-f32 step on the driver's states and caches
+        o16 = sc["o16"][:B]
+        f32_input(P, x.view(B, -1), sc["xin32"][:B], h32, h16)
+        f32_blocks(P, h32, h16, x16, sc["o32"][:B], sc["qkvg32"][:B], o16, glu, dw, sc["ff32"], _ret_f32(ret_states, B, H, o16), dwconv)
+        return h32.view(B, 1, D).clone()
+    ops.bn_cast_pad(x, None, xin16, 1, 1, False)
+    ops.linear_res_ln(xin16, P["in.w"], P["in.b"], None, P["in.g"], P["in.beta"], h32, h16, P["in.eps"])
+    nb = len(P["blocks"])
+    for i, Bk in enumerate(P["blocks"]):
+        Fi = Bk["w1a"].shape[0]
+        if i == 0:
+            ops.layernorm_f16(h32, Bk["lna"][0], Bk["lna"][1], x16, Bk["lna"][2])
+        ff = sc["ff16"][:B * Fi].view(B, Fi)
+        ops.linear(x16, Bk["w1a"], Bk["b1a"], ff, act=ops.ACT_SWISH)
+        ops.linear_res_scale_ln16(ff, Bk["w2a"], Bk["b2a"], h32, Bk["fa"], Bk["lnb"][0], Bk["lnb"][1], h32, x16, Bk["lnb"][2])
+        o16 = _ret_step(x16, h32, Bk["lnb"], Bk, ret_states[i], B, H, sc)
+        ops.linear_res_scale_ln16(o16, Bk["wo"], Bk["bo"], h32, 1.0, Bk["lnc"][0], Bk["lnc"][1], h32, x16, Bk["lnc"][2])
+        ops.linear_glu(x16, Bk["pw1"], Bk["pb1"], glu)
+        dwconv(i, Bk, glu, dw)
         ops.linear_res_scale_ln16(dw, Bk["pw2"], Bk["pb2"], h32, 1.0, Bk["lnd"][0], Bk["lnd"][1], h32, x16, Bk["lnd"][2])
-        if f32_ffn:
-            ops.layernorm_rows_f32(h32, Bk["lnd"][0], Bk["lnd"][1], xn32, Bk["lnd"][2])
-            ops.linear_step_f32(xn32, Bk["w1b32"], Bk["b1b"], ff32, act=ops.ACT_SWISH)
-            ops.linear_res_ln_step_f32(ff32, Bk["w2b32"], Bk["b2b"], h32, Bk["lne"][0], Bk["lne"][1], h32, Bk["lne"][2], alpha=Bk["fb"],
-                                       out16=h16)
-            if i + 1 < nb:
-                nx = P["blocks"][i + 1]["lna"]
-                ops.layernorm_rows_f32(h32, nx[0], nx[1], xn32, nx[2])
-            continue
         ops.linear(x16, Bk["w1b"], Bk["b1b"], ff, act=ops.ACT_SWISH)
         ops.linear_res_ln(ff, Bk["w2b"], Bk["b2b"], h32, Bk["lne"][0], Bk["lne"][1], h32, h16, Bk["lne"][2], alpha=Bk["fb"])
         if i + 1 < nb:
@@ -159,20 +210,9 @@ def dec_step(owner, emb_t, t, max_nspks, ret_states):
         ops.convert_fanout_step_f32(e32, P["convert.w32"], owner._convert_const(C), a32, a16, B, C)
     else:
         ops.convert_fanout(e32.to(F16), P["convert.w1"], owner._convert_const(C), a32, a16, B, 1, C)
-    if F32_PROJ and DEC_F32 and N <= ops.STEP_F32_MAX_ROWS:
-        # one frame x <= 16 slots: the whole layer in f32 (weights included) -- the f16 operand rounding of the linears in
-        # front of the retention's per-head LayerNorm was the heavy tail of the one-hour stream
-        o32, qkv32 = sc["o32"][:N], sc["qkv32"][:N]
-        for i, Ld in enumerate(P["dec.layers"]):
-            Fi = Ld["w1_32"].shape[0]
-            ff32 = sc["ff32"][:N * Fi].view(N, Fi)
-            _ret_step(a16, a32, None, Ld, ret_states[i], N, H, sc, out32=o32)
-            ops.linear_res_ln_step_f32(o32, Ld["out1_w32"], Ld["out1_b"], a32, Ld["g11"], Ld["be11"], a32, Ld["eps11"])
-            ops.linear_step_f32(a32, Ld["in2_w32"], Ld["in2_b"], qkv32)
-            ops.spk_attn_step_f32(qkv32, o32, B, C)
-            ops.linear_res_ln_step_f32(o32, Ld["out2_w32"], Ld["out2_b"], a32, Ld["g21"], Ld["be21"], a32, Ld["eps21"])
-            ops.linear_step_f32(a32, Ld["w1_32"], Ld["b1"], ff32, act=ops.ACT_RELU)
-            ops.linear_res_ln_step_f32(ff32, Ld["w2_32"], Ld["b2"], a32, Ld["g22"], Ld["be22"], a32, Ld["eps22"])
+    if F32_PROJ and DEC_F32 and N <= ops.STEP_F32_MAX_ROWS:               # the all-f32 layers on the driver's states
+        f32_dec_layers(P, a32, sc["qkvg32"][:N], sc["o32"][:N], sc["qkv32"][:N], sc["ff32"], _ret_f32(ret_states, N, H, sc["o16"][:N]),
+                       B, C, 1)
         return a32.view(B, 1, C, D).clone()
     for i, Ld in enumerate(P["dec.layers"]):
         Fi = Ld["w1"].shape[0]
