@@ -723,6 +723,19 @@ int eend_spk_attn_rows_f32(const float* qkv, float* out_f32, int B, int C, int T
     return eend_launch_spk_attn_rows_f32(qkv, out_f32, B, C, Tp, scale, (hipStream_t)stream);
 }
 
+int eend_retention_prefill_f32(const float* qkvg_f32, float* kv_state, void* out_f16, float* out_f32, float* ws, long ws_floats,
+                               int Ncache, int seq0, int Nseq, int H, int t0, int T, float gn_eps, void* stream) {
+    return eend_launch_ret_prefill(qkvg_f32, kv_state, out_f16, out_f32, ws, ws_floats, Ncache, seq0, Nseq, H, t0, T, gn_eps,
+                                   (hipStream_t)stream);
+}
+
+int eend_dwconv_prefill_f16(const void* x_f16, float* cache, int b, int t0, const float* w, const float* bn_weight, const float* bn_bias,
+                            const float* bn_mean, const float* bn_var, float eps, void* out_f16, int T, int B, int D, int k,
+                            void* stream) {
+    return eend_launch_dwconv_prefill(x_f16, cache, b, t0, w, bn_weight, bn_bias, bn_mean, bn_var, eps, out_f16, T, B, D, k,
+                                      (hipStream_t)stream);
+}
+
 int eend_retention_step_f16(const void* qkvg, float* kv_state, const float* scale_in, float* scale_out,
                             void* out_f16, int N, int H, float gn_eps, void* stream) {
     if (!qkvg || !kv_state || !scale_in || !scale_out || !out_f16) return EEND_EINVAL;

@@ -244,6 +244,13 @@ int eend_launch_dwconv_chunk_ragged(const void* x16, float* cache, const int* le
 int eend_launch_window_chunk_f32(float* win, const float* x, float* cols, const int* npush, const int* ndummy, const int* ndec, int S,
                                  int nmax, int k, int D, hipStream_t stream);
 int eend_launch_spk_attn_rows_f32(const float* qkv, float* out, int B, int C, int Tp, float scale, hipStream_t stream);
+// ls_prefill.hip: one slot taken forward by a backlog of any length (chunk-parallel f32 retention, frame-parallel conv cache)
+long eend_ret_prefill_ws_floats(int Nseq, int H, int T);
+int eend_launch_ret_prefill(const float* qkvg, float* kv, void* out16, float* out32, float* ws, long ws_floats, int Ncache, int seq0,
+                            int Nseq, int H, int t0, int T, float eps, hipStream_t stream);
+int eend_launch_dwconv_prefill(const void* x16, float* cache, int b, int t0, const float* w, const float* bn_w, const float* bn_b,
+                               const float* bn_mean, const float* bn_var, float eps, void* out16, int T, int B, int D, int k,
+                               hipStream_t stream);
 int eend_launch_gather_bn_cast_pad(const float* const* x_ptrs, const int* lens, float pad_value, const float* bn_w,
                                    const float* bn_b, const float* bn_mean, const float* bn_var, float eps, void* out16,
                                    int B, int T, int Tp, int Fin, int Fpad, int apply_bn, hipStream_t stream);

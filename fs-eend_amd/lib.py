@@ -102,6 +102,8 @@ PROTOTYPES = {
     "eend_dwconv_chunk_ragged_f16": [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _vp],
     "eend_window_chunk_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "eend_spk_attn_rows_f32": [_vp, _vp, _i, _i, _i, _f, _vp],
+    "eend_retention_prefill_f32": [_vp, _vp, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _i, _f, _vp],
+    "eend_dwconv_prefill_f16": [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _i, _vp],
     "eend_retention_step_f16": [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp],
     "eend_retention_proj_step_f32": [_vp, _vp, _vp, _f, _vp, _vp, _vp, _i, _vp],
     "eend_retention_step_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp],

@@ -19,7 +19,7 @@ import torch
 from . import ops
 from .lib import EendHipError
 from .ls_stream import f32_blocks, f32_dec_layers, f32_input
-from .multistream import MultiStreamSession
+from .multistream import OPEN, MultiStreamSession, SlotError
 
 F16, F32, I32 = torch.float16, torch.float32, torch.int32
 
@@ -37,6 +37,10 @@ class LsMultiStreamSession(MultiStreamSession):
         ses.step(flush=[a])                    # then conv_delay zero embeddings, one per step, beside the other slots
         ses.close(a)
 
+    prefill(slot, feats) takes one open slot forward by a backlog of any length in one eager pass (the same all-f32 step at
+    B = 1 over the backlog's rows, the chunk-parallel f32 retention `ops.retention_prefill` and the frame-parallel conv cache
+    `ops.dwconv_prefill` on the slot's own state); the slot then streams on frame by frame.
+
     State: retention kv f32 (S, H, 64, 64) per encoder block and (S*C, H, 64, 64) per decoder layer, conv caches f32 (S, D, k-1)
     per block, the window f32 (S, k*D) and two int32 length vectors.  States are never cleared: a length of 0 means "empty" to
     every kernel that reads them, so a reopened slot computes exactly what a fresh one does.
@@ -48,10 +52,13 @@ class LsMultiStreamSession(MultiStreamSession):
 
     input_transform = "logmel23_cummn"
 
-    def __init__(self, model, slots: int, max_nspks: int = 10, use_graph: bool = True, max_frames: int = 1):
+    def __init__(self, model, slots: int, max_nspks: int = 10, use_graph: bool = True, max_frames: int = 1,
+                 prefill_rows: int = 1024):
         m = model
         if not isinstance(max_frames, int) or isinstance(max_frames, bool) or not 1 <= max_frames <= 64:
             raise EendHipError("max_frames must be in 1..64")
+        if not isinstance(prefill_rows, int) or isinstance(prefill_rows, bool) or prefill_rows < 1:
+            raise EendHipError("prefill_rows must be a positive int")
         P = m._prepare()
         if max_nspks <= 0 or max_nspks > 16:
             raise EendHipError("max_nspks must be in 1..16 (the f32 speaker attention of the frame step)")
@@ -71,6 +78,7 @@ class LsMultiStreamSession(MultiStreamSession):
         self._rows = {n: self._alloc_rows(n, P) for n in sorted({1, max_frames})}
         r = self._rows[1]                                             # the per-frame rows under their long-standing names
         self.x_in, self.logits, self.modes, self.attr = r.x_in, r.logits, r.ctl, r.attr
+        self.prefill_rows, self._pre = prefill_rows, None             # prefill's row set: allocated on first use and kept
 
     def _alloc_rows(self, n, P):
         """The rows of a step of Tp = n frames per slot: S*n encoder rows, S*C*n decoder rows (slabs: row (s*C + c)*n + j)."""
@@ -139,3 +147,88 @@ class LsMultiStreamSession(MultiStreamSession):
         f32_dec_layers(P, r.a32, r.q32, r.o32, r.qkv32, r.ff32, ret, S, C, n)
         advance(self.len_dec, dec_c)
         ops.head_l2dot(r.e32, r.a32, r.attr, r.logits, S, n, n, C, self.D)
+
+    # ---- prefill: one slot taken forward by a backlog of any length (eager, no graph)
+    def _alloc_prefill(self, P):
+        """The rows of one prefill piece: prefill_rows encoder rows (after the k window taps in z), C * prefill_rows decoder rows
+        (about 17.5 KB of f32 scratch each), and the retention prefill's workspace."""
+        n, C, D = self.prefill_rows, self.C, self.D
+        Fmax = max([Bk["w1a32"].shape[0] for Bk in P["blocks"]] + [Ld["w1_32"].shape[0] for Ld in P["dec.layers"]] + [1])
+        z = lambda *s_, dt=F32: torch.zeros(*s_, dtype=dt, device=self.dev)
+        R = C * n
+        r = SimpleNamespace()
+        r.xin32 = z(n, P["Fin_pad"])
+        r.h32, r.h16, r.x16, r.xn32 = z(n, D), z(n, D, dt=F16), z(n, D, dt=F16), z(n, D)
+        r.o16, r.glu16, r.dw16 = z(n, D, dt=F16), z(n, D, dt=F16), z(n, D, dt=F16)
+        r.q32 = z(R, 4 * D)
+        r.ff32 = z(R * Fmax)
+        r.z = z(self.k + n, D)                                        # the slot's k stored taps, then the piece's encoder rows
+        r.y32, r.e32 = z(n, D), z(n, D)
+        r.a32, r.a16, r.o32, r.qkv32 = z(R, D), z(R, D, dt=F16), z(R, D), z(R, 3 * D)
+        r.attr, r.logits = z(R * D), z(R)
+        r.ws = z(ops.retention_prefill_ws(C, self.H, n))
+        return r
+
+    def _prefill_piece(self, r, s, x, t_enc, t_dec, ne):
+        """Slot s takes the N frames x (N, in) f32 at encoder position t_enc; the last ne of the N windows emit, at decoder
+        position t_dec.  -> logits (1, ne, C), a view of the row set.  `_body` with B = 1 and Tp = N: the retention prefill on
+        the slot's own state sequences, the conv prefill on its cache rows, and the Conv1d reading the emitting windows as
+        overlapping rows of z."""
+        P, C, D, H, k, N = self.m._prepare(), self.C, self.D, self.H, self.k, x.shape[0]
+        h32, h16 = r.h32[:N], r.h16[:N]
+        ret = lambda i, Bk, q32, **out: ops.retention_prefill(q32, self.enc_kv[i], r.ws, s, 1, H, t_enc, N, Bk["gn_eps"], **out)
+        dwconv = lambda i, Bk, glu16, dw16: ops.dwconv_prefill(glu16, self.caches[i], s, t_enc, Bk["dw"], Bk["bn"], dw16, Bk["bn_eps"])
+        f32_input(P, x, r.xin32[:N], h32, h16)
+        f32_blocks(P, h32, h16, r.x16[:N], r.xn32[:N], r.q32[:N], r.o16[:N], r.glu16[:N], r.dw16[:N], r.ff32, ret, dwconv)
+        # look-ahead window (f32): z = the stored taps, then the new frames; the window after push m is z[m .. m + k - 1]
+        r.z[:k].copy_(self.win32[s].view(k, D))
+        r.z[k:k + N].copy_(h32)
+        self.win32[s].copy_(r.z[N:N + k].reshape(-1))
+        if not ne:
+            return r.logits[:0].view(1, 0, C)
+        cols = r.z.as_strided((ne, k * D), (D, 1), r.z.storage_offset() + (N - ne + 1) * D)
+        e32 = r.e32[:ne]
+        ops.linear_step_f32(cols, P["cnn.w32"], P["cnn.b"], r.y32[:ne])
+        ops.l2norm_rows_f32(r.y32[:ne], e32)
+        R = C * ne
+        a32 = r.a32[:R]
+        ops.convert_fanout_f32(e32, P["convert.w32"], self.m._convert_const(C), a32, r.a16[:R], 1, ne, C)
+        ret = lambda i, Ld, q32, **out: ops.retention_prefill(q32, self.dec_kv[i], r.ws, s * C, C, H, t_dec, ne, Ld["gn_eps"], **out)
+        f32_dec_layers(P, a32, r.q32[:R], r.o32[:R], r.qkv32[:R], r.ff32, ret, 1, C, ne)
+        logits = r.logits[:R].view(1, ne, C)
+        ops.head_l2dot(e32, a32, r.attr[:R * D].view(1, ne, C, D), logits, 1, ne, ne, C, D)
+        return logits
+
+    @torch.no_grad()
+    def prefill(self, s: int, feats):
+        """Take open slot `s`, at any position, forward by the T >= 0 frames feats ((T, in) or (1, T, in)) in one pass at batch
+        rate: the slot's retention states, conv caches, look-ahead window, counters and accounting end as after T pushes through
+        `step`, and the slot streams on from there.  -> logits (1, m, C), m = max(0, min(T, t + T - conv_delay)): the frames it
+        emitted, in order.  No other slot is touched; flushing stays with step / step_frames.  Runs eagerly on the current stream
+        in pieces of at most prefill_rows frames.  The retention prefill has one work item per (sequence, head, 64 frames): a
+        few frames are step_frames' case, not this one's."""
+        self.table._check(s)
+        if self.table.state[s] != OPEN:
+            raise SlotError(f"prefill of slot {s}, which is {self.table.state[s]}")
+        if not torch.is_tensor(feats):
+            raise SlotError(f"prefill of slot {s}: expected a tensor of features")
+        x = feats.reshape(-1, self.m._in_size)
+        T = int(x.shape[0])
+        out = []
+        if T:
+            self._check_weights()
+            if self._pre is None:
+                self._pre = self._alloc_prefill(self.m._prepare())
+            x = x.to(device=self.dev, dtype=F32).contiguous()
+            for a in range(0, T, self.prefill_rows):
+                xp = x[a:a + self.prefill_rows]
+                plan = self.table.plan_prefill(s, int(xp.shape[0]))
+                y = self._prefill_piece(self._pre, s, xp, self.table.n_enc[s], self.table.n_dec[s], plan.dec[s])
+                self.table.commit(plan)
+                self.len_enc[s] = self.table.n_enc[s]
+                self.len_dec[s] = self.table.n_dec[s]
+                if plan.dec[s]:
+                    out.append(y.clone())
+        if not out:
+            return torch.zeros(1, 0, self.C, dtype=F32, device=self.dev)
+        return out[0] if len(out) == 1 else torch.cat(out, dim=1)

@@ -543,7 +543,11 @@ STEP_F32_MAX_ROWS = 1 << 30
 def linear_step_f32(a32, w32, bias, out32, act=ACT_NONE):
     """out32 = act(a32 w32^T + bias), everything f32 (the all-f32 LS decoder frame step)."""
     L = _lib.load()
-    _chk(a32, F32, "a32"); _chk(w32, F32, "w32"); _chk(bias, F32, "bias"); _chk(out32, F32, "out32")
+    if a32.is_contiguous() or a32.dim() != 2 or a32.stride(1) != 1 or a32.stride(0) % 4:
+        _chk(a32, F32, "a32")
+    elif not a32.is_cuda or a32.dtype != F32:         # rows at any stride that is a multiple of 4 floats; they may overlap (a
+        raise _lib.EendHipError("a32: expected an f32 GPU tensor")     # Conv1d's windows as a strided view of its input frames)
+    _chk(w32, F32, "w32"); _chk(bias, F32, "bias"); _chk(out32, F32, "out32")
     M, K = a32.shape
     _lib.check(L.eend_linear_step_f32(_p(a32), a32.stride(0), _p(w32), w32.stride(0), _p(bias), _p(out32), out32.stride(0), M,
                                       w32.shape[0], K, act, _stream()), "eend_linear_step_f32")
@@ -876,6 +880,53 @@ def dwconv_chunk_ragged(x16, cache, len_dev, cnt_dev, w, bn, out16, nmax, eps=1e
         raise _lib.EendHipError("dwconv_chunk_ragged: shape mismatch")
     _lib.check(L.eend_dwconv_chunk_ragged_f16(_p(x16), _p(cache), _p(len_dev), _p(cnt_dev), nmax, _p(w), _p(bn[0]), _p(bn[1]), _p(bn[2]),
                                               _p(bn[3]), eps, _p(out16), B, D, k, _stream()), "eend_dwconv_chunk_ragged_f16")
+
+
+def retention_prefill_ws(Nseq, H, T):
+    """Floats of workspace retention_prefill needs: one 64 x 64 tile per (sequence, head, chunk of 64 frames)."""
+    return Nseq * H * ((T + 63) // 64) * 4096
+
+
+def retention_prefill(qkvg32, kv_state, ws, seq0, Nseq, H, t0, T, gn_eps=1e-6, out16=None, out32=None):
+    """The retention recurrence over a backlog in chunk-parallel f32 form: rows i*T + j of qkvg32 (Nseq*T, 4*H*64) are frames
+    t0 + j of state sequence seq0 + i of kv_state f32 (Ncache, H, 64, 64), i < Nseq, which all stand at position t0 >= 0 (0: the
+    state is not read).  out16 / out32 (Nseq*T, H*64) get the frames' outputs and the state ends as after T per-frame updates;
+    no other sequence or row is touched.  ws: f32 scratch of retention_prefill_ws(Nseq, H, T) floats."""
+    L = _lib.load()
+    _chk(qkvg32, F32, "qkvg32"); _chk(kv_state, F32, "kv_state"); _chk(out16, F16, "out16"); _chk(out32, F32, "out32")
+    _chk(ws, F32, "ws")
+    if out16 is None and out32 is None:
+        raise _lib.EendHipError("retention_prefill: out16 and / or out32")
+    if T < 1 or Nseq < 1 or t0 < 0 or seq0 < 0:
+        raise _lib.EendHipError("retention_prefill: Nseq >= 1 sequences from seq0 >= 0, T >= 1 frames at t0 >= 0")
+    D = H * 64
+    if (kv_state.dim() != 4 or kv_state.shape[1:] != (H, 64, 64) or qkvg32.shape != (Nseq * T, 4 * D)
+            or (out16 is not None and out16.shape != (Nseq * T, D)) or (out32 is not None and out32.shape != (Nseq * T, D))):
+        raise _lib.EendHipError("retention_prefill: shape mismatch")
+    if seq0 + Nseq > kv_state.shape[0]:
+        raise _lib.EendHipError(f"retention_prefill: sequences {seq0}..{seq0 + Nseq - 1} outside a state of {kv_state.shape[0]}")
+    if ws.numel() < retention_prefill_ws(Nseq, H, T):
+        raise _lib.EendHipError("retention_prefill: workspace too small (retention_prefill_ws)")
+    _lib.check(L.eend_retention_prefill_f32(_p(qkvg32), _p(kv_state), _p(out16), _p(out32), _p(ws), ws.numel(), kv_state.shape[0],
+                                            seq0, Nseq, H, t0, T, gn_eps, _stream()), "eend_retention_prefill_f32")
+
+
+def dwconv_prefill(x16, cache, b, t0, w, bn, out16, eps=1e-5):
+    """dwconv_step_ragged for slot b alone over the T frames x16 / out16 (T, D), frame-parallel: outputs and the slot's row of
+    cache f32 (B, D, k-1) end bit for bit as after T one-frame calls from position t0 (0: the row is read as zeros)."""
+    L = _lib.load()
+    _chk(x16, F16, "x16"); _chk(cache, F32, "cache"); _chk(w, F32, "w"); _chk(out16, F16, "out16")
+    for t in bn:
+        _chk(t, F32, "bn")
+    if x16.dim() != 2 or cache.dim() != 3:
+        raise _lib.EendHipError("dwconv_prefill: x16 (T, D), cache (B, D, k-1)")
+    T, D = x16.shape
+    B, k = cache.shape[0], w.shape[1]
+    if (T < 1 or t0 < 0 or not 0 <= b < B or cache.shape != (B, D, k - 1) or out16.shape != (T, D) or w.shape[0] != D
+            or any(t.numel() < D for t in bn)):
+        raise _lib.EendHipError("dwconv_prefill: shape mismatch")
+    _lib.check(L.eend_dwconv_prefill_f16(_p(x16), _p(cache), b, t0, _p(w), _p(bn[0]), _p(bn[1]), _p(bn[2]), _p(bn[3]), eps, _p(out16),
+                                         T, B, D, k, _stream()), "eend_dwconv_prefill_f16")
 
 
 def window_chunk_f32(win32, x32, cols32, npush_i32, ndummy_i32, ndec_i32, nmax):

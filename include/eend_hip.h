@@ -541,6 +541,31 @@ int eend_window_chunk_f32(float* win_f32, const float* x, float* cols_f32, const
  * (b, t) attend to each other.  C <= 16; Tp = 1 is the layout of eend_spk_attn_step_f32. */
 int eend_spk_attn_rows_f32(const float* qkv, float* out_f32, int B, int C, int Tp, float scale, void* stream);
 
+/* Prefill of an LS-EEND stream from a backlog (LsMultiStreamSession.prefill; additive to ABI version 5).
+ *
+ * eend_retention_prefill_f32: T >= 1 new frames per sequence through the recurrence of eend_retention_step_ragged_f32, for Nseq
+ * sequences that share the position t0 >= 0 (a host int, as in eend_attn_prefill_f16), in chunk-parallel form: call sequence i is
+ * sequence seq0 + i of kv_state f32 [Ncache][H][64][64] (Nseq = 1 on an encoder state, C at s*C on a decoder state); row i*T + j of
+ * qkvg_f32 [Nseq*T][4*H*64] (q | k | v | g) is its frame t0 + j, and out_f16 and / or out_f32 [Nseq*T][H*64] get the same rows.
+ * With kv_t = (sqrt(t0) kv_{t0-1} + sum_{i = t0..t} v_i k_i^T) / sqrt(t + 1) the frames go in chunks of 64 through three passes,
+ * each with one work item per (sequence, head, chunk): the chunk sums P_c = sum v_i k_i^T; their exclusive prefix S_c = sqrt(t0)
+ * kv_in + sum_{c' < c} P_c' in chunk order, with kv_out = (S_last + P_last) / sqrt(t0 + T); and the outputs o_i = ((Q K^T .
+ * [j <= i]) V + Q S_c^T)_i / sqrt(t0 + 64 c + i + 1) followed by the per-head LayerNorm and swish gate.  All operands and
+ * accumulators are f32 (v_mfma_f32_16x16x4_f32); out_f16 is the saturating f16 rounding of the value written to out_f32.  The
+ * state ends as after T per-frame updates (up to the summation order); with t0 == 0 it is not read, whatever the memory holds.
+ * No other state sequence and no other row is read or written; rows of a tail chunk beyond T are taken as zeros, not read.  ws:
+ * at least Nseq * H * ceil(T / 64) * 4096 floats.  A NULL or unaligned (16 B) pointer, T < 1, t0 < 0, both outputs NULL, a
+ * sequence range outside [0, Ncache) or a workspace that is too small returns EEND_EINVAL before any launch. */
+int eend_retention_prefill_f32(const float* qkvg_f32, float* kv_state, void* out_f16, float* out_f32, float* ws, long ws_floats,
+                               int Ncache, int seq0, int Nseq, int H, int t0, int T, float gn_eps, void* stream);
+/* eend_dwconv_step_ragged_f16 for slot b alone over T >= 1 frames x_f16 / out_f16 [T][D], one thread per (frame, channel): the taps
+ * of frame i are the last k - 1 entries of (old cache ++ x[0..i-1]), a slot at t0 == 0 reads its cache row as zeros, and the fma
+ * chain is the one-frame kernel's, so outputs and the final cache row (the last k - 1 entries of (old cache ++ x), written by a
+ * second launch) are bit for bit those of T one-frame calls.  Only row b of cache f32 [B][D][k-1] is touched. */
+int eend_dwconv_prefill_f16(const void* x_f16, float* cache, int b, int t0, const float* w, const float* bn_weight, const float* bn_bias,
+                            const float* bn_mean, const float* bn_var, float eps, void* out_f16, int T, int B, int D, int k,
+                            void* stream);
+
 /* One frame of MultiScaleRetention.recurrent_forward (retention.py:126-144, decay 1) + per-head
  * LayerNorm + swish gate, state updated in place.  qkvg f16 [N][4*H*64] = [q | k*dk^-0.5 | v | g];
  * kv_state f32 [N][H][64][64] in the reference's incremental_state["prev_key_value"] layout;
