@@ -457,6 +457,7 @@ int eend_bn_train_stats_f32(const void* const* x_ptrs, const int* lens, float pa
                             float* mean, float* var, float* run_mean, float* run_var, float momentum, int B, int T,
                             int F, void* stream) {
     if (!ws || !mean || !var || B <= 0 || T <= 0 || F <= 0) return EEND_EINVAL;
+    if ((long)B * T < 2) return EEND_EINVAL;            // the unbiased running variance divides by n - 1: refused before any launch
     long ns = ((long)B * T + 255) / 256;
     if (ns > 512) ns = 512;
     if (ws_floats < (ns + 1) * 2L * F) return EEND_EINVAL;

@@ -892,7 +892,8 @@ int eend_colsum_f32(const void* Y, int ld, long M, int N, int is_bf16, float* ws
  * gradient w.r.t. the input as f32 (ds_f32, may alias g) and bf16, and dgamma / dbeta [256].  `drop`: the spec of the
  * producing eend_linear_res_ln_train_f16 -- applied to the bf16 copy only (the branch gradient), not to ds_f32 (the
  * residual stream).  dbias (optional, [256]): column sums of that branch gradient = the bias gradient of the linear layer in
- * front of the LayerNorm (saves a separate pass over ds_bf16). */
+ * front of the LayerNorm (saves a separate pass over ds_bf16).
+ * ws_floats >= 1024 * 768 (the row pass writes [blocks <= 1024][3][256] partials), whatever M. */
 int eend_layernorm_bwd_f32(const float* g, const void* xhat_f16, const float* rstd, const float* gamma, float* ds_f32,
                            void* ds_bf16, float* ws, long ws_floats, float* dgamma, float* dbeta, float* dbias, long M,
                            const eend_dropout* drop, void* stream);
@@ -902,7 +903,8 @@ int eend_layernorm_bwd_f32(const float* g, const void* xhat_f16, const float* rs
  * [B]; loss_out[0] = BCE loss; da f32 slab [(b*C+c)*Tp+t][256] = gradient w.r.t. the un-normalised attractors,
  * de f32 [B*Tp][256] = gradient w.r.t. the unit embeddings (overwritten); logits (optional) f32 [B][T][C].
  * With dlogits_in (f32 [B][T][C]: the caller's own d loss / d logits, e.g. torch autograd over the reference's
- * standard_loss) the loss part is skipped and that gradient is propagated (labels / ilens / ncols may be null). */
+ * standard_loss) the loss part is skipped and that gradient is propagated (labels / ilens / ncols may be null).
+ * ws_floats >= ceil(B * Tp / 4) (one loss partial per block of four frames). */
 int eend_head_bce_f32(const float* emb, const float* attr, const float* labels, const int* ilens, const int* ncols,
                       float inv_frames, const float* dlogits_in, float* logits, float* da, float* de, float* ws,
                       long ws_floats, float* loss_out, int B, int T, int Tp, int C, void* stream);
@@ -912,7 +914,7 @@ int eend_l2norm_bwd_bf16(const float* y, const float* dy, const float* inv_norm,
                          void* stream);
 
 /* `convert` fan-out backward (FS model :113-114): gsum bf16 [B*Tp][256] = sum over speaker slots of g0,
- * dpc f32 [C][256] = sum over (b, t) of g0 per slot. */
+ * dpc f32 [C][256] = sum over (b, t) of g0 per slot.  ws_floats >= 256 * C * 256 ([blocks <= 256][C][256] partials), whatever B * Tp; 1 <= C <= 12. */
 int eend_convert_fanout_bwd_f32(const float* g0, void* gsum_bf16, float* ws, long ws_floats, float* dpc, int B, int Tp,
                                 int C, void* stream);
 /* mode 0: pc[c] = W[:, 256:] pe[c] + bias (the forward's per-slot constant); mode 1: dW[:, 256:] and dbias from dpc.
@@ -926,11 +928,12 @@ int eend_spk_attn_bwd_bf16(const void* qkv_f16, const void* dO_bf16, void* dqkv_
                            float scale, const eend_dropout* drop, void* stream);
 
 /* Train-mode BatchNorm1d statistics over the padded input (FS model :165-166): mean / biased var [F] of all B*T
- * frames (pad_value for frames beyond each length) and the running-statistics update (momentum, unbiased var). */
+ * frames (pad_value for frames beyond each length) and the running-statistics update (momentum, unbiased var).
+ * ws_floats >= (ns + 1) * 2 * F with ns = min(ceil(B * T / 256), 512) row splits; B * T >= 2 (the unbiased variance). */
 int eend_bn_train_stats_f32(const void* const* x_ptrs, const int* lens, float pad_value, float* ws, long ws_floats,
                             float* mean, float* var, float* run_mean, float* run_var, float momentum, int B, int T,
                             int F, void* stream);
-/* BatchNorm weight / bias gradients from dy bf16 [B*Tp][ld] (gradient w.r.t. the BN output). */
+/* BatchNorm weight / bias gradients from dy bf16 [B*Tp][ld] (gradient w.r.t. the BN output).  ws_floats >= ns * 2 * F, ns as above. */
 int eend_bn_bwd_f32(const void* const* x_ptrs, const int* lens, float pad_value, const float* mean, const float* var,
                     float eps, const void* dy_bf16, int ld, float* ws, long ws_floats, float* dgamma, float* dbeta,
                     int B, int T, int Tp, int F, void* stream);
@@ -940,7 +943,7 @@ int eend_emb_consistency_bwd_f16(const void* emb_f16, const float* labels, const
                                  int B, int T, int Tp, int D, int C, void* stream);
 
 /* Optimiser on flat f32 buffers (FS-EEND/train_dia.py:83-100,153): sum of squares of the gradient; Adam step with
- * clip_grad_norm_ folded in (hp = {lr, 1-beta1^t, 1-beta2^t, max_norm} on the device). */
+ * clip_grad_norm_ folded in (hp = {lr, 1-beta1^t, 1-beta2^t, max_norm} on the device).  eend_grad_sumsq_f32: ws_floats >= 1024 (one partial per block), whatever n. */
 int eend_grad_sumsq_f32(const float* g, long n, float* ws, long ws_floats, float* out, void* stream);
 int eend_adam_step_f32(float* p, const float* g, float* m, float* v, long n, const float* hp, const float* gsumsq,
                        float beta1, float beta2, float eps, void* stream);
@@ -985,13 +988,13 @@ int eend_layernorm_train_f16(const float* x, const float* gamma, const float* be
 /* LayerNorm backward, general form.  g: gradient w.r.t. the LayerNorm output, f32 or (g_is_bf16) bf16 [M][256].
  * ds_f32 (optional): the input gradient, overwritten or (accumulate) added to -- the latter is the pre-norm residual
  * block of conformer/modules.py:32-33, where the LayerNorm sits on the branch.  ds_bf16 (optional) = alpha16 *
- * dropout(input gradient), dbias (optional, needs ds_bf16) its column sums.  dgamma / dbeta [256] are overwritten. */
+ * dropout(input gradient), dbias (optional, needs ds_bf16) its column sums.  dgamma / dbeta [256] are overwritten.  ws_floats >= 1024 * 768, whatever M. */
 int eend_layernorm_bwd2_f32(const void* g, int g_is_bf16, const void* xhat_f16, const float* rstd, const float* gamma,
                             float* ds_f32, int accumulate, void* ds_bf16, float alpha16, float* ws, long ws_floats,
                             float* dgamma, float* dbeta, float* dbias, long M, const eend_dropout* drop, void* stream);
 
 /* Residual-stream gradient g f32 [M][256] -> gradient of a pre-norm branch output: ds_bf16 = alpha * dropout(g)
- * (ResidualConnectionModule module_factor, the branch's trailing nn.Dropout) and dbias [256] = its column sums. */
+ * (ResidualConnectionModule module_factor, the branch's trailing nn.Dropout) and dbias [256] = its column sums.  ws_floats >= 1024 * 256, whatever M. */
 int eend_resgrad_cast_bf16(const float* g, void* ds_bf16, float alpha, float* ws, long ws_floats, float* dbias, long M,
                            const eend_dropout* drop, void* stream);
 
@@ -1007,7 +1010,8 @@ int eend_linear_res_scale_ln_train_f16(const void* A, int lda, const void* W, in
  * [nseq*Tp][256], zero for t >= Tv. */
 int eend_glu_dwconv_f16(const void* P_f16, const float* w, void* c_f16, int nseq, int Tp, int Tv, int k, void* stream);
 /* BatchNorm1d batch statistics of c over the nseq*Tv valid frames, two-pass: stats f32 [513] = mean[256], M2[256]
- * (sum of squared deviations), n.  The triples of several ranks merge exactly (SyncBatchNorm, train_dia_simu.py:167). */
+ * (sum of squared deviations), n.  The triples of several ranks merge exactly (SyncBatchNorm, train_dia_simu.py:167).
+ * ws_floats >= (nb + 1) * 256 with nb = min(ceil(nseq * Tv / 32), 4096) row blocks. */
 int eend_bn_batch_stats_f16(const void* c_f16, float* ws, long ws_floats, float* stats, int nseq, int Tp, int Tv,
                             void* stream);
 /* stats [R][513] of R ranks -> mean, biased var [256], n_out[1] = total frame count; running statistics updated
@@ -1019,14 +1023,16 @@ int eend_bn_swish_f16(const void* c_f16, const float* mean, const float* var, fl
                       const float* beta, void* s_f16, long M, void* stream);
 /* Backward of the two, pass 1: sums f32 [512] = per-channel sum of d_y and of d_y * c_hat over this rank's valid
  * frames (d_y = ds * swish'(BN(c))); also written as dbeta / dgamma.  Pass 2 (sums / n may be the all-reduced global
- * ones): ds <- d_c = gamma * rstd * (d_y - S1/n - c_hat * S2/n), zero for t >= Tv, in place (bf16). */
+ * ones): ds <- d_c = gamma * rstd * (d_y - S1/n - c_hat * S2/n), zero for t >= Tv, in place (bf16).
+ * eend_bn_swish_bwd_stats_bf16: ws_floats >= nb * 512, nb = min(ceil(nseq * Tv / 32), 4096). */
 int eend_bn_swish_bwd_stats_bf16(const void* ds_bf16, const void* c_f16, const float* mean, const float* var, float eps,
                                  const float* gamma, const float* beta, float* ws, long ws_floats, float* sums,
                                  float* dgamma, float* dbeta, int nseq, int Tp, int Tv, void* stream);
 int eend_bn_swish_bwd_apply_bf16(void* ds_bf16, const void* c_f16, const float* mean, const float* var, float eps,
                                  const float* gamma, const float* beta, const float* sums, const float* n_dev, int nseq,
                                  int Tp, int Tv, void* stream);
-/* Depthwise conv + GLU backward: dP bf16 [nseq*Tp][512] (gradient of the pointwise-conv-1 output), dw f32 [256][k]. */
+/* Depthwise conv + GLU backward: dP bf16 [nseq*Tp][512] (gradient of the pointwise-conv-1 output), dw f32 [256][k].
+ * ws_floats >= nseq * ceil(Tp / 64) * 256 * k (one [256][k] partial per 64-frame strip); k in {7, 15, 16, 31}. */
 int eend_dwconv_glu_bwd_bf16(const void* dc_bf16, const void* P_f16, const float* w, void* dP_bf16, float* ws,
                              long ws_floats, float* dw, int nseq, int Tp, int Tv, int k, void* stream);
 
