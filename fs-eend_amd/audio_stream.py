@@ -22,7 +22,7 @@ import torch
 
 from . import feature
 from . import lib as _lib
-from .multistream import SlotError
+from .multistream import SlotError, check_parts
 
 F32 = torch.float32
 HOP, WIN_END = 80, 100                   # frame f reads samples 80 f - 100 .. 80 f + 99
@@ -172,6 +172,37 @@ class AudioFrontEnd:
     def state(self, s: int) -> str:
         return self.table.state[s]
 
+    # ---- a slot's stream leaves / comes back (the "frontend" part of a multistream.StreamSnapshot)
+    def _config(self):
+        return {"mode": self.mode, "context_size": self.ctx, "subsampling": self.sub}
+
+    def export(self, s: int) -> dict:
+        """Slot s's front-end state as plain values and tensors: its device rows (copies) and its table fields."""
+        self.table._check(s)
+        if self.table.state[s] == FREE:
+            raise SlotError(f"slot {s} is not open (reset it first)")
+        t = self.table
+        return {"config": self._config(), "tail": self.tail[s].clone(), "ring": self.ring[s].clone(), "sums": self.sums[s].clone(),
+                "state": t.state[s], "recv": t.recv[s], "frames": t.frames[s], "mframes": t.mframes[s]}
+
+    def check_part(self, part):
+        """SlotError unless `part` is an export of a front-end configured like this one."""
+        ok = (isinstance(part, dict) and part.get("config") == self._config() and part.get("state") in (OPEN, ENDED)
+              and all(isinstance(part.get(k), int) and part[k] >= 0 for k in ("recv", "frames", "mframes"))
+              and all(torch.is_tensor(part.get(k)) and part[k].shape == row.shape[1:] and part[k].dtype == row.dtype
+                      for k, row in (("tail", self.tail), ("ring", self.ring), ("sums", self.sums))))
+        if not ok:
+            raise SlotError("resume: the snapshot's front-end part does not fit this front-end "
+                            f"(here {self._config()}, there {part.get('config') if isinstance(part, dict) else part!r})")
+
+    def adopt(self, s: int, part):
+        """Slot s goes on from an exported `part` (checked by check_part): ordinary row copies on the current stream."""
+        self.table._check(s)
+        for k, rows in (("tail", self.tail), ("ring", self.ring), ("sums", self.sums)):
+            rows[s].copy_(part[k], non_blocking=True)
+        t = self.table
+        t.state[s], t.recv[s], t.frames[s], t.mframes[s] = part["state"], part["recv"], part["frames"], part["mframes"]
+
     @staticmethod
     def _samples(s, w):
         if not isinstance(w, torch.Tensor):
@@ -277,6 +308,35 @@ class AudioStreamSession:
 
     def state(self, s: int) -> str:
         return self.ses.state(s)
+
+    # ---- snapshot / suspend / resume: the wrapped session's, plus the front-end's part for the same slot
+    @property
+    def parts(self):
+        return tuple(self.ses.parts) + ("frontend",)
+
+    def snapshot(self, s: int):
+        """The wrapped session's snapshot of slot s with the front-end's state of that slot (sample tail, log-mel ring, running
+        sums, counters) as its "frontend" part.  The slot goes on."""
+        snap = self.ses.snapshot(s)
+        snap.parts["frontend"] = self.fe.export(s)
+        return snap
+
+    def suspend(self, s: int):
+        snap = self.snapshot(s)
+        self.close(s)
+        return snap
+
+    def resume(self, snap) -> int:
+        """A suspended stream into a free slot -> the slot; the audio goes on at the sample it stopped at.  SlotError, with
+        nothing changed, when the snapshot's parts are not this stack's or a part does not fit."""
+        check_parts(snap, self.parts)
+        return self._resume(snap)
+
+    def _resume(self, snap):
+        self.fe.check_part(snap.parts["frontend"])
+        s = self.ses._resume(snap)
+        self.fe.adopt(s, snap.parts["frontend"])
+        return s
 
     def _collect(self, out, y):
         for s, v in y.items():

@@ -684,6 +684,28 @@ int eend_attn_prefill_f16(const void* qkv, long ldq, void* K_cache, void* V_cach
     return eend_launch_attn_prefill(qkv, ldq, K_cache, V_cache, out_f16, Ncache, seq0, Nseq, H, cap, t0, Tq, scale, (hipStream_t)stream);
 }
 
+int eend_copy_blocks(const eend_block_copy* entries, int n, void* stream) {
+    if (n < 0 || n > EEND_COPY_BLOCKS_MAX || (n > 0 && !entries)) return EEND_EINVAL;
+    for (int i = 0; i < n; ++i) {
+        const eend_block_copy& e = entries[i];
+        if (e.nblocks < 0 || e.block_bytes < 0 || e.src_stride < 0 || e.dst_stride < 0) return EEND_EINVAL;
+        if (((size_t)e.src | (size_t)e.dst | (size_t)e.block_bytes | (size_t)e.src_stride | (size_t)e.dst_stride) & 15) return EEND_EINVAL;
+        if (e.nblocks == 0 || e.block_bytes == 0) continue;           // moves nothing: its pointers may be null
+        if (!e.src || !e.dst) return EEND_EINVAL;
+        if (e.nblocks > 1 && (e.src_stride < e.block_bytes || e.dst_stride < e.block_bytes)) return EEND_EINVAL;
+        long ssz, dsz;                                                // the bytes each side spans, first block to last
+        if (__builtin_mul_overflow(e.nblocks - 1, e.src_stride, &ssz) || __builtin_add_overflow(ssz, e.block_bytes, &ssz) ||
+            __builtin_mul_overflow(e.nblocks - 1, e.dst_stride, &dsz) || __builtin_add_overflow(dsz, e.block_bytes, &dsz))
+            return EEND_EINVAL;
+        const size_t s0 = (size_t)e.src, d0 = (size_t)e.dst;
+        if (s0 + (size_t)ssz < s0 || d0 + (size_t)dsz < d0) return EEND_EINVAL;
+        if (s0 < d0 + (size_t)dsz && d0 < s0 + (size_t)ssz) return EEND_EINVAL;     // the two ranges overlap
+    }
+    return eend_launch_copy_blocks(entries, n, (hipStream_t)stream);
+}
+
+long eend_copy_blocks_tile_bytes(void) { return eend_copy_blocks_tile(); }
+
 int eend_retention_step_ragged_f32(const float* qkvg_f32, float* kv_state, const int* len_dev, const int* mask_dev, int rows_per_seq,
                                    void* out_f16, float* out_f32, int N, int H, float gn_eps, void* stream) {
     return eend_launch_ret_step_ragged(qkvg_f32, kv_state, len_dev, mask_dev, rows_per_seq, out_f16, out_f32, N, H, gn_eps,

@@ -226,6 +226,9 @@ int eend_launch_counter_add_count(int* len, const int* cnt, int S, hipStream_t s
 // attn_prefill.hip: causal prefill attention over the multi-stream K/V caches (appends, then one flash pass per query tile)
 int eend_launch_attn_prefill(const void* qkv, long ldq, void* Kc, void* Vc, void* out16, int Ncache, int seq0, int Nseq, int H, int cap,
                              int t0, int Tq, float scale, hipStream_t stream);
+// copy_blocks.hip: the entries validated by the caller; the tile size of one workgroup
+int eend_launch_copy_blocks(const eend_block_copy* entries, int n, hipStream_t stream);
+long eend_copy_blocks_tile();
 int eend_launch_window_chunk(void* win16, const float* x, void* cols16, const int* npush, const int* ndummy, const int* ndec, int S,
                              int nmax, int k, int D, hipStream_t stream);
 // ls_multi.hip: the per-slot state touches of the multi-stream LS frame step

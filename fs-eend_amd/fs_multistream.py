@@ -48,6 +48,7 @@ class FsMultiStreamSession(MultiStreamSession):
     every read, so a reopened slot computes exactly what a fresh one does."""
 
     input_transform = "logmel23"
+    kind = "fs"
 
     def __init__(self, streaming_model, slots: int, max_nspks: int = 6, cap: int = 1024, use_graph: bool = True,
                  max_frames: int = 1, prefill_rows: int = 4096):
@@ -120,6 +121,23 @@ class FsMultiStreamSession(MultiStreamSession):
 
     def _clear_window(self, s):
         self.win16[s].zero_()
+
+    # ---- snapshot / resume (multistream.py): what a slot's state is
+    def _signature(self):
+        return {"kind": self.kind, "D": self.D, "H": self.H, "C": self.C, "k": self.k, "enc_layers": len(self.enc_kv),
+                "dec_layers": len(self.dec_kv), "in_size": self.m._in_size, "dtypes": "kv float16, window float16"}
+
+    def _pieces(self, s, n_enc, n_dec):
+        """Slot s's state: rows [0, n_enc) of its sequence in every encoder layer's K and V, rows [0, n_dec) of its C sequences
+        in every decoder layer's, and its window row.  A K (or V) piece is nseq * H blocks of n * 128 bytes, cap * 128 apart."""
+        H, C, row = self.H, self.C, 64 * 2
+        out = []
+        for side, caches, seq0, nseq, n in (("enc", self.enc_kv, s, 1, n_enc), ("dec", self.dec_kv, s * C, C, n_dec)):
+            for i, kv in enumerate(caches):
+                for name, t in zip("kv", kv):
+                    out.append((f"{side}{i}.{name}", t.data_ptr() + seq0 * H * self.cap * row, nseq * H, n * row, self.cap * row))
+        out.append(("win", self.win16[s].data_ptr(), 1, self.win16.shape[1] * 2, 0))
+        return out
 
     # ---- the step of r.Tp frames per slot (eager body; captured once per cache capacity and row set)
     def _attn(self, r, qkv, kc, vc, o16, N, per_slot, lens, cnt):

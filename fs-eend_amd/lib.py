@@ -95,6 +95,7 @@ PROTOTYPES = {
     "eend_counter_add_count_i32": [_vp, _vp, _i, _vp],
     "eend_window_chunk_f16": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "eend_attn_prefill_f16": [_vp, _l, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp],
+    "eend_copy_blocks": [_vp, _i, _vp],
     "eend_retention_step_ragged_f32": [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _f, _vp],
     "eend_dwconv_step_ragged_f16": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _vp],
     "eend_window_push_f32": [_vp, _vp, _vp, _i, _i, _i, _vp],
@@ -182,6 +183,17 @@ PROTOTYPES = {
     "eend_retention_bwd_bf16": [_vp] * 8 + [_i, _vp, _vp] + [_vp] * 6 + [_i] * 6 + [_f, _vp],
 }
 
+# entries that return a long rather than an int status
+LONG_PROTOTYPES = {
+    "eend_copy_blocks_tile_bytes": [],
+}
+
+
+class BlockCopy(ctypes.Structure):
+    """eend_block_copy of include/eend_hip.h."""
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("nblocks", ctypes.c_long), ("block_bytes", ctypes.c_long),
+                ("src_stride", ctypes.c_long), ("dst_stride", ctypes.c_long)]
+
 
 class PrepEntry(ctypes.Structure):
     """eend_prep_entry of include/eend_hip.h."""
@@ -219,13 +231,14 @@ def load():
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950). There is no fallback path.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argtypes in PROTOTYPES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:
-            raise EendHipError(f"{LIB_PATH} does not export {name}") from e
-        fn.argtypes = argtypes
-        fn.restype = ctypes.c_int
+    for protos, restype in ((PROTOTYPES, ctypes.c_int), (LONG_PROTOTYPES, ctypes.c_long)):
+        for name, argtypes in protos.items():
+            try:
+                fn = getattr(lib, name)
+            except AttributeError as e:
+                raise EendHipError(f"{LIB_PATH} does not export {name}") from e
+            fn.argtypes = argtypes
+            fn.restype = restype
     got = lib.eend_abi_version()
     if got != ABI_VERSION and not os.environ.get("EEND_HIP_LIB"):     # (an A/B study may load an older build on purpose)
         raise EendHipError(f"{LIB_PATH} has ABI version {got}, this binding was written for {ABI_VERSION} (include/eend_hip.h)")

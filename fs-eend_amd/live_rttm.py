@@ -17,7 +17,7 @@ import torch
 
 from . import lib as _lib
 from . import ops
-from .multistream import SlotError
+from .multistream import SlotError, check_parts
 from .postproc import rttm_lines
 
 F32, I32, I64 = torch.float32, torch.int32, torch.int64
@@ -70,6 +70,23 @@ class SegmentLog:
         self.state[s], self.segs[s], self.overflowed[s] = FREE, [], False
         self.unreported.discard(s)
         self.pending.pop(s, None)
+
+    def export(self, s):
+        """Slot s's host fields, as plain values."""
+        self.check(s)
+        if self.state[s] == FREE:
+            raise SlotError(f"slot {s} is not open")
+        return {"state": self.state[s], "segs": list(self.segs[s]), "pending": list(self.pending.get(s, [])),
+                "overflowed": self.overflowed[s], "unreported": s in self.unreported}
+
+    def adopt(self, s, f):
+        self.reset(s)
+        triples = lambda v: [tuple(int(x) for x in seg) for seg in v]
+        self.state[s], self.segs[s], self.overflowed[s] = f["state"], triples(f["segs"]), bool(f["overflowed"])
+        if f["pending"]:
+            self.pending[s] = triples(f["pending"])
+        if f["unreported"]:
+            self.unreported.add(s)
 
     def check_feed(self, slots, end):
         slots, end = list(slots), list(end)
@@ -161,6 +178,34 @@ class SegmentTracker:
 
     def state(self, s: int) -> str:
         return self.log.state[s]
+
+    # ---- a slot's stream leaves / comes back (the "tracker" part of a multistream.StreamSnapshot)
+    def _config(self):
+        return {"ntracks": self.ntracks, "col0": self.col0, "threshold": self.threshold, "median": self.median,
+                "is_prob": self.is_prob, "capacity": self.cap}
+
+    def export(self, s: int) -> dict:
+        """Slot s's tracker state as plain values and tensors: its device rows (copies; the segments no poll has taken yet
+        travel in the box row) and its host fields."""
+        part = self.log.export(s)
+        part.update(config=self._config(), hist=self.hist[s].clone(), open=self.open_[s].clone(), box=self.box[s].clone())
+        return part
+
+    def check_part(self, part):
+        """SlotError unless `part` is an export of a tracker configured like this one."""
+        ok = (isinstance(part, dict) and part.get("config") == self._config() and part.get("state") in (OPEN, ENDED)
+              and all(isinstance(part.get(k), (list, tuple)) for k in ("segs", "pending"))
+              and all(torch.is_tensor(part.get(k)) and part[k].shape == row.shape[1:] and part[k].dtype == row.dtype
+                      for k, row in (("hist", self.hist), ("open", self.open_), ("box", self.box))))
+        if not ok:
+            raise SlotError("resume: the snapshot's tracker part does not fit this tracker "
+                            f"(here {self._config()}, there {part.get('config') if isinstance(part, dict) else part!r})")
+
+    def adopt(self, s: int, part):
+        """Slot s goes on from an exported `part` (checked by check_part): ordinary row copies on the current stream."""
+        self.log.adopt(s, part)
+        for k, rows in (("hist", self.hist), ("open", self.open_), ("box", self.box)):
+            rows[s].copy_(part[k], non_blocking=True)
 
     # ---- feeding
     def _launch(self, desc, counts, ends, n, ld):
@@ -302,6 +347,36 @@ class SegmentSession:
 
     def state(self, s: int) -> str:
         return self.ses.state(s)
+
+    # ---- snapshot / suspend / resume: the wrapped session's, plus the tracker's part for the same slot
+    @property
+    def parts(self):
+        return tuple(self.ses.parts) + ("tracker",)
+
+    def snapshot(self, s: int):
+        """The wrapped session's snapshot of slot s with the tracker's state of that slot (decision history, open segments,
+        segment ring, the lines collected so far and the segments no poll has returned) as its "tracker" part.  The slot goes on."""
+        snap = self.ses.snapshot(s)
+        snap.parts["tracker"] = self.tracker.export(s)
+        return snap
+
+    def suspend(self, s: int):
+        snap = self.snapshot(s)
+        self.close(s)
+        return snap
+
+    def resume(self, snap) -> int:
+        """A suspended stream into a free slot -> the slot; its segments go on across the cut (an open one included), and
+        rttm / poll return what the uninterrupted stream's would.  SlotError, with nothing changed, when the snapshot's parts
+        are not this stack's or a part does not fit."""
+        check_parts(snap, self.parts)
+        return self._resume(snap)
+
+    def _resume(self, snap):
+        self.tracker.check_part(snap.parts["tracker"])
+        s = self.ses._resume(snap)
+        self.tracker.adopt(s, snap.parts["tracker"])
+        return s
 
     def _step(self, step, push, flush):
         before = [self.ses.state(s) for s in range(self.S)]

@@ -51,6 +51,7 @@ class LsMultiStreamSession(MultiStreamSession):
     (B = S, C, Tp = n) slabs.  Without it step_frames takes one frame per slot and step."""
 
     input_transform = "logmel23_cummn"
+    kind = "ls"
 
     def __init__(self, model, slots: int, max_nspks: int = 10, use_graph: bool = True, max_frames: int = 1,
                  prefill_rows: int = 1024):
@@ -103,6 +104,23 @@ class LsMultiStreamSession(MultiStreamSession):
 
     def _clear_window(self, s):
         self.win32[s].zero_()
+
+    # ---- snapshot / resume (multistream.py): what a slot's state is
+    def _signature(self):
+        return {"kind": self.kind, "D": self.D, "H": self.H, "C": self.C, "k": self.k, "enc_layers": len(self.enc_kv),
+                "dec_layers": len(self.dec_kv), "in_size": self.m._in_size, "dtypes": "kv float32, conv cache float32, window float32"}
+
+    def _pieces(self, s, n_enc, n_dec):
+        """Slot s's state, O(1) whatever its position: its retention state and conv cache in every encoder block, the
+        retention states of its C sequences in every decoder layer and its window row -- one block each."""
+        C = self.C
+        one = lambda name, t, a, n: (name, t[a].data_ptr(), 1, n * t[a].numel() * t.element_size(), 0)
+        out = []
+        for i, (kv, cache) in enumerate(zip(self.enc_kv, self.caches)):
+            out += [one(f"enc{i}.kv", kv, s, 1), one(f"enc{i}.conv", cache, s, 1)]
+        out += [one(f"dec{i}.kv", kv, s * C, C) for i, kv in enumerate(self.dec_kv)]
+        out.append(one("win", self.win32, s, 1))
+        return out
 
     # ---- the step of r.Tp frames per slot (eager body; captured once per row set)
     def _ret(self, r, q32, kv, lens, ctl, per_slot, Nseq, eps, out16=None, out32=None):

@@ -6,6 +6,10 @@ slot pushes, how many dummy frames a flushing slot takes and how many frames of 
 such a plan: it stages the pushed features, writes the plan's int32 control rows to the device with one copy and replays
 the captured graph of the step (or runs its eager body), then commits the plan.  A session has one set of rows and one graph
 per frame count Tp per slot and step: Tp = 1 (`step`), and Tp = max_frames (`step_frames`) when that is larger.
+
+A slot can leave its session: `snapshot(s)` packs its state into a `StreamSnapshot` (one batched copy launch into one blob),
+`suspend(s)` = snapshot + close, and `resume(snap)` puts it into a free slot of any session of the same model configuration --
+another slot count, cache capacity, max_frames or graph setting, another GPU, or another process after `save` / `load`.
 """
 import torch
 
@@ -85,6 +89,39 @@ class SlotTable:
         if self.state[s] == FREE:
             raise SlotError(f"slot {s} is not open")
         self.state[s] = FREE
+
+    def export(self, s) -> dict:
+        """The fields of slot s (any state but free), as plain values: what `adopt` of any table of the same center takes."""
+        self._check(s)
+        if self.state[s] == FREE:
+            raise SlotError(f"slot {s} is not open")
+        return {"state": self.state[s], "t": self.t[s], "n_enc": self.n_enc[s], "n_dec": self.n_dec[s],
+                "flush_left": self.flush_left[s]}
+
+    @staticmethod
+    def check_fields(f):
+        """Raise SlotError unless f is what `export` makes."""
+        ok = (isinstance(f, dict) and f.get("state") in (OPEN, FLUSHING, DONE)
+              and all(isinstance(f.get(k), int) and not isinstance(f.get(k), bool) and f[k] >= 0
+                      for k in ("t", "n_enc", "n_dec", "flush_left")))
+        if not ok:
+            raise SlotError(f"not the fields of a slot: {f!r}")
+
+    def free_slot(self) -> int:
+        """The slot the next open() or adopt() takes (the lowest free one); SlotError when all are in use."""
+        for s, st in enumerate(self.state):
+            if st == FREE:
+                return s
+        raise SlotError(f"all {self.S} slots are in use")
+
+    def adopt(self, fields) -> int:
+        """Claim a free slot, the lowest as open() does, for a stream that goes on from exported `fields`."""
+        self.check_fields(fields)
+        s = self.free_slot()
+        self.state[s] = fields["state"]
+        self.t[s], self.n_enc[s], self.n_dec[s] = fields["t"], fields["n_enc"], fields["n_dec"]
+        self.flush_left[s] = fields["flush_left"]
+        return s
 
     def plan(self, push=(), flush=()) -> SlotPlan:
         """One frame per slot.  push: slots that push a frame; flush: slots whose stream ended (not pushed in the same call)."""
@@ -169,6 +206,117 @@ class SlotTable:
         """The longest K/V history of any slot in use."""
         return max([max(self.n_enc[s], self.n_dec[s]) for s in range(self.S) if self.state[s] != FREE] + [0])
 
+SNAPSHOT_FORMAT = 1
+SECTION_ALIGN = 256                             # every section of a snapshot's blob starts on this boundary
+
+
+def _map_tensors(v, fn):
+    """v with every tensor in it (dicts, lists and tuples searched) replaced by fn(tensor)."""
+    if torch.is_tensor(v):
+        return fn(v)
+    if isinstance(v, dict):
+        return {k: _map_tensors(x, fn) for k, x in v.items()}
+    if isinstance(v, (list, tuple)):
+        return type(v)(_map_tensors(x, fn) for x in v)
+    return v
+
+
+def _tensors(v):
+    out = []
+    _map_tensors(v, out.append)
+    return out
+
+
+class StreamSnapshot:
+    """One stream taken out of a session: a plain container, no device work of its own.
+
+        kind        "fs" or "ls"
+        signature   the model configuration the state belongs to: kind, D, H, C, window taps k, encoder and decoder layer counts,
+                    in_size and the state dtypes.  `resume` refuses a session with another one.
+        table       the slot's SlotTable fields: state, t, n_enc, n_dec, flush_left
+        parts       {"model": ..., and one part per wrapper around the session ("frontend", "tracker")}: each a dict of plain
+                    Python values and tensors.  parts["model"] = {"blob": one contiguous uint8 tensor, "sections": [(name,
+                    offset, bytes), ...]}: the slot's state pieces packed back to back, each on a SECTION_ALIGN boundary (the
+                    bytes between sections are unspecified).
+
+    The weights are NOT part of a snapshot and are not identified by it: resuming under other weights than the stream ran
+    with is the caller's error and goes undetected.
+
+    `to("cpu")` returns a copy in pinned host memory, complete on return; `to(device)` a copy on that device.  `save` /
+    `load` go through torch.save / torch.load(weights_only=True) of a dict of plain values and CPU tensors."""
+
+    def __init__(self, kind, signature, table, parts):
+        self.kind, self.signature, self.table, self.parts = kind, dict(signature), dict(table), dict(parts)
+
+    @property
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in _tensors(self.parts))
+
+    @property
+    def device(self):
+        return self.parts["model"]["blob"].device
+
+    def mismatch(self, signature):
+        """-> the fields in which this snapshot's signature differs from `signature`, as {field: (snapshot's, other)}."""
+        keys = sorted(set(self.signature) | set(signature))
+        return {k: (self.signature.get(k), signature.get(k)) for k in keys if self.signature.get(k) != signature.get(k)}
+
+    def to(self, device):
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if device.type == "cpu":
+            pin = torch.cuda.is_available()
+
+            def move(t):
+                out = torch.empty(t.shape, dtype=t.dtype, pin_memory=pin)
+                out.copy_(t, non_blocking=True)
+                return out
+        else:
+            def move(t):
+                return t.clone() if t.device == device else t.to(device, non_blocking=True)
+        src = {t.device for t in _tensors(self.parts) if t.is_cuda}
+        out = StreamSnapshot(self.kind, self.signature, self.table, _map_tensors(self.parts, move))
+        if device.type == "cpu":
+            for d in src:
+                torch.cuda.synchronize(d)                             # the host copy is complete on return
+        return out
+
+    def _as_dict(self):
+        return {"format": SNAPSHOT_FORMAT, "kind": self.kind, "signature": self.signature, "table": self.table,
+                "parts": self.parts}
+
+    def save(self, path):
+        snap = self if not any(t.is_cuda for t in _tensors(self.parts)) else self.to("cpu")
+        torch.save(snap._as_dict(), path)
+
+    @classmethod
+    def load(cls, path):
+        d = torch.load(path, map_location="cpu", weights_only=True)
+        if not isinstance(d, dict) or d.get("format") != SNAPSHOT_FORMAT:
+            raise SlotError(f"{path}: not a stream snapshot of format {SNAPSHOT_FORMAT}")
+        parts = {name: dict(p) for name, p in d["parts"].items()}
+        parts["model"]["sections"] = [tuple(sec) for sec in parts["model"]["sections"]]
+        return cls(d["kind"], d["signature"], d["table"], parts)
+
+
+def check_parts(snap, parts):
+    """SlotError unless `snap` is a StreamSnapshot that carries exactly the parts `parts` of a session stack."""
+    if not isinstance(snap, StreamSnapshot):
+        raise SlotError(f"resume: expected a StreamSnapshot, got {type(snap).__name__}")
+    if sorted(snap.parts) != sorted(parts):
+        raise SlotError(f"resume: the snapshot carries the parts {sorted(snap.parts)}, this session stack {sorted(parts)}")
+
+
+def _layout(pieces):
+    """pieces: [(name, address, nblocks, block_bytes, stride)] -> ([(name, offset, bytes)], total bytes) of the packed blob."""
+    sections, off = [], 0
+    for name, _, nblocks, block_bytes, _ in pieces:
+        size = nblocks * block_bytes
+        sections.append((name, off, size))
+        off += (size + SECTION_ALIGN - 1) // SECTION_ALIGN * SECTION_ALIGN
+    return sections, off
+
 
 class MultiStreamSession:
     """What the multi-stream sessions share: the slots' lifetimes, the step core and the protocol of the wrappers
@@ -181,9 +329,13 @@ class MultiStreamSession:
         self.len_enc, self.len_dec   int32 (S,) device history lengths, zeroed by open()
 
     and provides _body(rows), the eager step over one row set (captured once into a graph per row set), and
-    _clear_window(s); a session whose caches grow overrides _room(need), which is called before every step that runs."""
+    _clear_window(s); a session whose caches grow overrides _room(need), which is called before every step that runs.  For
+    snapshot / resume it sets `kind` and provides _signature() and _pieces(s, n_enc, n_dec): the state pieces of slot s at
+    those history lengths as [(name, device address, nblocks, block_bytes, stride)] (the session's side of ops.copy_blocks)."""
 
     max_frames = 1
+    kind = None
+    parts = ("model",)                          # the parts of this stack's snapshots; a wrapper adds its own
     input_transform = None                      # the feature transform of the model's reference config
 
     def __init__(self, model, slots: int, max_nspks: int, use_graph: bool, center: int, dev):
@@ -233,6 +385,59 @@ class MultiStreamSession:
 
     def state(self, s: int) -> str:
         return self.table.state[s]
+
+    # ---- a slot leaves the session, a snapshot comes back
+    @torch.no_grad()
+    def snapshot(self, s: int) -> StreamSnapshot:
+        """Slot s (open, flushing or done) as a StreamSnapshot on this session's device: one ops.copy_blocks launch on the
+        current stream packs its state pieces into an exactly sized blob.  The slot is untouched and goes on; the snapshot is
+        a fork of it."""
+        fields = self.table.export(s)
+        pieces = self._pieces(s, fields["n_enc"], fields["n_dec"])
+        sections, total = _layout(pieces)
+        with torch.cuda.device(self.dev):
+            blob = torch.empty(total, dtype=torch.uint8, device=self.dev)
+            base = blob.data_ptr()
+            ops.copy_blocks([(ptr, base + off, nb, bb, stride, bb) for (_, ptr, nb, bb, stride), (_, off, _) in zip(pieces, sections)])
+        return StreamSnapshot(self.kind, self._signature(), fields, {"model": {"blob": blob, "sections": sections}})
+
+    def suspend(self, s: int) -> StreamSnapshot:
+        """snapshot(s), then close(s): the stream leaves the session and its slot is free."""
+        snap = self.snapshot(s)
+        self.close(s)
+        return snap
+
+    def resume(self, snap: StreamSnapshot) -> int:
+        """Put a suspended stream into a free slot (the lowest, as open() does) -> the slot; it goes on, bit for bit, as the
+        stream it was taken from.  The snapshot may come from any session of the same signature -- other slots, cap, max_frames,
+        use_graph or prefill_rows -- and from the host (staged to the device first).  SlotError, with nothing changed, when no
+        slot is free or the signature differs.  The slot's rows at or beyond the snapshot's lengths keep whatever they held."""
+        check_parts(snap, self.parts)
+        return self._resume(snap)
+
+    @torch.no_grad()
+    def _resume(self, snap):
+        diff = snap.mismatch(self._signature())
+        if diff:
+            raise SlotError("resume: the snapshot belongs to another model configuration: "
+                            + ", ".join(f"{k} {a!r} (here {b!r})" for k, (a, b) in diff.items()))
+        f, part = snap.table, snap.parts["model"]
+        SlotTable.check_fields(f)
+        s = self.table.free_slot()
+        sections, total = _layout(self._pieces(s, f["n_enc"], f["n_dec"]))
+        blob = part["blob"]
+        if [tuple(x) for x in part["sections"]] != sections or blob.dtype != torch.uint8 or blob.numel() != total:
+            raise SlotError("resume: the snapshot's sections are not this session's state pieces")
+        self._room(max(f["n_enc"], f["n_dec"]))                       # caches grow (and graphs go) as before a step
+        pieces = self._pieces(s, f["n_enc"], f["n_dec"])              # ... so the addresses are taken after it
+        with torch.cuda.device(self.dev):
+            blob = blob.to(self.dev, non_blocking=True).contiguous()
+            base = blob.data_ptr()
+            ops.copy_blocks([(base + off, ptr, nb, bb, bb, stride) for (_, ptr, nb, bb, stride), (_, off, _) in zip(pieces, sections)])
+            self.table.adopt(f)                                       # takes slot s, the lowest free one
+            self.len_enc[s] = f["n_enc"]
+            self.len_dec[s] = f["n_dec"]
+        return s
 
     @torch.no_grad()
     def step(self, push=None, flush=()):

@@ -707,6 +707,27 @@ def segtrack_feed(desc_i64, counts_i32, ends_i32, n, ld, col0, ntracks, threshol
                                         int(bool(is_prob)), _p(hist), _p(open_i32), _p(box), S, cap, _stream()), "eend_segtrack_feed_f32")
 
 
+COPY_BLOCKS_MAX = 64                             # EEND_COPY_BLOCKS_MAX: entries of one eend_copy_blocks launch
+
+
+def copy_blocks(entries):
+    """Batched strided block copy between device buffers on the current stream: entries = [(src, dst, nblocks, block_bytes,
+    src_stride, dst_stride), ...], device addresses and byte counts, every one a multiple of 16 (include/eend_hip.h
+    eend_copy_blocks).  One launch per COPY_BLOCKS_MAX entries; entries that move nothing are skipped by the library.  The
+    entries travel in the kernel arguments, so nothing has to outlive the call but the buffers themselves."""
+    L = _lib.load()
+    entries = list(entries)
+    for a in range(0, len(entries), COPY_BLOCKS_MAX):
+        part = entries[a:a + COPY_BLOCKS_MAX]
+        arr = (_lib.BlockCopy * len(part))(*[_lib.BlockCopy(*(int(v) for v in e)) for e in part])
+        _lib.check(L.eend_copy_blocks(arr, len(part), _stream()), "eend_copy_blocks")
+
+
+def copy_blocks_tile_bytes() -> int:
+    """Bytes one workgroup of eend_copy_blocks moves per tile."""
+    return int(_lib.load().eend_copy_blocks_tile_bytes())
+
+
 WIN_KEEP, WIN_PUSH, WIN_FLUSH = 0, 1, 2
 
 

@@ -494,6 +494,30 @@ int eend_window_chunk_f16(void* win_f16, const float* x, void* cols_f16, const i
 int eend_attn_prefill_f16(const void* qkv, long ldq, void* K_cache, void* V_cache, void* out_f16, int Ncache, int seq0, int Nseq, int H,
                           int cap, int t0, int Tq, float scale, void* stream);
 
+/* Suspend / resume of a stream slot (MultiStreamSession.snapshot / resume; additive to ABI version 5).
+ *
+ * eend_copy_blocks: a batched strided block copy, device memory to device memory.  Entry i moves nblocks blocks of block_bytes
+ * bytes: block b from src + b * src_stride to dst + b * dst_stride.  That is every piece of a slot's state: the rows [0, len) of
+ * nseq * H K (or V) sequences of an f16 [N][H][cap][64] cache are nseq * H blocks of len * 128 bytes at a stride of cap * 128 on
+ * the cache side and len * 128 in a packed blob; a retention state, a conv cache or a window row is one block.  `entries` is a
+ * HOST array of n <= EEND_COPY_BLOCKS_MAX entries: they are passed by value in the kernel arguments (one launch for all of
+ * them, no device table, nothing the caller must keep alive), and every check happens on the host.  Every address, size and
+ * stride is a multiple of 16 bytes; offsets are 64-bit.  EEND_EINVAL, before any launch, for: entries == NULL with n > 0; n < 0
+ * or n > EEND_COPY_BLOCKS_MAX; a negative or misaligned field; a NULL src or dst in an entry that moves bytes; a stride below
+ * block_bytes where nblocks > 1; a source range [src, src + (nblocks - 1) * src_stride + block_bytes) that overlaps the entry's
+ * destination range.  An entry with nblocks == 0 or block_bytes == 0 is skipped (its pointers may be NULL), and a call that moves
+ * nothing returns EEND_OK without a launch.  Bytes outside the destination blocks are not written and no source byte is.  Two
+ * entries of one call must not write the same bytes (not checked).  Work is cut into tiles of eend_copy_blocks_tile_bytes()
+ * bytes, one workgroup each, that never span two blocks; the grid is sized to the device and strides over the tiles. */
+#define EEND_COPY_BLOCKS_MAX 64
+typedef struct eend_block_copy {
+    const void* src;
+    void* dst;
+    long nblocks, block_bytes, src_stride, dst_stride;
+} eend_block_copy;
+int eend_copy_blocks(const eend_block_copy* entries, int n, void* stream);
+long eend_copy_blocks_tile_bytes(void);
+
 /* Many LS-EEND streams in one frame step (LsMultiStreamSession): the state touches of the LS frame step per slot (additive to
  * ABI version 5).  Row n belongs to sequence s = n / rows_per_seq (1 for encoder rows, C for decoder rows); len_dev / mask_dev
  * are int32 [S] in device memory, so a captured hipGraph stays valid from frame to frame.
