@@ -13,7 +13,7 @@
 //     half rows (256 / 512 contiguous bytes) leave through a staging tile as full 128-byte lines.
 #include "common.h"
 #include "kernels.h"
-#include "wstream.h"
+#include "wave_rows.h"
 
 namespace {
 
@@ -190,13 +190,13 @@ void conv_stream_kernel(const ConvStreamParams p) {
                 // f32 half rows: 8 chunks of 16 B at chunk g*8 + e of a 512-byte row
                 if ((frow >> 3) == half) {
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) *(f32x4*)(st + (frow & 7) * 512 + (((g * 8 + e) ^ (frow & 7)) << 4)) = acc[e][j] * rinv;
+                    for (int e = 0; e < 8; ++e) stage_put(st, frow, g, e, acc[e][j] * rinv);
                 }
                 wave_lds_sync();
 #pragma unroll
                 for (int ps = 0; ps < 4; ++ps) {
                     const int rr = lane >> 3, cc = (lane & 7) + 8 * ps;
-                    const f32x4 v = *(const f32x4*)(st + rr * 512 + ((cc ^ rr) << 4));
+                    const f32x4 v = stage_get<f32x4>(st, rr, cc);
                     if (rb + rr < tlim) *(f32x4*)(p.out32 + ((size_t)seq * p.Tp + t0 + rb + rr) * 256 + nh * 128 + cc * 4) = v;
                 }
                 wave_lds_sync();

@@ -21,7 +21,7 @@
 // Shipped for C = 3 and 6 only (eend_dec_stream_supported).
 #include "common.h"
 #include "kernels.h"
-#include "wstream.h"
+#include "wave_rows.h"
 
 namespace {
 
@@ -69,12 +69,6 @@ __global__ void dec_stream_pack_kernel(const _Float16* __restrict__ Wo1, const _
     }
 }
 
-template <int N>
-__device__ __forceinline__ float row_rot(float x) {          // value of the lane N places away inside the 16-lane row
-    if constexpr (N == 0) return x;
-    else return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x120 + N, 0xF, 0xF, false));
-}
-
 // ---------------------------------------------------------------------------------------------------------------
 // G frames per wave, R = 16/G slot positions per token fragment, C = 3R positions of which the first CC hold the model's slots (the
 // phantom positions read the last slot's rows, are masked as keys and never stored: spk_stream.hip).
@@ -100,7 +94,6 @@ void dec_stream_kernel(const DecStreamParams p) {
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, (M - 1) * p.lda * 2 + 512, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsR = __builtin_amdgcn_make_buffer_rsrc((void*)p.res16, 0, M * 512, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsO = __builtin_amdgcn_make_buffer_rsrc(p.out16, 0, M * 512, 0x00020000);
-    auto bload = [&](const __amdgpu_buffer_rsrc_t& r, int off) __attribute__((always_inline)) { return __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0); };
     WeightRing<NSLOT> ring(p.wstream, S, wave, lane);
     ring.prime();
 
@@ -127,16 +120,15 @@ void dec_stream_kernel(const DecStreamParams p) {
     f32x4 acc[16][NJ];                                    // Wo1 / Wo2 + W2 accumulators, features fo + i*4 + r
     f32x4 qkv[12][NJ];                                    // one head: [t*4 + ff], features g*16 + ff*4 + r of the head
     f16x8 xf[8][NJ];                                      // input fragments, then x1 (LN11), then x (LN21)
-    f16x8 ob[8][NJ];                                      // O of head h, features h*64 + g*16 + u*8 + e: ob[h*2 + u]
+    f16x8 ob[4][2][NJ];                                   // O of head h, features h*64 + g*16 + u*8 + e: ob[h][u]
     f32x4 h[2][NJ];
     f16x8 hbA[NJ], hbB[NJ];                               // hidden activations (W2 B operand), ping-pong
     f32x4 bcv[2];                                         // b1 of the half-chunk held in h
     f16x8 r8[NJ][8];                                      // residual rows of LayerNorm11
 
-    auto slot_of = [&](int j, int fr) __attribute__((always_inline)) { return j * R + fr / G; };
     auto row_tok = [&](int tile, int j, int fr) __attribute__((always_inline)) {
         const int b = tile / TPB, tt = tile - b * TPB;
-        int c = slot_of(j, fr);
+        int c = slot_of<G>(j, fr);
         if constexpr (!FULL) c = c < CC ? c : CC - 1;
         return (b * CC + c) * p.Tp + tt * (4 * G) + wave * G + (fr % G);
     };
@@ -157,13 +149,10 @@ void dec_stream_kernel(const DecStreamParams p) {
     __builtin_amdgcn_s_barrier();
     sfor<NJ>([&](auto J) __attribute__((always_inline)) { load_in_frags(blockIdx.x, J); });
 
-    auto act_cvt = [&](float v) __attribute__((always_inline)) -> _Float16 {
-        return (_Float16)__builtin_amdgcn_fmed3f(v, 0.f, 65504.f);       // ReLU + saturation in one instruction
-    };
     auto conv_part = [&](auto PART, f16x8 (&hbo)[NJ]) __attribute__((always_inline)) {          // part = hf * NJ + j  (2 NJ parts)
         constexpr int hf = decltype(PART)::value / NJ, j = decltype(PART)::value % NJ;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) hbo[j][hf * 4 + r] = act_cvt(h[hf][j][r]);
+        for (int r = 0; r < 4; ++r) hbo[j][hf * 4 + r] = relu_sat_f16(h[hf][j][r]);
     };
 
     // One stream item = 16 fragments, 3 MFMAs each:
@@ -175,66 +164,32 @@ void dec_stream_kernel(const DecStreamParams p) {
                     f16x8 (&hbo)[NJ]) __attribute__((always_inline)) {
         constexpr int kind = decltype(KIND)::value, src = decltype(SRCc)::value, vw = INFL + decltype(VWXc)::value;
         constexpr bool conv = decltype(CONVc)::value, cold = decltype(COLDc)::value, pfn = decltype(PFNc)::value;
-        wait_vm<vw>();
-        __builtin_amdgcn_s_barrier();
-        const char* wc = wl + ring.slot * SLOT;
-        const char* wn = wl + ring.next_slot() * SLOT;
-        const int sd = ring.refill_slot();
-        if constexpr (cold) {
-            sfor<PD>([&](auto Q) __attribute__((always_inline)) {
-                wf[decltype(Q)::value % NB] = *(const f16x8*)(wc + decltype(Q)::value * 1024);
-            });
-        }
-        if constexpr (kind == 3) {
-            bcv[0] = *(const f32x4*)(b1l + k * 32 + g * 4);
-            bcv[1] = *(const f32x4*)(b1l + k * 32 + 16 + g * 4);
-        }
-        sfor<8>([&](auto P2) __attribute__((always_inline)) {
-            sfor<2>([&](auto PH) __attribute__((always_inline)) {
-                constexpr int pi = decltype(P2)::value * 2 + decltype(PH)::value;
-                const f16x8 w = wf[pi % NB];
-                if constexpr (kind == 0) {
+        stream_item<vw, PD, cold, pfn>(ring, wf, wl, [&](auto PI, const f16x8 w) __attribute__((always_inline)) {
+            constexpr int pi = decltype(PI)::value, s_ = pi >> 1, hf = pi & 1;
+            auto& hv = h; auto& xv = xf; auto& bv = bcv;      // (wave_rows.h)
+            if constexpr (kind == 3 && pi == 0) {
+                bcv[0] = *(const f32x4*)(b1l + k * 32 + g * 4);
+                bcv[1] = *(const f32x4*)(b1l + k * 32 + 16 + g * 4);
+            }
 #pragma unroll
-                    for (int j = 0; j < NJ; ++j) acc[pi][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w, xf[src][j], acc[pi][j], 0, 0, 0);
-                } else if constexpr (kind == 1) {
-                    constexpr int s_ = pi >> 1, hf = pi & 1, idx = src * 2 + hf;
-#pragma unroll
-                    for (int j = 0; j < NJ; ++j)
-                        qkv[idx][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w, xf[s_][j], s_ == 0 ? f32x4{0.f, 0.f, 0.f, 0.f} : qkv[idx][j], 0, 0, 0);
-                } else if constexpr (kind == 2) {
-#pragma unroll
-                    for (int j = 0; j < NJ; ++j) acc[pi][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w, ob[src][j], acc[pi][j], 0, 0, 0);
-                } else if constexpr (kind == 3) {
+            for (int j = 0; j < NJ; ++j) {
+                if constexpr (kind == 0) acc[pi][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w, xf[src][j], acc[pi][j], 0, 0, 0);
+                else if constexpr (kind == 1)
+                    qkv[src * 2 + hf][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w, xf[s_][j], s_ == 0 ? f32x4{0.f, 0.f, 0.f, 0.f} : qkv[src * 2 + hf][j], 0, 0, 0);
+                else if constexpr (kind == 2) acc[pi][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w, ob[src >> 1][src & 1][j], acc[pi][j], 0, 0, 0);
+                else if constexpr (kind == 3) {
                     // VGPR-destination MFMA by hand, the first k-step starts from the bias (ffn_stream.hip)
-                    constexpr int s_ = pi >> 1, hf = pi & 1;
-#pragma unroll
-                    for (int j = 0; j < NJ; ++j) {
-                        if constexpr (s_ == 0)
-                            asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %3" : "=&v"(h[hf][j]) : "v"(w), "v"(xf[s_][j]), "v"(bcv[hf]));
-                        else
-                            asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(h[hf][j]) : "v"(w), "v"(xf[s_][j]));
-                    }
-                } else {
-#pragma unroll
-                    for (int j = 0; j < NJ; ++j) acc[pi][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w, hb[j], acc[pi][j], 0, 0, 0);
-                }
-                if constexpr (pi + PD < 16) wf[(pi + PD) % NB] = *(const f16x8*)(wc + (pi + PD) * 1024);
-                else if constexpr (pfn) wf[(pi + PD) % NB] = *(const f16x8*)(wn + (pi + PD - 16) * 1024);
-                if constexpr (pi < 4) ring.piece<pi>(sd);
-                if constexpr (kind == 4 && conv && pi >= 2 && pi < 2 + 4 * NJ && !(pi & 1)) conv_part(IC<(pi - 2) / 2>{}, hbo);
-            });
-            __builtin_amdgcn_sched_barrier(0);
+                    if constexpr (s_ == 0)
+                        asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %3" : "=&v"(hv[hf][j]) : "v"(w), "v"(xv[s_][j]), "v"(bv[hf]));
+                    else
+                        asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(hv[hf][j]) : "v"(w), "v"(xv[s_][j]));
+                } else acc[pi][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w, hb[j], acc[pi][j], 0, 0, 0);
+            }
+        }, [&](auto PI) __attribute__((always_inline)) {
+            constexpr int pi = decltype(PI)::value;
+            if constexpr (kind == 4 && conv && pi >= 2 && pi < 2 + 4 * NJ && !(pi & 1)) conv_part(IC<(pi - 2) / 2>{}, hbo);
         });
-        ring.advance();
-        ring.rotate();
     };
-    auto pin_acc = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i)
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) asm volatile("" : "+a"(acc[i][j]));
-    };
-
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         // (the lane index is recomputed from the exec mask at every phase boundary: nothing lane-dependent stays live -- or is
         // spilled -- across a phase, the thread index included)
@@ -256,7 +211,7 @@ void dec_stream_kernel(const DecStreamParams p) {
 #pragma unroll
             for (int j = 0; j < NJ; ++j) acc[i][j] = b4;
         }
-        pin_acc();
+        pin_acc(acc);
         // items 0..5: the tile's 24 input-row loads (first tile) or the previous tile's 24 output stores are younger than the pieces
         // they wait for
         step(IC<0>{}, IC<0>{}, Fa{}, T{}, T{}, IC<24>{}, 0, hbA, hbB);
@@ -268,25 +223,13 @@ void dec_stream_kernel(const DecStreamParams p) {
         step(IC<0>{}, IC<6>{}, Fa{}, Fa{}, T{}, IC<0>{}, 0, hbA, hbB);
         load_res16(tile, IC<0>{});
         step(IC<0>{}, IC<7>{}, Fa{}, Fa{}, Fa{}, IC<8>{}, 0, hbA, hbB);
-        pin_acc();
+        pin_acc(acc);
         relaunder();
         sfor<NJ>([&](auto J) __attribute__((always_inline)) {
             constexpr int j = decltype(J)::value;
             auto resv = [&](int i, int q) __attribute__((always_inline)) { return (float)r8[j][i >> 1][(i & 1) * 4 + q]; };
-            f32x2 sm = f32x2{0.f, 0.f}, sq2 = f32x2{0.f, 0.f};
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const f32x4 a4 = acc[i][j];
-                const f32x2 x0 = f32x2{a4[0] + resv(i, 0), a4[1] + resv(i, 1)};
-                const f32x2 x1 = f32x2{a4[2] + resv(i, 2), a4[3] + resv(i, 3)};
-                sm += x0 + x1;
-                sq2 = x1 * x1 + (x0 * x0 + sq2);
-            }
-            const float sum = wave_g_allreduce_add(sm[0] + sm[1]);
-            const float sqs = wave_g_allreduce_add(sq2[0] + sq2[1]);
-            const float mean = sum * (1.0f / 256);
-            const float var = __builtin_fmaxf(sqs * (1.0f / 256) - mean * mean, 0.f);
-            const float rstd = 1.0f / __builtin_sqrtf(var + p.eps11);
+            const LnStats ln = ln_stats_1pass([&](int i, int q) __attribute__((always_inline)) { return acc[i][j][q] + resv(i, q); }, p.eps11);
+            const float mean = ln.mean, rstd = ln.rstd;
             __builtin_amdgcn_sched_barrier(0);
             if constexpr (j + 1 < NJ) load_res16(tile, IC<j + 1>{});
 #pragma unroll
@@ -306,13 +249,7 @@ void dec_stream_kernel(const DecStreamParams p) {
 
         // ---- per head: q, k, v of the wave's 48 tokens (6 items), then the C x C attention of its frames in registers -> ob
         float kbias[FULL ? 1 : C];
-        if constexpr (!FULL) {
-            sfor<NJ>([&](auto J2) __attribute__((always_inline)) {
-                constexpr int j2 = decltype(J2)::value;
-                const float own = slot_of(j2, frow) < CC ? 0.f : -1e30f;
-                sfor<R>([&](auto D) __attribute__((always_inline)) { kbias[j2 * R + decltype(D)::value] = row_rot<decltype(D)::value * G>(own); });
-            });
-        }
+        slot_kbias<G, CC, NJ>(kbias, frow);
         sfor<4>([&](auto HEAD) __attribute__((always_inline)) {
             constexpr int head = decltype(HEAD)::value;
             // head 0: the residual loads of fragments 1, 2 (16) are younger than the pieces its waits need
@@ -324,82 +261,7 @@ void dec_stream_kernel(const DecStreamParams p) {
             step(IC<1>{}, IC<4>{}, Fa{}, Fa{}, T{}, IC<yng>{}, 0, hbA, hbB);
             step(IC<1>{}, IC<5>{}, Fa{}, Fa{}, Fa{}, IC<yng>{}, 0, hbA, hbB);
 
-            const float* bq = vecs + V_BQ * 256 + head * 64 + g * 16;
-            const float* bv = vecs + V_BV * 256 + head * 64 + g * 16;
-            f32x4 bnext = *(const f32x4*)bq;
-            f32x2 s2[NJ][C];
-#pragma unroll
-            for (int a = 0; a < NJ; ++a)
-#pragma unroll
-                for (int c = 0; c < C; ++c) s2[a][c] = f32x2{0.f, 0.f};
-            sfor<4>([&](auto FF) __attribute__((always_inline)) {
-                constexpr int ff = decltype(FF)::value;
-                const f32x4 b4 = bnext;
-                bnext = ff < 3 ? *(const f32x4*)(bq + (ff + 1) * 4) : *(const f32x4*)bv;
-                f32x2 q[NJ][2];
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) {
-                    const f32x4 t = (qkv[ff][j] + b4) * p.scale;
-                    q[j][0] = f32x2{t[0], t[1]}; q[j][1] = f32x2{t[2], t[3]};
-                }
-                sfor<NJ>([&](auto J2) __attribute__((always_inline)) {
-                    constexpr int j2 = decltype(J2)::value;
-                    const f32x4 k = qkv[4 + ff][j2];
-                    sfor<R>([&](auto D) __attribute__((always_inline)) {
-                        constexpr int d = decltype(D)::value;
-                        const f32x2 k0 = f32x2{row_rot<d * G>(k[0]), row_rot<d * G>(k[1])};
-                        const f32x2 k1 = f32x2{row_rot<d * G>(k[2]), row_rot<d * G>(k[3])};
-#pragma unroll
-                        for (int j1 = 0; j1 < NJ; ++j1) s2[j1][j2 * R + d] = q[j1][1] * k1 + (q[j1][0] * k0 + s2[j1][j2 * R + d]);
-                    });
-                });
-            });
-            float s[NJ][C];
-#pragma unroll
-            for (int a = 0; a < NJ; ++a) {
-                float mx = -INFINITY, den = 0.f;
-#pragma unroll
-                for (int c = 0; c < C; ++c) {
-                    s[a][c] = s2[a][c][0] + s2[a][c][1];
-                    if constexpr (!FULL) s[a][c] += kbias[c];
-                    s[a][c] = wave_g_allreduce_add(s[a][c]);
-                    mx = __builtin_fmaxf(mx, s[a][c]);
-                }
-#pragma unroll
-                for (int c = 0; c < C; ++c) { s[a][c] = __expf(s[a][c] - mx); den += s[a][c]; }
-                const float inv = __builtin_amdgcn_rcpf(den);
-#pragma unroll
-                for (int c = 0; c < C; ++c) s[a][c] *= inv;
-            }
-            sfor<4>([&](auto FF) __attribute__((always_inline)) {
-                constexpr int ff = decltype(FF)::value;
-                const f32x4 b4 = bnext;
-                if constexpr (ff < 3) bnext = *(const f32x4*)(bv + (ff + 1) * 4);
-                f32x2 o[NJ][2];
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) { o[j][0] = f32x2{b4[0], b4[1]}; o[j][1] = f32x2{b4[2], b4[3]}; }
-                sfor<NJ>([&](auto J2) __attribute__((always_inline)) {
-                    constexpr int j2 = decltype(J2)::value;
-                    const f32x4 vv = qkv[8 + ff][j2];
-                    sfor<R>([&](auto D) __attribute__((always_inline)) {
-                        constexpr int d = decltype(D)::value;
-                        const f32x2 v0 = f32x2{row_rot<d * G>(vv[0]), row_rot<d * G>(vv[1])};
-                        const f32x2 v1 = f32x2{row_rot<d * G>(vv[2]), row_rot<d * G>(vv[3])};
-#pragma unroll
-                        for (int j1 = 0; j1 < NJ; ++j1) {
-                            const f32x2 pw = f32x2{s[j1][j2 * R + d], s[j1][j2 * R + d]};
-                            o[j1][0] = pw * v0 + o[j1][0];
-                            o[j1][1] = pw * v1 + o[j1][1];
-                        }
-                    });
-                });
-                constexpr int ui = head * 2 + (ff >> 1);
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) {
-                    ob[ui][j][(ff & 1) * 4 + 0] = to_f16_sat(o[j][0][0]); ob[ui][j][(ff & 1) * 4 + 1] = to_f16_sat(o[j][0][1]);
-                    ob[ui][j][(ff & 1) * 4 + 2] = to_f16_sat(o[j][1][0]); ob[ui][j][(ff & 1) * 4 + 3] = to_f16_sat(o[j][1][1]);
-                }
-            });
+            slot_attention<G, CC>(qkv, vecs + V_BQ * 256 + head * 64 + g * 16, vecs + V_BV * 256 + head * 64 + g * 16, p.scale, kbias, ob[head]);
             __builtin_amdgcn_sched_barrier(0);
         });
 
@@ -411,7 +273,7 @@ void dec_stream_kernel(const DecStreamParams p) {
 #pragma unroll
             for (int j = 0; j < NJ; ++j) acc[i][j] = b4;
         }
-        pin_acc();
+        pin_acc(acc);
         step(IC<2>{}, IC<0>{}, Fa{}, T{}, T{}, IC<0>{}, 0, hbA, hbB);
         step(IC<2>{}, IC<1>{}, Fa{}, Fa{}, T{}, IC<0>{}, 0, hbA, hbB);
         step(IC<2>{}, IC<2>{}, Fa{}, Fa{}, T{}, IC<0>{}, 0, hbA, hbB);
@@ -420,22 +282,13 @@ void dec_stream_kernel(const DecStreamParams p) {
         step(IC<2>{}, IC<5>{}, Fa{}, Fa{}, T{}, IC<0>{}, 0, hbA, hbB);
         step(IC<2>{}, IC<6>{}, Fa{}, Fa{}, T{}, IC<0>{}, 0, hbA, hbB);
         step(IC<2>{}, IC<7>{}, Fa{}, Fa{}, Fa{}, IC<0>{}, 0, hbA, hbB);
-        pin_acc();
+        pin_acc(acc);
         relaunder();
         sfor<NJ>([&](auto J) __attribute__((always_inline)) {
             constexpr int j = decltype(J)::value;
             auto xval = [&](int i, int q) __attribute__((always_inline)) { return acc[i][j][q] + (float)xf[i >> 1][j][(i & 1) * 4 + q]; };
-            f32x2 sm = f32x2{0.f, 0.f}, sq2 = f32x2{0.f, 0.f};
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const f32x2 x0 = f32x2{xval(i, 0), xval(i, 1)}, x1 = f32x2{xval(i, 2), xval(i, 3)};
-                sm += x0 + x1;
-                sq2 = x1 * x1 + (x0 * x0 + sq2);
-            }
-            const float sum = wave_g_allreduce_add(sm[0] + sm[1]);
-            const float sqs = wave_g_allreduce_add(sq2[0] + sq2[1]);
-            const float mean = sum * (1.0f / 256);
-            const float rstd = 1.0f / __builtin_sqrtf(__builtin_fmaxf(sqs * (1.0f / 256) - mean * mean, 0.f) + p.eps21);
+            const LnStats ln = ln_stats_1pass(xval, p.eps21);
+            const float mean = ln.mean, rstd = ln.rstd;
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
@@ -454,7 +307,7 @@ void dec_stream_kernel(const DecStreamParams p) {
 
         // ---- FFN: item k = { h = W1h(k) x | acc += W2h(k-1) hb(k-1), hb(k) = ReLU(h + b1) }, k = 0 .. U   (ffn_stream.hip)
         relaunder();
-        pin_acc();
+        pin_acc(acc);
         step(IC<3>{}, IC<0>{}, Fa{}, T{}, Fa{}, IC<0>{}, 0, hbA, hbB);
         asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");      // the hand-written MFMAs' results are read by VALU instructions next
         sfor<2 * NJ>([&](auto Q) __attribute__((always_inline)) { conv_part(Q, hbA); });
@@ -471,7 +324,7 @@ void dec_stream_kernel(const DecStreamParams p) {
         sfor<NJ>([&](auto J) __attribute__((always_inline)) { load_in_frags(ntile, J); });
         step(IC<4>{}, IC<0>{}, T{}, Fa{}, T{}, IC<8 * NJ>{}, 0, hbA, hbB);          // W2h(U-2) x hbA, h(U-1) -> hbB
         step(IC<4>{}, IC<0>{}, Fa{}, Fa{}, Fa{}, IC<8 * NJ>{}, 0, hbB, hbA);        // W2h(U-1) x hbB
-        pin_acc();
+        pin_acc(acc);
 
         // ---- epilogue, one token fragment at a time: LayerNorm22; rows leave through the wave's 2-KB staging tile as whole
         // 512-byte rows, four at a time; phantom slot rows get an offset beyond the buffer and are dropped
@@ -479,18 +332,8 @@ void dec_stream_kernel(const DecStreamParams p) {
         char* st = smem + STAGE + wave * 2048;
         sfor<NJ>([&](auto J) __attribute__((always_inline)) {
             constexpr int j = decltype(J)::value;
-            f32x2 sm = f32x2{0.f, 0.f}, sq2 = f32x2{0.f, 0.f};
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const f32x4 a4 = acc[i][j];
-                const f32x2 x0 = f32x2{a4[0], a4[1]}, x1 = f32x2{a4[2], a4[3]};
-                sm += x0 + x1;
-                sq2 = x1 * x1 + (x0 * x0 + sq2);
-            }
-            const float sum = wave_g_allreduce_add(sm[0] + sm[1]);
-            const float sqs = wave_g_allreduce_add(sq2[0] + sq2[1]);
-            const float mean = sum * (1.0f / 256);
-            const float rstd = 1.0f / __builtin_sqrtf(__builtin_fmaxf(sqs * (1.0f / 256) - mean * mean, 0.f) + p.eps22);
+            const LnStats ln = ln_stats_1pass([&](int i, int q) __attribute__((always_inline)) { return acc[i][j][q]; }, p.eps22);
+            const float mean = ln.mean, rstd = ln.rstd;
             __builtin_amdgcn_sched_barrier(0);
             f16x8 o[8];
 #pragma unroll
@@ -512,7 +355,7 @@ void dec_stream_kernel(const DecStreamParams p) {
                 for (int q2 = 0; q2 < 2; ++q2) {
                     const int rr = 2 * q2 + (lane >> 5), cc = lane & 31, fr = qr * 4 + rr;
                     const f16x8 v = *(const f16x8*)(st + rr * 512 + ((cc ^ rr) << 4));
-                    const int off = (FULL || slot_of(j, fr) < CC) ? row_tok(tile, j, fr) * 512 + cc * 16 : 0x7FFFFFF0;
+                    const int off = (FULL || slot_of<G>(j, fr) < CC) ? row_tok(tile, j, fr) * 512 + cc * 16 : 0x7FFFFFF0;
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsO, off, 0, 0);
                 }
                 wave_lds_sync();

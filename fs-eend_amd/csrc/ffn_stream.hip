@@ -22,7 +22,7 @@
 //     the Hs exchange on top), which was its measured bound.
 #include "common.h"
 #include "kernels.h"
-#include "wstream.h"
+#include "wave_rows.h"
 #include <cstdlib>
 
 #include <atomic>
@@ -130,7 +130,6 @@ void ffn_stream_kernel(const FfnStreamParams p) {
     const __amdgpu_buffer_rsrc_t rsO16 = __builtin_amdgcn_make_buffer_rsrc(p.out16, 0, p.M * 512, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsO32 = __builtin_amdgcn_make_buffer_rsrc((void*)p.out32, 0, p.out32 ? p.M * 1024 : 0, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsO16L = __builtin_amdgcn_make_buffer_rsrc(p.out16lo, 0, LO && p.out16lo ? p.M * 512 : 0, 0x00020000);
-    auto bload = [&](const __amdgpu_buffer_rsrc_t& r, int off) __attribute__((always_inline)) { return __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0); };
 #ifdef EEND_FS_TRACE
     int tix = -1;
 #endif
@@ -184,7 +183,7 @@ void ffn_stream_kernel(const FfnStreamParams p) {
     if (blockIdx.x < ntiles) { sfor<NJ>([&](auto J) __attribute__((always_inline)) { load_in_frags(blockIdx.x, J); }); load_res16(blockIdx.x, IC<0>{}); }
 
     auto act_cvt = [&](float v) __attribute__((always_inline)) -> _Float16 {
-        if (ACT == 1) return (_Float16)__builtin_amdgcn_fmed3f(v, 0.f, 65504.f);       // ReLU + saturation in one instruction
+        if (ACT == 1) return relu_sat_f16(v);
         v = v / (1.0f + __expf(-v));
         return (_Float16)__builtin_fminf(__builtin_fmaxf(v, -65504.f), 65504.f);
     };
@@ -207,57 +206,37 @@ void ffn_stream_kernel(const FfnStreamParams p) {
         constexpr bool pfn = decltype(PFNc)::value;      // request the next item's first fragments (not in front of a VALU phase)
         if (loose) wait_vm<LOOSE>();
         else wait_vm<vw>();
-        __builtin_amdgcn_s_barrier();
-        const char* wc = wl + ring.slot * SLOT;
-        const char* wn = wl + ring.next_slot() * SLOT;
-        const int sd = ring.refill_slot();
-        if constexpr (cold) {
-            sfor<PD>([&](auto Q) __attribute__((always_inline)) {
-                wf[decltype(Q)::value % NB] = *(const f16x8*)(wc + decltype(Q)::value * 1024);
-            });
-        }
-        if constexpr (kind == 1) {
-            bcv[0] = *(const f32x4*)(b1l + k * 32 + g * 4);
-            bcv[1] = *(const f32x4*)(b1l + k * 32 + 16 + g * 4);
-        }
-        sfor<8>([&](auto P2) __attribute__((always_inline)) {
-            sfor<2>([&](auto PH) __attribute__((always_inline)) {
-                constexpr int pi = decltype(P2)::value * 2 + decltype(PH)::value;
-                const f16x8 w = wf[pi % NB];
-                if constexpr (kind == 0) {
+        stream_item_waited<PD, cold, pfn>(ring, wf, wl, [&](auto PI, const f16x8 w) __attribute__((always_inline)) {
+            constexpr int pi = decltype(PI)::value, s_ = pi >> 1, hf = pi & 1;
+            auto& hv = h; auto& xv = xf; auto& bv = bcv;      // (wave_rows.h)
+            if constexpr (kind == 1 && pi == 0) {
+                bcv[0] = *(const f32x4*)(b1l + k * 32 + g * 4);
+                bcv[1] = *(const f32x4*)(b1l + k * 32 + 16 + g * 4);
+            }
 #pragma unroll
-                    for (int j = 0; j < NJ; ++j) acc[pi][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w, xf[src][j], acc[pi][j], 0, 0, 0);
-                } else if constexpr (kind == 1) {
+            for (int j = 0; j < NJ; ++j) {
+                if constexpr (kind == 0) acc[pi][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w, xf[src][j], acc[pi][j], 0, 0, 0);
+                else if constexpr (kind == 1) {
                     // GEMM1 accumulates in VGPRs (the activation reads them with VALU instructions; hipcc would put every MFMA
                     // result of a 512-register kernel in the accumulator half and copy it out): VGPR-destination MFMA by hand,
                     // the first k-step starts from the bias.  Their first VALU reader is a whole item later.
-                    constexpr int s_ = pi >> 1, hf = pi & 1;
-#pragma unroll
-                    for (int j = 0; j < NJ; ++j) {
-                        if constexpr (s_ == 0)
-                            asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %3" : "=&v"(h[hf][j]) : "v"(w), "v"(xf[s_][j]), "v"(bcv[hf]));
-                        else
-                            asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(h[hf][j]) : "v"(w), "v"(xf[s_][j]));
-                    }
+                    if constexpr (s_ == 0)
+                        asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %3" : "=&v"(hv[hf][j]) : "v"(w), "v"(xv[s_][j]), "v"(bv[hf]));
+                    else
+                        asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(hv[hf][j]) : "v"(w), "v"(xv[s_][j]));
                 } else {
                     // (hand-written accumulator-tied MFMAs here and in kind 0 were tried to stop hipcc permuting the 192 accumulator
                     // registers at the phase boundaries: same speed, and their operand hazards are not padded -- builtin kept)
-#pragma unroll
-                    for (int j = 0; j < NJ; ++j) acc[pi][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w, hb[j], acc[pi][j], 0, 0, 0);
+                    acc[pi][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w, hb[j], acc[pi][j], 0, 0, 0);
                 }
-                if constexpr (pi + PD < 16) wf[(pi + PD) % NB] = *(const f16x8*)(wc + (pi + PD) * 1024);
-                else if constexpr (pfn) wf[(pi + PD) % NB] = *(const f16x8*)(wn + (pi + PD - 16) * 1024);
-                // the 4 DMA pieces of the item NSLOT-1 ahead, on fragments 0 .. 3
-                if constexpr (pi < 4) ring.piece<pi>(sd);
-                // activation of the half-chunk held in h (6 fragment parts) on fragments 2, 4, ..., 12
-                if constexpr (kind == 2 && conv && pi >= 2 && pi < 2 + 4 * NJ && !(pi & 1)) conv_part(IC<(pi - 2) / 2>{}, hbo);
-            });
-            __builtin_amdgcn_sched_barrier(0);
+            }
+        }, [&](auto PI) __attribute__((always_inline)) {      // activation of the half-chunk held in h (2 NJ fragment parts) on fragments 2, 4, ...
+            constexpr int pi = decltype(PI)::value;
+            if constexpr (kind == 2 && conv && pi >= 2 && pi < 2 + 4 * NJ && !(pi & 1)) conv_part(IC<(pi - 2) / 2>{}, hbo);
         });
-        ring.advance();
-        ring.rotate();
     };
-    // the accumulators sit in the accumulator half of the register file whenever matrix work is about to run on them
+    // the accumulators sit in the accumulator half of the register file whenever matrix work is about to run on them (local: with
+    // wave_rows.h's pin_acc the three MODE 1, NJ = 3 kernels place their accumulator copies differently)
     auto pin_acc = [&](int where) __attribute__((always_inline)) {
         {
 #pragma unroll
@@ -341,17 +320,8 @@ void ffn_stream_kernel(const FfnStreamParams p) {
                     if constexpr (RES16) return acc[i][j][q] + (float)r8[j][i >> 1][(i & 1) * 4 + q];
                     else return acc[i][j][q] + t4[i][q];
                 };
-                f32x2 sm = f32x2{0.f, 0.f}, sq2 = f32x2{0.f, 0.f};
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const f32x2 x0 = f32x2{xval(i, 0), xval(i, 1)}, x1 = f32x2{xval(i, 2), xval(i, 3)};
-                    sm += x0 + x1;
-                    sq2 = x1 * x1 + (x0 * x0 + sq2);
-                }
-                const float sum = wave_g_allreduce_add(sm[0] + sm[1]);
-                const float sqs = wave_g_allreduce_add(sq2[0] + sq2[1]);
-                const float mean = sum * (1.0f / 256);
-                const float rstd = 1.0f / __builtin_sqrtf(__builtin_fmaxf(sqs * (1.0f / 256) - mean * mean, 0.f) + p.eps1);
+                const LnStats ln = ln_stats_1pass(xval, p.eps1);
+                const float mean = ln.mean, rstd = ln.rstd;
                 __builtin_amdgcn_sched_barrier(0);
                 if constexpr (RES16) {
                     if constexpr (j == 0) { load_res16(tile, IC<1>{}); if constexpr (NJ > 2) load_res16(tile, IC<2>{}); }
@@ -426,6 +396,8 @@ void ffn_stream_kernel(const FfnStreamParams p) {
             constexpr int j = decltype(J)::value;
             const int rbase = tile * TM + wave * WM + j * 16;
             // two passes over the accumulators, no 64-value buffer (see LayerNorm1)
+            // (spelled out, not ln_stats_1pass: behind a callable the acc * alpha product is shared with out32_val's, the register
+            // counts of most instantiations move and the MODE 1, NJ = 3 kernels spill)
             f32x2 sm = f32x2{0.f, 0.f}, sq2 = f32x2{0.f, 0.f};
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
@@ -458,13 +430,13 @@ void ffn_stream_kernel(const FfnStreamParams p) {
             for (int half = 0; half < 2; ++half) {          // token rows 0..7 / 8..15 of the fragment
                 if ((frow >> 3) == half) {
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) *(f16x8*)(st + (frow & 7) * 512 + (((g * 8 + e) ^ (frow & 7)) << 4)) = o[e];
+                    for (int e = 0; e < 8; ++e) stage_put(st, frow, g, e, o[e]);
                 }
                 wave_lds_sync();
 #pragma unroll
                 for (int q4 = 0; q4 < 4; ++q4) {
                     const int rr = 2 * q4 + (lane >> 5), cc = lane & 31;
-                    const f16x8 v = *(const f16x8*)(st + rr * 512 + ((cc ^ rr) << 4));      // (same type as the writes: no type-based reordering)
+                    const f16x8 v = stage_get<f16x8>(st, rr, cc);
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsO16, (rbase + half * 8 + rr) * 512 + cc * 16, 0, 0);
                 }
                 wave_lds_sync();
@@ -485,13 +457,13 @@ void ffn_stream_kernel(const FfnStreamParams p) {
                 for (int half = 0; half < 2; ++half) {
                     if ((frow >> 3) == half) {
 #pragma unroll
-                        for (int e = 0; e < 8; ++e) *(f16x8*)(st + (frow & 7) * 512 + (((g * 8 + e) ^ (frow & 7)) << 4)) = o[e];
+                        for (int e = 0; e < 8; ++e) stage_put(st, frow, g, e, o[e]);
                     }
                     wave_lds_sync();
 #pragma unroll
                     for (int q4 = 0; q4 < 4; ++q4) {
                         const int rr = 2 * q4 + (lane >> 5), cc = lane & 31;
-                        const f16x8 v = *(const f16x8*)(st + rr * 512 + ((cc ^ rr) << 4));
+                        const f16x8 v = stage_get<f16x8>(st, rr, cc);
                         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsO16L, (rbase + half * 8 + rr) * 512 + cc * 16, 0, 0);
                     }
                     wave_lds_sync();
@@ -505,14 +477,13 @@ void ffn_stream_kernel(const FfnStreamParams p) {
                         if ((frow >> 3) == half) {
 #pragma unroll
                             for (int e = 0; e < 8; ++e)
-                                *(f32x4*)(st + (frow & 7) * 512 + (((g * 8 + e) ^ (frow & 7)) << 4)) =
-                                    f32x4{out32_val(fh * 8 + e, 0), out32_val(fh * 8 + e, 1), out32_val(fh * 8 + e, 2), out32_val(fh * 8 + e, 3)};
+                                stage_put(st, frow, g, e, f32x4{out32_val(fh * 8 + e, 0), out32_val(fh * 8 + e, 1), out32_val(fh * 8 + e, 2), out32_val(fh * 8 + e, 3)});
                         }
                         wave_lds_sync();
 #pragma unroll
                         for (int q4 = 0; q4 < 4; ++q4) {
                             const int rr = 2 * q4 + (lane >> 5), cc = lane & 31;
-                            const f32x4 v = *(const f32x4*)(st + rr * 512 + ((cc ^ rr) << 4));
+                            const f32x4 v = stage_get<f32x4>(st, rr, cc);
                             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsO32,
                                                                    (rbase + half * 8 + rr) * 1024 + (cc >> 3) * 256 + fh * 128 + (cc & 7) * 16, 0, 0);
                         }

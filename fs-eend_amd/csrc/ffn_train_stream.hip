@@ -28,7 +28,7 @@
 //     account for them (two of the last three converting items' accesses are assumed younger than the awaited pieces: conservative by one).
 #include "common.h"
 #include "kernels.h"
-#include "wstream.h"
+#include "wave_rows.h"
 
 namespace {
 
@@ -109,7 +109,6 @@ void ffn_train_stream_kernel(const FfnTrainStreamParams p) {
     const unsigned hid_bytes = (unsigned)((p.M + 15) & ~15) * (unsigned)p.F * 2u;        // whole 16-row blocks
     const __amdgpu_buffer_rsrc_t rsH = __builtin_amdgcn_make_buffer_rsrc(p.hid, 0, hid_bytes, 0x00020000);                   // TR 1: written; TR 2: the mask
     const __amdgpu_buffer_rsrc_t rsDH = __builtin_amdgcn_make_buffer_rsrc(p.dH, 0, FWD ? 0u : hid_bytes, 0x00020000);
-    auto bload = [&](const __amdgpu_buffer_rsrc_t& r, int off) __attribute__((always_inline)) { return __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0); };
     WeightRing<NSLOT> ring(p.wstream, S, wave, lane);
     ring.prime();
 
@@ -196,68 +195,38 @@ void ffn_train_stream_kernel(const FfnTrainStreamParams p) {
             case VW_LAST1: wait_vm<LAST1>(); break;
             default: wait_vm<STEADY>(); break;
         }
-        __builtin_amdgcn_s_barrier();
-        const char* wc = wl + ring.slot * SLOT;
-        const char* wn = wl + ring.next_slot() * SLOT;
-        const int sd = ring.refill_slot();
-        if constexpr (cold) {
-            sfor<PD>([&](auto Q) __attribute__((always_inline)) {
-                wf[decltype(Q)::value % NB] = *(const T8*)(wc + decltype(Q)::value * 1024);
-            });
-        }
-        if constexpr (kind == 1) {
-            if constexpr (FWD) {
-                bcv[0] = *(const f32x4*)(b1l + k * 32 + g * 8);
-                bcv[1] = *(const f32x4*)(b1l + k * 32 + g * 8 + 4);
-            } else {
-                bcv[0] = f32x4{0.f, 0.f, 0.f, 0.f};
-                bcv[1] = bcv[0];
-            }
-        }
-        sfor<8>([&](auto P2) __attribute__((always_inline)) {
-            sfor<2>([&](auto PH) __attribute__((always_inline)) {
-                constexpr int pi = decltype(P2)::value * 2 + decltype(PH)::value;
-                const T8 w = wf[pi % NB];
-                if constexpr (kind == 1) {
-                    constexpr int s_ = pi >> 1, hf = pi & 1;
-#pragma unroll
-                    for (int j = 0; j < NJ; ++j) {
-                        if constexpr (FWD) {
-                            if constexpr (s_ == 0)
-                                asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %3" : "=&v"(h[hf][j]) : "v"(w), "v"(xf[s_][j]), "v"(bcv[hf]));
-                            else
-                                asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(h[hf][j]) : "v"(w), "v"(xf[s_][j]));
-                        } else {
-                            if constexpr (s_ == 0)
-                                asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %3" : "=&v"(h[hf][j]) : "v"(w), "v"(xf[s_][j]), "v"(bcv[hf]));
-                            else
-                                asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(h[hf][j]) : "v"(w), "v"(xf[s_][j]));
-                        }
-                    }
+        stream_item_waited<PD, cold, pfn>(ring, wf, wl, [&](auto PI, const T8 w) __attribute__((always_inline)) {
+            constexpr int pi = decltype(PI)::value, s_ = pi >> 1, hf = pi & 1;
+            auto& hv = h; auto& xv = xf; auto& bv = bcv;      // (wave_rows.h)
+            if constexpr (kind == 1 && pi == 0) {
+                if constexpr (FWD) {
+                    bcv[0] = *(const f32x4*)(b1l + k * 32 + g * 8);
+                    bcv[1] = *(const f32x4*)(b1l + k * 32 + g * 8 + 4);
                 } else {
-#pragma unroll
-                    for (int j = 0; j < NJ; ++j) {
-                        if constexpr (FWD) acc[pi][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w, hb[j], acc[pi][j], 0, 0, 0);
-                        else acc[pi][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, hb[j], acc[pi][j], 0, 0, 0);
-                    }
+                    bcv[0] = f32x4{0.f, 0.f, 0.f, 0.f};
+                    bcv[1] = bcv[0];
                 }
-                if constexpr (pi + PD < 16) wf[(pi + PD) % NB] = *(const T8*)(wc + (pi + PD) * 1024);
-                else if constexpr (pfn) wf[(pi + PD) % NB] = *(const T8*)(wn + (pi + PD - 16) * 1024);
-                if constexpr (pi < 4) ring.piece<pi>(sd);
-                // conversion of the half-chunk held in h (2 NJ parts) on fragments 4, 6, ...: behind the item's DMA pieces
-                if constexpr (kind == 2 && conv && pi >= 4 && pi < 4 + 4 * NJ && !(pi & 1)) conv_part(IC<(pi - 4) / 2>{}, PARc, hbo, kc);
-
-            });
-            __builtin_amdgcn_sched_barrier(0);
+            }
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+                if constexpr (kind == 1 && FWD) {
+                    if constexpr (s_ == 0)
+                        asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %3" : "=&v"(hv[hf][j]) : "v"(w), "v"(xv[s_][j]), "v"(bv[hf]));
+                    else
+                        asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(hv[hf][j]) : "v"(w), "v"(xv[s_][j]));
+                } else if constexpr (kind == 1) {
+                    if constexpr (s_ == 0)
+                        asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %3" : "=&v"(hv[hf][j]) : "v"(w), "v"(xv[s_][j]), "v"(bv[hf]));
+                    else
+                        asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(hv[hf][j]) : "v"(w), "v"(xv[s_][j]));
+                } else if constexpr (FWD) acc[pi][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w, hb[j], acc[pi][j], 0, 0, 0);
+                else acc[pi][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, hb[j], acc[pi][j], 0, 0, 0);
+            }
+        }, [&](auto PI) __attribute__((always_inline)) {
+            // conversion of the half-chunk held in h (2 NJ parts) on fragments 4, 6, ...: behind the item's DMA pieces
+            constexpr int pi = decltype(PI)::value;
+            if constexpr (kind == 2 && conv && pi >= 4 && pi < 4 + 4 * NJ && !(pi & 1)) conv_part(IC<(pi - 4) / 2>{}, PARc, hbo, kc);
         });
-        ring.advance();
-        ring.rotate();
-    };
-    auto pin_acc = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i)
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) asm volatile("" : "+a"(acc[i][j]));
     };
 
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
@@ -306,7 +275,7 @@ void ffn_train_stream_kernel(const FfnTrainStreamParams p) {
         {
             using T = std::true_type;
             using Fa = std::false_type;
-            pin_acc();
+            pin_acc(acc);
             step(IC<1>{}, Fa{}, IC<0>{}, T{}, Fa{}, VW_LOOSE, 0, 0, hbA, hbB);
             asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");      // the hand-written MFMAs' results are read by VALU instructions next
             sfor<2 * NJ>([&](auto Q) __attribute__((always_inline)) { conv_part(Q, IC<0>{}, hbA, 0); });
@@ -324,7 +293,7 @@ void ffn_train_stream_kernel(const FfnTrainStreamParams p) {
             step(IC<2>{}, T{}, IC<1>{}, Fa{}, T{}, n < 6 ? VW_LOOSE : VW_LAST2, 0, U - 1, hbA, hbB);
             load_res(IC<0>{});
             step(IC<2>{}, Fa{}, IC<0>{}, Fa{}, Fa{}, n + 1 < 6 ? VW_LOOSE : VW_LAST1, 0, 0, hbB, hbA);
-            pin_acc();
+            pin_acc(acc);
         }
 
         // ---- epilogue, one token fragment at a time; rows leave through the wave's 4-KB staging tile as whole rows
@@ -339,14 +308,13 @@ void ffn_train_stream_kernel(const FfnTrainStreamParams p) {
                     if ((frow >> 3) == half) {
 #pragma unroll
                         for (int e = 0; e < 8; ++e)
-                            *(f32x4*)(st + (frow & 7) * 512 + (((g * 8 + e) ^ (frow & 7)) << 4)) =
-                                f32x4{val(fh * 8 + e, 0), val(fh * 8 + e, 1), val(fh * 8 + e, 2), val(fh * 8 + e, 3)};
+                            stage_put(st, frow, g, e, f32x4{val(fh * 8 + e, 0), val(fh * 8 + e, 1), val(fh * 8 + e, 2), val(fh * 8 + e, 3)});
                     }
                     wave_lds_sync();
 #pragma unroll
                     for (int q4 = 0; q4 < 4; ++q4) {
                         const int rr = 2 * q4 + (lane >> 5), cc = lane & 31;
-                        const f32x4 v = *(const f32x4*)(st + rr * 512 + ((cc ^ rr) << 4));
+                        const f32x4 v = stage_get<f32x4>(st, rr, cc);
                         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsO32,
                                                                (rbase + half * 8 + rr) * 1024 + (cc >> 3) * 256 + fh * 128 + (cc & 7) * 16, 0, 0);
                     }
@@ -358,13 +326,13 @@ void ffn_train_stream_kernel(const FfnTrainStreamParams p) {
             for (int half = 0; half < 2; ++half) {
                 if ((frow >> 3) == half) {
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) *(f16x8*)(st + (frow & 7) * 512 + (((g * 8 + e) ^ (frow & 7)) << 4)) = o[e];
+                    for (int e = 0; e < 8; ++e) stage_put(st, frow, g, e, o[e]);
                 }
                 wave_lds_sync();
 #pragma unroll
                 for (int q4 = 0; q4 < 4; ++q4) {
                     const int rr = 2 * q4 + (lane >> 5), cc = lane & 31;
-                    const f16x8 v = *(const f16x8*)(st + rr * 512 + ((cc ^ rr) << 4));
+                    const f16x8 v = stage_get<f16x8>(st, rr, cc);
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsrc, (rbase + half * 8 + rr) * 512 + cc * 16, 0, 0);
                 }
                 wave_lds_sync();

@@ -13,7 +13,7 @@
 // passes per 16 rows with their loads exposed, and the accumulators spilling.  Not kept; the caller runs the two launches.)
 #include "common.h"
 #include "kernels.h"
-#include "wstream.h"
+#include "wave_rows.h"
 
 namespace {
 
@@ -54,7 +54,6 @@ void gemm_acc_stream_kernel(const GemmAccStreamParams p) {
 
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, (p.M - 1) * p.lda * 2 + p.K * 2, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsG = __builtin_amdgcn_make_buffer_rsrc((void*)p.g, 0, p.M * 1024, 0x00020000);
-    auto bload = [&](const __amdgpu_buffer_rsrc_t& r, int off) __attribute__((always_inline)) { return __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0); };
     WeightRing<NSLOT> ring(p.wstream, S, wave, lane);
     ring.prime();
 
@@ -73,13 +72,6 @@ void gemm_acc_stream_kernel(const GemmAccStreamParams p) {
 #pragma unroll
         for (int j = 0; j < NJ; ++j) hq[sl][j] = __builtin_bit_cast(bf16x8, bload(rsA, aoff[j] + k * 64));
     };
-    auto pin_acc = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i)
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) asm volatile("" : "+a"(acc[i][j]));
-    };
-
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         asm volatile("" : "+v"(tid));
         lane = tid & 63; frow = lane & 15; g = lane >> 4; fo = g * 64;
@@ -97,7 +89,7 @@ void gemm_acc_stream_kernel(const GemmAccStreamParams p) {
             for (int i = 0; i < 16; ++i) acc[i][j] = __builtin_bit_cast(f32x4, bload(rsG, off + i * 16));
         });
         sfor<PA>([&](auto D) __attribute__((always_inline)) { load_a(D, decltype(D)::value); });
-        pin_acc();
+        pin_acc(acc);
 
         for (int k0 = 0; k0 < S; k0 += PA) {
             sfor<PA>([&](auto U) __attribute__((always_inline)) {
@@ -107,30 +99,17 @@ void gemm_acc_stream_kernel(const GemmAccStreamParams p) {
                 // from the sixth item of a tile on, the NJ operand-row loads of each of the last five items (counting fewer is the safe side)
                 if (k < 5) wait_vm<INFL>();
                 else wait_vm<STEADY>();
-                __builtin_amdgcn_s_barrier();
-                const char* wc = wl + ring.slot * SLOT;
-                const char* wn = wl + ring.next_slot() * SLOT;
-                const int sd = ring.refill_slot();
-                sfor<8>([&](auto P2) __attribute__((always_inline)) {
-                    sfor<2>([&](auto PH) __attribute__((always_inline)) {
-                        constexpr int pi = decltype(P2)::value * 2 + decltype(PH)::value;
-                        const bf16x8 w = wf[pi % NB];
+                stream_item_waited<PD, false, true>(ring, wf, wl, [&](auto PI, const bf16x8 w) __attribute__((always_inline)) {
+                    constexpr int pi = decltype(PI)::value;
 #pragma unroll
-                        for (int j = 0; j < NJ; ++j) acc[pi][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, hq[u][j], acc[pi][j], 0, 0, 0);
-                        if constexpr (pi + PD < 16) wf[(pi + PD) % NB] = *(const bf16x8*)(wc + (pi + PD) * 1024);
-                        else wf[(pi + PD) % NB] = *(const bf16x8*)(wn + (pi + PD - 16) * 1024);
-                        if constexpr (pi < 4) ring.piece<pi>(sd);
-                    });
-                    __builtin_amdgcn_sched_barrier(0);
+                    for (int j = 0; j < NJ; ++j) acc[pi][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, hq[u][j], acc[pi][j], 0, 0, 0);
                 });
-                ring.advance();
-                ring.rotate();
                 // the rows of item k + PA take the registers this item has just used (past the last item: a repeat of it, so that every
                 // item issues the same number of accesses)
                 load_a(U, k + PA < S ? k + PA : S - 1);
             });
         }
-        pin_acc();
+        pin_acc(acc);
 
         // ---- the rows leave through the wave's 4-KB staging tile as whole rows
         asm volatile("" : "+v"(tid));
@@ -145,13 +124,13 @@ void gemm_acc_stream_kernel(const GemmAccStreamParams p) {
                 for (int half = 0; half < 2; ++half) {
                     if ((frow >> 3) == half) {
 #pragma unroll
-                        for (int e = 0; e < 8; ++e) *(f32x4*)(st + (frow & 7) * 512 + (((g * 8 + e) ^ (frow & 7)) << 4)) = acc[fh * 8 + e][j];
+                        for (int e = 0; e < 8; ++e) stage_put(st, frow, g, e, acc[fh * 8 + e][j]);
                     }
                     wave_lds_sync();
 #pragma unroll
                     for (int q4 = 0; q4 < 4; ++q4) {
                         const int rr = 2 * q4 + (lane >> 5), cc = lane & 31;
-                        const f32x4 v = *(const f32x4*)(st + rr * 512 + ((cc ^ rr) << 4));
+                        const f32x4 v = stage_get<f32x4>(st, rr, cc);
                         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsG,
                                                                (rbase + half * 8 + rr) * 1024 + (cc >> 3) * 256 + fh * 128 + (cc & 7) * 16, 0, 0);
                     }

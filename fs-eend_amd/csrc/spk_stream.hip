@@ -5,7 +5,7 @@
 // Replaces eend_linear_res16_ln_f16 + eend_spk_qkv_attn_f16 on the hot path for every slot count C <= 12 (3 / 6 / 12 fill the tiling
 // exactly; the others leave phantom slot positions that are masked and never stored).
 //
-// Same machinery as ffn_stream.hip, shared through wstream.h (one wave per SIMD, 48 token rows per wave, weight fragments streamed by
+// Same machinery as ffn_stream.hip, shared through wstream.h and wave_rows.h (one wave per SIMD, 48 token rows per wave, weight fragments streamed by
 // LDS-DMA through an 8-slot ring, one barrier per 16-KB item, LayerNorm output == next GEMM's B operand), with two differences:
 //   * a wave's 48 rows are the C slots of 48/C consecutive frames (row = (b*C + c)*Tp + t), token index = c*G + t', so every
 //     frame's slots sit in ONE wave: in the MFMA output layout (lane = token column, 4 rows per 16-lane group) the keys and
@@ -17,7 +17,7 @@
 // The key bias is dropped: q . b_k is the same for every key of a query and cancels in the softmax.
 #include "common.h"
 #include "kernels.h"
-#include "wstream.h"
+#include "wave_rows.h"
 
 namespace {
 
@@ -64,12 +64,6 @@ __device__ unsigned long long g_spks_trace[256 * 4 * 12];
 #define SPK_STAMP(k) do {} while (0)
 #endif
 
-template <int N>
-__device__ __forceinline__ float row_rot(float x) {          // value of the lane N places away inside the 16-lane row
-    if constexpr (N == 0) return x;
-    else return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x120 + N, 0xF, 0xF, false));
-}
-
 // ---------------------------------------------------------------------------------------------------------------
 // G frames per wave, R = 16/G slot positions per token fragment, C = 3R positions of which the first CC hold the model's slots.
 // CC < C: the phantom positions read the last slot's rows (any valid rows do), are masked as keys (a -1e30 score bias that is rotated
@@ -113,10 +107,9 @@ void spk_stream_kernel(const SpkStreamParams p) {
     f16x8 xf[8][NJ];
 
     // memory row of token (fragment j, column fr) of a tile
-    auto slot_of = [&](int j, int fr) __attribute__((always_inline)) { return j * R + fr / G; };
     auto row_tok = [&](int tile, int j, int fr) __attribute__((always_inline)) {
         const int b = tile / TPB, tt = tile - b * TPB;
-        int c = slot_of(j, fr);
+        int c = slot_of<G>(j, fr);
         if constexpr (!FULL) c = c < CC ? c : CC - 1;
         return (b * CC + c) * p.Tp + tt * (4 * G) + wave * G + (fr % G);
     };
@@ -158,37 +151,14 @@ void spk_stream_kernel(const SpkStreamParams p) {
     auto step = [&](auto KIND, auto SRCc, auto COLDc, auto PFNc, auto VWXc) __attribute__((always_inline)) {
         constexpr int kind = decltype(KIND)::value, src = decltype(SRCc)::value, vw = INFL + decltype(VWXc)::value;
         constexpr bool cold = decltype(COLDc)::value, pfn = decltype(PFNc)::value;
-        wait_vm<vw>();
-        __builtin_amdgcn_s_barrier();
-        const char* wc = wl + ring.slot * SLOT;
-        const char* wn = wl + ring.next_slot() * SLOT;
-        const int sd = ring.refill_slot();
-        if constexpr (cold) {
-            sfor<PD>([&](auto Q) __attribute__((always_inline)) {
-                wf[decltype(Q)::value % NB] = *(const f16x8*)(wc + decltype(Q)::value * 1024);
-            });
-        }
-        sfor<8>([&](auto P2) __attribute__((always_inline)) {
-            sfor<2>([&](auto PH) __attribute__((always_inline)) {
-                constexpr int pi = decltype(P2)::value * 2 + decltype(PH)::value;
-                const f16x8 w = wf[pi % NB];
-                if constexpr (kind == 0) {
+        stream_item<vw, PD, cold, pfn>(ring, wf, wl, [&](auto PI, const f16x8 w) __attribute__((always_inline)) {
+            constexpr int pi = decltype(PI)::value, s_ = pi >> 1, hf = pi & 1;
 #pragma unroll
-                    for (int j = 0; j < NJ; ++j) acc[pi][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w, xf[src][j], acc[pi][j], 0, 0, 0);
-                } else {
-                    constexpr int s_ = pi >> 1, hf = pi & 1, idx = src * 2 + hf;
-#pragma unroll
-                    for (int j = 0; j < NJ; ++j)
-                        qkv[idx][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w, xf[s_][j], s_ == 0 ? f32x4{0.f, 0.f, 0.f, 0.f} : qkv[idx][j], 0, 0, 0);
-                }
-                if constexpr (pi + PD < 16) wf[(pi + PD) % NB] = *(const f16x8*)(wc + (pi + PD) * 1024);
-                else if constexpr (pfn) wf[(pi + PD) % NB] = *(const f16x8*)(wn + (pi + PD - 16) * 1024);
-                if constexpr (pi < 4) ring.piece<pi>(sd);
-            });
-            __builtin_amdgcn_sched_barrier(0);
+            for (int j = 0; j < NJ; ++j) {
+                if constexpr (kind == 0) acc[pi][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w, xf[src][j], acc[pi][j], 0, 0, 0);
+                else qkv[src * 2 + hf][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w, xf[s_][j], s_ == 0 ? f32x4{0.f, 0.f, 0.f, 0.f} : qkv[src * 2 + hf][j], 0, 0, 0);
+            }
         });
-        ring.advance();
-        ring.rotate();
     };
 
     char* st = smem + STAGE + wave * 4096;
@@ -217,10 +187,7 @@ void spk_stream_kernel(const SpkStreamParams p) {
 #pragma unroll
             for (int j = 0; j < NJ; ++j) acc[i][j] = b4;
         }
-#pragma unroll
-        for (int i = 0; i < 16; ++i)
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) asm volatile("" : "+a"(acc[i][j]));
+        pin_acc(acc);
         // items 0..4: the tile's 24 input-row loads are younger than the pieces they wait for (first tile: issued behind the ring
         // prime; later: behind the previous tile's last item, with 6 output stores on top).  The residual rows are requested
         // three, two and one item ahead of the LayerNorm that adds them, into registers the consumed input fragments freed.
@@ -235,10 +202,7 @@ void spk_stream_kernel(const SpkStreamParams p) {
         load_res16(tile, IC<0>{});
         load_res32(tile, IC<1>{}, IC<1>{});
         step(IC<0>{}, IC<7>{}, Fa{}, Fa{}, IC<(R32 ? 32 : 8)>{});
-#pragma unroll
-        for (int i = 0; i < 16; ++i)
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) asm volatile("" : "+a"(acc[i][j]));
+        pin_acc(acc);
         SPK_STAMP(1);
         _Float16* x16 = (_Float16*)p.x16;
         sfor<NJ>([&](auto J) __attribute__((always_inline)) {
@@ -282,20 +246,8 @@ void spk_stream_kernel(const SpkStreamParams p) {
                     if ((i & 3) == 3) __builtin_amdgcn_sched_barrier(0);
                 }
             } else {
-            f32x2 sm = f32x2{0.f, 0.f}, sq2 = f32x2{0.f, 0.f};
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const f32x4 a4 = acc[i][j];
-                const f32x2 x0 = f32x2{a4[0] + resv(i, 0), a4[1] + resv(i, 1)};
-                const f32x2 x1 = f32x2{a4[2] + resv(i, 2), a4[3] + resv(i, 3)};
-                sm += x0 + x1;
-                sq2 = x1 * x1 + (x0 * x0 + sq2);
-            }
-            const float sum = wave_g_allreduce_add(sm[0] + sm[1]);
-            const float sqs = wave_g_allreduce_add(sq2[0] + sq2[1]);
-            const float mean = sum * (1.0f / 256);
-            const float var = __builtin_fmaxf(sqs * (1.0f / 256) - mean * mean, 0.f);
-            const float rstd = 1.0f / __builtin_sqrtf(var + p.eps1);
+            const LnStats ln = ln_stats_1pass([&](int i, int q) __attribute__((always_inline)) { return acc[i][j][q] + resv(i, q); }, p.eps1);
+            const float mean = ln.mean, rstd = ln.rstd;
             __builtin_amdgcn_sched_barrier(0);
             if constexpr (j + 1 < NJ) load_res16(tile, IC<j + 1>{});
 #pragma unroll
@@ -316,14 +268,14 @@ void spk_stream_kernel(const SpkStreamParams p) {
                     for (int half = 0; half < 2; ++half) {
                         if ((frow >> 3) == half) {
 #pragma unroll
-                            for (int e = 0; e < 8; ++e) *(f32x4*)(st + (frow & 7) * 512 + (((g * 8 + e) ^ (frow & 7)) << 4)) = t4[tb][fh * 8 + e];
+                            for (int e = 0; e < 8; ++e) stage_put(st, frow, g, e, t4[tb][fh * 8 + e]);
                         }
                         wave_lds_sync();
 #pragma unroll
                         for (int q4 = 0; q4 < 4; ++q4) {
                             const int rr = 2 * q4 + (lane >> 5), cc = lane & 31;
-                            const f32x4 v4 = *(const f32x4*)(st + rr * 512 + ((cc ^ rr) << 4));
-                            if ((FULL || slot_of(j, half * 8 + rr) < CC))
+                            const f32x4 v4 = stage_get<f32x4>(st, rr, cc);
+                            if ((FULL || slot_of<G>(j, half * 8 + rr) < CC))
                                 *(f32x4*)(x32 + (size_t)row_tok(tile, j, half * 8 + rr) * 256 + (cc >> 3) * 64 + fh * 32 + (cc & 7) * 4) = v4;
                         }
                         wave_lds_sync();
@@ -335,14 +287,14 @@ void spk_stream_kernel(const SpkStreamParams p) {
             for (int half = 0; half < (R32 ? 0 : 2); ++half) {
                 if ((frow >> 3) == half) {
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) *(f16x8*)(st + (frow & 7) * 512 + (((g * 8 + e) ^ (frow & 7)) << 4)) = xf[e][j];
+                    for (int e = 0; e < 8; ++e) stage_put(st, frow, g, e, xf[e][j]);
                 }
                 wave_lds_sync();
 #pragma unroll
                 for (int q4 = 0; q4 < 4; ++q4) {
                     const int rr = 2 * q4 + (lane >> 5), cc = lane & 31;
-                    const f16x8 v4 = *(const f16x8*)(st + rr * 512 + ((cc ^ rr) << 4));
-                    if ((FULL || slot_of(j, half * 8 + rr) < CC)) *(f16x8*)(x16 + (size_t)row_tok(tile, j, half * 8 + rr) * 256 + cc * 8) = v4;
+                    const f16x8 v4 = stage_get<f16x8>(st, rr, cc);
+                    if ((FULL || slot_of<G>(j, half * 8 + rr) < CC)) *(f16x8*)(x16 + (size_t)row_tok(tile, j, half * 8 + rr) * 256 + cc * 8) = v4;
                 }
                 wave_lds_sync();
             }
@@ -355,13 +307,7 @@ void spk_stream_kernel(const SpkStreamParams p) {
         // (the last head is peeled: the next tile's input loads issued there would otherwise look pending at every iteration's top)
         // score bias of the key each (fragment, rotation) delivers to this lane: 0 for a real slot, -1e30 for a phantom position
         float kbias[FULL ? 1 : C];
-        if constexpr (!FULL) {
-            sfor<NJ>([&](auto J2) __attribute__((always_inline)) {
-                constexpr int j2 = decltype(J2)::value;
-                const float own = slot_of(j2, frow) < CC ? 0.f : -1e30f;
-                sfor<R>([&](auto D) __attribute__((always_inline)) { kbias[j2 * R + decltype(D)::value] = row_rot<decltype(D)::value * G>(own); });
-            });
-        }
+        slot_kbias<G, CC, NJ>(kbias, frow);
         // YNG: this wave's stores certainly younger than the pieces the head's six waits need -- the 6 output stores of the previous
         // head, or (head 0) the x1 row stores: 8 per fragment, or 16 as f32 (capped by the 6-bit counter)
         auto head_body = [&](int head, auto LAST, auto YNG) __attribute__((always_inline)) {
@@ -376,85 +322,8 @@ void spk_stream_kernel(const SpkStreamParams p) {
             if (decltype(LAST)::value && ntile < ntiles)              // x1 is dead: the next tile's input rows travel under the last attention
                 sfor<NJ>([&](auto J) __attribute__((always_inline)) { load_in_frags(ntile, J); });
 
-            // packed f32 arithmetic (v_pk_fma_f32: two FMAs per lane and instruction) on register pairs of the accumulator quads
-            const float* bq = vecs + 3 * 256 + head * 64 + g * 16;
-            const float* bv = vecs + 5 * 256 + head * 64 + g * 16;
-            f32x4 bnext = *(const f32x4*)bq;              // bias quads are requested one fragment ahead of their use
-            f32x2 s2[NJ][C];
-#pragma unroll
-            for (int a = 0; a < NJ; ++a)
-#pragma unroll
-                for (int c = 0; c < C; ++c) s2[a][c] = f32x2{0.f, 0.f};
-            f16x8 of[NJ][2];
-            sfor<4>([&](auto FF) __attribute__((always_inline)) {
-                constexpr int ff = decltype(FF)::value;
-                const f32x4 b4 = bnext;
-                bnext = ff < 3 ? *(const f32x4*)(bq + (ff + 1) * 4) : *(const f32x4*)bv;
-                f32x2 q[NJ][2];
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) {
-                    const f32x4 t = (qkv[ff][j] + b4) * p.scale;
-                    q[j][0] = f32x2{t[0], t[1]}; q[j][1] = f32x2{t[2], t[3]};
-                }
-                sfor<NJ>([&](auto J2) __attribute__((always_inline)) {
-                    constexpr int j2 = decltype(J2)::value;
-                    const f32x4 k = qkv[4 + ff][j2];
-                    sfor<R>([&](auto D) __attribute__((always_inline)) {
-                        constexpr int d = decltype(D)::value;
-                        const f32x2 k0 = f32x2{row_rot<d * G>(k[0]), row_rot<d * G>(k[1])};
-                        const f32x2 k1 = f32x2{row_rot<d * G>(k[2]), row_rot<d * G>(k[3])};
-#pragma unroll
-                        for (int j1 = 0; j1 < NJ; ++j1) {
-                            s2[j1][j2 * R + d] = q[j1][1] * k1 + (q[j1][0] * k0 + s2[j1][j2 * R + d]);
-                        }
-                    });
-                });
-            });
-            float s[NJ][C];
-#pragma unroll
-            for (int a = 0; a < NJ; ++a) {
-                float mx = -INFINITY, den = 0.f;
-#pragma unroll
-                for (int c = 0; c < C; ++c) {
-                    s[a][c] = s2[a][c][0] + s2[a][c][1];
-                    if constexpr (!FULL) s[a][c] += kbias[c];
-                    s[a][c] = wave_g_allreduce_add(s[a][c]);
-                    mx = __builtin_fmaxf(mx, s[a][c]);
-                }
-#pragma unroll
-                for (int c = 0; c < C; ++c) { s[a][c] = __expf(s[a][c] - mx); den += s[a][c]; }
-                const float inv = __builtin_amdgcn_rcpf(den);
-#pragma unroll
-                for (int c = 0; c < C; ++c) s[a][c] *= inv;
-            }
-            sfor<4>([&](auto FF) __attribute__((always_inline)) {
-                constexpr int ff = decltype(FF)::value;
-                const f32x4 b4 = bnext;
-                if constexpr (ff < 3) bnext = *(const f32x4*)(bv + (ff + 1) * 4);
-                f32x2 o[NJ][2];
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) { o[j][0] = f32x2{b4[0], b4[1]}; o[j][1] = f32x2{b4[2], b4[3]}; }
-                sfor<NJ>([&](auto J2) __attribute__((always_inline)) {
-                    constexpr int j2 = decltype(J2)::value;
-                    const f32x4 vv = qkv[8 + ff][j2];
-                    sfor<R>([&](auto D) __attribute__((always_inline)) {
-                        constexpr int d = decltype(D)::value;
-                        const f32x2 v0 = f32x2{row_rot<d * G>(vv[0]), row_rot<d * G>(vv[1])};
-                        const f32x2 v1 = f32x2{row_rot<d * G>(vv[2]), row_rot<d * G>(vv[3])};
-#pragma unroll
-                        for (int j1 = 0; j1 < NJ; ++j1) {
-                            const f32x2 pw = f32x2{s[j1][j2 * R + d], s[j1][j2 * R + d]};
-                            o[j1][0] = pw * v0 + o[j1][0];
-                            o[j1][1] = pw * v1 + o[j1][1];
-                        }
-                    });
-                });
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) {
-                    of[j][ff >> 1][(ff & 1) * 4 + 0] = to_f16_sat(o[j][0][0]); of[j][ff >> 1][(ff & 1) * 4 + 1] = to_f16_sat(o[j][0][1]);
-                    of[j][ff >> 1][(ff & 1) * 4 + 2] = to_f16_sat(o[j][1][0]); of[j][ff >> 1][(ff & 1) * 4 + 3] = to_f16_sat(o[j][1][1]);
-                }
-            });
+            f16x8 of[2][NJ];
+            slot_attention<G, CC>(qkv, vecs + 3 * 256 + head * 64 + g * 16, vecs + 5 * 256 + head * 64 + g * 16, p.scale, kbias, of);
             // the head's 64 features of 16 tokens = 16 full 128-byte lines per token fragment, through the staging tile (2 KB per
             // fragment: fragments 0 and 1 in one LDS round trip, fragment 2 in a second)
             auto stage_out = [&](auto J0, auto NF) __attribute__((always_inline)) {
@@ -462,8 +331,8 @@ void spk_stream_kernel(const SpkStreamParams p) {
 #pragma unroll
                 for (int jj = 0; jj < nf; ++jj) {
                     char* sj = st + jj * 2048;
-                    *(f16x8*)(sj + frow * 128 + (((g * 2) ^ (frow & 7)) << 4)) = of[j0 + jj][0];
-                    *(f16x8*)(sj + frow * 128 + (((g * 2 + 1) ^ (frow & 7)) << 4)) = of[j0 + jj][1];
+                    *(f16x8*)(sj + frow * 128 + (((g * 2) ^ (frow & 7)) << 4)) = of[0][j0 + jj];
+                    *(f16x8*)(sj + frow * 128 + (((g * 2 + 1) ^ (frow & 7)) << 4)) = of[1][j0 + jj];
                 }
                 wave_lds_sync();
                 f16x8 v4[nf][2];
@@ -476,7 +345,7 @@ void spk_stream_kernel(const SpkStreamParams p) {
                 for (int jj = 0; jj < nf; ++jj)
 #pragma unroll
                     for (int half = 0; half < 2; ++half)
-                        if ((FULL || slot_of(j0 + jj, half * 8 + rr) < CC))
+                        if ((FULL || slot_of<G>(j0 + jj, half * 8 + rr) < CC))
                             *(f16x8*)(O + (size_t)row_tok(tile, j0 + jj, half * 8 + rr) * 256 + head * 64 + cc * 8) = v4[jj][half];
                 wave_lds_sync();
             };
