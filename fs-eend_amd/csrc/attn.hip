@@ -17,7 +17,9 @@
 // never materialised: allowed(i,j) <=> j - i <= mask_delay is evaluated on the
 // indices (and j < kv_len), only in tiles that straddle the boundary; fully masked tiles are
 // skipped (that is the "causal-useful" 2*D*T*(T+1) flop count).
-#include "common.h"
+// The 64-key step itself -- scores, mask, running-maximum softmax, dropout, P^T and the V^T P^T MFMAs -- is flash_tile.h's, shared with
+// attn_full.hip and attn_stream.hip; this file keeps the register-staged double-buffered tile loads and the row store.
+#include "flash_tile.h"
 #include "kernels.h"
 #include <stdlib.h>
 
@@ -26,8 +28,6 @@ namespace {
 constexpr int QB = 128;   // query rows per workgroup (4 waves x 32)
 constexpr int KB = 64;    // keys per LDS tile
 constexpr int TILE = KB * 128;   // bytes of one [64][64] bf16 tile
-
-DEV int swap23(int r) { return (r & 0x13) | ((r & 4) << 1) | ((r & 8) >> 1); }
 
 __global__ __launch_bounds__(256)
 void attn_causal_kernel(const AttnParams p) {
@@ -98,73 +98,13 @@ void attn_causal_kernel(const AttnParams p) {
             const char* kb_ = smem + buf * TILE;
             const char* vb_ = smem + (2 + buf) * TILE;
             f32x16 s[2];
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb) {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) s[kb][i] = 0.f;
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) {
-                    const bf16x8 kf = *(const bf16x8*)(kb_ + swz128(kb * 32 + krow, ks * 2 + hi));
-                    s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], s[kb], 0, 0, 0);
-                }
-            }
-            // reg i of s[kb] in lane (q, hi) <-> key = key0 + kb*32 + (i&7) + 8*hi + 16*(i>>3)
+            tile_scores<bf16x8>(s, zero16(), kb_, krow, hi, qf);
             const int wlim = qw0 + p.mask_delay < p.kv_len - 1 ? qw0 + p.mask_delay : p.kv_len - 1;
-            const bool diag = key0 + KB - 1 > wlim;                 // some element may be masked
-            if (diag) {
-                const int lim = q + p.mask_delay < p.kv_len - 1 ? q + p.mask_delay : p.kv_len - 1;
-#pragma unroll
-                for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) {
-                        const int key = key0 + kb * 32 + (i & 7) + 8 * hi + 16 * (i >> 3);
-                        if (key > lim) s[kb][i] = -INFINITY;
-                    }
-            }
-            float tmax = s[0][0];
-#pragma unroll
-            for (int i = 1; i < 16; ++i) tmax = __builtin_fmaxf(tmax, s[0][i]);
-#pragma unroll
-            for (int i = 0; i < 16; ++i) tmax = __builtin_fmaxf(tmax, s[1][i]);
-            tmax = wave_xor_max(tmax, 32);
-            const float m_new = __builtin_fmaxf(m_run, tmax * p.scale_log2);
-            const float m_use = (m_new == -INFINITY) ? 0.f : m_new;
-            const float alpha = __builtin_amdgcn_exp2f(m_run - m_use);
-            float lsum = 0.f;
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(s[kb][i], p.scale_log2, -m_use));
-                    s[kb][i] = pv;
-                    lsum += pv;
-                }
-            l_run = l_run * alpha + lsum;
-            m_run = m_new;
-            if (p.drop.thresh24) {                         // training: dropout of the probabilities (row sum un-dropped)
-                const unsigned da = (unsigned)(sh * p.Tp + qc);
-#pragma unroll
-                for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                    for (int i = 0; i < 16; ++i)
-                        s[kb][i] = drop_apply(p.drop, s[kb][i], da, (unsigned)(key0 + kb * 32 + (i & 7) + 8 * hi + 16 * (i >> 3)));
-            }
-#pragma unroll
-            for (int i = 0; i < 16; ++i) { oT[0][i] *= alpha; oT[1][i] *= alpha; }
-            // P^T fragments (B operand of O^T): elem j of k-step (kb,kk) = reg kk*8 + j
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int kk = 0; kk < 2; ++kk) {
-                    bf16x8 pf;
-#pragma unroll
-                    for (int jj = 0; jj < 8; ++jj) pf[jj] = (__bf16)s[kb][kk * 8 + jj];
-#pragma unroll
-                    for (int db = 0; db < 2; ++db) {
-                        const bf16x8 vf = *(const bf16x8*)(vb_ + swz128(db * 32 + lq, kb * 4 + kk * 2 + hi));
-                        oT[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf, oT[db], 0, 0, 0);
-                    }
-                }
+            if (key0 + KB - 1 > wlim)                               // some element may be masked
+                tile_mask(s, key0, hi, -INFINITY, q + p.mask_delay < p.kv_len - 1 ? q + p.mask_delay : p.kv_len - 1);
+            softmax_running(s, oT, m_run, l_run, tile_rowmax(s), p.scale_log2);
+            if (p.drop.thresh24) tile_dropout(s, p.drop, (unsigned)(sh * p.Tp + qc), key0, hi);       // training
+            att_pv(oT, s, vb_, lq, hi);
         }
         if (j + 1 < ntiles) ATT_LSTORE(buf ^ 1);
         __syncthreads();

@@ -19,16 +19,13 @@
 // bits 2<->3 swapped (swap23), which makes the 8 contraction elements a lane holds after the first MFMA
 // contiguous for the second one (same trick as the forward kernel).
 #include "train_common.h"
+#include "flash_tile.h"
 #include "kernels.h"
 
 namespace {
 
-typedef __attribute__((address_space(3))) char lds_char;
-
 constexpr int KB = 64;
 constexpr int TILE = KB * 128;       // one [64][64] bf16 tile
-
-DEV int swap23(int r) { return (r & 0x13) | ((r & 4) << 1) | ((r & 8) >> 1); }
 
 __global__ __launch_bounds__(256, 2)
 void attn_bwd_dq_kernel(const AttnBwdParams p) {

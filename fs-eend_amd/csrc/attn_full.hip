@@ -11,12 +11,13 @@
 // Causal load balance: the Tp/32 query blocks are dealt to the 8 waves in pairs (w, nq-1-w): a
 // late block needs many key tiles, its early partner few -- every wave does ~the same work.
 //
-// Same arithmetic as attn.hip (transposed formulation, S^T = K Q^T and O^T = V^T P^T on
-// v_mfma_f32_32x32x16_bf16, key rows fed with index bits 2<->3 swapped, online softmax in the
-// log2 domain, index-predicate mask j - i <= mask_delay && j < kv_len); results are bit-identical
-// to it.  O is staged through a per-wave 4 KB LDS tile so that global stores are full 128-byte
-// rows (16 B per lane).
-#include "common.h"
+// Same arithmetic as attn.hip: the 64-key step is flash_tile.h's (transposed formulation, S^T = K Q^T and
+// O^T = V^T P^T on v_mfma_f32_32x32x16_bf16, key rows fed with index bits 2<->3 swapped, online softmax in
+// the log2 domain -- lazy reference or running maximum --, index-predicate mask j - i <= mask_delay &&
+// j < kv_len); results are bit-identical to it.  O leaves through flash_tile.h's row hand-off: a per-wave
+// 4 KB LDS tile, so that global stores are full 128-byte rows (16 B per lane).  This file keeps the LDS-DMA
+// load pipeline, the dealing of query blocks to waves and the trace / ablation switches.
+#include "flash_tile.h"
 #include "kernels.h"
 
 namespace {
@@ -27,18 +28,9 @@ constexpr int TILE = KB * 128;                       // one [64][64] bf16 tile
 constexpr int NW = 8;                                // waves per workgroup
 constexpr int OSTG = 32 * 128;                       // per-wave O staging: 32 rows x 128 B (chunk-swizzled)
 
-DEV int swap23(int r) { return (r & 0x13) | ((r & 4) << 1) | ((r & 8) >> 1); }
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-// LAZY (scale_log2 == 1: the caller folded 1/sqrt(dh) * log2(e) into the q projection): the softmax is
-// VALU-bound at dh = 64 (PMC: 19 VALU instructions per MFMA, VALU busy 44 % vs MFMA 18 %), so the loop
-// sheds VALU work per score: the running reference m_ref of a query row is only moved when a tile's
-// scores exceed it by more than 2^8 (exact result either way: numerator and denominator share m_ref),
-// and -m_ref is the C operand of the first QK^T MFMA, so the scores leave the matrix pipe already
-// re-referenced -- no per-score scale, subtract or rescale of O on the common path.
-typedef __attribute__((address_space(3))) char lds_char;
-
+// LAZY (scale_log2 == 1: the caller folded 1/sqrt(dh) * log2(e) into the q projection): flash_tile.h's softmax_lazy.  The
+// softmax is VALU-bound at dh = 64 (PMC: 19 VALU instructions per MFMA, VALU busy 44 % vs MFMA 18 %), so -m_ref is the C operand of
+// the first QK^T MFMA and the scores leave the matrix pipe already re-referenced.
 // Perf-study build (-DEEND_ATT_TRACE, tools/attn_trace.py): p.Lse is a u64 buffer [blocks][8 waves][16 stamps] of
 // s_memtime values at the phase boundaries below; never defined in the shipped library.
 #ifdef EEND_ATT_TRACE
@@ -171,98 +163,14 @@ void attn_causal_full_kernel(const AttnParams p) {
         const char* kb_ = Ks + j * TILE;
         const char* vb_ = Vs + j * TILE;
         f32x16 s[2];
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-            if constexpr (!LAZY) {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) s[kb][i] = 0.f;
-            }
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                const bf16x8 kf = *(const bf16x8*)(kb_ + swz128(kb * 32 + krow, ks * 2 + hi));
-                s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], (LAZY && ks == 0) ? mneg : s[kb], 0, 0, 0);
-            }
-        }
+        tile_scores<bf16x8>(s, LAZY ? mneg : zero16(), kb_, krow, hi, qf);
         const int wlim = qw0 + p.mask_delay < p.kv_len - 1 ? qw0 + p.mask_delay : p.kv_len - 1;
-        if (key0 + KB - 1 > wlim) {
-            const int lim = q + p.mask_delay < p.kv_len - 1 ? q + p.mask_delay : p.kv_len - 1;
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const int key = key0 + kb * 32 + (i & 7) + 8 * hi + 16 * (i >> 3);
-                    if (key > lim) s[kb][i] = -INFINITY;
-                }
-        }
-        float tmax = s[0][0];
-#pragma unroll
-        for (int i = 1; i < 16; ++i) tmax = __builtin_fmaxf(tmax, s[0][i]);
-#pragma unroll
-        for (int i = 0; i < 16; ++i) tmax = __builtin_fmaxf(tmax, s[1][i]);
-        tmax = wave_xor_max(tmax, 32);
-        if constexpr (LAZY) {
-            // move the reference only when a row outgrows it by 2^8 (or, on the first tile, sits far below it)
-            const bool move = tmax > 8.0f || (j == 0 && tmax < -8.0f);
-            if (__builtin_amdgcn_ballot_w64(move) != 0) {
-                float d = j == 0 ? tmax : __builtin_fmaxf(tmax, 0.f);
-                d = d == -INFINITY ? 0.f : d;
-                const float alpha = __builtin_amdgcn_exp2f(-d);
-                l_run *= alpha;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    oT[0][i] *= alpha; oT[1][i] *= alpha;
-                    s[0][i] -= d; s[1][i] -= d;
-                    mneg[i] -= d;
-                }
-            }
-            float lsum0 = 0.f, lsum1 = 0.f;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                s[0][i] = __builtin_amdgcn_exp2f(s[0][i]);
-                s[1][i] = __builtin_amdgcn_exp2f(s[1][i]);
-                lsum0 += s[0][i];
-                lsum1 += s[1][i];
-            }
-            l_run += lsum0 + lsum1;
-        } else {
-            const float m_new = __builtin_fmaxf(m_run, tmax * p.scale_log2);
-            const float m_use = (m_new == -INFINITY) ? 0.f : m_new;
-            const float alpha = __builtin_amdgcn_exp2f(m_run - m_use);
-            float lsum = 0.f;
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(s[kb][i], p.scale_log2, -m_use));
-                    s[kb][i] = pv;
-                    lsum += pv;
-                }
-            l_run = l_run * alpha + lsum;
-            m_run = m_new;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) { oT[0][i] *= alpha; oT[1][i] *= alpha; }
-        }
-        if constexpr (DROP) {                          // training: dropout of the probabilities (the row sum stays un-dropped)
-            const unsigned da = (unsigned)(sh * p.Tp + q);
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int i = 0; i < 16; ++i)
-                    s[kb][i] = drop_apply(p.drop, s[kb][i], da, (unsigned)(key0 + kb * 32 + (i & 7) + 8 * hi + 16 * (i >> 3)));
-        }
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk) {
-                bf16x8 pf;
-#pragma unroll
-                for (int jj = 0; jj < 8; ++jj) pf[jj] = (__bf16)s[kb][kk * 8 + jj];
-#pragma unroll
-                for (int db = 0; db < 2; ++db) {
-                    const bf16x8 vf = *(const bf16x8*)(vb_ + swz128(db * 32 + lq, kb * 4 + kk * 2 + hi));
-                    oT[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf, oT[db], 0, 0, 0);
-                }
-            }
+        if (key0 + KB - 1 > wlim) tile_mask(s, key0, hi, -INFINITY, q + p.mask_delay < p.kv_len - 1 ? q + p.mask_delay : p.kv_len - 1);
+        const float tmax = tile_rowmax(s);
+        if constexpr (LAZY) softmax_lazy(s, oT, mneg, l_run, tmax, j == 0);
+        else softmax_running(s, oT, m_run, l_run, tmax, p.scale_log2);
+        if constexpr (DROP) tile_dropout(s, p.drop, (unsigned)(sh * p.Tp + q), key0, hi);      // training
+        att_pv(oT, s, vb_, lq, hi);
     };
 
     // O[q][d] = O^T / l: stage the wave's 32 x 64 f16 tile, then 128-byte rows to HBM
@@ -274,28 +182,8 @@ void attn_causal_full_kernel(const AttnParams p) {
         if (p.Lse && hi == 0)                          // training: log2-domain log-sum-exp of the row, for the backward
             p.Lse[sh * p.Tp + q] = m_ref_final + __builtin_amdgcn_logf(l_tot);
 #endif
-#pragma unroll
-        for (int db = 0; db < 2; ++db)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                f16x4 o;
-                o[0] = to_f16_sat(oT[db][g * 4 + 0] * inv);
-                o[1] = to_f16_sat(oT[db][g * 4 + 1] * inv);
-                o[2] = to_f16_sat(oT[db][g * 4 + 2] * inv);
-                o[3] = to_f16_sat(oT[db][g * 4 + 3] * inv);
-                *(f16x4*)(Ow + lq * 128 + (((db * 4 + g) ^ (lq & 7)) << 4) + hi * 8) = o;
-            }
-        // wave-local hand-off through LDS: a wave's DS operations complete in order, and the
-        // compiler's s_waitcnt lgkmcnt covers the read-after-write within the wave
-        __builtin_amdgcn_wave_barrier();
-        _Float16* __restrict__ Og = (_Float16*)p.O + ((size_t)seq * p.Tp + qw0) * p.ldo + h * 64;
-#pragma unroll
-        for (int it = 0; it < 4; ++it) {
-            const int row = it * 8 + (lane >> 3), ch = lane & 7;           // 8 rows x 8 chunks per instruction
-            const uint4 v = *(const uint4*)(Ow + row * 128 + ((ch ^ (row & 7)) << 4));
-            *(uint4*)(Og + (size_t)row * p.ldo + ch * 8) = v;
-        }
-        __builtin_amdgcn_wave_barrier();
+        stage_rows(Ow, lq, hi, [&](int db, int i) __attribute__((always_inline)) { return to_f16_sat(oT[db][i] * inv); });
+        store_staged_rows(Ow, lane, (_Float16*)p.O + ((size_t)seq * p.Tp + qw0) * p.ldo + h * 64, p.ldo);
     };
 
     // ---- late block of the pair: group by group behind the load stream (every wave takes part in every

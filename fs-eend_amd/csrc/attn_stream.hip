@@ -7,12 +7,14 @@
 //   a barrier behind their last reader), two into the 32-KB staging region -- and every 1-KB fragment read feeds four MFMAs.
 //   768 KB of LDS reads and six barriers per item.  Q never leaves the wave: packed bf16 in 32 registers until its pass, then
 //   through the wave's 4-KB staging tile into the flash loop's operand layout.  K and V live in LDS only: no HBM / L2 round trip.
+//   The flash loop's softmax, dropout and P V, the Q hand-off into it and the row hand-off out of it are flash_tile.h's (shared with
+//   attn.hip, attn_full.hip and the retention kernels); the projection items, the block map and the trace stamps are this file's.
 // (Round 3's form of the operator, attn_fused.hip -- weight slices in registers split by FEATURE across the waves, X streamed through
 //  an LDS tile every wave read completely, Q through an L2 scratch -- was LDS-read-bound, 19 us of a 32-us decoder item; removed in
 //  round 6 together with its A/B switch.)
 // Tp = 64 m <= 512 (eight waves x two query blocks of the 16 slots; round 6: shorter windows leave slots empty, see tokbase); longer chunk
 // lengths take eend_inproj_heads_bf16 + eend_attn_causal_bf16.
-#include "common.h"
+#include "flash_tile.h"
 #include "kernels.h"
 #include "wstream.h"
 #include <stdlib.h>
@@ -29,10 +31,6 @@ constexpr int WITEM = 16384;              // one weight item: 16 fragments of 1 
 constexpr int NITEM = 6;                  // Q (features 0-31, 32-63), K, K, V, V
 constexpr int L_K = 0, L_V = NT * TILE, L_X = 2 * NT * TILE;
 constexpr int SMEM = L_X + NW * OSTG;     // 160 KB
-
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-DEV int swap23(int r) { return (r & 0x13) | ((r & 4) << 1) | ((r & 8) >> 1); }
 
 DEV u32x2 pack_bf16x4(const f32x4 v) {
     bf16x4 o;
@@ -298,7 +296,7 @@ void inproj_attn_stream_kernel(const InprojAttnParams p) {
         AS_STAMP(8);
     }
 
-    // ================================================================== phase 2: the flash loop (attn_full.hip, LAZY)
+    // ================================================================== phase 2: the flash loop (flash_tile.h, lazy softmax)
     relaunder();
     const int lq = lane & 31, hi = lane >> 5;
     const int krow = swap23(lq);
@@ -314,17 +312,8 @@ void inproj_attn_stream_kernel(const InprojAttnParams p) {
         qw0 = qb * 32;
         q = qw0 + lq;
         // Q of the pass's 32 queries: registers -> the wave's staging tile ([query][64 d] bf16 rows) -> operand layout
-#pragma unroll
-        for (int jl = 0; jl < 2; ++jl)
-#pragma unroll
-            for (int ff = 0; ff < 4; ++ff) {
-                const int row = jl * 16 + frow;
-                *(u32x2*)(Ow + row * 128 + (((ff * 2 + (fkg >> 1)) ^ (row & 7)) << 4) + (fkg & 1) * 8) = qpk[ff][jt0 + jl];
-            }
-        wave_lds_sync();
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) qf[ks] = __builtin_bit_cast(bf16x8, *(const u32x4*)(Ow + lq * 128 + (((ks * 2 + hi) ^ (lq & 7)) << 4)));
-        wave_lds_sync();
+        stage_packed(Ow, frow, fkg, qpk, jt0);
+        staged_operand(Ow, lq, hi, qf);
 #pragma unroll
         for (int i = 0; i < 16; ++i) { oT[0][i] = 0.f; oT[1][i] = 0.f; mneg[i] = 0.f; }
         l_run = 0.f;
@@ -334,6 +323,8 @@ void inproj_attn_stream_kernel(const InprojAttnParams p) {
         const char* kb_ = Ks + j * TILE;
         const char* vb_ = Vs + j * TILE;
         f32x16 s[2];
+        // (scores and mask stay in the kernel's own text: behind flash_tile.h's tile_scores and tile_mask the two TRAIN forms, which sit at the
+        // register limit, spill 30 more SGPRs -- their dropout arithmetic is then vectorised 32 wide instead of 2 x 16)
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
@@ -348,62 +339,14 @@ void inproj_attn_stream_kernel(const InprojAttnParams p) {
             for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
-                    const int key = key0 + kb * 32 + (i & 7) + 8 * hi + 16 * (i >> 3);
-                    if (key > lim) s[kb][i] = -INFINITY;
+                    if (tile_key(key0, kb, i, hi) > lim) s[kb][i] = -INFINITY;
                 }
         }
-        float tmax = s[0][0];
-#pragma unroll
-        for (int i = 1; i < 16; ++i) tmax = __builtin_fmaxf(tmax, s[0][i]);
-#pragma unroll
-        for (int i = 0; i < 16; ++i) tmax = __builtin_fmaxf(tmax, s[1][i]);
-        tmax = wave_xor_max(tmax, 32);
-        // the reference only moves when a row outgrows it by 2^8 (or, on the first tile, sits far below it)
-        const bool move = tmax > 8.0f || (j == 0 && tmax < -8.0f);
-        if (__builtin_amdgcn_ballot_w64(move) != 0) {
-            float d = j == 0 ? tmax : __builtin_fmaxf(tmax, 0.f);
-            d = d == -INFINITY ? 0.f : d;
-            const float alpha = __builtin_amdgcn_exp2f(-d);
-            l_run *= alpha;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                oT[0][i] *= alpha; oT[1][i] *= alpha;
-                s[0][i] -= d; s[1][i] -= d;
-                mneg[i] -= d;
-            }
+        softmax_lazy(s, oT, mneg, l_run, tile_rowmax(s), j == 0);
+        if constexpr (TRAIN) {
+            if (p.drop.thresh24) tile_dropout(s, p.drop, (unsigned)((seq * 4 + h) * p.Tp + q), key0, hi);
         }
-        float lsum0 = 0.f, lsum1 = 0.f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            s[0][i] = __builtin_amdgcn_exp2f(s[0][i]);
-            s[1][i] = __builtin_amdgcn_exp2f(s[1][i]);
-            lsum0 += s[0][i];
-            lsum1 += s[1][i];
-        }
-        l_run += lsum0 + lsum1;
-        if constexpr (TRAIN) {                         // dropout of the probabilities (the row sum stays un-dropped)
-            if (p.drop.thresh24) {
-                const unsigned da = (unsigned)((seq * 4 + h) * p.Tp + q);
-#pragma unroll
-                for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                    for (int i = 0; i < 16; ++i)
-                        s[kb][i] = drop_apply(p.drop, s[kb][i], da, (unsigned)(key0 + kb * 32 + (i & 7) + 8 * hi + 16 * (i >> 3)));
-            }
-        }
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk) {
-                bf16x8 pf;
-#pragma unroll
-                for (int jj = 0; jj < 8; ++jj) pf[jj] = (__bf16)s[kb][kk * 8 + jj];
-#pragma unroll
-                for (int db = 0; db < 2; ++db) {
-                    const bf16x8 vf = *(const bf16x8*)(vb_ + swz128(db * 32 + lq, kb * 4 + kk * 2 + hi));
-                    oT[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf, oT[db], 0, 0, 0);
-                }
-            }
+        att_pv(oT, s, vb_, lq, hi);
     };
     auto run_pass = [&](int qb, auto JT0) __attribute__((always_inline)) {
         begin_pass(qb, JT0);
@@ -421,30 +364,13 @@ void inproj_attn_stream_kernel(const InprojAttnParams p) {
         if constexpr (TRAIN) {                         // log2-domain log-sum-exp of the row, for the backward
             if (hi == 0) p.lse[(size_t)(seq * 4 + h) * p.Tp + q] = __builtin_amdgcn_logf(l_tot) - mneg[0];
         }
-#pragma unroll
-        for (int db = 0; db < 2; ++db)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                f16x4 o;
-                o[0] = to_f16_sat(oT[db][g * 4 + 0] * inv);
-                o[1] = to_f16_sat(oT[db][g * 4 + 1] * inv);
-                o[2] = to_f16_sat(oT[db][g * 4 + 2] * inv);
-                o[3] = to_f16_sat(oT[db][g * 4 + 3] * inv);
-                *(f16x4*)(Ow + lq * 128 + (((db * 4 + g) ^ (lq & 7)) << 4) + hi * 8) = o;
-            }
-        wave_lds_sync();
+        stage_rows(Ow, lq, hi, [&](int db, int i) __attribute__((always_inline)) { return to_f16_sat(oT[db][i] * inv); });
         _Float16* __restrict__ Og = (_Float16*)p.O + ((size_t)seq * p.Tp + qoff + qw0) * p.ldo + h * 64;
         int ldo = p.ldo;
         if constexpr (LONG) {
             if (offd) { Og = (_Float16*)p.Opart + ((size_t)(p.pslot[pair] * p.nseq + seq) * TP + qw0) * 256 + h * 64; ldo = 256; }
         }
-#pragma unroll
-        for (int it = 0; it < 4; ++it) {
-            const int row = it * 8 + (lane >> 3), ch = lane & 7;
-            const f16x8 v = __builtin_bit_cast(f16x8, *(const u32x4*)(Ow + row * 128 + ((ch ^ (row & 7)) << 4)));
-            *(f16x8*)(Og + (size_t)row * ldo + ch * 8) = v;
-        }
-        wave_lds_sync();
+        store_staged_rows(Ow, lane, Og, ldo);
     };
     if (FULL || b2 < nblk) run_pass(b2, std::integral_constant<int, 2>{});      // (wave-uniform: a pass has no workgroup barrier)
     AS_STAMP(9);

@@ -10,6 +10,9 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));      // 8 / 16 bytes moved as they are
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) char lds_char;         // destination of an LDS-DMA (raw_ptr_buffer_load_lds)
 
 #define EEND_OK 0
 #define EEND_EINVAL (-1)

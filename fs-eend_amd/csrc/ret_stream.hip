@@ -12,7 +12,8 @@
 //   pass 2  ret_stream_kernel<false>  one item per (sequence, head, chunk, query half): the 8 waves project K / V^T of the keys the
 //                                     half can see (256 or 512 frames: 2 or 4 token fragments per wave) into LDS, Q and the gate G
 //                                     only for their own 32 queries, then run the masked linear-attention loop of
-//                                     ret_chunk_full_kernel (retention_full.hip: same scales, per-head LayerNorm, gate).
+//                                     ret_chunk_full_kernel (flash_tile.h: same step and row hand-off, here with q as a hi/lo
+//                                     pair and the gate from registers; same scales and per-head LayerNorm).
 // The attn_stream.hip machinery: a wave keeps its tokens' X rows in registers as MFMA operand fragments (whole-row requests,
 // wave-private LDS transposition), the head's weights arrive pre-packed in fragment order by LDS-DMA into regions that are free
 // at that time, every 1-KB fragment read feeds 2 - 4 MFMAs, Q and G never leave the wave.
@@ -26,7 +27,7 @@
 // QUERY path carries ~22 significand bits: q = (W_hi + W_lo)(x_hi + x_lo) with three f16 MFMA products (x_lo = the f16 remainder of the
 // f32 residual stream, optional input), q itself is a hi/lo f16 pair in the score product (2 MFMAs per tile) and the cross-chunk
 // term.  K, V, G, the probabilities and the state stay as before (f16 operands, f32 accumulation, hi/lo state).
-#include "common.h"
+#include "flash_tile.h"
 #include "kernels.h"
 #include "wstream.h"
 #include <stdlib.h>
@@ -42,10 +43,6 @@ constexpr int NITEM = 10;
 enum { I_Q0H = 0, I_Q1H = 1, I_Q0L = 2, I_Q1L = 3, I_G0 = 4, I_G1 = 5, I_K0 = 6, I_K1 = 7, I_V0 = 8, I_V1 = 9 };
 constexpr int L_K = 0, L_V = 8 * TILE, L_X = 16 * TILE;
 constexpr int SMEM = L_X + NW * OSTG;     // 160 KB
-
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-DEV int swap23(int r) { return (r & 0x13) | ((r & 4) << 1) | ((r & 8) >> 1); }
 
 DEV _Float16 f16_sat(float x) { return (_Float16)__builtin_amdgcn_fmed3f(x, -65504.0f, 65504.0f); }      // one clamp instruction
 DEV u32x2 pack_f16x4(const f32x4 v) {
@@ -551,7 +548,7 @@ void ret_stream_kernel(const RetStreamParams p) {
                 for (int r = 0; r < 4; ++r) KV[(ti * 32 + 8 * g + 4 * hi + r) * 64 + tj * 32 + lq] = acc[g * 4 + r] + other[(g * 4 + r) * 64 + lane];
         }
     } else {
-        // ================================================================== the chunk loop (retention_full.hip), one 32-query block per wave
+        // ================================================================== the chunk loop (flash_tile.h), one 32-query block per wave
         const int qw0 = tq0;
         if (qw0 < n) {
             const int q = qw0 + lq;
@@ -559,23 +556,10 @@ void ret_stream_kernel(const RetStreamParams p) {
             const int krow = swap23(lq);
             f16x8 qfh[4], qfl[4];
             // Q of the block: registers -> the wave's staging tile ([query][64 d] f16 rows) -> operand layout; hi then lo
-#pragma unroll
-            for (int part = 0; part < 2; ++part) {
-#pragma unroll
-                for (int jl = 0; jl < 2; ++jl)
-#pragma unroll
-                    for (int ff = 0; ff < 4; ++ff) {
-                        const int row = jl * 16 + frow;
-                        *(u32x2*)(Ow + row * 128 + (((ff * 2 + (fkg >> 1)) ^ (row & 7)) << 4) + (fkg & 1) * 8) = part == 0 ? qh[ff][jl] : ql[ff][jl];
-                    }
-                wave_lds_sync();
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) {
-                    const f16x8 v = __builtin_bit_cast(f16x8, *(const u32x4*)(Ow + lq * 128 + (((ks * 2 + hi) ^ (lq & 7)) << 4)));
-                    if (part == 0) qfh[ks] = v; else qfl[ks] = v;
-                }
-                wave_lds_sync();
-            }
+            stage_packed(Ow, frow, fkg, qh, 0);
+            staged_operand(Ow, lq, hi, qfh);
+            stage_packed(Ow, frow, fkg, ql, 0);
+            staged_operand(Ow, lq, hi, qfl);
             RS_STAMP(17);
             f32x16 oT[2];
 #pragma unroll
@@ -589,66 +573,16 @@ void ret_stream_kernel(const RetStreamParams p) {
                 const char* kb_ = Ks + j * TILE;
                 const char* vb_ = Vs + j * TILE;
                 f32x16 s[2];
-#pragma unroll
-                for (int kb = 0; kb < 2; ++kb) {
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) s[kb][i] = 0.f;
-#pragma unroll
-                    for (int ks = 0; ks < 4; ++ks) {
-                        const f16x8 kf = *(const f16x8*)(kb_ + swz128(kb * 32 + krow, ks * 2 + hi));
-                        s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qfh[ks], s[kb], 0, 0, 0);
-                        s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qfl[ks], s[kb], 0, 0, 0);
-                    }
-                }
-                if (key0 + KB - 1 > qw0) {               // the tile straddles the diagonal for some row of the wave
-#pragma unroll
-                    for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                        for (int i = 0; i < 16; ++i) {
-                            const int key = key0 + kb * 32 + (i & 7) + 8 * hi + 16 * (i >> 3);
-                            if (key > qc) s[kb][i] = 0.f;
-                        }
-                }
-#pragma unroll
-                for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) absum += __builtin_fabsf(s[kb][i]);
-#pragma unroll
-                for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                    for (int kk = 0; kk < 2; ++kk) {
-                        f16x8 pf;
-#pragma unroll
-                        for (int jj = 0; jj < 8; ++jj) pf[jj] = f16_sat(s[kb][kk * 8 + jj]);
-#pragma unroll
-                        for (int db = 0; db < 2; ++db) {
-                            const f16x8 vf = *(const f16x8*)(vb_ + swz128(db * 32 + lq, kb * 4 + kk * 2 + hi));
-                            oT[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf, oT[db], 0, 0, 0);
-                        }
-                    }
+                tile_scores<f16x8>(s, zero16(), kb_, krow, hi, qfh, qfl);
+                if (key0 + KB - 1 > qw0) tile_mask(s, key0, hi, 0.f, qc);      // the tile straddles the diagonal for some row of the wave
+                tile_abs_sum(s, absum);
+                tile_pv<f16x8>(oT, s, vb_, lq, hi, [](float x) __attribute__((always_inline)) { return f16_sat(x); });
             }
             RS_STAMP(18);
             // ---- cross-chunk term O^T += S_c^T Q^T (hi/lo f16 state x hi/lo q, prescale undone by sexp)
-            if (c > 0 || p.has_state_in) {
-                // (the state fragments come from L2 / HBM right here: requested before the tile loop their registers spill)
-                const _Float16* __restrict__ Sg = (const _Float16*)p.St + (sh * p.nc + c) * 2 * 4096;
-                const float sexp = p.sexp[sh * p.nc + c];
-                f32x16 x[2];
-#pragma unroll
-                for (int i = 0; i < 16; ++i) { x[0][i] = 0.f; x[1][i] = 0.f; }
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks)
-#pragma unroll
-                    for (int db = 0; db < 2; ++db) {
-                        const f16x8 sa = *(const f16x8*)(Sg + (db * 32 + lq) * 64 + ks * 16 + hi * 8);
-                        const f16x8 sb = *(const f16x8*)(Sg + 4096 + (db * 32 + lq) * 64 + ks * 16 + hi * 8);
-                        x[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(sa, qfh[ks], x[db], 0, 0, 0);
-                        x[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(sb, qfh[ks], x[db], 0, 0, 0);
-                        x[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(sa, qfl[ks], x[db], 0, 0, 0);
-                    }
-#pragma unroll
-                for (int i = 0; i < 16; ++i) { oT[0][i] = __builtin_fmaf(x[0][i], sexp, oT[0][i]); oT[1][i] = __builtin_fmaf(x[1][i], sexp, oT[1][i]); }
-            }
+            // (the state fragments come from L2 / HBM right here: requested before the tile loop their registers spill)
+            if (c > 0 || p.has_state_in)
+                cross_chunk_add(oT, (const _Float16*)p.St + (sh * p.nc + c) * 2 * 4096, p.sexp[sh * p.nc + c], lq, hi, true, qfh, qfl);
             RS_STAMP(19);
             // ---- scale, per-head LayerNorm, swish gate
             const float cscale = p.cscale[sh * p.nc + c];
@@ -670,40 +604,17 @@ void ret_stream_kernel(const RetStreamParams p) {
             var += __shfl_xor(var, 32, 64);
             const float rstd = 1.0f / __builtin_sqrtf(var * (1.0f / 64.0f) + p.gn_eps);
             // the gate of the block: registers -> staging tile -> this lane's (query, d) positions
-#pragma unroll
-            for (int jl = 0; jl < 2; ++jl)
-#pragma unroll
-                for (int ff = 0; ff < 4; ++ff) {
-                    const int row = jl * 16 + frow;
-                    *(u32x2*)(Ow + row * 128 + (((ff * 2 + (fkg >> 1)) ^ (row & 7)) << 4) + (fkg & 1) * 8) = gk[ff][jl];
-                }
-            wave_lds_sync();
+            stage_packed(Ow, frow, fkg, gk, 0);
             f16x4 gg[2][4];
 #pragma unroll
             for (int db = 0; db < 2; ++db)
 #pragma unroll
-                for (int g = 0; g < 4; ++g) gg[db][g] = *(const f16x4*)(Ow + lq * 128 + (((db * 4 + g) ^ (lq & 7)) << 4) + hi * 8);
+                for (int g = 0; g < 4; ++g) gg[db][g] = *(const f16x4*)stage_o_at(Ow, lq, hi, db, g);
             wave_lds_sync();
-#pragma unroll
-            for (int db = 0; db < 2; ++db)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    f16x4 o;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) o[r] = to_f16_sat((float)gg[db][g][r] * (oT[db][g * 4 + r] - mean) * rstd);
-                    *(f16x4*)(Ow + lq * 128 + (((db * 4 + g) ^ (lq & 7)) << 4) + hi * 8) = o;
-                }
-            wave_lds_sync();
-            _Float16* __restrict__ Og = (_Float16*)p.O + ((size_t)seq * p.Tp + f0 + qw0) * p.ldo + h * 64;
-#pragma unroll
-            for (int it = 0; it < 4; ++it) {
-                const int row = it * 8 + (lane >> 3), ch = lane & 7;
-                if (qw0 + row < n) {
-                    const u32x4 v = *(const u32x4*)(Ow + row * 128 + ((ch ^ (row & 7)) << 4));
-                    *(u32x4*)(Og + (size_t)row * p.ldo + ch * 8) = v;
-                }
-            }
-            wave_lds_sync();
+            stage_rows(Ow, lq, hi, [&](int db, int i) __attribute__((always_inline)) {
+                return to_f16_sat((float)gg[db][i >> 2][i & 3] * (oT[db][i] - mean) * rstd);
+            });
+            store_staged_rows<true>(Ow, lane, (_Float16*)p.O + ((size_t)seq * p.Tp + f0 + qw0) * p.ldo + h * 64, p.ldo, n - qw0);
         }
     }
     RS_STAMP(16);

@@ -16,13 +16,15 @@
 //                    (fp32 accumulate), and emits for every chunk the state *before* it as a
 //                    hi/lo f16 pair (power-of-two prescaled: 22 significant bits, no overflow)
 //                    plus the reference's cross_scale.
-//   ret_chunk      : flash-style tile loop (same transposed formulation as attn.hip, no
-//                    softmax): S^T = K Q^T, |S| row sums, O^T += V^T S^T, then the cross term
-//                    O^T += S_c^T Q^T, the scale, the per-head LayerNorm and the gate.
+//   ret_chunk      : flash-style tile loop (flash_tile.h: the transposed formulation of the
+//                    attention kernels, no softmax): S^T = K Q^T, |S| row sums, O^T += V^T S^T,
+//                    then the cross term O^T += S_c^T Q^T, the scale, the per-head LayerNorm
+//                    (the cross term is flash_tile.h's cross_chunk_add, shared with
+//                    ret_stream.hip) and the gate.
 // All MFMA operands are f16 (bf16's 8 significand bits cost > 1e-3 on the logits here; the
 // retention output is not a convex combination, and the eps = 1e-6 LayerNorm amplifies
 // relative error -- measured in the precision study).
-#include "common.h"
+#include "flash_tile.h"
 #include "kernels.h"
 
 namespace {
@@ -30,8 +32,6 @@ namespace {
 constexpr int QB = 128;
 constexpr int KB = 64;
 constexpr int TILE = KB * 128;
-
-DEV int swap23(int r) { return (r & 0x13) | ((r & 4) << 1) | ((r & 8) >> 1); }
 
 // zero the elements of an 8 x f16 fragment whose frame index j0 + e lies outside [lo, hi)
 DEV uint4 mask_frames(uint4 v, int j0, int lo, int hi) {
@@ -243,24 +243,15 @@ void ret_chunk_kernel(const RetParams p) {
             const char* kb_ = smem + buf * TILE;
             const char* vb_ = smem + (2 + buf) * TILE;
             f32x16 s[2];
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb) {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) s[kb][i] = 0.f;
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) {
-                    const f16x8 kf = *(const f16x8*)(kb_ + swz128(kb * 32 + krow, ks * 2 + hi));
-                    s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[ks], s[kb], 0, 0, 0);
-                }
-            }
-            // reg i of s[kb] in lane (q, hi) <-> key = key0 + kb*32 + (i&7) + 8*hi + 16*(i>>3)
+            tile_scores<f16x8>(s, zero16(), kb_, krow, hi, qf);
+            // (mask, |s| sum and P V in the kernel's own text: behind flash_tile.h's pieces this kernel takes 8 more VGPRs)
             const bool edge = (key0 + KB - 1 > wq_first) || (key0 < w_hi_start);
             if (edge) {
 #pragma unroll
                 for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
                     for (int i = 0; i < 16; ++i) {
-                        const int key = key0 + kb * 32 + (i & 7) + 8 * hi + 16 * (i >> 3);
+                        const int key = tile_key(key0, kb, i, hi);
                         if (key > qc || key < cs_q) s[kb][i] = 0.f;
                     }
             }
@@ -291,30 +282,7 @@ void ret_chunk_kernel(const RetParams p) {
     const _Float16* __restrict__ Sg = (const _Float16*)p.St + sh * p.nc * 2 * 4096;
     for (int c = c_lo; c <= c_hi; ++c) {
         if (c == 0 && !p.state_in) continue;                  // state before the first chunk is zero unless carried in
-        f32x16 x[2];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) { x[0][i] = 0.f; x[1][i] = 0.f; }
-        const _Float16* hi_m = Sg + (size_t)c * 2 * 4096;
-        const _Float16* lo_m = hi_m + 4096;
-        const bool mine = (c_q == c);
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            f16x8 qm = qf[ks];
-            if (!mine) {
-#pragma unroll
-                for (int jj = 0; jj < 8; ++jj) qm[jj] = (_Float16)0.f;
-            }
-#pragma unroll
-            for (int db = 0; db < 2; ++db) {
-                const f16x8 sa = *(const f16x8*)(hi_m + (db * 32 + lq) * 64 + ks * 16 + hi * 8);
-                const f16x8 sb = *(const f16x8*)(lo_m + (db * 32 + lq) * 64 + ks * 16 + hi * 8);
-                x[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(sa, qm, x[db], 0, 0, 0);
-                x[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(sb, qm, x[db], 0, 0, 0);
-            }
-        }
-        const float up = p.sexp[sh * p.nc + c];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) { oT[0][i] = __builtin_fmaf(x[0][i], up, oT[0][i]); oT[1][i] = __builtin_fmaf(x[1][i], up, oT[1][i]); }
+        cross_chunk_add(oT, Sg + (size_t)c * 2 * 4096, p.sexp[sh * p.nc + c], lq, hi, c_q == c, qf);
     }
 
     // ---- scale, per-head LayerNorm (eps 1e-6, no affine), swish gate, f16 store

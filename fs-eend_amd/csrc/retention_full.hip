@@ -6,10 +6,11 @@
 // single state S_c for all rows and the lower index bound of the mask disappears.
 //
 // Arithmetic, scaling, per-head LayerNorm and swish gate are those of ret_chunk_kernel
-// (retention.hip; reference LS-EEND/nnet/modules/retention.py:146-194,222-224); the chunk states
+// (retention.hip; reference LS-EEND/nnet/modules/retention.py:146-194,222-224): the 64-key step and
+// the staged 128-byte row stores of O and Rhat are flash_tile.h's; the chunk states
 // and cross_scale come from ret_state_scan_kernel.  Chunk starts are multiples of L = 500, i.e. not
 // 16-byte aligned in the V^T rows: V^T is fetched with 8-byte loads.
-#include "common.h"
+#include "flash_tile.h"
 #include "kernels.h"
 
 namespace {
@@ -19,10 +20,6 @@ constexpr int KB = 64;
 constexpr int TILE = KB * 128;
 constexpr int NW = 8;
 constexpr int OSTG = 32 * 128;
-
-DEV int swap23(int r) { return (r & 0x13) | ((r & 4) << 1) | ((r & 8) >> 1); }
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 __global__ __launch_bounds__(512)
 void ret_chunk_full_kernel(const RetParams p) {
@@ -123,44 +120,12 @@ void ret_chunk_full_kernel(const RetParams p) {
             const char* kb_ = Ks + j * TILE;
             const char* vb_ = Vs + j * TILE;
             f32x16 s[2];
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb) {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) s[kb][i] = 0.f;
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) {
-                    const f16x8 kf = *(const f16x8*)(kb_ + swz128(kb * 32 + krow, ks * 2 + hi));
-                    s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[ks], s[kb], 0, 0, 0);
-                }
-            }
-            if (key0 + KB - 1 > qw0) {                  // tile straddles the diagonal for some row of the wave
-#pragma unroll
-                for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) {
-                        const int key = key0 + kb * 32 + (i & 7) + 8 * hi + 16 * (i >> 3);
-                        if (key > qc) s[kb][i] = 0.f;
-                    }
-            }
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) absum += __builtin_fabsf(s[kb][i]);
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int kk = 0; kk < 2; ++kk) {
-                    f16x8 pf;
-#pragma unroll
-                    for (int jj = 0; jj < 8; ++jj) pf[jj] = to_f16_sat(s[kb][kk * 8 + jj]);
-#pragma unroll
-                    for (int db = 0; db < 2; ++db) {
-                        const f16x8 vf = *(const f16x8*)(vb_ + swz128(db * 32 + lq, kb * 4 + kk * 2 + hi));
-                        oT[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf, oT[db], 0, 0, 0);
-                    }
-                }
+            tile_scores<f16x8>(s, zero16(), kb_, krow, hi, qf);
+            if (key0 + KB - 1 > qw0) tile_mask(s, key0, hi, 0.f, qc);      // the tile straddles the diagonal for some row of the wave
+            tile_abs_sum(s, absum);
+            tile_pv<f16x8>(oT, s, vb_, lq, hi, [](float x) __attribute__((always_inline)) { return to_f16_sat(x); });
         }
-        // ---- cross-chunk term O^T += S_c^T Q^T (hi/lo f16 state, prescale undone by sexp)
+        // (in the kernel's own text: behind flash_tile.h's cross_chunk_add this kernel takes 11 more VGPRs)
         if (c > 0 || p.state_in) {                      // chunk 0 has a predecessor state only when one is carried in
             f32x16 x[2];
 #pragma unroll
@@ -197,55 +162,22 @@ void ret_chunk_full_kernel(const RetParams p) {
         const float rstd = 1.0f / __builtin_sqrtf(var * (1.0f / 64.0f) + p.gn_eps);
         const size_t grow = (size_t)seq * p.Tp + f0 + qc;
         const _Float16* __restrict__ Gg = (const _Float16*)p.G + grow * p.ldg + h * 64;
+        f16x4 gg[2][4];
 #pragma unroll
         for (int db = 0; db < 2; ++db)
 #pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int d = db * 32 + g * 8 + hi * 4;
-                const f16x4 gg = *(const f16x4*)(Gg + d);
-                f16x4 o;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float gv = (float)gg[r];
-                    o[r] = to_f16_sat(gv / (1.0f + __expf(-gv)) * (oT[db][g * 4 + r] - mean) * rstd);
-                }
-                *(f16x4*)(Ow + lq * 128 + (((db * 4 + g) ^ (lq & 7)) << 4) + hi * 8) = o;
-            }
-        __builtin_amdgcn_wave_barrier();
-        _Float16* __restrict__ Og = (_Float16*)p.O + ((size_t)seq * p.Tp + f0 + qw0) * p.ldo + h * 64;
-#pragma unroll
-        for (int it = 0; it < 4; ++it) {
-            const int row = it * 8 + (lane >> 3), ch = lane & 7;
-            if (qw0 + row < n) {
-                const uint4 v = *(const uint4*)(Ow + row * 128 + ((ch ^ (row & 7)) << 4));
-                *(uint4*)(Og + (size_t)row * p.ldo + ch * 8) = v;
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
+            for (int g = 0; g < 4; ++g) gg[db][g] = *(const f16x4*)(Gg + db * 32 + g * 8 + hi * 4);
+        stage_rows(Ow, lq, hi, [&](int db, int i) __attribute__((always_inline)) {
+            const float gv = (float)gg[db][i >> 2][i & 3];
+            return to_f16_sat(gv / (1.0f + __expf(-gv)) * (oT[db][i] - mean) * rstd);
+        });
+        store_staged_rows<true>(Ow, lane, (_Float16*)p.O + ((size_t)seq * p.Tp + f0 + qw0) * p.ldo + h * 64, p.ldo, n - qw0);
         if (p.Rhat) {
             // training forward: the normalised rows (input of the gate) and, per (row, head), 1/sigma times the detached
             // row scale f -- d out_t / d (q_t . prefix) = f exactly because the reference detaches inner_scale / kv_scale
-#pragma unroll
-            for (int db = 0; db < 2; ++db)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    f16x4 o;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) o[r] = to_f16_sat((oT[db][g * 4 + r] - mean) * rstd);
-                    *(f16x4*)(Ow + lq * 128 + (((db * 4 + g) ^ (lq & 7)) << 4) + hi * 8) = o;
-                }
-            __builtin_amdgcn_wave_barrier();
-            _Float16* __restrict__ Rg = (_Float16*)p.Rhat + ((size_t)seq * p.Tp + f0 + qw0) * p.ldo + h * 64;
-#pragma unroll
-            for (int it = 0; it < 4; ++it) {
-                const int row = it * 8 + (lane >> 3), ch = lane & 7;
-                if (qw0 + row < n) {
-                    const uint4 v = *(const uint4*)(Ow + row * 128 + ((ch ^ (row & 7)) << 4));
-                    *(uint4*)(Rg + (size_t)row * p.ldo + ch * 8) = v;
-                }
-            }
+            stage_rows(Ow, lq, hi, [&](int db, int i) __attribute__((always_inline)) { return to_f16_sat((oT[db][i] - mean) * rstd); });
             if (p.Rc && hi == 0 && q < n) p.Rc[((size_t)seq * p.Tp + f0 + q) * p.H + h] = rstd * f;
-            __builtin_amdgcn_wave_barrier();
+            store_staged_rows<true>(Ow, lane, (_Float16*)p.Rhat + ((size_t)seq * p.Tp + f0 + qw0) * p.ldo + h * 64, p.ldo, n - qw0);
         }
     }
 }

@@ -13,8 +13,6 @@ template <int N, class F>
 __device__ __forceinline__ void sfor(F&& f) { sfor_impl(f, std::make_integer_sequence<int, N>{}); }
 template <int V> using IC = std::integral_constant<int, V>;
 
-typedef __attribute__((address_space(3))) char lds_char;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // ---- s_waitcnt immediates: vmcnt is a 6-bit field split over bits 3:0 and 15:14, expcnt bits 6:4, lgkmcnt bits 11:8

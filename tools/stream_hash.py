@@ -1,6 +1,7 @@
 """SHA-256 of every output tensor of the weight-stream entries at small fixed-seed shapes that reach each tiling, the phantom-slot
-forms, a ragged last tile, both tile sizes and a second grid round.  Two builds of the library compute the same bits exactly when
-their listings are identical:   python tools/stream_hash.py > a.txt;  EEND_HIP_LIB=<other .so> python tools/stream_hash.py > b.txt"""
+forms, a ragged last tile, both tile sizes and a second grid round, and of the forward entries that reach the flash and retention tile
+loops (flash_tile.h): resident / tiled / packed / long / training attention, chunk-resident / tiled / fused retention.
+Two builds of the library compute the same bits exactly when their listings are identical:   python tools/stream_hash.py > a.txt;  EEND_HIP_LIB=<other .so> python tools/stream_hash.py > b.txt"""
 import ctypes, hashlib, importlib, math, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -115,3 +116,63 @@ for nseq, Tp, lens in ((1, 64, [64]), (3, 128, [128, 77, 1])):
     o32, o16 = torch.zeros(nseq * Tp, 256, device="cuda"), torch.zeros(nseq * Tp, 256, dtype=torch.float16, device="cuda")
     ops.conv1d_l2norm_stream(x, ops.conv_stream_pack(wr, ktaps), bias, il, o32, o16, nseq, Tp, ktaps, pad)
     show(f"conv1d_l2norm_stream nseq={nseq} Tp={Tp}", out32=o32, out16=o16)
+
+# ---- the flash and retention tile loops (flash_tile.h): every forward entry that reaches attn*.hip, retention*.hip and ret_stream.hip
+nseq, H = 2, 4
+z16 = lambda *s: torch.zeros(*s, dtype=torch.float16, device="cuda")
+drops = lambda: ((0.0, None), (0.2, ctypes.byref(lib.Dropout(777, int(round(0.2 * (1 << 24))), 1.0 / 0.8))))
+w_in = r(768, 256, sc=1 / 8).half()
+w_in[:256] = (w_in[:256].float() * ops.QSCALE_LOG2).half()
+wp, b_in = ops.inproj_attn_pack(w_in), v(768, sc=0.3)
+for Tp in (64, 192, 512, 576):                     # <= 512: the resident kernel (192: odd tile count), 576: the tiled one
+    q, k, vt = (r(nseq * H * Tp * 64).bfloat16() for _ in range(3))
+    for delay in (0, 65):
+        for sname, scale in (("lazy", ops.LN2), ("scaled", 0.125)):
+            o = z16(nseq * Tp, 256)
+            ops.attn_causal(q, k, vt, o, nseq, H, Tp, delay, Tp - 3, scale)
+            show(f"attn_causal Tp={Tp} delay={delay} {sname}", out16=o)
+    if Tp in (64, 512):
+        for pdrop, dr in drops():
+            o, lse = z16(nseq * Tp, 256), torch.zeros(nseq * H * Tp, device="cuda")
+            train._call("eend_attn_causal_lse_bf16", q, k, vt, o, lse, nseq, H, Tp, 256, 0, Tp - 3, ops.LN2, dr)
+            show(f"attn_causal_lse Tp={Tp} p={pdrop}", out16=o, lse=lse)
+for Tp in (64, 192, 512, 576, 1024):               # <= 512: packed, beyond: the long form (576: a short last group)
+    x = r(nseq * Tp, 256).half()
+    for delay in (0, 65):
+        o = z16(nseq * Tp, 256)
+        if Tp <= 512:
+            ops.inproj_attn_causal_packed(x, wp, b_in, o, nseq, H, Tp, delay, Tp - 3)
+        else:
+            need = ops.inproj_attn_long_scratch(nseq, Tp, delay, Tp - 3)
+            ops.inproj_attn_causal_long(x, wp, b_in, o, z16(need[0]), torch.zeros(need[1], device="cuda"), nseq, H, Tp, delay, Tp - 3)
+        show(f"inproj_attn_causal Tp={Tp} delay={delay}", out16=o)
+    if Tp in (64, 512):
+        for pdrop, dr in drops():
+            o, lse = z16(nseq * Tp, 256), torch.zeros(nseq * H * Tp, device="cuda")
+            qh, kh, vh = (torch.zeros(nseq * H * Tp * 64, dtype=torch.bfloat16, device="cuda") for _ in range(3))
+            train._call("eend_inproj_attn_train_bf16", x, 256, wp, b_in, o, 256, qh, kh, vh, lse, nseq, H, Tp, 0, Tp - 3, dr)
+            show(f"inproj_attn_train Tp={Tp} p={pdrop}", out16=o, lse=lse, q=qh, k=kh, v=vh)
+
+wq = r(1024, 256, sc=1 / 16)
+wret, bret = ops.retention_stream_pack(wq), v(1024, sc=0.3)
+for Tp, Lc in ((128, 64), (192, 100), (320, 300), (640, 576)):      # ragged last chunk; L > 256: two query halves; L > 512: the tiled kernel
+    nc = (Tp + Lc - 1) // Lc
+    q, k, vv = (r(nseq, H, Tp, 64, sc=0.5).half() for _ in range(3))
+    kt, vt, gate, x = k.transpose(-1, -2).contiguous(), vv.transpose(-1, -2).contiguous(), r(nseq * Tp, 256).half(), r(nseq * Tp, 256).half()
+    st, cs, se = z16(nseq * H * nc * 2 * 4096), torch.zeros(nseq * H * nc, device="cuda"), torch.zeros(nseq * H * nc, device="cuda")
+    for carried in (False, True):
+        s_in = r(nseq, H, 64, 64) if carried else None
+        s_out = torch.zeros(nseq, H, 64, 64, device="cuda") if carried else None
+        o = z16(nseq * Tp, 256)
+        ops.retention_chunk(q, k, kt, vt, gate, o, st, cs, se, nseq, H, Tp, Lc, state_in=s_in, state_out=s_out)
+        show(f"retention_chunk Tp={Tp} L={Lc} state={int(carried)}", out16=o, **({"state": s_out} if carried else {}))
+        if Lc <= 512:
+            o = z16(nseq * Tp, 256)
+            s_out = torch.zeros(nseq, H, 64, 64, device="cuda") if carried else None
+            ops.retention_stream(x, None, wret, bret, o, st, cs, se, nseq, Tp, Lc, state_in=s_in, state_out=s_out)
+            show(f"retention_stream Tp={Tp} L={Lc} state={int(carried)}", out16=o, **({"state": s_out} if carried else {}))
+    if (Tp, Lc) == (128, 64):
+        ctx, rhat, rc = z16(nseq * Tp, 256), z16(nseq * Tp, 256), torch.zeros(nseq * Tp, H, device="cuda")
+        kv = torch.zeros(nseq * H * nc * 4096, device="cuda")
+        train._call("eend_retention_chunk_train_f16", q, k, kt, vt, gate, ctx, rhat, rc, st, kv, cs, se, nseq, H, Tp, Lc, 256, 256, 1e-6, Tp)
+        show(f"retention_chunk_train Tp={Tp} L={Lc}", ctx=ctx, rhat=rhat, rc=rc)
