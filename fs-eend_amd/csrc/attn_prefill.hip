@@ -8,13 +8,15 @@
 // [0, t0 + end of its tile) once in 64-key tiles anchored at key 0.  A tile's K rows and V^T (keys in the k order of the second
 // product) lie in LDS for all four waves; the next tile's global loads are in flight while the current one is computed.  Per
 // 32-key chunk and 16-query tile S^T = K Q^T and O^T += V^T P^T run on mfma_f32_16x16x32_f16 with an online softmax, and P^T feeds
-// the second product straight from the score registers, as in attn_chunk_ragged_kernel (stream_chunk.hip): k index 8h + e of
-// the second product stands for key 4h + e (e < 4) or 16 + 4h + e - 4 of the chunk.  Causal tiles differ in length, so block
-// ids count the query tiles down: the long items start first.  A row's result depends on its own sequence, t0 and Tq alone:
-// not on cap, seq0, the other sequences or cache rows at or beyond t0 + Tq, which are never read.
+// the second product straight from the score registers (decode_mfma_step of decode_tile.h, the step attn_chunk_ragged_kernel
+// of stream_chunk.hip runs): k index 8h + e of the second product stands for key 4h + e (e < 4) or 16 + 4h + e - 4 of the
+// chunk.  Causal tiles differ in length, so block ids count the query tiles down: the long items start first.  A row's result
+// depends on its own sequence, t0 and Tq alone: not on cap, seq0, the other sequences or cache rows at or beyond t0 + Tq,
+// which are never read.
 // Few queries over a long history give few work items: that case stays with the chunk attention of step_frames.
 #include "common.h"
 #include "kernels.h"
+#include "decode_tile.h"
 
 namespace {
 
@@ -125,39 +127,8 @@ void attn_prefill_kernel(const _Float16* __restrict__ qkv, long ldq, const _Floa
 #pragma unroll
             for (int qt = 0; qt < 2; ++qt) {
                 if (c0 > last[qt]) continue;                        // wave-uniform; key c0 is visible to the tile's last query
-                f32x4 s[2];
-#pragma unroll
-                for (int kt = 0; kt < 2; ++kt) {
-                    s[kt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[kt][0], qf[qt][0], (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-                    s[kt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[kt][1], qf[qt][1], s[kt], 0, 0, 0);
-                }
-                float cm = -INFINITY;
-#pragma unroll
-                for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int key = c0 + kt * 16 + hq * 4 + r;
-                        s[kt][r] = key <= lim[qt] ? s[kt][r] * scale : -INFINITY;
-                        cm = __builtin_fmaxf(cm, s[kt][r]);
-                    }
-                cm = wave_xor_max(cm, 16);
-                cm = wave_xor_max(cm, 32);
-                const float m_new = __builtin_fmaxf(m_run[qt], cm);  // finite: key 0, in the first chunk, is visible to every query
-                const float alpha = __expf(m_run[qt] - m_new);      // exp(-inf) = 0 on the first chunk
-                f16x8 pf;
-                float ps = 0.f;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    pf[e] = (_Float16)__expf(s[e >> 2][e & 3] - m_new);
-                    ps += (float)pf[e];                             // the sum of the rounded weights the product uses
-                }
-                l_run[qt] = l_run[qt] * alpha + ps;
-                m_run[qt] = m_new;
-#pragma unroll
-                for (int dt = 0; dt < 4; ++dt) {
-                    o[qt][dt] *= alpha;
-                    o[qt][dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf[dt], pf, o[qt][dt], 0, 0, 0);
-                }
+                // finite row maximum: key 0, in the first chunk, is visible to every query
+                decode_mfma_step(kf, vf, qf[qt], o[qt], m_run[qt], l_run[qt], c0, hq, scale, [&](int key) { return key <= lim[qt]; });
             }
         }
     }

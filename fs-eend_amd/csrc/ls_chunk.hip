@@ -41,7 +41,7 @@ void ret_chunk_ragged_kernel(const float* __restrict__ qkvg, float* __restrict__
         for (int j = 0; j < c; ++j) {
             const float* row = qkvg + (r0 + j) * 4 * D;
             float keep, add;
-            ret_scale_factors(t + j, keep, add);
+            ret_scale_factors((float)(t + j), keep, add);
             const float va = row[2 * D + h * 64 + lane] * add;
             const float o = ret_row_update_reg(s, row + D + h * 64, row + h * 64, keep, va);
             const float r = ret_norm_gate(o, row[3 * D + h * 64 + lane], eps);
@@ -84,8 +84,10 @@ void dwconv_chunk_ragged_kernel(const _Float16* __restrict__ x, float* __restric
     for (int j = c; j < nmax; ++j) out[r0 + (size_t)j * D] = (_Float16)0.f;
 }
 
-// spk_attn_step_f32_kernel of stream.hip on decoder slabs: qkv f32 [(b*C + c)*Tp + t][768], out f32 [(b*C + c)*Tp + t][256];
-// the C rows of frame (b, t) attend to each other.  One wave per (row, head); lane = head dimension; C <= 16.
+// Speaker-axis attention in f32 (self_attn2 of the LS decoder layer, merge_retnet_layer.py:300-307, inside the all-f32 decoder
+// frame step; eend_launch_spk_attn_step_f32 of stream.hip is this kernel at Tp = 1) on decoder slabs: qkv f32
+// [(b*C + c)*Tp + t][768] = [q | k | v] (head h at column h*64), out f32 [(b*C + c)*Tp + t][256]; the C rows of frame (b, t)
+// attend to each other.  One wave per (row, head); lane = head dimension; C <= 16 scores per wave.
 __global__ __launch_bounds__(64)
 void spk_attn_rows_f32_kernel(const float* __restrict__ qkv, float* __restrict__ out, int C, int Tp, float scale) {
     const int lane = threadIdx.x, row = blockIdx.x, h = blockIdx.y;

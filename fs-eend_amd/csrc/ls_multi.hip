@@ -1,8 +1,9 @@
 // Many LS-EEND streams in one frame step (LsMultiStreamSession, ls_multistream.py): S slots, each at its own stream position
 // and with its own lifetime, advanced together by one graph replay per frame.  The kernels here are the state touches of the
-// LS frame step made per slot: the recurrent retention step (whose scale is the slot's own position), the Conformer's
-// depthwise-conv cache and the f32 look-ahead window.  Every row computes every frame (fixed shapes for the captured graph);
-// per-slot int32 lengths and masks in device memory decide what each row reads and which state changes.
+// LS frame step made per slot: the recurrent retention step (whose scale is the slot's own position) and the Conformer's
+// depthwise-conv cache (the f32 look-ahead window is window_push_kernel<float> of stream_multi.hip).  Every row computes
+// every frame (fixed shapes for the captured graph); per-slot int32 lengths and masks in device memory decide what each row
+// reads and which state changes.
 #include "common.h"
 #include "kernels.h"
 #include "ls_rows.h"
@@ -16,8 +17,8 @@ namespace {
 //   mask[s] != 0, t >= 0: state updated in place, output row written.  t == 0 is an empty state: the old state is not read
 //                         (a reused slot's leftovers, NaN included, cannot leak; keep = 0 times NaN would still be NaN).
 //   otherwise:            state neither read nor written, output row = 0.
-// The keep / add factors are formed in double exactly as ret_step_kernel forms them, so a slot at position t is bit-identical
-// to eend_retention_step_f32 with scale_in = t.  One wave per (n, h): lane a owns row kv[a][:].
+// The keep / add factors and the row update are the functions ret_step_kernel<float> calls (ls_rows.h), so a slot at position
+// t is bit-identical to eend_retention_step_f32 with scale_in = t.  One wave per (n, h): lane a owns row kv[a][:].
 __global__ __launch_bounds__(256)
 void ret_step_ragged_kernel(const float* __restrict__ qkvg, float* __restrict__ kv, const int* __restrict__ len,
                             const int* __restrict__ mask, int rows_per_seq, _Float16* __restrict__ out, float* __restrict__ out32,
@@ -37,7 +38,7 @@ void ret_step_ragged_kernel(const float* __restrict__ qkvg, float* __restrict__ 
     }
     const float* row = qkvg + (size_t)n * 4 * D;
     float keep, add;
-    ret_scale_factors(t, keep, add);
+    ret_scale_factors((float)t, keep, add);
     const float va = row[2 * D + h * 64 + lane] * add;
     float* st = kv + ((size_t)idx * 64 + lane) * 64;
     const float o = t == 0 ? ret_row_update<true>(st, row + D + h * 64, row + h * 64, keep, va)
@@ -69,21 +70,6 @@ void dwconv_step_ragged_kernel(const _Float16* __restrict__ x, float* __restrict
     out[i] = to_f16_sat(y);
 }
 
-// The f32 look-ahead window of each slot (f32 [S][k*D], [tap*D + c], oldest tap first): mode 1 shifts it by one frame and
-// appends x[s], mode 2 shifts and appends zeros (the reference driver's zero frames while flushing), any other mode leaves
-// the slot alone -- window_push_kernel of stream_multi.hip without the f16 cast.  A thread owns one channel of one slot.
-__global__ __launch_bounds__(256)
-void window_push_f32_kernel(float* __restrict__ win, const float* __restrict__ x, const int* __restrict__ mode, int S, int k, int D) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= S * D) return;
-    const int s = i / D, c = i - s * D;
-    const int m = mode[s];
-    if (m != 1 && m != 2) return;
-    float* w = win + (size_t)s * k * D + c;
-    for (int j = 0; j + 1 < k; ++j) w[(size_t)j * D] = w[(size_t)(j + 1) * D];
-    w[(size_t)(k - 1) * D] = m == 1 ? x[i] : 0.f;
-}
-
 }  // namespace
 
 int eend_launch_ret_step_ragged(const float* qkvg, float* kv, const int* len, const int* mask, int rows_per_seq, void* out16, float* out32,
@@ -104,11 +90,5 @@ int eend_launch_dwconv_step_ragged(const void* x16, float* cache, const int* len
         return EEND_EINVAL;
     hipLaunchKernelGGL(dwconv_step_ragged_kernel, dim3((B * D + 255) / 256), dim3(256), 0, stream, (const _Float16*)x16, cache, len, mask,
                        w, bn_w, bn_b, bn_mean, bn_var, eps, (_Float16*)out16, B, D, k);
-    return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
-}
-
-int eend_launch_window_push_f32(float* win, const float* x, const int* mode, int S, int k, int D, hipStream_t stream) {
-    if (!win || !x || !mode || S <= 0 || k < 1 || D <= 0 || (long)S * D > 0x7fffffffL - 255) return EEND_EINVAL;
-    hipLaunchKernelGGL(window_push_f32_kernel, dim3((S * D + 255) / 256), dim3(256), 0, stream, win, x, mode, S, k, D);
     return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
 }

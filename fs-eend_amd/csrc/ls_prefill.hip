@@ -170,7 +170,7 @@ void ret_prefill_out_kernel(const float* __restrict__ qkvg, const float* __restr
     }
     // 1 / sqrt(t + 1) of the frame, the per-head LayerNorm over a (16 values here, the rest in lanes f + 16 / 32 / 48), the gate
     float keep, add;
-    ret_scale_factors(t0 + 64 * it.c + i, keep, add);
+    ret_scale_factors((float)(t0 + 64 * it.c + i), keep, add);
     float sum = 0.f;
 #pragma unroll
     for (int at = 0; at < 4; ++at)

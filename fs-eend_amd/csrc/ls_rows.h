@@ -1,8 +1,8 @@
-// The per-row arithmetic of the LS-EEND multi-stream state touches, shared by the one-frame kernels (ls_multi.hip) and the
-// chunk kernels (ls_chunk.hip), so that c frames of a chunk are bit for bit c one-frame calls.  Every contraction is written
-// out (__builtin_fmaf) and the compiler's own contraction is off inside these functions (ret_norm_gate excepted, see there):
-// the two callers reach the same instructions whatever surrounds the call.  The forms are the ones ret_step_kernel<float> / dwconv_step_kernel of stream.hip
-// compile to (tests/test_ls_multistream.py holds the one-frame kernels bit-equal to those).
+// The per-row arithmetic of the LS-EEND state touches, shared by the single-stream kernels (stream.hip), the one-frame
+// many-stream kernels (ls_multi.hip) and the chunk kernels (ls_chunk.hip), so that c frames of a chunk are bit for bit c
+// one-frame calls in any of them.  Every contraction is written out (__builtin_fmaf) and the compiler's own contraction is
+// off inside these functions (ret_norm_gate excepted, see there): every caller reaches the same instructions whatever
+// surrounds the call.
 #pragma once
 #include "common.h"
 
@@ -39,10 +39,11 @@ DEV float ret_row_update_reg(float4 (&s)[16], const float* __restrict__ kr, cons
     return o;
 }
 
-// keep = sqrt(t / (t + 1)), add = 1 / sqrt(t + 1) of the frame at position t (decay 1: the running scale is the frame count),
-// formed in double as ret_step_kernel forms them.
-DEV void ret_scale_factors(int t, float& keep, float& add) {
-    const float ps = (float)t;
+// keep = sqrt(ps / (ps + 1)), add = 1 / sqrt(ps + 1) of the frame behind a running scale ps (decay 1: the scale is the frame
+// count t).  The decay of the old state is applied 36 000 times over an hour of audio: formed in double and rounded once, the
+// running product of the factors follows sqrt(s / t) to f32 rounding noise instead of accumulating the bias of the device's
+// fast f32 sqrt / divide sequences.
+DEV void ret_scale_factors(float ps, float& keep, float& add) {
     const float ns = ps + 1.0f;
     keep = (float)__builtin_sqrt((double)ps / (double)ns);
     add = (float)(1.0 / __builtin_sqrt((double)ns));
@@ -50,8 +51,8 @@ DEV void ret_scale_factors(int t, float& keep, float& add) {
 
 // Per-head LayerNorm (no affine) over the wave's 64 values o, then the swish gate g.  Left to the compiler's contraction on
 // purpose: it folds the first step of the variance reduction into an fma on the shuffled operand (var = d*d + d'*d' with d' the
-// neighbour lane's d), in ret_step_kernel<float> as here, and that cannot be written in the source.  The expression is local,
-// so both callers compile it alike (the chunk tests hold them bit-equal on the device).
+// neighbour lane's d), and that cannot be written in the source.  The expression is local, so every caller compiles it alike
+// (the chunk tests hold them bit-equal on the device).
 DEV float ret_norm_gate(float o, float g, float eps) {
     float sum = o;
 #pragma unroll
@@ -64,8 +65,8 @@ DEV float ret_norm_gate(float o, float g, float eps) {
     return g / (1.0f + __expf(-g)) * y;
 }
 
-// One frame through one channel's depthwise-conv cache cc[k-1] (shifted in place; fresh: read as zeros), BatchNorm, swish.
-DEV float dwconv_frame(float* __restrict__ cc, const float* __restrict__ wc, float xn, bool fresh, int k, float bm, float sc, float bb) {
+// One frame through one channel's depthwise-conv cache cc[k-1] (shifted in place; fresh: read as zeros): the taps' sum.
+DEV float dwconv_taps(float* __restrict__ cc, const float* __restrict__ wc, float xn, bool fresh, int k) {
 #pragma clang fp contract(off)
     float y = wc[k - 1] * xn;
     float prev = xn;
@@ -75,6 +76,17 @@ DEV float dwconv_frame(float* __restrict__ cc, const float* __restrict__ wc, flo
         cc[j] = prev;                            // new_cache[j] = window[j+1]
         prev = cur;
     }
+    return y;
+}
+
+// BatchNorm (eval; sc = weight / sqrt(var + eps)) and swish behind the taps' sum.
+DEV float bn_swish(float y, float bm, float sc, float bb) {
+#pragma clang fp contract(off)
     y = __builtin_fmaf(y - bm, sc, bb);
     return y / (1.0f + __expf(-y));
+}
+
+// One frame through one channel: taps, BatchNorm, swish.
+DEV float dwconv_frame(float* __restrict__ cc, const float* __restrict__ wc, float xn, bool fresh, int k, float bm, float sc, float bb) {
+    return bn_swish(dwconv_taps(cc, wc, xn, fresh, k), bm, sc, bb);
 }

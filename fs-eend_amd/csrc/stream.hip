@@ -1,9 +1,14 @@
-// Frame-by-frame (streaming) state kernels of LS-EEND.  One frame of one stream is far too
-// little work for the matrix pipe: these are latency-bound VALU kernels whose job is to keep
-// the recurrent state resident in HBM/L2 in the layout the reference's driver owns
-// (LS-EEND/streaming_infer_dia.py:37-49) and to touch it exactly once per frame.
+// Frame-by-frame (streaming) state kernels of one stream.  One frame is far too little work for the matrix pipe: these are
+// latency-bound VALU kernels whose job is to keep the state resident in HBM/L2 and to touch it exactly once per frame.
+// First half: the LS-EEND frame step -- the recurrent retention state, the f32 projections around it and the Conformer's
+// depthwise-conv cache, in the layout the reference's driver owns (LS-EEND/streaming_infer_dia.py:37-49); the per-frame
+// arithmetic is ls_rows.h's, the many-stream forms (ls_multi.hip, ls_chunk.hip) run the same functions.
+// Second half: the FS-EEND decode attention over a growing K/V cache, whole and split over the key axis; its steps are
+// decode_tile.h's, shared with the ragged, chunk and prefill forms (stream_multi.hip, stream_chunk.hip, attn_prefill.hip).
 #include "common.h"
 #include "kernels.h"
+#include "decode_tile.h"
+#include "ls_rows.h"
 
 namespace {
 
@@ -16,7 +21,25 @@ namespace {
 // updated in place; scale_in/scale_out f32 [H] (first frame: scale_in = 0, kv = 0).
 // One wave per (n, h): lane a owns row kv[a][:].
 // QT = _Float16: the batch path's operand precision; QT = float: the projections of eend_retention_proj_step_f32 (frame-by-
-// frame sessions: see there).
+// frame sessions: see there), on the row update of ls_rows.h.  The f16 form keeps its own text: on ret_upd4 it gains a VGPR.
+DEV float ret_step_row(float* __restrict__ st, const float* __restrict__ kr, const float* __restrict__ qr, float keep, float va) {
+    return ret_row_update<false>(st, kr, qr, keep, va);
+}
+DEV float ret_step_row(float* __restrict__ st, const _Float16* __restrict__ kr, const _Float16* __restrict__ qr, float keep, float va) {
+    float o = 0.f;
+#pragma unroll
+    for (int b = 0; b < 64; b += 4) {
+        float4 s = *(const float4*)(st + b);
+        const f16x4 kk = *(const f16x4*)(kr + b), qq = *(const f16x4*)(qr + b);
+        s.x = __builtin_fmaf(s.x, keep, va * (float)kk[0]);
+        s.y = __builtin_fmaf(s.y, keep, va * (float)kk[1]);
+        s.z = __builtin_fmaf(s.z, keep, va * (float)kk[2]);
+        s.w = __builtin_fmaf(s.w, keep, va * (float)kk[3]);
+        *(float4*)(st + b) = s;
+        o += (float)qq[0] * s.x + (float)qq[1] * s.y + (float)qq[2] * s.z + (float)qq[3] * s.w;
+    }
+    return o;
+}
 template <class QT>
 __global__ __launch_bounds__(256)
 void ret_step_kernel(const QT* __restrict__ qkvg, float* __restrict__ kv, const float* __restrict__ scale_in,
@@ -28,41 +51,14 @@ void ret_step_kernel(const QT* __restrict__ qkvg, float* __restrict__ kv, const 
     const int D = H * 64;
     const QT* row = qkvg + (size_t)n * 4 * D;
     const float ps = scale_in[h];
-    const float ns = ps + 1.0f;
-    // the decay of the old state is applied 36 000 times over an hour of audio: evaluate it in double and round once, so
-    // that the running product of the factors follows sqrt(s/t) to fp32 rounding noise instead of accumulating the bias
-    // of the device's fast f32 sqrt / divide sequences
-    const float keep = (float)__builtin_sqrt((double)ps / (double)ns);
-    const float add = (float)(1.0 / __builtin_sqrt((double)ns));
+    float keep, add;
+    ret_scale_factors(ps, keep, add);
     const float va = (float)row[2 * D + h * 64 + lane] * add;
-    float* st = kv + ((size_t)idx * 64 + lane) * 64;
-    float o = 0.f;
-#pragma unroll
-    for (int b = 0; b < 64; b += 4) {
-        float4 s = *(const float4*)(st + b);
-        typedef QT qt4 __attribute__((ext_vector_type(4)));
-        const qt4 kk = *(const qt4*)(row + D + h * 64 + b);
-        const qt4 qq = *(const qt4*)(row + h * 64 + b);
-        s.x = __builtin_fmaf(s.x, keep, va * (float)kk[0]);
-        s.y = __builtin_fmaf(s.y, keep, va * (float)kk[1]);
-        s.z = __builtin_fmaf(s.z, keep, va * (float)kk[2]);
-        s.w = __builtin_fmaf(s.w, keep, va * (float)kk[3]);
-        *(float4*)(st + b) = s;
-        o += (float)qq[0] * s.x + (float)qq[1] * s.y + (float)qq[2] * s.z + (float)qq[3] * s.w;
-    }
-    float sum = o;
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) sum = wave_xor_add(sum, m);
-    const float mean = sum * (1.0f / 64.0f);
-    float var = (o - mean) * (o - mean);
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) var = wave_xor_add(var, m);
-    const float y = (o - mean) / __builtin_sqrtf(var * (1.0f / 64.0f) + eps);
-    const float g = (float)row[3 * D + h * 64 + lane];
-    const float r = g / (1.0f + __expf(-g)) * y;
+    const float o = ret_step_row(kv + ((size_t)idx * 64 + lane) * 64, row + D + h * 64, row + h * 64, keep, va);
+    const float r = ret_norm_gate(o, (float)row[3 * D + h * 64 + lane], eps);
     if (out) out[(size_t)n * D + h * 64 + lane] = to_f16_sat(r);
     if (out32) out32[(size_t)n * D + h * 64 + lane] = r;
-    if (n == 0 && lane == 0) scale_out[h] = ns;
+    if (n == 0 && lane == 0) scale_out[h] = ps + 1.0f;
 }
 
 // Retention projections of ONE frame in full f32 (frame-by-frame sessions): qkvg[n][f] = <LN(x[n]), W[f]> + b[f] for the
@@ -140,38 +136,6 @@ void convert_step_f32_kernel(const float* __restrict__ emb, const float* __restr
     }
 }
 
-// Speaker-axis attention of one frame in f32 (self_attn2 of the LS decoder layer, merge_retnet_layer.py:300-307, inside
-// the all-f32 decoder frame step): qkv f32 [B*C][768] = [q | k | v] (head h at column h*64), out f32 [B*C][256].
-// One wave per (row, head); lane = head dimension; C <= 16 scores per wave.
-__global__ __launch_bounds__(64)
-void spk_attn_step_f32_kernel(const float* __restrict__ qkv, float* __restrict__ out, int C, float scale) {
-    const int lane = threadIdx.x, row = blockIdx.x, h = blockIdx.y;
-    const int b0 = (row / C) * C;
-    const float q = qkv[(size_t)row * 768 + h * 64 + lane] * scale;
-    float sc[16];
-    float mx = -INFINITY;
-#pragma unroll
-    for (int c = 0; c < 16; ++c) {
-        float d = 0.f;
-        if (c < C) {
-            d = q * qkv[(size_t)(b0 + c) * 768 + 256 + h * 64 + lane];
-#pragma unroll
-            for (int m = 1; m < 64; m <<= 1) d = wave_xor_add(d, m);
-            mx = __builtin_fmaxf(mx, d);
-        }
-        sc[c] = d;
-    }
-    float den = 0.f, o = 0.f;
-#pragma unroll
-    for (int c = 0; c < 16; ++c)
-        if (c < C) {
-            const float pr = __expf(sc[c] - mx);
-            den += pr;
-            o = __builtin_fmaf(pr, qkv[(size_t)(b0 + c) * 768 + 512 + h * 64 + lane], o);
-        }
-    out[(size_t)row * 256 + h * 64 + lane] = o / den;
-}
-
 // y[r] = x[r] / ||x[r]||_2 over 256 features, f32 rows (the embedding normalisation of the f32 frame step; LS model :87, no eps).
 __global__ __launch_bounds__(64)
 void l2norm_rows_f32_kernel(const float* __restrict__ x, float* __restrict__ y) {
@@ -194,20 +158,8 @@ void dwconv_step_kernel(const _Float16* __restrict__ x, float* __restrict__ cach
     const int i = blockIdx.x * blockDim.x + threadIdx.x;       // b*D + c
     if (i >= B * D) return;
     const int c = i % D;
-    float* cc = cache + (size_t)i * (k - 1);
-    const float* wc = w + (size_t)c * k;
-    const float xn = (float)x[i];
-    float y = wc[k - 1] * xn;
-    float prev = xn;
-    for (int j = k - 2; j >= 0; --j) {           // walk backwards so the shift can be done in place
-        const float cur = cc[j];
-        y = __builtin_fmaf(wc[j], cur, y);
-        cc[j] = prev;                            // new_cache[j] = window[j+1]
-        prev = cur;
-    }
-    const float sc = bw[c] / __builtin_sqrtf(bv[c] + eps);
-    y = (y - bm[c]) * sc + bb[c];
-    out[i] = to_f16_sat(y / (1.0f + __expf(-y)));
+    const float y = dwconv_taps(cache + (size_t)i * (k - 1), w + (size_t)c * k, (float)x[i], false, k);
+    out[i] = to_f16_sat(bn_swish(y, bm[c], bw[c] / __builtin_sqrtf(bv[c] + eps), bb[c]));
 }
 
 // FS-EEND incremental self-attention (FS-EEND/nnet/modules/streaming_tfm.py:15-37): one new token
@@ -232,30 +184,16 @@ void attn_decode_kernel(const _Float16* __restrict__ qkv, _Float16* __restrict__
     const _Float16* row = qkv + (size_t)n * 3 * D + h * 64;
     _Float16* Kh = Kc + (size_t)idx * cap * 64;
     _Float16* Vh = Vc + (size_t)idx * cap * 64;
-    const _Float16 kn = row[D + lane], vn = row[2 * D + lane];
-    Kh[(size_t)t * 64 + lane] = kn;
-    Vh[(size_t)t * 64 + lane] = vn;
+    decode_append(Kh, Vh, t, row, D, lane);
     float qf[64];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const f16x8 q8 = *(const f16x8*)(row + i * 8);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) qf[i * 8 + e] = (float)q8[e] * scale;
-    }
-    // the new token's own score and value come from registers (its cache rows are not read back)
-    float s_new = qf[0] * 0.f;
-    {
-        float part = (float)row[lane] * scale * (float)kn;
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) part = wave_xor_add(part, m);
-        s_new = part;
-    }
-    float m_run = s_new, l_run = 1.0f, o = (float)vn;        // softmax state seeded with the new token
+    decode_q_scaled(qf, row, scale);
+    // softmax state seeded with the new token: its score and value come from the qkv row (its cache rows are not read back)
+    float m_run = decode_self_score(row, D, lane, scale), l_run = 1.0f, o = (float)row[2 * D + lane];
     for (int c0 = 0; c0 < t; c0 += 64) {
         const int key = c0 + lane;
         float s = -INFINITY;
-        if (key < t) {
-            const _Float16* kr = Kh + (size_t)key * 64;
+        if (key < t) {                                        // decode_score with the K row requested piece by piece: its
+            const _Float16* kr = Kh + (size_t)key * 64;       // row-first form costs this kernel 6 VGPRs
             float acc = 0.f;
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
@@ -265,23 +203,14 @@ void attn_decode_kernel(const _Float16* __restrict__ qkv, _Float16* __restrict__
             }
             s = acc;
         }
-        float cm = s;
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) cm = wave_xor_max(cm, m);
-        const float m_new = __builtin_fmaxf(m_run, cm);
-        const float alpha = __expf(m_run - m_new);
-        const float p = __expf(s - m_new);                    // 0 for key >= t
-        float ps = p;
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) ps = wave_xor_add(ps, m);
-        l_run = l_run * alpha + ps;
+        float alpha;
+        const float p = decode_softmax_chunk(s, m_run, l_run, alpha);      // 0 for key >= t
         o *= alpha;
         const int nk = (t - c0) < 64 ? (t - c0) : 64;
         for (int j = 0; j < nk; ++j) {
             const float pj = __shfl(p, j, 64);
             o = __builtin_fmaf(pj, (float)Vh[(size_t)(c0 + j) * 64 + lane], o);
         }
-        m_run = m_new;
     }
     out[(size_t)n * D + h * 64 + lane] = to_f16_sat(o / l_run);
 }
@@ -290,16 +219,14 @@ void attn_decode_kernel(const _Float16* __restrict__ qkv, _Float16* __restrict__
 // ---- long histories: the same decode step split over the key axis ("flash decoding").  One wave per (n, h) walks its
 // history serially -- fine for the t <= 1000 the model is trained on, but at the one-hour position of BASELINE config 5
 // (t = 36 000) a frame then costs 86 ms: 64 waves on a 256-CU part, each chasing 36 000 dependent rows.  Here a
-// workgroup owns DEC_R consecutive keys of one (n, h) (its 4 waves take the 64-key chunks round-robin, online softmax
+// workgroup owns DT_R consecutive keys of one (n, h) (its 4 waves take the 64-key chunks round-robin, online softmax
 // per wave, merged through LDS) and writes (max, sum, o[64]) partials; a second tiny kernel merges the partials of a
-// (n, h) and adds the new token.  Grid = (N*H, cap / DEC_R): fixed per cache capacity, so a captured hipGraph stays valid
+// (n, h) and adds the new token.  Grid = (N*H, cap / DT_R): fixed per cache capacity, so a captured hipGraph stays valid
 // while t (read from device memory) grows; blocks whose key range starts at or beyond t write an empty partial.
-constexpr int DEC_R = 512;
-
 __global__ __launch_bounds__(256)
 void attn_decode_split_kernel(const _Float16* __restrict__ qkv, _Float16* __restrict__ Kc, _Float16* __restrict__ Vc,
                               float* __restrict__ part, int N, int H, int cap, int nsplit, const int* __restrict__ t_dev, float scale) {
-    __shared__ float red[4][66];
+    __shared__ float red[4][DT_PART];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int idx = blockIdx.x, sp = blockIdx.y;
     const int t = __builtin_amdgcn_readfirstlane(*t_dev);
@@ -308,46 +235,19 @@ void attn_decode_split_kernel(const _Float16* __restrict__ qkv, _Float16* __rest
     const _Float16* row = qkv + (size_t)n * 3 * D + h * 64;
     _Float16* Kh = Kc + (size_t)idx * cap * 64;
     _Float16* Vh = Vc + (size_t)idx * cap * 64;
-    if (sp == 0 && wave == 0 && t < cap) {                    // append the new token's k / v (never read back this step)
-        Kh[(size_t)t * 64 + lane] = row[D + lane];
-        Vh[(size_t)t * 64 + lane] = row[2 * D + lane];
-    }
-    const int k0 = sp * DEC_R;
-    int k1 = k0 + DEC_R;
+    if (sp == 0 && wave == 0 && t < cap) decode_append(Kh, Vh, t, row, D, lane);      // never read back this step
+    const int k0 = sp * DT_R;
+    int k1 = k0 + DT_R;
     k1 = k1 < t ? k1 : t;
     float m_run = -INFINITY, l_run = 0.f, o = 0.f;
     if (k0 < t && t < cap) {
         float qf[64];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const f16x8 q8 = *(const f16x8*)(row + i * 8);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) qf[i * 8 + e] = (float)q8[e] * scale;
-        }
+        decode_q_scaled(qf, row, scale);
         for (int c0 = k0 + wave * 64; c0 < k1; c0 += 256) {
             const int key = c0 + lane;
-            float s = -INFINITY;
-            if (key < k1) {
-                const _Float16* kr = Kh + (size_t)key * 64;
-                float acc = 0.f;
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const f16x8 k8 = *(const f16x8*)(kr + i * 8);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) acc = __builtin_fmaf(qf[i * 8 + e], (float)k8[e], acc);
-                }
-                s = acc;
-            }
-            float cm = s;
-#pragma unroll
-            for (int m = 1; m < 64; m <<= 1) cm = wave_xor_max(cm, m);
-            const float m_new = __builtin_fmaxf(m_run, cm);
-            const float alpha = __expf(m_run - m_new);         // exp(-inf) = 0 on the first chunk
-            const float p = __expf(s - m_new);                 // 0 for key >= k1
-            float ps = p;
-#pragma unroll
-            for (int m = 1; m < 64; m <<= 1) ps = wave_xor_add(ps, m);
-            l_run = l_run * alpha + ps;
+            const float s = key < k1 ? decode_score(qf, Kh + (size_t)key * 64) : -INFINITY;
+            float alpha;
+            const float p = decode_softmax_chunk(s, m_run, l_run, alpha);      // 0 for key >= k1
             o *= alpha;
             const int nk = (k1 - c0) < 64 ? (k1 - c0) : 64;
             for (int j8 = 0; j8 < nk; j8 += 8) {               // 8 independent V rows in flight per step
@@ -357,29 +257,12 @@ void attn_decode_split_kernel(const _Float16* __restrict__ qkv, _Float16* __rest
 #pragma unroll
                 for (int jj = 0; jj < 8; ++jj) o = __builtin_fmaf(__shfl(p, j8 + jj, 64), v[jj], o);
             }
-            m_run = m_new;
         }
     }
     red[wave][lane] = o;
     if (lane == 0) { red[wave][64] = m_run; red[wave][65] = l_run; }
     __syncthreads();
-    if (wave == 0) {
-        const float m0 = red[0][64], m1 = red[1][64], m2 = red[2][64], m3 = red[3][64];
-        const float M = __builtin_fmaxf(__builtin_fmaxf(m0, m1), __builtin_fmaxf(m2, m3));
-        float L = 0.f, O = 0.f;
-        if (M > -INFINITY) {
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                const float mw = red[w][64];
-                const float f = mw > -INFINITY ? __expf(mw - M) : 0.f;
-                L += red[w][65] * f;
-                O += red[w][lane] * f;
-            }
-        }
-        float* pp = part + ((size_t)idx * nsplit + sp) * 66;
-        pp[lane] = O;
-        if (lane == 0) { pp[64] = M; pp[65] = L; }
-    }
+    if (wave == 0) decode_combine4<true>(&red[0][0], DT_PART, lane, part + ((size_t)idx * nsplit + sp) * DT_PART);
 }
 
 __global__ __launch_bounds__(64)
@@ -391,21 +274,9 @@ void attn_decode_merge_kernel(const _Float16* __restrict__ qkv, const float* __r
     const int n = idx / H, h = idx - n * H;
     const int D = H * 64;
     const _Float16* row = qkv + (size_t)n * 3 * D + h * 64;
-    float sn = (float)row[lane] * scale * (float)row[D + lane];            // the new token's own score q . k_new
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) sn = wave_xor_add(sn, m);
-    float M = sn, L = 1.0f, O = (float)row[2 * D + lane];
-    const int ns = (t + DEC_R - 1) / DEC_R;
-    for (int s = 0; s < ns && s < nsplit; ++s) {
-        const float* pp = part + ((size_t)idx * nsplit + s) * 66;
-        const float ms = pp[64], ls = pp[65];
-        if (!(ls > 0.f)) continue;
-        const float Mn = __builtin_fmaxf(M, ms);
-        const float a = __expf(M - Mn), b = __expf(ms - Mn);
-        L = L * a + ls * b;
-        O = O * a + pp[lane] * b;
-        M = Mn;
-    }
+    float M = decode_self_score(row, D, lane, scale), L = 1.0f, O = (float)row[2 * D + lane];
+    const int ns = (t + DT_R - 1) / DT_R;
+    decode_walk<true, false>(M, L, O, part + (size_t)idx * nsplit * DT_PART, DT_PART, ns < nsplit ? ns : nsplit, lane);
     out[(size_t)n * D + h * 64 + lane] = to_f16_sat(O / L);
 }
 
@@ -426,8 +297,8 @@ int eend_launch_attn_decode(const void* qkv, void* Kc, void* Vc, void* out16, in
 int eend_launch_attn_decode_split(const void* qkv, void* Kc, void* Vc, void* out16, float* part, long part_floats, int N, int H, int cap,
                                   const int* t_dev, float scale, hipStream_t stream) {
     if (N <= 0 || H <= 0 || cap <= 0 || !t_dev || !part) return EEND_EINVAL;
-    const int nsplit = (cap + DEC_R - 1) / DEC_R;
-    if (nsplit > 65535 || part_floats < (long)N * H * nsplit * 66) return EEND_EINVAL;
+    const int nsplit = decode_nsplit(cap);
+    if (nsplit > 65535 || part_floats < decode_ws_floats(N, H, cap, 1)) return EEND_EINVAL;
     hipLaunchKernelGGL(attn_decode_split_kernel, dim3(N * H, nsplit), dim3(256), 0, stream, (const _Float16*)qkv, (_Float16*)Kc, (_Float16*)Vc,
                        part, N, H, cap, nsplit, t_dev, scale);
     if (hipGetLastError() != hipSuccess) return EEND_ELAUNCH;
@@ -479,9 +350,7 @@ int eend_launch_l2norm_rows_f32(const float* x, float* y, int rows, hipStream_t 
 }
 
 int eend_launch_spk_attn_step_f32(const float* qkv, float* out, int B, int C, float scale, hipStream_t stream) {
-    if (!qkv || !out || B <= 0 || C <= 0 || C > 16) return EEND_EINVAL;
-    hipLaunchKernelGGL(spk_attn_step_f32_kernel, dim3(B * C, 4), dim3(64), 0, stream, qkv, out, C, scale);
-    return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
+    return eend_launch_spk_attn_rows_f32(qkv, out, B, C, 1, scale, stream);      // one frame: slabs of Tp = 1
 }
 
 int eend_launch_dwconv_step(const void* x16, float* cache, const float* w, const float* bn_w, const float* bn_b,

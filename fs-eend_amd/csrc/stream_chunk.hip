@@ -5,6 +5,7 @@
 // window over a chunk of frames and the history counters advanced by a count.
 #include "common.h"
 #include "kernels.h"
+#include "decode_tile.h"
 
 namespace {
 
@@ -17,10 +18,9 @@ namespace {
 // 16-query tile S^T = K Q^T and O^T += V^T P^T on mfma_f32_16x16x32_f16 (C/D: column = lane & 15 = query, rows
 // 4 (lane >> 4) + r).  The P^T tile feeds the second product straight from the score registers: its k index 8h + e stands
 // for key 4h + e (e < 4, first 16-key tile) or 16 + 4h + e - 4 (second tile), and V^T takes the same keys from a row-major
-// LDS copy of the chunk.  The merge launch walks a query's partials in key order, then folds in the causal part inside
-// the chunk, read from qkv (never from the cache: the appends of the same launch cannot race with it).
-constexpr int CK_R = 512;                                // keys per split block, anchored at key 0
-constexpr int CK_PART = 66;                              // o[64], max, sum
+// LDS copy of the chunk (decode_mfma_step of decode_tile.h, the step the prefill runs).  The merge launch walks a query's
+// partials in key order, then folds in the causal part inside the chunk, read from qkv (never from the cache: the appends of
+// the same launch cannot race with it).
 constexpr int CK_SV = 72;                                // LDS row stride of the V chunk (halves)
 
 DEV bool chunk_live(int t, int c, int cap, int nmax) { return c > 0 && c <= nmax && t >= 0 && t + c <= cap; }
@@ -30,16 +30,16 @@ void attn_chunk_ragged_kernel(const _Float16* __restrict__ qkv, const _Float16* 
                               float* __restrict__ part, int H, int cap, int nsplit, int nmax, int rows_per_seq,
                               const int* __restrict__ len, const int* __restrict__ cnt, float scale) {
     __shared__ _Float16 vs[4][32 * CK_SV];
-    __shared__ float red[4][16][CK_PART];
+    __shared__ float red[4][16][DT_PART];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int idx = blockIdx.x, sp = blockIdx.y;
     const int q = idx / H, h = idx - q * H;
     const int slot = q / rows_per_seq;
     const int t = __builtin_amdgcn_readfirstlane(len[slot]);
     const int c = __builtin_amdgcn_readfirstlane(cnt[slot]);
-    const int k0 = sp * CK_R;
+    const int k0 = sp * DT_R;
     if (!chunk_live(t, c, cap, nmax) || k0 >= t) return;            // the merge reads no partial of this block
-    const int k1 = k0 + CK_R < t ? k0 + CK_R : t;
+    const int k1 = k0 + DT_R < t ? k0 + DT_R : t;
     const int D = H * 64;
     const int col = lane & 15, hq = lane >> 4;
     const int nt = (c + 15) >> 4;                                   // 16-query tiles in use (<= 4)
@@ -92,39 +92,7 @@ void attn_chunk_ragged_kernel(const _Float16* __restrict__ qkv, const _Float16* 
 #pragma unroll
         for (int qt = 0; qt < 4; ++qt) {
             if (qt >= nt) break;
-            f32x4 s[2];
-#pragma unroll
-            for (int kt = 0; kt < 2; ++kt) {
-                s[kt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[kt][0], qf[qt][0], (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-                s[kt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[kt][1], qf[qt][1], s[kt], 0, 0, 0);
-            }
-            float cm = -INFINITY;
-#pragma unroll
-            for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int key = c0 + kt * 16 + hq * 4 + r;
-                    s[kt][r] = key < k1 ? s[kt][r] * scale : -INFINITY;
-                    cm = __builtin_fmaxf(cm, s[kt][r]);
-                }
-            cm = wave_xor_max(cm, 16);
-            cm = wave_xor_max(cm, 32);                              // finite: key c0 < k1 is in every query's column
-            const float m_new = __builtin_fmaxf(m_run[qt], cm);
-            const float alpha = __expf(m_run[qt] - m_new);          // exp(-inf) = 0 on the first chunk
-            f16x8 pf;
-            float ps = 0.f;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                pf[e] = (_Float16)__expf(s[e >> 2][e & 3] - m_new);
-                ps += (float)pf[e];                                 // the sum of the rounded weights the product uses
-            }
-            l_run[qt] = l_run[qt] * alpha + ps;
-            m_run[qt] = m_new;
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) {
-                o[qt][dt] *= alpha;
-                o[qt][dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf[dt], pf, o[qt][dt], 0, 0, 0);
-            }
+            decode_mfma_step(kf, vf, qf[qt], o[qt], m_run[qt], l_run[qt], c0, hq, scale, [&](int key) { return key < k1; });
         }
         __builtin_amdgcn_wave_barrier();
     }
@@ -143,20 +111,7 @@ void attn_chunk_ragged_kernel(const _Float16* __restrict__ qkv, const _Float16* 
         __syncthreads();
         for (int e = threadIdx.x; e < 16 * 64; e += 256) {
             const int jj = e >> 6, d = e & 63, j = qt * 16 + jj;
-            if (j < c) {
-                const float M = __builtin_fmaxf(__builtin_fmaxf(red[0][jj][64], red[1][jj][64]), __builtin_fmaxf(red[2][jj][64], red[3][jj][64]));
-                float L = 0.f, O = 0.f;
-#pragma unroll
-                for (int w = 0; w < 4; ++w) {                       // M is finite: wave 0's first chunk holds key k0 < t
-                    const float mw = red[w][jj][64];
-                    const float f = mw > -INFINITY ? __expf(mw - M) : 0.f;
-                    L += red[w][jj][65] * f;
-                    O += red[w][jj][d] * f;
-                }
-                float* pp = part + (((size_t)idx * nsplit + sp) * nmax + j) * CK_PART;
-                pp[d] = O;
-                if (d == 0) { pp[64] = M; pp[65] = L; }
-            }
+            if (j < c) decode_combine4<false>(&red[0][jj][0], 16 * DT_PART, d, part + (((size_t)idx * nsplit + sp) * nmax + j) * DT_PART);
         }
         __syncthreads();
     }
@@ -192,18 +147,10 @@ void attn_chunk_ragged_merge_kernel(const _Float16* __restrict__ qkv, const floa
         Vc[((size_t)idx * cap + t + j) * 64 + lane] = vx;
     }
     __syncthreads();
-    const int ns = (t + CK_R - 1) / CK_R;
+    const int ns = (t + DT_R - 1) / DT_R;
     for (int j = wave; j < c; j += 4) {
         float M = -INFINITY, L = 0.f, O = 0.f;
-        for (int s = 0; s < ns; ++s) {
-            const float* pp = part + (((size_t)idx * nsplit + s) * nmax + j) * CK_PART;
-            const float ms = pp[64], ls = pp[65];
-            const float Mn = __builtin_fmaxf(M, ms);
-            const float a = M > -INFINITY ? __expf(M - Mn) : 0.f, b = __expf(ms - Mn);
-            L = L * a + ls * b;
-            O = O * a + pp[lane] * b;
-            M = Mn;
-        }
+        decode_walk<false, true>(M, L, O, part + ((size_t)idx * nsplit * nmax + j) * DT_PART, (size_t)nmax * DT_PART, ns, lane);
         // in-chunk keys 0..j: lane = key
         float sc = -INFINITY;
         if (lane <= j) {
@@ -221,10 +168,7 @@ void attn_chunk_ragged_merge_kernel(const _Float16* __restrict__ qkv, const floa
         for (int m = 1; m < 64; m <<= 1) lc = wave_xor_add(lc, m);
         float oc = 0.f;
         for (int kk = 0; kk <= j; ++kk) oc = __builtin_fmaf(__shfl(p, kk, 64), vsh[kk][lane], oc);
-        const float Mn = __builtin_fmaxf(M, mc);
-        const float a = M > -INFINITY ? __expf(M - Mn) : 0.f, b = __expf(mc - Mn);
-        L = L * a + lc * b;
-        O = O * a + oc * b;
+        decode_fold<true>(M, L, O, mc, lc, oc);
         out[((size_t)q * nmax + j) * D + h * 64 + lane] = to_f16_sat(O / L);
     }
 }
@@ -269,8 +213,6 @@ void window_chunk_kernel(T* __restrict__ win, const float* __restrict__ x, T* __
         for (int tap = 0; tap < k; ++tap) w[(size_t)tap * D] = z(P + tap);      // ascending: reads index P + tap >= tap
 }
 
-long chunk_ws_floats(int Nseq, int H, int cap, int nmax) { return (long)Nseq * H * ((cap + CK_R - 1) / CK_R) * nmax * CK_PART; }
-
 }  // namespace
 
 int eend_launch_attn_chunk_ragged(const void* qkv, void* Kc, void* Vc, void* out16, float* part, long part_floats, int Nseq, int H,
@@ -278,9 +220,9 @@ int eend_launch_attn_chunk_ragged(const void* qkv, void* Kc, void* Vc, void* out
     if (!qkv || !Kc || !Vc || !out16 || !part || !len || !cnt || Nseq <= 0 || H <= 0 || cap <= 0 || nmax < 1 || nmax > 64 ||
         rows_per_seq <= 0 || Nseq % rows_per_seq)
         return EEND_EINVAL;
-    const int nsplit = (cap + CK_R - 1) / CK_R;
+    const int nsplit = decode_nsplit(cap);
     if (nsplit > 65535 || (long)Nseq * H > 0x7fffffffL || (long)Nseq * nmax * 3 * H * 64 > 0x7fffffffL ||
-        part_floats < chunk_ws_floats(Nseq, H, cap, nmax))
+        part_floats < decode_ws_floats(Nseq, H, cap, nmax))
         return EEND_EINVAL;
     hipLaunchKernelGGL(attn_chunk_ragged_kernel, dim3(Nseq * H, nsplit), dim3(256), 0, stream, (const _Float16*)qkv, (const _Float16*)Kc,
                        (const _Float16*)Vc, part, H, cap, nsplit, nmax, rows_per_seq, len, cnt, scale);

@@ -1,6 +1,7 @@
 """SHA-256 of every output tensor of the weight-stream entries at small fixed-seed shapes that reach each tiling, the phantom-slot
 forms, a ragged last tile, both tile sizes and a second grid round, and of the forward entries that reach the flash and retention tile
-loops (flash_tile.h): resident / tiled / packed / long / training attention, chunk-resident / tiled / fused retention.
+loops (flash_tile.h): resident / tiled / packed / long / training attention, chunk-resident / tiled / fused retention; and of every
+streaming state entry (decode_tile.h, ls_rows.h) with the state it leaves: K/V caches, partials, retention state, conv cache, windows.
 Two builds of the library compute the same bits exactly when their listings are identical:   python tools/stream_hash.py > a.txt;  EEND_HIP_LIB=<other .so> python tools/stream_hash.py > b.txt"""
 import ctypes, hashlib, importlib, math, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -176,3 +177,104 @@ for Tp, Lc in ((128, 64), (192, 100), (320, 300), (640, 576)):      # ragged las
         kv = torch.zeros(nseq * H * nc * 4096, device="cuda")
         train._call("eend_retention_chunk_train_f16", q, k, kt, vt, gate, ctx, rhat, rc, st, kv, cs, se, nseq, H, Tp, Lc, 256, 256, 1e-6, Tp)
         show(f"retention_chunk_train Tp={Tp} L={Lc}", ctx=ctx, rhat=rhat, rc=rc)
+
+# ---- the streaming state kernels (decode_tile.h, ls_rows.h): outputs and the whole state after each call, stale rows included
+i32 = lambda *vals: torch.tensor(vals, dtype=torch.int32, device="cuda")
+H, D = 4, 256
+for t in (0, 1, 63, 64, 65, 130):                  # one wave per (n, h): 64-key chunks, the last one ragged
+    N, cap = 2, 256
+    qkv, K0, V0 = r(N, 3 * D).half(), r(N, H, cap, 64).half(), r(N, H, cap, 64).half()
+    K, V, o = K0.clone(), V0.clone(), z16(N, D)
+    ops.attn_decode(qkv, K, V, o, N, H, cap, t)
+    show(f"attn_decode t={t}", out16=o, K=K, V=V)
+    K, V, o = K0.clone(), V0.clone(), z16(N, D)
+    ops.attn_decode_dev(qkv, K, V, o, N, H, cap, i32(t))
+    show(f"attn_decode_dev t={t}", out16=o, K=K, V=V)
+for t in (0, 1, 255, 256, 257, 511, 512, 513, 1300):     # 512-key blocks of four waves x 64 keys
+    N, cap = 2, 2048
+    qkv, K, V, o = r(N, 3 * D).half(), r(N, H, cap, 64).half(), r(N, H, cap, 64).half(), z16(N, D)
+    ws = r(ops.attn_decode_split_ws(N, H, cap))
+    ops.attn_decode_split(qkv, K, V, o, ws, N, H, cap, i32(t))
+    show(f"attn_decode_split t={t}", out16=o, K=K, V=V, ws=ws)
+for rps in (1, 3):
+    for lens, mask in (((0, 65, 513, 1300), (1, 1, 1, 1)), ((0, 65, 513, 1300), (1, 0, 1, 1)), ((0, 65, 2048, 1300), (1, 1, 1, 1))):
+        N, cap = 4 * rps, 2048
+        qkv, K, V, o = r(N, 3 * D).half(), r(N, H, cap, 64).half(), r(N, H, cap, 64).half(), r(N, D).half()
+        ws = r(ops.attn_decode_ragged_ws(N, H, cap))
+        ops.attn_decode_ragged(qkv, K, V, o, ws, N, H, cap, rps, i32(*lens), i32(*mask))
+        show(f"attn_decode_ragged rps={rps} lens={lens} mask={mask}", out16=o, K=K, V=V, ws=ws)
+for nmax in (1, 16, 17, 64):
+    for rps in (1, 3):
+        lens, cnt = (0, 31, 33, 129, 512, 600), tuple(min(c, nmax) for c in (64, 1, 0, 16, 17, 64))
+        Nseq, cap = 6 * rps, 1024
+        qkv, K, V, o = r(Nseq * nmax, 3 * D).half(), r(Nseq, H, cap, 64).half(), r(Nseq, H, cap, 64).half(), r(Nseq * nmax, D).half()
+        ws = r(ops.attn_chunk_ragged_ws(Nseq, H, cap, nmax))
+        ops.attn_chunk_ragged(qkv, K, V, o, ws, Nseq, H, cap, nmax, rps, i32(*lens), i32(*cnt))
+        show(f"attn_chunk_ragged nmax={nmax} rps={rps}", out16=o, K=K, V=V, ws=ws)
+for t0, Tq in ((0, 1), (0, 128), (0, 129), (37, 33), (500, 200)):
+    for ldq in (768, 800):
+        Nseq, cap = 2, 1024
+        qkv = r(Nseq * Tq, ldq).half()[:, :3 * D]
+        K, V, o = r(3, H, cap, 64).half(), r(3, H, cap, 64).half(), r(Nseq * Tq, D).half()
+        ops.attn_prefill(qkv, K, V, o, 1, Nseq, H, t0, Tq)
+        show(f"attn_prefill t0={t0} Tq={Tq} ldq={ldq}", out16=o, K=K, V=V)
+
+for s0 in (0.0, 1.0, 7.0):                         # two steps in a row: the second runs on the first's state and scale
+    N = 3
+    kv16, kv32 = r(N, H, 64, 64), r(N, H, 64, 64)
+    sc16, sc32 = torch.full((H,), s0, device="cuda"), torch.full((H,), s0, device="cuda")
+    for step in (1, 2):
+        o, nsc = z16(N, D), torch.zeros(H, device="cuda")
+        ops.retention_step(r(N, 4 * D, sc=0.5).half(), kv16, sc16, nsc, o, N, H)
+        show(f"retention_step scale_in={s0} step={step}", out16=o, kv=kv16, scale=nsc)
+        sc16 = nsc
+        o, o32, nsc = z16(N, D), torch.zeros(N, D, device="cuda"), torch.zeros(H, device="cuda")
+        ops.retention_step_f32(r(N, 4 * D, sc=0.5), kv32, sc32, nsc, o, N, H, out32=o32)
+        show(f"retention_step_f32 scale_in={s0} step={step}", out16=o, out32=o32, kv=kv32, scale=nsc)
+        sc32 = nsc
+lens, mask = (0, 1, 7, 100), (1, 1, 0, 1)
+kv, o, o32 = r(4, H, 64, 64), r(4, D).half(), r(4, D)
+ops.retention_step_ragged(r(4, 4 * D, sc=0.5), kv, i32(*lens), i32(*mask), 1, 4, H, out16=o, out32=o32)
+show("retention_step_ragged", out16=o, out32=o32, kv=kv)
+for nmax in (1, 5):
+    cnt = (nmax, 0, 1, min(3, nmax))
+    kv, o, o32 = r(4, H, 64, 64), r(4 * nmax, D).half(), r(4 * nmax, D)
+    ops.retention_chunk_ragged(r(4 * nmax, 4 * D, sc=0.5), kv, i32(*lens), i32(*cnt), 1, 4, H, nmax, out16=o, out32=o32)
+    show(f"retention_chunk_ragged nmax={nmax}", out16=o, out32=o32, kv=kv)
+
+ktap = 16                                          # conv_kernel_size of the LS-EEND Conformer
+wdw, bn = r(D, ktap, sc=0.3), (v(D, 1.0), v(D), v(D), v(D, 1.0).abs() + 0.1)
+cache = r(3, D, ktap - 1)
+for step in (1, 2):
+    o = z16(3, D)
+    ops.dwconv_step(r(3, D).half(), cache, wdw, bn, o)
+    show(f"dwconv_step step={step}", out16=o, cache=cache)
+cache, o = r(4, D, ktap - 1), r(4, D).half()
+ops.dwconv_step_ragged(r(4, D).half(), cache, i32(*lens), i32(*mask), wdw, bn, o)
+show("dwconv_step_ragged", out16=o, cache=cache)
+for nmax in (1, 5):
+    cnt = (nmax, 0, 1, min(3, nmax))
+    cache, o = r(4, D, ktap - 1), r(4 * nmax, D).half()
+    ops.dwconv_chunk_ragged(r(4 * nmax, D).half(), cache, i32(*lens), i32(*cnt), wdw, bn, o, nmax)
+    show(f"dwconv_chunk_ragged nmax={nmax}", out16=o, cache=cache)
+
+for C in (1, 3, 12, 16):
+    o = r(2 * C, D)
+    ops.spk_attn_step_f32(r(2 * C, 3 * D), o, 2, C)
+    show(f"spk_attn_step_f32 C={C}", out32=o)
+o = r(2 * 3 * 3, D)
+ops.spk_attn_rows_f32(r(2 * 3 * 3, 3 * D), o, 2, 3, 3)
+show("spk_attn_rows_f32 C=3 Tp=3", out32=o)
+
+ktap, S = 19, 5                                    # the look-ahead window: keep / push / dummy, alone and over a chunk
+mode = i32(0, 1, 2, 1, 3)
+w16, w32, x = r(S, ktap * D).half(), r(S, ktap * D), r(S, D)
+ops.window_push(w16, x, mode)
+ops.window_push_f32(w32, x, mode)
+show("window_push", win16=w16, win32=w32)
+nmax, npush, ndummy, ndec = 5, i32(3, 0, 0, 5, 2), i32(0, 2, 0, 0, 1), i32(2, 2, 0, 5, 3)
+w16, w32, x = r(S, ktap * D).half(), r(S, ktap * D), r(S * nmax, D)
+c16, c32 = r(S * nmax, ktap * D).half(), r(S * nmax, ktap * D)
+ops.window_chunk(w16, x, c16, npush, ndummy, ndec, nmax)
+ops.window_chunk_f32(w32, x, c32, npush, ndummy, ndec, nmax)
+show("window_chunk", win16=w16, cols16=c16, win32=w32, cols32=c32)
