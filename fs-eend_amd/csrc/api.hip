@@ -18,6 +18,172 @@ GemmParams base_params(const void* A, int lda, const void* W, int ldw, const flo
 #endif
     return p;
 }
+
+// ---- routing of the linear entries ------------------------------------------------------------------------------------------------
+// Every linear entry below is a thin wrapper over a function of the same arguments plus `route`: with route == nullptr it validates and
+// launches; with a route pointer (eend_linear_route, called with stand-in addresses) the same code runs up to the launcher, which
+// stores the kernel it would have launched and returns.  The conditions that choose between launchers are the predicates here; the
+// ones inside a launcher (split-K, straight-line K, row groups, the tile checks) are answered by the launcher itself.
+hipStream_t hs(void* stream) { return (hipStream_t)stream; }
+
+// eend_linear_f16 -> proj.hip: no activation, the model width, packed weight rows, whole 256-feature groups, 16-byte output rows
+bool linear_takes_proj(int act, const float* bias, int ldw, int ldo, int N, int K) {
+    return act == 0 && K == 256 && ldw == 256 && bias && (N % 256) == 0 && N <= 1024 && (ldo & 7) == 0;
+}
+// the head-row entries: frames in whole 64-row slabs, 64-wide heads in pairs (one 128-feature tile never straddles Q | K | V)
+bool heads_shape_ok(int nseq, int Tp, int H, int dh) {
+    return nseq > 0 && Tp > 0 && (Tp % 64) == 0 && dh == 64 && H > 0 && ((H * dh) % 128) == 0;
+}
+// ... -> proj.hip: the model width with packed weight rows and 4 heads
+bool heads_take_proj(int ldw, int H, int K) { return K == 256 && ldw == 256 && H == 4; }
+
+int linear_f16(const void* A, int lda, const void* W, int ldw, const float* bias, void* out_f16, int ldo, int M, int N, int K, int act,
+               hipStream_t stream, int* route) {
+    if (!A || !W || !out_f16 || (ldo & 3) || act < 0 || act > 2) return EEND_EINVAL;
+    if (eend_skinny_ok(A, lda, W, ldw, M, K))        // streaming steps: a few rows, weights spread over the chip
+        return eend_launch_skinny_plain(A, lda, W, ldw, bias, out_f16, ldo, M, N, K, act, stream, route);
+    if (linear_takes_proj(act, bias, ldw, ldo, N, K)) {
+        ProjParams q;                                     // X-resident projection kernel (proj.hip)
+        memset(&q, 0, sizeof(q));
+        q.X = A; q.ldx = lda; q.W = W; q.bias = bias; q.M = M; q.N = N; q.Tp = 64; q.H = 4;
+        for (int g = 0; g < N / 256; ++g) { q.kind[g] = PROJ_ROWMAJOR; q.out[g] = (char*)out_f16 + (size_t)g * 256 * 2; q.ld[g] = ldo; }
+        return eend_launch_proj_xres(q, stream, route);
+    }
+    if (ldo & 7) return EEND_EINVAL;                  // the GEMM tile stores 16-byte pieces of the output rows
+    GemmParams p = base_params(A, lda, W, ldw, bias, M, N, K);
+    p.out16 = out_f16; p.ldo = ldo;
+    const int epi = act == 1 ? EPI_PLAIN_RELU_F16 : act == 2 ? EPI_PLAIN_SWISH_F16 : EPI_PLAIN_F16;
+    return eend_launch_gemm(p, epi, stream, route);
+}
+
+int linear_glu_f16(const void* A, int lda, const void* Wi, int ldw, const float* bias_i, void* out_f16, int ldo, int M, int N2, int K,
+                   hipStream_t stream, int* route) {
+    if (!A || !Wi || !bias_i || !out_f16 || (ldo & 1) || (N2 & 1)) return EEND_EINVAL;
+    if (eend_skinny_ok(A, lda, Wi, ldw, M, K))
+        return eend_launch_skinny_glu(A, lda, Wi, ldw, bias_i, out_f16, ldo, M, N2, K, stream, route);
+    GemmParams p = base_params(A, lda, Wi, ldw, bias_i, M, N2, K);
+    p.out16 = out_f16; p.ldo = ldo;
+    return eend_launch_gemm(p, EPI_GLU_F16, stream, route);
+}
+
+int inproj_heads_bf16(const void* A, int lda, const void* W, int ldw, const float* bias, void* Q_bf16, void* K_bf16, void* Vt_bf16,
+                      int nseq, int Tp, int H, int dh, int K, hipStream_t stream, int* route) {
+    if (!A || !W || !bias || !Q_bf16 || !K_bf16 || !Vt_bf16) return EEND_EINVAL;
+    if (!heads_shape_ok(nseq, Tp, H, dh)) return EEND_EINVAL;
+    const int D = H * dh;
+    if (heads_take_proj(ldw, H, K)) {
+        ProjParams q;
+        memset(&q, 0, sizeof(q));
+        q.X = A; q.ldx = lda; q.W = W; q.bias = bias; q.M = nseq * Tp; q.N = 768; q.Tp = Tp; q.H = H;
+        q.kind[0] = PROJ_HEADS; q.out[0] = Q_bf16; q.kind[1] = PROJ_HEADS; q.out[1] = K_bf16;
+        q.kind[2] = PROJ_HEADS_T; q.out[2] = Vt_bf16;
+        q.is_bf16[0] = q.is_bf16[1] = q.is_bf16[2] = 1;
+        return eend_launch_proj_xres(q, stream, route);
+    }
+    GemmParams p = base_params(A, lda, W, ldw, bias, nseq * Tp, 2 * D, K);
+    p.Tp = Tp; p.H = H; p.dh = dh; p.out16 = Q_bf16; p.out16b = K_bf16;
+    int rc = eend_launch_gemm(p, EPI_QK_HEADS, stream, route);
+    if (rc != EEND_OK) return rc;
+    GemmParams v = base_params(A, lda, (const char*)W + (size_t)2 * D * ldw * 2, ldw, bias + 2 * D, nseq * Tp, D, K);
+    v.Tp = Tp; v.H = H; v.dh = dh; v.out16 = Vt_bf16;
+    return eend_launch_gemm(v, EPI_VT_HEADS, stream, route);
+}
+
+int linear_res_ln_f16(const void* A, int lda, const void* W, int ldw, const float* bias, const float* res, float alpha,
+                      const float* gamma, const float* beta, float eps, float* out_f32, void* out_f16, int M, int K, hipStream_t stream,
+                      int* route) {
+    if (!A || !W || (!out_f32 && !out_f16) || ((gamma == nullptr) != (beta == nullptr))) return EEND_EINVAL;
+    if (out_f32 && eend_skinny_ok(A, lda, W, ldw, M, K))         // (the skinny form stages its rows in out_f32)
+        return eend_launch_skinny_res(A, lda, W, ldw, bias, res, alpha, gamma, beta, eps, out_f32, out_f16, M, K, 1, stream, route);
+    GemmParams p = base_params(A, lda, W, ldw, bias, M, 256, K);
+    p.res = res; p.alpha = alpha; p.gamma = gamma; p.beta = beta; p.eps = eps; p.out32 = out_f32; p.out16 = out_f16;
+    return eend_launch_gemm(p, EPI_RES_LN, stream, route);
+}
+
+int linear_res16_ln_f16(const void* A, int lda, const void* W, int ldw, const float* bias, const void* res_f16, float alpha,
+                        const float* gamma, const float* beta, float eps, float* out_f32, void* out_f16, int M, int K,
+                        hipStream_t stream, int* route) {
+    if (!A || !W || !res_f16 || !out_f16 || !gamma || !beta) return EEND_EINVAL;
+    GemmParams p = base_params(A, lda, W, ldw, bias, M, 256, K);
+    p.res16 = res_f16; p.alpha = alpha; p.gamma = gamma; p.beta = beta; p.eps = eps; p.out32 = out_f32; p.out16 = out_f16;
+    return eend_launch_gemm(p, EPI_RES_LN, stream, route);
+}
+
+int linear_res_scale_ln16_f16(const void* A, int lda, const void* W, int ldw, const float* bias, const float* res, float alpha,
+                              const float* gamma, const float* beta, float eps, float* out_f32, void* out_f16, int M, int K,
+                              hipStream_t stream, int* route) {
+    if (!A || !W || !out_f32 || !out_f16 || !gamma || !beta) return EEND_EINVAL;
+    if (eend_skinny_ok(A, lda, W, ldw, M, K))
+        return eend_launch_skinny_res(A, lda, W, ldw, bias, res, alpha, gamma, beta, eps, out_f32, out_f16, M, K, 2, stream, route);
+    GemmParams p = base_params(A, lda, W, ldw, bias, M, 256, K);
+    p.res = res; p.alpha = alpha; p.gamma = gamma; p.beta = beta; p.eps = eps; p.out32 = out_f32; p.out16 = out_f16;
+    return eend_launch_gemm(p, EPI_RES_SCALE_LN16, stream, route);
+}
+
+int retention_proj_f16(const void* A, int lda, const void* Wqkvg, int ldw, const float* bias, void* Q, void* K, void* Kt, void* Vt,
+                       void* G, int nseq, int Tp, int H, int dh, int Kdim, hipStream_t stream, int* route) {
+    if (!A || !Wqkvg || !bias || !Q || !K || !Kt || !Vt || !G) return EEND_EINVAL;
+    if (!heads_shape_ok(nseq, Tp, H, dh)) return EEND_EINVAL;
+    const int D = H * dh, M = nseq * Tp;
+    if (heads_take_proj(ldw, H, Kdim)) {
+        ProjParams q;
+        memset(&q, 0, sizeof(q));
+        q.X = A; q.ldx = lda; q.W = Wqkvg; q.bias = bias; q.M = M; q.N = 1024; q.Tp = Tp; q.H = H;
+        q.kind[0] = PROJ_HEADS; q.out[0] = Q;
+        q.kind[1] = PROJ_HEADS_BOTH; q.out[1] = K; q.out2[1] = Kt;
+        q.kind[2] = PROJ_HEADS_T; q.out[2] = Vt;
+        q.kind[3] = PROJ_ROWMAJOR; q.out[3] = G; q.ld[3] = D;
+        return eend_launch_proj_xres(q, stream, route);
+    }
+    const char* W = (const char*)Wqkvg;
+    const size_t rowb = (size_t)ldw * 2;
+    GemmParams qk = base_params(A, lda, W, ldw, bias, M, 2 * D, Kdim);                      // rows [0, 2D): q, k
+    qk.Tp = Tp; qk.H = H; qk.dh = dh; qk.out16 = Q; qk.out16b = K;
+    int rc = eend_launch_gemm(qk, EPI_QK_HEADS_F16, stream, route);
+    if (rc != EEND_OK) return rc;
+    GemmParams kv = base_params(A, lda, W + (size_t)D * rowb, ldw, bias + D, M, 2 * D, Kdim);  // rows [D, 3D): k, v
+    kv.Tp = Tp; kv.H = H; kv.dh = dh; kv.out16 = Kt; kv.out16b = Vt;
+    rc = eend_launch_gemm(kv, EPI_KTVT_HEADS_F16, stream, route);
+    if (rc != EEND_OK) return rc;
+    GemmParams g = base_params(A, lda, W + (size_t)3 * D * rowb, ldw, bias + 3 * D, M, D, Kdim);  // rows [3D, 4D): g
+    g.out16 = G; g.ldo = D;
+    return eend_launch_gemm(g, EPI_PLAIN_F16, stream, route);
+}
+
+int linear_res_ln_step_f32(const float* A, int lda, const float* W, int ldw, const float* bias, const float* res, float alpha,
+                           const float* gamma, const float* beta, float eps, float* out_f32, void* out_f16, int M, int K,
+                           hipStream_t stream, int* route) {
+    if (!gamma || !beta) return EEND_EINVAL;
+    return eend_launch_skinny_res_f32(A, lda, W, ldw, bias, res, alpha, gamma, beta, eps, out_f32, out_f16, M, K, 1, stream, nullptr, route);
+}
+
+int linear_res_scale_ln_step_f32(const float* A, int lda, const float* W, int ldw, const float* bias, const float* res, float alpha,
+                                 const float* gamma, const float* beta, float eps, float* out_f32, float* ln_out_f32, void* ln_out_f16,
+                                 int M, int K, hipStream_t stream, int* route) {
+    if (!gamma || !beta || !out_f32) return EEND_EINVAL;
+    return eend_launch_skinny_res_f32(A, lda, W, ldw, bias, res, alpha, gamma, beta, eps, out_f32, ln_out_f16, M, K, 2, stream, ln_out_f32,
+                                      route);
+}
+
+int linear_res_scale_f16(const void* A, int lda, const void* W, int ldw, const float* bias, const float* res, float alpha, float* out_f32,
+                         void* out_f16, int M, int K, hipStream_t stream, int* route) {
+    if (!A || !W || (!out_f32 && !out_f16)) return EEND_EINVAL;
+    if (eend_skinny_ok(A, lda, W, ldw, M, K))
+        return eend_launch_skinny_res(A, lda, W, ldw, bias, res, alpha, nullptr, nullptr, 0.f, out_f32, out_f16, M, K, 0, stream, route);
+    GemmParams p = base_params(A, lda, W, ldw, bias, M, 256, K);
+    p.res = res; p.alpha = alpha; p.out32 = out_f32; p.out16 = out_f16;
+    return eend_launch_gemm(p, EPI_RES_SCALE, stream, route);
+}
+
+int convert_fanout_f16(const void* E, const void* W1, const float* pc, float* out_f32, void* out_f16, int B, int Tp, int C,
+                       hipStream_t stream, int* route) {
+    if (!E || !W1 || !pc || !out_f16 || B <= 0 || C <= 0 || Tp <= 0) return EEND_EINVAL;     // out_f32 may be NULL (f16 stream only)
+    if (eend_convert_fanout_rows_ok(B, Tp, C))
+        return eend_launch_convert_fanout_rows(E, W1, pc, out_f32, out_f16, B, Tp, C, stream, route);
+    GemmParams p = base_params(E, 256, W1, 256, nullptr, B * Tp, 256, 256);
+    p.Tp = Tp; p.C = C; p.pc = pc; p.out32 = out_f32; p.out16 = out_f16;
+    return eend_launch_gemm(p, EPI_CONVERT, stream, route);
+}
 }  // namespace
 
 extern "C" {
@@ -44,84 +210,35 @@ int eend_gather_bn_cast_pad_f16(const void* const* x_ptrs, const int* lens, floa
 
 int eend_linear_f16(const void* A, int lda, const void* W, int ldw, const float* bias, void* out_f16, int ldo,
                     int M, int N, int K, int act, void* stream) {
-    if (!A || !W || !out_f16 || (ldo & 3) || act < 0 || act > 2) return EEND_EINVAL;
-    if (eend_skinny_ok(A, lda, W, ldw, M, K))        // streaming steps: a few rows, weights spread over the chip
-        return eend_launch_skinny_plain(A, lda, W, ldw, bias, out_f16, ldo, M, N, K, act, (hipStream_t)stream);
-    if (act == 0 && K == 256 && ldw == 256 && bias && (N % 256) == 0 && N <= 1024 && (ldo & 7) == 0) {
-        ProjParams q;                                     // X-resident projection kernel (proj.hip)
-        memset(&q, 0, sizeof(q));
-        q.X = A; q.ldx = lda; q.W = W; q.bias = bias; q.M = M; q.N = N; q.Tp = 64; q.H = 4;
-        for (int g = 0; g < N / 256; ++g) { q.kind[g] = PROJ_ROWMAJOR; q.out[g] = (char*)out_f16 + (size_t)g * 256 * 2; q.ld[g] = ldo; }
-        return eend_launch_proj_xres(q, (hipStream_t)stream);
-    }
-    GemmParams p = base_params(A, lda, W, ldw, bias, M, N, K);
-    p.out16 = out_f16; p.ldo = ldo;
-    const int epi = act == 1 ? EPI_PLAIN_RELU_F16 : act == 2 ? EPI_PLAIN_SWISH_F16 : EPI_PLAIN_F16;
-    return eend_launch_gemm(p, epi, (hipStream_t)stream);
+    return linear_f16(A, lda, W, ldw, bias, out_f16, ldo, M, N, K, act, hs(stream), nullptr);
 }
 
 int eend_linear_glu_f16(const void* A, int lda, const void* Wi, int ldw, const float* bias_i, void* out_f16,
                         int ldo, int M, int N2, int K, void* stream) {
-    if (!A || !Wi || !bias_i || !out_f16 || (ldo & 1) || (N2 & 1)) return EEND_EINVAL;
-    if (eend_skinny_ok(A, lda, Wi, ldw, M, K))
-        return eend_launch_skinny_glu(A, lda, Wi, ldw, bias_i, out_f16, ldo, M, N2, K, (hipStream_t)stream);
-    GemmParams p = base_params(A, lda, Wi, ldw, bias_i, M, N2, K);
-    p.out16 = out_f16; p.ldo = ldo;
-    return eend_launch_gemm(p, EPI_GLU_F16, (hipStream_t)stream);
+    return linear_glu_f16(A, lda, Wi, ldw, bias_i, out_f16, ldo, M, N2, K, hs(stream), nullptr);
 }
 
 int eend_inproj_heads_bf16(const void* A, int lda, const void* W, int ldw, const float* bias, void* Q_bf16,
                            void* K_bf16, void* Vt_bf16, int nseq, int Tp, int H, int dh, int K, void* stream) {
-    if (!A || !W || !bias || !Q_bf16 || !K_bf16 || !Vt_bf16) return EEND_EINVAL;
-    if (nseq <= 0 || Tp <= 0 || (Tp % 64) != 0 || dh != 64 || H <= 0 || ((H * dh) % 128) != 0) return EEND_EINVAL;
-    const int D = H * dh;
-    if (K == 256 && ldw == 256 && H == 4) {
-        ProjParams q;
-        memset(&q, 0, sizeof(q));
-        q.X = A; q.ldx = lda; q.W = W; q.bias = bias; q.M = nseq * Tp; q.N = 768; q.Tp = Tp; q.H = H;
-        q.kind[0] = PROJ_HEADS; q.out[0] = Q_bf16; q.kind[1] = PROJ_HEADS; q.out[1] = K_bf16;
-        q.kind[2] = PROJ_HEADS_T; q.out[2] = Vt_bf16;
-        q.is_bf16[0] = q.is_bf16[1] = q.is_bf16[2] = 1;
-        return eend_launch_proj_xres(q, (hipStream_t)stream);
-    }
-    GemmParams p = base_params(A, lda, W, ldw, bias, nseq * Tp, 2 * D, K);
-    p.Tp = Tp; p.H = H; p.dh = dh; p.out16 = Q_bf16; p.out16b = K_bf16;
-    int rc = eend_launch_gemm(p, EPI_QK_HEADS, (hipStream_t)stream);
-    if (rc != EEND_OK) return rc;
-    GemmParams v = base_params(A, lda, (const char*)W + (size_t)2 * D * ldw * 2, ldw, bias + 2 * D, nseq * Tp, D, K);
-    v.Tp = Tp; v.H = H; v.dh = dh; v.out16 = Vt_bf16;
-    return eend_launch_gemm(v, EPI_VT_HEADS, (hipStream_t)stream);
+    return inproj_heads_bf16(A, lda, W, ldw, bias, Q_bf16, K_bf16, Vt_bf16, nseq, Tp, H, dh, K, hs(stream), nullptr);
 }
 
 int eend_linear_res_ln_f16(const void* A, int lda, const void* W, int ldw, const float* bias, const float* res,
                            float alpha, const float* gamma, const float* beta, float eps, float* out_f32,
                            void* out_f16, int M, int K, void* stream) {
-    if (!A || !W || (!out_f32 && !out_f16) || ((gamma == nullptr) != (beta == nullptr))) return EEND_EINVAL;
-    if (out_f32 && eend_skinny_ok(A, lda, W, ldw, M, K))
-        return eend_launch_skinny_res(A, lda, W, ldw, bias, res, alpha, gamma, beta, eps, out_f32, out_f16, M, K, 1, (hipStream_t)stream);
-    GemmParams p = base_params(A, lda, W, ldw, bias, M, 256, K);
-    p.res = res; p.alpha = alpha; p.gamma = gamma; p.beta = beta; p.eps = eps; p.out32 = out_f32; p.out16 = out_f16;
-    return eend_launch_gemm(p, EPI_RES_LN, (hipStream_t)stream);
+    return linear_res_ln_f16(A, lda, W, ldw, bias, res, alpha, gamma, beta, eps, out_f32, out_f16, M, K, hs(stream), nullptr);
 }
 
 int eend_linear_res16_ln_f16(const void* A, int lda, const void* W, int ldw, const float* bias, const void* res_f16,
                              float alpha, const float* gamma, const float* beta, float eps, float* out_f32,
                              void* out_f16, int M, int K, void* stream) {
-    if (!A || !W || !res_f16 || !out_f16 || !gamma || !beta) return EEND_EINVAL;
-    GemmParams p = base_params(A, lda, W, ldw, bias, M, 256, K);
-    p.res16 = res_f16; p.alpha = alpha; p.gamma = gamma; p.beta = beta; p.eps = eps; p.out32 = out_f32; p.out16 = out_f16;
-    return eend_launch_gemm(p, EPI_RES_LN, (hipStream_t)stream);
+    return linear_res16_ln_f16(A, lda, W, ldw, bias, res_f16, alpha, gamma, beta, eps, out_f32, out_f16, M, K, hs(stream), nullptr);
 }
 
 int eend_linear_res_scale_ln16_f16(const void* A, int lda, const void* W, int ldw, const float* bias,
                                    const float* res, float alpha, const float* gamma, const float* beta, float eps,
                                    float* out_f32, void* out_f16, int M, int K, void* stream) {
-    if (!A || !W || !out_f32 || !out_f16 || !gamma || !beta) return EEND_EINVAL;
-    if (eend_skinny_ok(A, lda, W, ldw, M, K))
-        return eend_launch_skinny_res(A, lda, W, ldw, bias, res, alpha, gamma, beta, eps, out_f32, out_f16, M, K, 2, (hipStream_t)stream);
-    GemmParams p = base_params(A, lda, W, ldw, bias, M, 256, K);
-    p.res = res; p.alpha = alpha; p.gamma = gamma; p.beta = beta; p.eps = eps; p.out32 = out_f32; p.out16 = out_f16;
-    return eend_launch_gemm(p, EPI_RES_SCALE_LN16, (hipStream_t)stream);
+    return linear_res_scale_ln16_f16(A, lda, W, ldw, bias, res, alpha, gamma, beta, eps, out_f32, out_f16, M, K, hs(stream), nullptr);
 }
 
 int eend_ffn_fused_f16(const void* X, int ldx, const void* W1, const float* b1, const void* W2, const float* b2,
@@ -391,32 +508,7 @@ int eend_pit_assign_i32(const double* cost, const int* nspk, int B, int C, int* 
 
 int eend_retention_proj_f16(const void* A, int lda, const void* Wqkvg, int ldw, const float* bias, void* Q, void* K,
                             void* Kt, void* Vt, void* G, int nseq, int Tp, int H, int dh, int Kdim, void* stream) {
-    if (!A || !Wqkvg || !bias || !Q || !K || !Kt || !Vt || !G) return EEND_EINVAL;
-    if (nseq <= 0 || Tp <= 0 || (Tp % 64) != 0 || dh != 64 || H <= 0 || ((H * dh) % 128) != 0) return EEND_EINVAL;
-    const int D = H * dh, M = nseq * Tp;
-    if (Kdim == 256 && ldw == 256 && H == 4) {
-        ProjParams q;
-        memset(&q, 0, sizeof(q));
-        q.X = A; q.ldx = lda; q.W = Wqkvg; q.bias = bias; q.M = M; q.N = 1024; q.Tp = Tp; q.H = H;
-        q.kind[0] = PROJ_HEADS; q.out[0] = Q;
-        q.kind[1] = PROJ_HEADS_BOTH; q.out[1] = K; q.out2[1] = Kt;
-        q.kind[2] = PROJ_HEADS_T; q.out[2] = Vt;
-        q.kind[3] = PROJ_ROWMAJOR; q.out[3] = G; q.ld[3] = D;
-        return eend_launch_proj_xres(q, (hipStream_t)stream);
-    }
-    const char* W = (const char*)Wqkvg;
-    const size_t rowb = (size_t)ldw * 2;
-    GemmParams qk = base_params(A, lda, W, ldw, bias, M, 2 * D, Kdim);                      // rows [0, 2D): q, k
-    qk.Tp = Tp; qk.H = H; qk.dh = dh; qk.out16 = Q; qk.out16b = K;
-    int rc = eend_launch_gemm(qk, EPI_QK_HEADS_F16, (hipStream_t)stream);
-    if (rc != EEND_OK) return rc;
-    GemmParams kv = base_params(A, lda, W + (size_t)D * rowb, ldw, bias + D, M, 2 * D, Kdim);  // rows [D, 3D): k, v
-    kv.Tp = Tp; kv.H = H; kv.dh = dh; kv.out16 = Kt; kv.out16b = Vt;
-    rc = eend_launch_gemm(kv, EPI_KTVT_HEADS_F16, (hipStream_t)stream);
-    if (rc != EEND_OK) return rc;
-    GemmParams g = base_params(A, lda, W + (size_t)3 * D * rowb, ldw, bias + 3 * D, M, D, Kdim);  // rows [3D, 4D): g
-    g.out16 = G; g.ldo = D;
-    return eend_launch_gemm(g, EPI_PLAIN_F16, (hipStream_t)stream);
+    return retention_proj_f16(A, lda, Wqkvg, ldw, bias, Q, K, Kt, Vt, G, nseq, Tp, H, dh, Kdim, hs(stream), nullptr);
 }
 
 int eend_retention_chunk_f16(const void* Q, const void* K, const void* Kt, const void* Vt, const void* G,
@@ -496,16 +588,13 @@ int eend_linear_step_f32(const float* A, int lda, const float* W, int ldw, const
 int eend_linear_res_ln_step_f32(const float* A, int lda, const float* W, int ldw, const float* bias, const float* res, float alpha,
                                 const float* gamma, const float* beta, float eps, float* out_f32, void* out_f16, int M, int K,
                                 void* stream) {
-    if (!gamma || !beta) return EEND_EINVAL;
-    return eend_launch_skinny_res_f32(A, lda, W, ldw, bias, res, alpha, gamma, beta, eps, out_f32, out_f16, M, K, 1, (hipStream_t)stream);
+    return linear_res_ln_step_f32(A, lda, W, ldw, bias, res, alpha, gamma, beta, eps, out_f32, out_f16, M, K, hs(stream), nullptr);
 }
 
 int eend_linear_res_scale_ln_step_f32(const float* A, int lda, const float* W, int ldw, const float* bias, const float* res, float alpha,
                                       const float* gamma, const float* beta, float eps, float* out_f32, float* ln_out_f32,
                                       void* ln_out_f16, int M, int K, void* stream) {
-    if (!gamma || !beta || !out_f32) return EEND_EINVAL;
-    return eend_launch_skinny_res_f32(A, lda, W, ldw, bias, res, alpha, gamma, beta, eps, out_f32, ln_out_f16, M, K, 2, (hipStream_t)stream,
-                                      ln_out_f32);
+    return linear_res_scale_ln_step_f32(A, lda, W, ldw, bias, res, alpha, gamma, beta, eps, out_f32, ln_out_f32, ln_out_f16, M, K, hs(stream), nullptr);
 }
 
 int eend_layernorm_rows_f32(const float* x, const float* gamma, const float* beta, float eps, float* out_f32, int M, void* stream) {
@@ -537,12 +626,7 @@ int eend_dwconv_bn_swish_f16(const void* x_f16, const float* w, const float* bn_
 int eend_linear_res_scale_f16(const void* A, int lda, const void* W, int ldw, const float* bias,
                               const float* res, float alpha, float* out_f32, void* out_f16, int M, int K,
                               void* stream) {
-    if (!A || !W || (!out_f32 && !out_f16)) return EEND_EINVAL;
-    if (eend_skinny_ok(A, lda, W, ldw, M, K))
-        return eend_launch_skinny_res(A, lda, W, ldw, bias, res, alpha, nullptr, nullptr, 0.f, out_f32, out_f16, M, K, 0, (hipStream_t)stream);
-    GemmParams p = base_params(A, lda, W, ldw, bias, M, 256, K);
-    p.res = res; p.alpha = alpha; p.out32 = out_f32; p.out16 = out_f16;
-    return eend_launch_gemm(p, EPI_RES_SCALE, (hipStream_t)stream);
+    return linear_res_scale_f16(A, lda, W, ldw, bias, res, alpha, out_f32, out_f16, M, K, hs(stream), nullptr);
 }
 
 int eend_conv1d_l2norm_f16(const void* X, const void* Wr, const float* bias, const int* ilens, float* out_f32,
@@ -558,12 +642,46 @@ int eend_conv1d_l2norm_f16(const void* X, const void* Wr, const float* bias, con
 
 int eend_convert_fanout_f16(const void* E, const void* W1, const float* pc, float* out_f32, void* out_f16,
                             int B, int Tp, int C, void* stream) {
-    if (!E || !W1 || !pc || !out_f16 || B <= 0 || C <= 0 || Tp <= 0) return EEND_EINVAL;     // out_f32 may be NULL (f16 stream only)
-    if (C <= 32 && (long)B * Tp * 512 < (1L << 31))
-        return eend_launch_convert_fanout_rows(E, W1, pc, out_f32, out_f16, B, Tp, C, (hipStream_t)stream);
-    GemmParams p = base_params(E, 256, W1, 256, nullptr, B * Tp, 256, 256);
-    p.Tp = Tp; p.C = C; p.pc = pc; p.out32 = out_f32; p.out16 = out_f16;
-    return eend_launch_gemm(p, EPI_CONVERT, (hipStream_t)stream);
+    return convert_fanout_f16(E, W1, pc, out_f32, out_f16, B, Tp, C, hs(stream), nullptr);
+}
+
+int eend_linear_route(int entry, const eend_linear_route_args* a) {
+    if (!a || entry < 0 || entry >= EEND_ENTRY_COUNT) return EEND_EINVAL;
+    // stand-in addresses: NULL-ness and the low four bits are all the routing code reads; nothing dereferences them with `route` set
+    auto at = [](int bits) { return bits < 0 ? (char*)nullptr : (char*)(((size_t)1 << 20) + (size_t)(bits & 15)); };
+    const void *A = at(a->a), *W = at(a->w);
+    const float *bias = (const float*)at(a->bias), *res = (const float*)at(a->res);
+    const float *gamma = (const float*)at(a->gamma), *beta = (const float*)at(a->beta);
+    float* o32 = (float*)at(a->out_f32);
+    void* o16 = at(a->out_f16);
+    int route = EEND_ROUTE_REFUSED, rc = EEND_EINVAL;
+    switch (entry) {
+        case EEND_ENTRY_LINEAR_F16:
+            rc = linear_f16(A, a->lda, W, a->ldw, bias, o16, a->ldo, a->M, a->N, a->K, a->act, nullptr, &route); break;
+        case EEND_ENTRY_LINEAR_GLU_F16:
+            rc = linear_glu_f16(A, a->lda, W, a->ldw, bias, o16, a->ldo, a->M, a->N, a->K, nullptr, &route); break;
+        case EEND_ENTRY_INPROJ_HEADS_BF16:
+            rc = inproj_heads_bf16(A, a->lda, W, a->ldw, bias, o16, o16, o16, a->nseq, a->Tp, a->H, a->dh, a->K, nullptr, &route); break;
+        case EEND_ENTRY_RETENTION_PROJ_F16:
+            rc = retention_proj_f16(A, a->lda, W, a->ldw, bias, o16, o16, o16, o16, o16, a->nseq, a->Tp, a->H, a->dh, a->K, nullptr, &route); break;
+        case EEND_ENTRY_LINEAR_RES_LN_F16:
+            rc = linear_res_ln_f16(A, a->lda, W, a->ldw, bias, res, 1.0f, gamma, beta, 1e-5f, o32, o16, a->M, a->K, nullptr, &route); break;
+        case EEND_ENTRY_LINEAR_RES16_LN_F16:
+            rc = linear_res16_ln_f16(A, a->lda, W, a->ldw, bias, res, 1.0f, gamma, beta, 1e-5f, o32, o16, a->M, a->K, nullptr, &route); break;
+        case EEND_ENTRY_LINEAR_RES_SCALE_F16:
+            rc = linear_res_scale_f16(A, a->lda, W, a->ldw, bias, res, 1.0f, o32, o16, a->M, a->K, nullptr, &route); break;
+        case EEND_ENTRY_LINEAR_RES_SCALE_LN16_F16:
+            rc = linear_res_scale_ln16_f16(A, a->lda, W, a->ldw, bias, res, 1.0f, gamma, beta, 1e-5f, o32, o16, a->M, a->K, nullptr, &route); break;
+        case EEND_ENTRY_CONVERT_FANOUT_F16:
+            rc = convert_fanout_f16(A, W, res, o32, o16, a->nseq, a->Tp, a->C, nullptr, &route); break;
+        case EEND_ENTRY_LINEAR_STEP_F32:
+            rc = eend_launch_skinny_plain_f32((const float*)A, a->lda, (const float*)W, a->ldw, bias, o32, a->ldo, a->M, a->N, a->K, a->act, nullptr, &route); break;
+        case EEND_ENTRY_LINEAR_RES_LN_STEP_F32:
+            rc = linear_res_ln_step_f32((const float*)A, a->lda, (const float*)W, a->ldw, bias, res, 1.0f, gamma, beta, 1e-5f, o32, o16, a->M, a->K, nullptr, &route); break;
+        case EEND_ENTRY_LINEAR_RES_SCALE_LN_STEP_F32:
+            rc = linear_res_scale_ln_step_f32((const float*)A, a->lda, (const float*)W, a->ldw, bias, res, 1.0f, gamma, beta, 1e-5f, o32, nullptr, o16, a->M, a->K, nullptr, &route); break;
+    }
+    return rc == EEND_OK ? route : EEND_ROUTE_REFUSED;
 }
 
 int eend_attn_causal_bf16(const void* Q, const void* K, const void* Vt, void* O_f16, int nseq, int H, int Tp,

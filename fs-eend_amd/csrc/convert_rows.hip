@@ -85,9 +85,14 @@ void convert_fanout_rows_kernel(const _Float16* __restrict__ E, const _Float16* 
 
 }  // namespace
 
+bool eend_convert_fanout_rows_ok(int B, int Tp, int C) {
+    return B > 0 && Tp > 0 && C > 0 && C <= 32 && (long)B * Tp * 512 < (1L << 31);
+}
+
 int eend_launch_convert_fanout_rows(const void* E, const void* W1, const float* pc, float* out32, void* out16, int B, int Tp, int C,
-                                    hipStream_t stream) {
-    if (!E || !W1 || !pc || !out16 || B <= 0 || Tp <= 0 || C <= 0 || C > 32 || (long)B * Tp * 512 >= (1L << 31)) return EEND_EINVAL;
+                                    hipStream_t stream, int* route) {
+    if (!E || !W1 || !pc || !out16 || !eend_convert_fanout_rows_ok(B, Tp, C)) return EEND_EINVAL;
+    if (route) { *route = EEND_ROUTE_CONVERT_ROWS; return EEND_OK; }
     const int ncu = eend_cu_count();
     const int ntiles = (B * Tp + 31) / 32;
     hipLaunchKernelGGL(convert_fanout_rows_kernel, dim3(ntiles < 2 * ncu ? ntiles : 2 * ncu), dim3(256), C * 1024, stream, (const _Float16*)E,

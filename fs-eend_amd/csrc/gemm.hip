@@ -711,12 +711,16 @@ int launch_pf(const GemmParams& p, hipStream_t stream) {
 // K == 256 (4 k-tiles) takes the straight-line full-K variant when the tile's staging registers
 // fit (128x128: 8 uint4 per k-tile -> 128 VGPRs); everything else the looped variant.
 template <class ET, int BM, int BN, int WGM, int WGN, bool SWAP, int ALOAD, int EPI>
-int launch(const GemmParams& p, hipStream_t stream) {
+int launch(const GemmParams& p, hipStream_t stream, int* route) {
     if (p.M <= 0 || p.N <= 0 || p.K <= 0) return EEND_EINVAL;
     if (p.N % BN != 0 || p.K % 64 != 0 || (p.lda & 7) || (p.ldw & 7)) return EEND_EINVAL;
     if constexpr (BM + BN <= 256 && ALOAD == ALOAD_PLAIN) {
-        if (p.K == 256) return launch_pf<ET, BM, BN, WGM, WGN, SWAP, ALOAD, EPI, 2>(p, stream);
+        if (p.K == 256) {
+            if (route) { *route = EEND_ROUTE_GEMM128_STRAIGHT; return EEND_OK; }
+            return launch_pf<ET, BM, BN, WGM, WGN, SWAP, ALOAD, EPI, 2>(p, stream);
+        }
     }
+    if (route) { *route = BN == 256 ? EEND_ROUTE_GEMM64X256 : EEND_ROUTE_GEMM128_LOOPED; return EEND_OK; }
     return launch_pf<ET, BM, BN, WGM, WGN, SWAP, ALOAD, EPI, 0>(p, stream);
 }
 
@@ -726,60 +730,60 @@ int launch(const GemmParams& p, hipStream_t stream) {
 
 }  // namespace
 
-int eend_launch_gemm(const GemmParams& p, int epi, hipStream_t stream) {
+int eend_launch_gemm(const GemmParams& p, int epi, hipStream_t stream, int* route) {
     using H = _Float16;
     using B = __bf16;
     if (p.bf16) {                      // gradient GEMMs of the training step: bf16 operands
         switch (epi) {
-            case EPI_PLAIN_BF16:  return launch<B, 128, 128, 2, 2, true, ALOAD_PLAIN, EPI_PLAIN_BF16>(p, stream);
+            case EPI_PLAIN_BF16:  return launch<B, 128, 128, 2, 2, true, ALOAD_PLAIN, EPI_PLAIN_BF16>(p, stream, route);
             case EPI_MASK_BF16:
                 if (!p.mask || (p.ldmask & 7)) return EEND_EINVAL;
-                return launch<B, 128, 128, 2, 2, true, ALOAD_PLAIN, EPI_MASK_BF16>(p, stream);
+                return launch<B, 128, 128, 2, 2, true, ALOAD_PLAIN, EPI_MASK_BF16>(p, stream, route);
             case EPI_RES_SCALE:
                 if (p.N != 256) return EEND_EINVAL;
-                return launch<B, 64, 256, 1, 4, true, ALOAD_PLAIN, EPI_RES_SCALE>(p, stream);
+                return launch<B, 64, 256, 1, 4, true, ALOAD_PLAIN, EPI_RES_SCALE>(p, stream, route);
             case EPI_RES_LNBWD:
                 if (p.N != 256 || p.ldo != 256 || !p.res || !p.out32 || !p.out16 || !p.xhat16 || !p.rstat || !p.gamma || !p.colpart) return EEND_EINVAL;
-                return launch<B, 64, 256, 1, 4, true, ALOAD_PLAIN, EPI_RES_LNBWD>(p, stream);
+                return launch<B, 64, 256, 1, 4, true, ALOAD_PLAIN, EPI_RES_LNBWD>(p, stream, route);
             case EPI_F32_ROWMASK:
                 if (p.N != 256 || !p.ilens || !p.mask_lens || !p.out32) return EEND_EINVAL;
-                return launch<B, 64, 256, 1, 4, true, ALOAD_CONV, EPI_F32_ROWMASK>(p, stream);
+                return launch<B, 64, 256, 1, 4, true, ALOAD_CONV, EPI_F32_ROWMASK>(p, stream, route);
             default: return EEND_EINVAL;
         }
     }
     switch (epi) {
-        case EPI_PLAIN_F16:      return launch<H, 128, 128, 2, 2, true, ALOAD_PLAIN, EPI_PLAIN_F16>(p, stream);
-        case EPI_PLAIN_RELU_F16: return launch<H, 128, 128, 2, 2, true, ALOAD_PLAIN, EPI_PLAIN_RELU_F16>(p, stream);
-        case EPI_PLAIN_SWISH_F16:return launch<H, 128, 128, 2, 2, true, ALOAD_PLAIN, EPI_PLAIN_SWISH_F16>(p, stream);
-        case EPI_GLU_F16:        return launch<H, 128, 128, 2, 2, true, ALOAD_PLAIN, EPI_GLU_F16>(p, stream);
-        case EPI_QK_HEADS_F16:   return launch<H, 128, 128, 2, 2, true, ALOAD_PLAIN, EPI_QK_HEADS_F16>(p, stream);
-        case EPI_KTVT_HEADS_F16: return launch<H, 128, 128, 2, 2, false, ALOAD_PLAIN, EPI_KTVT_HEADS_F16>(p, stream);
-        case EPI_QK_HEADS:       return launch<H, 128, 128, 2, 2, true, ALOAD_PLAIN, EPI_QK_HEADS>(p, stream);
-        case EPI_VT_HEADS:       return launch<H, 128, 128, 2, 2, false, ALOAD_PLAIN, EPI_VT_HEADS>(p, stream);
+        case EPI_PLAIN_F16:      return launch<H, 128, 128, 2, 2, true, ALOAD_PLAIN, EPI_PLAIN_F16>(p, stream, route);
+        case EPI_PLAIN_RELU_F16: return launch<H, 128, 128, 2, 2, true, ALOAD_PLAIN, EPI_PLAIN_RELU_F16>(p, stream, route);
+        case EPI_PLAIN_SWISH_F16:return launch<H, 128, 128, 2, 2, true, ALOAD_PLAIN, EPI_PLAIN_SWISH_F16>(p, stream, route);
+        case EPI_GLU_F16:        return launch<H, 128, 128, 2, 2, true, ALOAD_PLAIN, EPI_GLU_F16>(p, stream, route);
+        case EPI_QK_HEADS_F16:   return launch<H, 128, 128, 2, 2, true, ALOAD_PLAIN, EPI_QK_HEADS_F16>(p, stream, route);
+        case EPI_KTVT_HEADS_F16: return launch<H, 128, 128, 2, 2, false, ALOAD_PLAIN, EPI_KTVT_HEADS_F16>(p, stream, route);
+        case EPI_QK_HEADS:       return launch<H, 128, 128, 2, 2, true, ALOAD_PLAIN, EPI_QK_HEADS>(p, stream, route);
+        case EPI_VT_HEADS:       return launch<H, 128, 128, 2, 2, false, ALOAD_PLAIN, EPI_VT_HEADS>(p, stream, route);
         case EPI_RES_LN:
             if (p.N != 256) return EEND_EINVAL;
-            return launch<H, 64, 256, 1, 4, true, ALOAD_PLAIN, EPI_RES_LN>(p, stream);
+            return launch<H, 64, 256, 1, 4, true, ALOAD_PLAIN, EPI_RES_LN>(p, stream, route);
         case EPI_RES_LN_TRAIN:
             if (p.N != 256) return EEND_EINVAL;
-            return launch<H, 64, 256, 1, 4, true, ALOAD_PLAIN, EPI_RES_LN_TRAIN>(p, stream);
+            return launch<H, 64, 256, 1, 4, true, ALOAD_PLAIN, EPI_RES_LN_TRAIN>(p, stream, route);
         case EPI_RES_SCALE_LN16_TRAIN:
             if (p.N != 256 || p.ldo != 256) return EEND_EINVAL;
-            return launch<H, 64, 256, 1, 4, true, ALOAD_PLAIN, EPI_RES_SCALE_LN16_TRAIN>(p, stream);
+            return launch<H, 64, 256, 1, 4, true, ALOAD_PLAIN, EPI_RES_SCALE_LN16_TRAIN>(p, stream, route);
         case EPI_RES_SCALE_LN16:
             if (p.N != 256) return EEND_EINVAL;
-            return launch<H, 64, 256, 1, 4, true, ALOAD_PLAIN, EPI_RES_SCALE_LN16>(p, stream);
+            return launch<H, 64, 256, 1, 4, true, ALOAD_PLAIN, EPI_RES_SCALE_LN16>(p, stream, route);
         case EPI_RES_SCALE:
             if (p.N != 256) return EEND_EINVAL;
-            return launch<H, 64, 256, 1, 4, true, ALOAD_PLAIN, EPI_RES_SCALE>(p, stream);
+            return launch<H, 64, 256, 1, 4, true, ALOAD_PLAIN, EPI_RES_SCALE>(p, stream, route);
         case EPI_L2NORM:
             if (p.N != 256) return EEND_EINVAL;
-            return launch<H, 64, 256, 1, 4, true, ALOAD_CONV, EPI_L2NORM>(p, stream);
+            return launch<H, 64, 256, 1, 4, true, ALOAD_CONV, EPI_L2NORM>(p, stream, route);
         case EPI_L2NORM_TRAIN:
             if (p.N != 256) return EEND_EINVAL;
-            return launch<H, 64, 256, 1, 4, true, ALOAD_CONV, EPI_L2NORM_TRAIN>(p, stream);
+            return launch<H, 64, 256, 1, 4, true, ALOAD_CONV, EPI_L2NORM_TRAIN>(p, stream, route);
         case EPI_CONVERT:
             if (p.N != 256) return EEND_EINVAL;
-            return launch<H, 64, 256, 1, 4, true, ALOAD_PLAIN, EPI_CONVERT>(p, stream);
+            return launch<H, 64, 256, 1, 4, true, ALOAD_PLAIN, EPI_CONVERT>(p, stream, route);
         default: return EEND_EINVAL;
     }
 }

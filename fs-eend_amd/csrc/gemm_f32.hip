@@ -119,13 +119,15 @@ bool eend_linear_f32_mfma_ok(const float* A, int lda, const float* W, int ldw, i
 
 // res_mode 0: out32 = act(y + bias); 1: out32 = (y + bias) * alpha + res
 int eend_launch_linear_f32_mfma(const float* A, int lda, const float* W, int ldw, const float* bias, const float* res, int ldres, float alpha,
-                                int res_mode, int act, float* out32, int ldo, int M, int N, int K, hipStream_t stream) {
+                                int res_mode, int act, float* out32, int ldo, int M, int N, int K, hipStream_t stream, int* route) {
     if (!A || !W || !out32 || !eend_linear_f32_mfma_ok(A, lda, W, ldw, M, N, K, ldo) || (bias && ((size_t)bias & 15)) ||
         (res && (((size_t)res & 15) || (ldres & 3))) || ((size_t)out32 & 15))
         return EEND_EINVAL;
+    const bool splitk = K > 768;
+    if (route) { *route = splitk ? EEND_ROUTE_F32_MFMA_SPLITK : EEND_ROUTE_F32_MFMA; return EEND_OK; }
     LinF32Params p{A, lda, W, ldw, bias, M, N, K, act, alpha, res, ldres, res_mode, out32, ldo};
     const int mb = (M + 63) / 64;
-    if (K > 768) hipLaunchKernelGGL(linear_f32_mfma_kernel<true>, dim3(N / 16, mb), dim3(256), 0, stream, p);
+    if (splitk) hipLaunchKernelGGL(linear_f32_mfma_kernel<true>, dim3(N / 16, mb), dim3(256), 0, stream, p);
     else hipLaunchKernelGGL(linear_f32_mfma_kernel<false>, dim3((N / 16 + 3) / 4, mb), dim3(256), 0, stream, p);
     return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
 }

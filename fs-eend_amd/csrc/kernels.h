@@ -135,7 +135,9 @@ struct RetParams {
                              // 1/(sqrt(i+1) * max(inner_scale, cross_scale)) (retention.py:163,185 -- no gradient flows into it)
 };
 
-int eend_launch_gemm(const GemmParams& p, int epi, hipStream_t stream);
+// `route` (here and in the launchers below that take one): when non-null the launcher runs its argument checks, stores the
+// EEND_ROUTE_* value of the kernel it would launch and returns without launching or touching memory (eend_linear_route of api.hip).
+int eend_launch_gemm(const GemmParams& p, int epi, hipStream_t stream, int* route = nullptr);
 
 // attn_stream.hip: in-projection + causal attention in one launch, token-owning waves and fragment-packed weights (Tp = 512, H = 4)
 #define EEND_ATTN_LONG_MAX_PAIRS 64
@@ -166,12 +168,12 @@ int eend_launch_inproj_attn_stream(const InprojAttnParams& p, hipStream_t stream
 #define EEND_SKINNY_MAX_M 16
 bool eend_skinny_ok(const void* A, int lda, const void* W, int ldw, int M, int K);
 int eend_launch_skinny_plain(const void* A, int lda, const void* W, int ldw, const float* bias, void* out16, int ldo,
-                             int M, int N, int K, int act, hipStream_t stream);
+                             int M, int N, int K, int act, hipStream_t stream, int* route = nullptr);
 int eend_launch_skinny_glu(const void* A, int lda, const void* W, int ldw, const float* bias, void* out16, int ldo,
-                           int M, int N2, int K, hipStream_t stream);
+                           int M, int N2, int K, hipStream_t stream, int* route = nullptr);
 int eend_launch_skinny_res(const void* A, int lda, const void* W, int ldw, const float* bias, const float* res, float alpha,
                            const float* gamma, const float* beta, float eps, float* out32, void* out16, int M, int K,
-                           int mode, hipStream_t stream);
+                           int mode, hipStream_t stream, int* route = nullptr);
 int eend_launch_ret_state_scan(const RetParams& p, hipStream_t stream);
 int eend_launch_ret_chunk(const RetParams& p, hipStream_t stream);
 int eend_launch_layernorm_f16(const float* x, const float* gamma, const float* beta, float eps, void* out16,
@@ -193,14 +195,14 @@ int eend_launch_ret_step_f32in(const float* qkvg, float* kv, const float* scale_
 int eend_launch_spk_attn_step_f32(const float* qkv, float* out, int B, int C, float scale, hipStream_t stream);
 int eend_launch_l2norm_rows_f32(const float* x, float* y, int rows, hipStream_t stream);
 int eend_launch_skinny_plain_f32(const float* A, int lda, const float* W, int ldw, const float* bias, float* out32, int ldo, int M, int N,
-                                 int K, int act, hipStream_t stream);
+                                 int K, int act, hipStream_t stream, int* route = nullptr);
 int eend_launch_skinny_res_f32(const float* A, int lda, const float* W, int ldw, const float* bias, const float* res, float alpha,
                                const float* gamma, const float* beta, float eps, float* out32, void* out16, int M, int K, int mode,
-                               hipStream_t stream, float* ln_out32 = nullptr);
+                               hipStream_t stream, float* ln_out32 = nullptr, int* route = nullptr);
 // gemm_f32.hip: f32 linear layers for M > 16 rows on the exact-f32 MFMA (multi-stream frame steps)
 bool eend_linear_f32_mfma_ok(const float* A, int lda, const float* W, int ldw, int M, int N, int K, int ldo);
 int eend_launch_linear_f32_mfma(const float* A, int lda, const float* W, int ldw, const float* bias, const float* res, int ldres, float alpha,
-                                int res_mode, int act, float* out32, int ldo, int M, int N, int K, hipStream_t stream);
+                                int res_mode, int act, float* out32, int ldo, int M, int N, int K, hipStream_t stream, int* route = nullptr);
 int eend_launch_layernorm_rows_f32(const float* x, const float* gamma, const float* beta, float eps, float* out32, int M, hipStream_t stream);
 int eend_launch_convert_step_f32(const float* emb, const float* W, int ldw, const float* pc, float* out32, void* out16, int B, int C,
                                  hipStream_t stream);
@@ -405,8 +407,9 @@ int eend_launch_dec_stream_pack(const void* Wo1, const void* Win, const void* Wo
                                 hipStream_t stream);
 int eend_launch_dec_stream(const DecStreamParams& p, hipStream_t stream);
 // convert_rows.hip: the decoder input fan-out as a store-shaped kernel (weights stationary)
+bool eend_convert_fanout_rows_ok(int B, int Tp, int C);      // the shapes the rows kernel serves (slots in LDS, 32-bit row offsets)
 int eend_launch_convert_fanout_rows(const void* E, const void* W1, const float* pc, float* out32, void* out16, int B, int Tp, int C,
-                                    hipStream_t stream);
+                                    hipStream_t stream, int* route = nullptr);
 // conv_stream.hip: look-ahead Conv1d(256 -> 256) + bias + L2 norm on a packed weight stream
 struct ConvStreamParams {
     const void* X;        // f16 [nseq][Tp][256]
@@ -456,7 +459,7 @@ struct ProjParams {       // proj.hip: up to four 256-feature output groups
     void* out2[4];        // HEADS_BOTH: the transposed copy
     int ld[4];
 };
-int eend_launch_proj_xres(const ProjParams& p, hipStream_t stream);
+int eend_launch_proj_xres(const ProjParams& p, hipStream_t stream, int* route = nullptr);
 // proj_stream.hip (round 6): the same projections on a packed weight stream, wave-owned rows, up to three destinations per 256-feature group
 struct ProjStreamParams {
     const void* X; int ldx;   // f16 [M][ldx], 256 features

@@ -235,7 +235,7 @@ void proj_xres_kernel(const ProjParams p) {
 
 }  // namespace
 
-int eend_launch_proj_xres(const ProjParams& p, hipStream_t stream) {
+int eend_launch_proj_xres(const ProjParams& p, hipStream_t stream, int* route) {
     if (p.M <= 0 || p.N <= 0 || (p.N % 256) != 0 || p.N > 1024 || (p.ldx & 7) || !p.X || !p.W || !p.bias || p.H != 4)
         return EEND_EINVAL;
     for (int g = 0; g < p.N / 256; ++g) {
@@ -244,6 +244,7 @@ int eend_launch_proj_xres(const ProjParams& p, hipStream_t stream) {
         if (p.kind[g] != PROJ_ROWMAJOR && (p.Tp <= 0 || (p.Tp % 64) != 0 || (p.M % p.Tp) != 0)) return EEND_EINVAL;
         if (p.kind[g] == PROJ_ROWMAJOR && (p.ld[g] & 7)) return EEND_EINVAL;
     }
+    if (route) { *route = EEND_ROUTE_PROJ; return EEND_OK; }
     static EendOncePerDevice attr_once;
     if (!eend_set_dynamic_lds(attr_once, (const void*)proj_xres_kernel, SMEM_BYTES)) return EEND_ELAUNCH;
     hipLaunchKernelGGL(proj_xres_kernel, dim3((p.M + BM - 1) / BM), dim3(NT), SMEM_BYTES, stream, p);

@@ -161,7 +161,7 @@ void skinny_ln_kernel(float* __restrict__ x32, _Float16* __restrict__ out16, con
 
 template <int EPI, bool SPLITK, bool F32>
 int launch_bucket(const SkinnyParams& p, hipStream_t stream) {
-    const dim3 grid(SPLITK ? p.N : (p.N + 3) / 4, p.M > 16 ? (p.M + 15) / 16 : 1), block(256);
+    const dim3 grid(SPLITK ? p.N : (p.N + 3) / 4, (p.M + EEND_SKINNY_MAX_M - 1) / EEND_SKINNY_MAX_M), block(256);
     if (p.M <= 1) hipLaunchKernelGGL((skinny_linear_kernel<1, EPI, SPLITK, F32>), grid, block, 0, stream, p);
     else if (p.M <= 2) hipLaunchKernelGGL((skinny_linear_kernel<2, EPI, SPLITK, F32>), grid, block, 0, stream, p);
     else if (p.M <= 4) hipLaunchKernelGGL((skinny_linear_kernel<4, EPI, SPLITK, F32>), grid, block, 0, stream, p);
@@ -172,8 +172,14 @@ int launch_bucket(const SkinnyParams& p, hipStream_t stream) {
 }
 
 template <int EPI, bool F32 = false>
-int launch_skinny(const SkinnyParams& p, hipStream_t stream) {
-    return p.K > 512 ? launch_bucket<EPI, true, F32>(p, stream) : launch_bucket<EPI, false, F32>(p, stream);
+int launch_skinny(const SkinnyParams& p, hipStream_t stream, int* route) {
+    const bool splitk = p.K > 512, groups = p.M > EEND_SKINNY_MAX_M;       // (row groups: the f32 entries alone admit M > 16)
+    if (route) {
+        *route = groups ? (splitk ? EEND_ROUTE_SKINNY_ROWGROUPS_SPLITK : EEND_ROUTE_SKINNY_ROWGROUPS)
+                        : (splitk ? EEND_ROUTE_SKINNY_SPLITK : EEND_ROUTE_SKINNY);
+        return EEND_OK;
+    }
+    return splitk ? launch_bucket<EPI, true, F32>(p, stream) : launch_bucket<EPI, false, F32>(p, stream);
 }
 
 }  // namespace
@@ -184,40 +190,40 @@ bool eend_skinny_ok(const void* A, int lda, const void* W, int ldw, int M, int K
 }
 
 int eend_launch_skinny_plain(const void* A, int lda, const void* W, int ldw, const float* bias, void* out16, int ldo,
-                             int M, int N, int K, int act, hipStream_t stream) {
+                             int M, int N, int K, int act, hipStream_t stream, int* route) {
     SkinnyParams p{A, lda, W, ldw, bias, M, N, K, act, 1.0f, nullptr, 0, nullptr, (_Float16*)out16, ldo};
-    return launch_skinny<SK_PLAIN>(p, stream);
+    return launch_skinny<SK_PLAIN>(p, stream, route);
 }
 
 int eend_launch_skinny_glu(const void* A, int lda, const void* W, int ldw, const float* bias, void* out16, int ldo,
-                           int M, int N2, int K, hipStream_t stream) {
+                           int M, int N2, int K, hipStream_t stream, int* route) {
     SkinnyParams p{A, lda, W, ldw, bias, M, N2 / 2, K, 0, 1.0f, nullptr, 0, nullptr, (_Float16*)out16, ldo};
-    return launch_skinny<SK_GLU>(p, stream);
+    return launch_skinny<SK_GLU>(p, stream, route);
 }
 
 // mode 0: out32 / out16 = v (EPI_RES_SCALE); 1: out32 = LN(v), out16 = f16 LN(v) (EPI_RES_LN);
 // 2: out32 = v, out16 = f16 LN(v) (EPI_RES_SCALE_LN16).  N = 256.  Modes 1 / 2 need out32 as the staging row buffer.
 int eend_launch_skinny_res(const void* A, int lda, const void* W, int ldw, const float* bias, const float* res, float alpha,
                            const float* gamma, const float* beta, float eps, float* out32, void* out16, int M, int K,
-                           int mode, hipStream_t stream) {
+                           int mode, hipStream_t stream, int* route) {
     if (mode != 0 && !out32) return EEND_EINVAL;
     SkinnyParams p{A, lda, W, ldw, bias, M, 256, K, 0, alpha, res, 256, out32, mode == 0 ? (_Float16*)out16 : nullptr, 256};
-    int rc = launch_skinny<SK_RES>(p, stream);
-    if (rc != EEND_OK || mode == 0) return rc;
+    int rc = launch_skinny<SK_RES>(p, stream, route);
+    if (rc != EEND_OK || mode == 0 || route) return rc;
     hipLaunchKernelGGL(skinny_ln_kernel, dim3(M), dim3(64), 0, stream, out32, (_Float16*)out16, gamma, beta, eps, mode == 1 ? 1 : 0);
     return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
 }
 
 // The same kernels on f32 activations AND f32 weights (torch nn.Linear layout), f32 out: the LS decoder's frame step.
 int eend_launch_skinny_plain_f32(const float* A, int lda, const float* W, int ldw, const float* bias, float* out32, int ldo, int M, int N,
-                                 int K, int act, hipStream_t stream) {
+                                 int K, int act, hipStream_t stream, int* route) {
     if (!A || !W || !out32 || M < 1 || (K & 7) || (lda & 3) || (ldw & 3) || (((size_t)A | (size_t)W) & 15))
         return EEND_EINVAL;
     // more than 16 rows (multi-stream sessions): the f32 MFMA kernel of gemm_f32.hip instead of serial 16-row groups
     if (eend_linear_f32_mfma_ok(A, lda, W, ldw, M, N, K, ldo) && !((size_t)out32 & 15) && !(bias && ((size_t)bias & 15)))
-        return eend_launch_linear_f32_mfma(A, lda, W, ldw, bias, nullptr, 0, 1.0f, 0, act, out32, ldo, M, N, K, stream);
+        return eend_launch_linear_f32_mfma(A, lda, W, ldw, bias, nullptr, 0, 1.0f, 0, act, out32, ldo, M, N, K, stream, route);
     SkinnyParams p{A, lda, W, ldw, bias, M, N, K, act, 1.0f, nullptr, 0, out32, nullptr, ldo};
-    return launch_skinny<SK_PLAIN, true>(p, stream);
+    return launch_skinny<SK_PLAIN, true>(p, stream, route);
 }
 
 int eend_launch_layernorm_rows_f32(const float* x, const float* gamma, const float* beta, float eps, float* out32, int M, hipStream_t stream) {
@@ -228,18 +234,18 @@ int eend_launch_layernorm_rows_f32(const float* x, const float* gamma, const flo
 
 int eend_launch_skinny_res_f32(const float* A, int lda, const float* W, int ldw, const float* bias, const float* res, float alpha,
                                const float* gamma, const float* beta, float eps, float* out32, void* out16, int M, int K, int mode,
-                               hipStream_t stream, float* ln_out32) {
+                               hipStream_t stream, float* ln_out32, int* route) {
     if (!A || !W || !out32 || M < 1 || (K & 7) || (lda & 3) || (ldw & 3) || (((size_t)A | (size_t)W) & 15))
         return EEND_EINVAL;
     int rc;
     if (mode != 0 && eend_linear_f32_mfma_ok(A, lda, W, ldw, M, 256, K, 256) && !((size_t)out32 & 15) && !(bias && ((size_t)bias & 15)) &&
         !(res && ((size_t)res & 15))) {
-        rc = eend_launch_linear_f32_mfma(A, lda, W, ldw, bias, res, 256, alpha, 1, 0, out32, 256, M, 256, K, stream);
+        rc = eend_launch_linear_f32_mfma(A, lda, W, ldw, bias, res, 256, alpha, 1, 0, out32, 256, M, 256, K, stream, route);
     } else {
         SkinnyParams p{A, lda, W, ldw, bias, M, 256, K, 0, alpha, res, 256, out32, mode == 0 ? (_Float16*)out16 : nullptr, 256};
-        rc = launch_skinny<SK_RES, true>(p, stream);
+        rc = launch_skinny<SK_RES, true>(p, stream, route);
     }
-    if (rc != EEND_OK || mode == 0) return rc;
+    if (rc != EEND_OK || mode == 0 || route) return rc;
     hipLaunchKernelGGL(skinny_ln_kernel, dim3(M), dim3(64), 0, stream, out32, (_Float16*)out16, gamma, beta, eps, mode == 1 ? 1 : 0, ln_out32);
     return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
 }

@@ -181,6 +181,7 @@ PROTOTYPES = {
     "eend_dwconv_glu_bwd_bf16": [_vp, _vp, _vp, _vp, _vp, _l, _vp, _i, _i, _i, _i, _vp],
     "eend_retention_chunk_train_f16": [_vp] * 12 + [_i] * 6 + [_f, _i, _vp],
     "eend_retention_bwd_bf16": [_vp] * 8 + [_i, _vp, _vp] + [_vp] * 6 + [_i] * 6 + [_f, _vp],
+    "eend_linear_route": [_i, _vp],
 }
 
 # entries that return a long rather than an int status
@@ -212,6 +213,35 @@ class ProjGroup(ctypes.Structure):
 class Dropout(ctypes.Structure):
     """eend_dropout of include/eend_hip.h."""
     _fields_ = [("seed", ctypes.c_uint), ("thresh24", ctypes.c_uint), ("scale", ctypes.c_float)]
+
+
+class LinearRouteArgs(ctypes.Structure):
+    """eend_linear_route_args of include/eend_hip.h (address fields: the pointer's low four bits, ROUTE_NULL for NULL)."""
+    _fields_ = [(n, ctypes.c_int) for n in ("M", "N", "K", "lda", "ldw", "ldo", "act", "nseq", "Tp", "H", "dh", "C",
+                                            "a", "w", "bias", "res", "gamma", "beta", "out_f32", "out_f16")]
+
+
+# EEND_ROUTE_* / eend_linear_entry of include/eend_hip.h, in the header's order (tests/test_linear_edges_ref.py compares them with it)
+ROUTES = ("refused", "skinny", "skinny_splitk", "skinny_rowgroups", "skinny_rowgroups_splitk", "proj", "gemm128_straight",
+          "gemm128_looped", "gemm64x256", "convert_rows", "f32_mfma", "f32_mfma_splitk")
+ROUTE_NULL = -1
+LINEAR_ENTRIES = ("linear_f16", "linear_glu_f16", "inproj_heads_bf16", "retention_proj_f16", "linear_res_ln_f16",
+                  "linear_res16_ln_f16", "linear_res_scale_f16", "linear_res_scale_ln16_f16", "convert_fanout_f16",
+                  "linear_step_f32", "linear_res_ln_step_f32", "linear_res_scale_ln_step_f32")
+
+
+def linear_route(entry, **fields):
+    """Name of the kernel route entry point eend_<entry> takes for these arguments (eend_linear_route; host arithmetic only).
+    Address fields default to present and 16-byte aligned; pass ROUTE_NULL for a NULL pointer."""
+    a = LinearRouteArgs()
+    for k, v in fields.items():
+        if k not in dict(a._fields_):
+            raise KeyError(k)
+        setattr(a, k, int(v))
+    rc = load().eend_linear_route(LINEAR_ENTRIES.index(entry), ctypes.byref(a))
+    if rc < 0:
+        raise EendHipError(f"eend_linear_route({entry}) failed with code {rc}")
+    return ROUTES[rc]
 
 
 _lib = None

@@ -72,7 +72,9 @@ int eend_encoder_input_f16(const float* const* x_ptrs, const int* lens, float pa
  * torch.nn.Linear call sites: FFN linear1+ReLU of nn.TransformerEncoderLayer (FS model :147) and of
  * the fusion layer (FS-EEND/nnet/modules/merge_tfm_encoder.py:397-399), packed in-proj of the speaker
  * MHA (merge_tfm_encoder.py:388-394), Linear+Swish of LS-EEND's FeedForwardModule
- * (LS-EEND/nnet/conformer/feed_forward.py:49-50).  A [M][lda], W [N][ldw], N % 128 == 0, K % 64 == 0. */
+ * (LS-EEND/nnet/conformer/feed_forward.py:49-50).  A [M][lda], W [N][ldw], N % 128 == 0, K % 64 == 0; up to 16 rows with
+ * 16-byte aligned A / W rows take any N and K % 8 == 0.  ldo % 4 == 0, and ldo % 8 == 0 where the GEMM tile serves the call
+ * (it writes 16-byte pieces of the output rows); eend_linear_route names the kernel a call takes. */
 int eend_linear_f16(const void* A, int lda, const void* W, int ldw, const float* bias, void* out_f16,
                     int ldo, int M, int N, int K, int act, void* stream);
 
@@ -608,7 +610,8 @@ int eend_retention_step_f32(const float* qkvg, float* kv_state, const float* sca
                             int N, int H, float gn_eps, void* stream);      /* out_f16 and / or out_f32 [N][256] */
 /* The remaining pieces of an all-f32 LS decoder frame step (merge_retnet_layer.py:255-276 with <= 16 rows = one frame x
  * max_nspks slots): y = act(A W^T + bias) with f32 activations AND f32 weights in torch's nn.Linear layout (act 0 none /
- * 1 relu / 2 swish; K % 8 == 0, M <= 16); the post-norm join out = LayerNorm((A W^T + bias) * alpha + res) (N = 256; out_f16
+ * 1 relu / 2 swish; K % 8 == 0, any M >= 1: up to 16 rows take the wave-per-feature kernel, more rows the f32 MFMA kernel where
+ * N % 16 == 0, K % 16 == 0 and bias / out are 16-byte aligned, else the wave-per-feature kernel in groups of 16 rows); the post-norm join out = LayerNorm((A W^T + bias) * alpha + res) (N = 256; out_f16
  * optional copy); the speaker-axis attention of the frame on f32 [B*C][768] = [q | k | v] rows (C <= 16).  Why f32: DESIGN
  * 9a -- the decoder retention's per-head LayerNorm amplifies f16 operand rounding ~30x on isolated frames. */
 int eend_linear_step_f32(const float* A, int lda, const float* W, int ldw, const float* bias, float* out_f32, int ldo, int M, int N,
@@ -1081,6 +1084,41 @@ int eend_retention_bwd_bf16(const void* Q, const void* Qt, const void* K, const 
                             const float* dctx_f32, const void* g_f16, int ldg, const void* rhat_f16, const float* rc,
                             void* ot_ws, void* ott_ws, float* kv_ws, float* g_ws, void* St_ws, void* dqkvg_bf16, int ldq,
                             int nseq, int H, int Tp, int L, int T_valid, float sk, void* stream);
+
+/* Host-only query: the kernel one of the linear entry points takes for these arguments.  The entries and the query run the same
+ * routing code -- the query passes stand-in addresses with the given NULL-ness and low address bits, and every launcher returns the
+ * route in place of launching -- so a condition that moves in an entry moves here too (tests/test_linear_edges.py asserts the route
+ * each of its cases was written for).  Launches nothing and touches no device memory.  Returns an EEND_ROUTE_* value;
+ * EEND_ROUTE_REFUSED where the entry returns EEND_EINVAL; EEND_EINVAL for an unknown entry or args == NULL.
+ * Fields an entry does not take are ignored: N of the N = 256 entries; lda / ldw / ldo of eend_convert_fanout_f16 (B = nseq,
+ * slots = C) and ldo of the residual entries; M of the two head entries (nseq * Tp rows).  An address field is the pointer's low
+ * four bits, or EEND_ROUTE_NULL for a NULL pointer: a, w, bias, res (f32 or f16 residual; pc of the fan-out), gamma, beta, out_f32,
+ * out_f16 (every 2-byte destination of a head entry). */
+#define EEND_ROUTE_REFUSED 0
+#define EEND_ROUTE_SKINNY 1              /* skinny.hip, one wave per output feature (K <= 512) */
+#define EEND_ROUTE_SKINNY_SPLITK 2       /* skinny.hip, one workgroup per output feature */
+#define EEND_ROUTE_SKINNY_ROWGROUPS 3    /* skinny.hip f32, M > 16 in groups of 16 rows (K <= 512) */
+#define EEND_ROUTE_SKINNY_ROWGROUPS_SPLITK 4
+#define EEND_ROUTE_PROJ 5                /* proj.hip, X-resident */
+#define EEND_ROUTE_GEMM128_STRAIGHT 6    /* gemm.hip 128x128 tile, K = 256 straight-line */
+#define EEND_ROUTE_GEMM128_LOOPED 7      /* gemm.hip 128x128 tile, k-tile loop */
+#define EEND_ROUTE_GEMM64X256 8          /* gemm.hip 64x256 whole-row tile */
+#define EEND_ROUTE_CONVERT_ROWS 9        /* convert_rows.hip */
+#define EEND_ROUTE_F32_MFMA 10           /* gemm_f32.hip (K <= 768) */
+#define EEND_ROUTE_F32_MFMA_SPLITK 11    /* gemm_f32.hip, K split over the workgroup's waves */
+#define EEND_ROUTE_NULL (-1)
+enum eend_linear_entry {
+    EEND_ENTRY_LINEAR_F16 = 0, EEND_ENTRY_LINEAR_GLU_F16, EEND_ENTRY_INPROJ_HEADS_BF16, EEND_ENTRY_RETENTION_PROJ_F16,
+    EEND_ENTRY_LINEAR_RES_LN_F16, EEND_ENTRY_LINEAR_RES16_LN_F16, EEND_ENTRY_LINEAR_RES_SCALE_F16,
+    EEND_ENTRY_LINEAR_RES_SCALE_LN16_F16, EEND_ENTRY_CONVERT_FANOUT_F16, EEND_ENTRY_LINEAR_STEP_F32,
+    EEND_ENTRY_LINEAR_RES_LN_STEP_F32, EEND_ENTRY_LINEAR_RES_SCALE_LN_STEP_F32, EEND_ENTRY_COUNT
+};
+typedef struct eend_linear_route_args {
+    int M, N, K, lda, ldw, ldo, act;
+    int nseq, Tp, H, dh, C;
+    int a, w, bias, res, gamma, beta, out_f32, out_f16;
+} eend_linear_route_args;
+int eend_linear_route(int entry, const eend_linear_route_args* args);
 
 #ifdef __cplusplus
 }
