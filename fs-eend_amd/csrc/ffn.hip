@@ -21,20 +21,10 @@
 #include "common.h"
 #include "kernels.h"
 #include "wstream.h"
-#include <type_traits>
-#include <utility>
+#include "row_epilogue.h"
 #include <cstdlib>
 
 namespace {
-
-template <class F, int... I>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
-
-#ifndef EEND_FFN_PRE_SRC
-#define EEND_FFN_PRE_SRC 2       // how the plain PRE kernel fetches its A rows (see proj_ln_phase); 0 = the older per-wave form (A/B)
-#endif
 
 // Perf-study build (-DEEND_FFN_TRACE, tools/ffn_trace.py): s_memtime stamps of the tile phases of thread 0 of every
 // workgroup, read back through eend_debug_ffn_trace; never defined in the shipped library.
@@ -66,24 +56,21 @@ constexpr int W2_BYTES = KD * 128;              // 32768
 // over the 256 features of each token, and both output tiles go through LDS so that every global store
 // instruction writes whole rows (64 lanes x 16 B contiguous) instead of 16 token-row segments of 64 B (fp32) /
 // 32 B (f16): measured, the segment stores drained at 2.7 TB/s and were the largest fixed cost of the kernel.
-struct RowsContiguous {              // tile row -> global row (or -1): plain 128-row tiles
-    int m0, M;
-    __device__ __forceinline__ long operator()(int r) const { return m0 + r < M ? (long)(m0 + r) : -1L; }
-};
-
+// Statistics, staging images and store passes are row_epilogue.h's (8 waves: 2 m x 4 n, 128-row tiles).
+//
 // TRAIN (round 5): the accumulators hold b2 + h W2^T only; dropout of the sub-layer output, scale and residual happen here, and the LayerNorm
 // also saves 1/sigma per row and the normalised pre-affine rows (third staged tile) for the backward.
 template <int EPI, bool TRAIN, class RowMap>
-__device__ __forceinline__ void ffn_epilogue(const FfnParams& p, f32x4 (&acc)[4][4], char* smem, int wave, int frow, int fkg,
-                                             int g2m, int g2n, const RowMap rowmap) {
+DEV void ffn_epilogue(const FfnParams& p, f32x4 (&acc)[4][4], char* smem, int wave, int frow, int fkg,
+                      int g2m, int g2n, const RowMap rowmap) {
     // acc[i][j][r]: feature n = g2n + i*16 + fkg*4 + r ; tile row = g2m + j*16 + frow
     float* red = (float*)(smem + 131072);                    // [4 n-waves][128 rows]; clear of the staging tiles
     const int wn = wave & 3;
-    const int N0 = g2n + fkg * 4;
+    const int N0 = g2n + fkg * 4, row0 = g2m + frow, lane = frow + fkg * 16;
     if constexpr (TRAIN) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const long gr = rowmap(g2m + j * 16 + frow);
+            const long gr = rowmap(row0 + j * 16);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const unsigned n = (unsigned)(N0 + i * 16);
@@ -104,164 +91,70 @@ __device__ __forceinline__ void ffn_epilogue(const FfnParams& p, f32x4 (&acc)[4]
 #pragma unroll
             for (int r = 0; r < 4; ++r) acc[i][j][r] *= p.alpha;
     }
-    auto block_rowsum = [&](float (&part)[4]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            part[j] = wave_xor_add(part[j], 16);
-            part[j] = wave_xor_add(part[j], 32);
-        }
-        __syncthreads();
-        if (fkg == 0) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) red[wn * BM + g2m + j * 16 + frow] = part[j];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int row = g2m + j * 16 + frow;
-            part[j] = red[row] + red[BM + row] + red[2 * BM + row] + red[3 * BM + row];
-        }
-    };
-    float part[4], mean[4], rstd[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        float s = 0.f;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) s += acc[i][j][0] + acc[i][j][1] + acc[i][j][2] + acc[i][j][3];
-        part[j] = s;
-    }
-    block_rowsum(part);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) mean[j] = part[j] * (1.0f / KD);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        float s = 0.f;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) { const float d = acc[i][j][r] - mean[j]; s += d * d; }
-        part[j] = s;
-    }
-    block_rowsum(part);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) rstd[j] = 1.0f / __builtin_sqrtf(part[j] * (1.0f / KD) + p.eps);
+    float mean[4], rstd[4];
+    row_stats<true, 4, false>(acc, 1.0f / KD, p.eps, mean, rstd, red, BM, wn, row0, fkg);
     if constexpr (TRAIN) {
         if (wn == 0 && fkg == 0) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const long gr = rowmap(g2m + j * 16 + frow);
+                const long gr = rowmap(row0 + j * 16);
                 if (gr >= 0) p.rstat[gr] = rstd[j];
             }
         }
     }
 
-    float* __restrict__ o32 = p.out32;
-    _Float16* __restrict__ o16 = (_Float16*)p.out16;
-    {
-        const int lane = frow + fkg * 16;
-        f16x4 h16[4][4], l16[4][4];
-        // fp32 tile -> LDS [128 rows][1 KB], 16-B chunk c of row r at chunk c ^ (r & 7)
+    f16x4 h16[4][4], l16[4][4];
+    float4 g[4], be[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int n = N0 + i * 16;
-            const float4 g = *(const float4*)(p.gamma + n), be = *(const float4*)(p.beta + n);
+    for (int i = 0; i < 4; ++i) { g[i] = *(const float4*)(p.gamma + N0 + i * 16); be[i] = *(const float4*)(p.beta + N0 + i * 16); }
+    stage_frags32<4, 4>(smem, row0, N0, [&](int i, int j) __attribute__((always_inline)) {
+        f32x4 v;
+        v[0] = (acc[i][j][0] - mean[j]) * rstd[j] * g[i].x + be[i].x;
+        v[1] = (acc[i][j][1] - mean[j]) * rstd[j] * g[i].y + be[i].y;
+        v[2] = (acc[i][j][2] - mean[j]) * rstd[j] * g[i].z + be[i].z;
+        v[3] = (acc[i][j][3] - mean[j]) * rstd[j] * g[i].w + be[i].w;
+        h16[i][j][0] = to_f16_sat(v[0]); h16[i][j][1] = to_f16_sat(v[1]);
+        h16[i][j][2] = to_f16_sat(v[2]); h16[i][j][3] = to_f16_sat(v[3]);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int row = g2m + j * 16 + frow;
-                f32x4 v;
-                v[0] = (acc[i][j][0] - mean[j]) * rstd[j] * g.x + be.x;
-                v[1] = (acc[i][j][1] - mean[j]) * rstd[j] * g.y + be.y;
-                v[2] = (acc[i][j][2] - mean[j]) * rstd[j] * g.z + be.z;
-                v[3] = (acc[i][j][3] - mean[j]) * rstd[j] * g.w + be.w;
-                h16[i][j][0] = to_f16_sat(v[0]); h16[i][j][1] = to_f16_sat(v[1]);
-                h16[i][j][2] = to_f16_sat(v[2]); h16[i][j][3] = to_f16_sat(v[3]);
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    l16[i][j][r] = TRAIN ? to_f16_sat((acc[i][j][r] - mean[j]) * rstd[j]) : (_Float16)(v[r] - (float)h16[i][j][r]);
-                *(f32x4*)(smem + row * 1024 + (((n >> 2) ^ (row & 7)) << 4)) =
-                    EPI == FFN_EPI_RES_SCALE_LN16 ? acc[i][j] : v;       // LS: the residual stream stays un-normalised
-            }
-        }
+        for (int r = 0; r < 4; ++r)
+            l16[i][j][r] = TRAIN ? to_f16_sat((acc[i][j][r] - mean[j]) * rstd[j]) : (_Float16)(v[r] - (float)h16[i][j][r]);
+        return EPI == FFN_EPI_RES_SCALE_LN16 ? acc[i][j] : v;       // LS: the residual stream stays un-normalised
+    });
+    __syncthreads();
+    if (p.out32) store_rows32<8, BM>(smem, p.out32, KD, 0, wave, lane, rowmap);      // (null: the caller keeps only the f16 stream)
+    __syncthreads();
+    stage_frags16<4, 4>(smem, row0, N0, [&](int i, int j) __attribute__((always_inline)) { return h16[i][j]; });
+    __syncthreads();
+    store_rows16<8, BM>(smem, (_Float16*)p.out16, KD, 0, wave, lane, rowmap);
+    if (TRAIN || p.out16lo) {                            // the f16 remainder tile (TRAIN: the normalised pre-affine rows), same way
         __syncthreads();
-        if (o32) {                                           // (null: the caller keeps only the f16 stream)
-#pragma unroll
-            for (int k = 0; k < 16; ++k) {
-                const int row = k * 8 + wave;
-                const f32x4 v = *(const f32x4*)(smem + row * 1024 + ((lane ^ (row & 7)) << 4));
-                const long gr = rowmap(row);
-                if (gr >= 0) *(f32x4*)(o32 + (size_t)gr * KD + lane * 4) = v;
-            }
-        }
+        stage_frags16<4, 4>(smem, row0, N0, [&](int i, int j) __attribute__((always_inline)) { return l16[i][j]; });
         __syncthreads();
-        // f16 tile -> LDS [128 rows][512 B], 16-B chunk c of row r at chunk c ^ ((r >> 1) & 7)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int n = N0 + i * 16;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int row = g2m + j * 16 + frow;
-                *(f16x4*)(smem + row * 512 + (((n >> 3) ^ ((row >> 1) & 7)) << 4) + ((n >> 2) & 1) * 8) = h16[i][j];
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int row = (k * 8 + wave) * 2 + (lane >> 5), c = lane & 31;
-            const u32x4 v = *(const u32x4*)(smem + row * 512 + ((c ^ ((row >> 1) & 7)) << 4));
-            const long gr = rowmap(row);
-            if (gr >= 0) *(u32x4*)(o16 + (size_t)gr * KD + c * 8) = v;
-        }
-        if (TRAIN || p.out16lo) {                            // the f16 remainder tile (TRAIN: the normalised pre-affine rows), same way
-            _Float16* __restrict__ o16l = (_Float16*)(TRAIN ? p.xhat16 : p.out16lo);
-            __syncthreads();
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int n = N0 + i * 16;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int row = g2m + j * 16 + frow;
-                    *(f16x4*)(smem + row * 512 + (((n >> 3) ^ ((row >> 1) & 7)) << 4) + ((n >> 2) & 1) * 8) = l16[i][j];
-                }
-            }
-            __syncthreads();
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const int row = (k * 8 + wave) * 2 + (lane >> 5), c = lane & 31;
-                const u32x4 v = *(const u32x4*)(smem + row * 512 + ((c ^ ((row >> 1) & 7)) << 4));
-                const long gr = rowmap(row);
-                if (gr >= 0) *(u32x4*)(o16l + (size_t)gr * KD + c * 8) = v;
-            }
-        }
+        store_rows16<8, BM>(smem, (_Float16*)(TRAIN ? p.xhat16 : p.out16lo), KD, 0, wave, lane, rowmap);
     }
 }
 
 // MODE 4 epilogue: out32 = acc + res (the f32 residual-gradient stream, in place), whole-row stores through the staging tile; no LayerNorm.
 template <class RowMap>
-__device__ __forceinline__ void ffn_epilogue_acc(const FfnParams& p, f32x4 (&acc)[4][4], char* smem, int wave, int frow, int fkg,
-                                                 int g2m, int g2n, const RowMap rowmap) {
-    const int N0 = g2n + fkg * 4;
-    const int lane = frow + fkg * 16;
+DEV void ffn_epilogue_acc(const FfnParams& p, f32x4 (&acc)[4][4], char* smem, int wave, int frow, int fkg,
+                          int g2m, int g2n, const RowMap rowmap) {
+    const int N0 = g2n + fkg * 4, row0 = g2m + frow;
+    float4 r4[4][4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        const int row = g2m + j * 16 + frow;
-        const long gr = rowmap(row);
+        const long gr = rowmap(row0 + j * 16);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const int n = N0 + i * 16;
-            float4 r4 = make_float4(0, 0, 0, 0);
-            if (gr >= 0) r4 = *(const float4*)(p.res + (size_t)gr * KD + n);
-            const f32x4 v = f32x4{acc[i][j][0] * p.alpha + r4.x, acc[i][j][1] * p.alpha + r4.y, acc[i][j][2] * p.alpha + r4.z, acc[i][j][3] * p.alpha + r4.w};
-            *(f32x4*)(smem + row * 1024 + (((n >> 2) ^ (row & 7)) << 4)) = v;
+            r4[i][j] = make_float4(0, 0, 0, 0);
+            if (gr >= 0) r4[i][j] = *(const float4*)(p.res + (size_t)gr * KD + N0 + i * 16);
         }
     }
+    stage_frags32<4, 4>(smem, row0, N0, [&](int i, int j) __attribute__((always_inline)) {
+        return f32x4{acc[i][j][0] * p.alpha + r4[i][j].x, acc[i][j][1] * p.alpha + r4[i][j].y,
+                     acc[i][j][2] * p.alpha + r4[i][j].z, acc[i][j][3] * p.alpha + r4[i][j].w};
+    });
     __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        const int row = k * 8 + wave;
-        const f32x4 v = *(const f32x4*)(smem + row * 1024 + ((lane ^ (row & 7)) << 4));
-        const long gr = rowmap(row);
-        if (gr >= 0) *(f32x4*)(p.out32 + (size_t)gr * KD + lane * 4) = v;
-    }
+    store_rows32<8, BM>(smem, p.out32, KD, 0, wave, frow + fkg * 16, rowmap);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -285,10 +178,9 @@ constexpr int V2_SMEM = V2_HS + 2 * HS_BYTES;  // 163840
 
 // PRE: the block first computes its X tile itself, X = LayerNorm1(A Wo^T + bo + res) (attention
 // out-projection + residual + norm1 of the layer), so that the normalised activations between the two
-// sub-layers never travel through HBM: Wo (128 KB) sits in the still-unused weight buffers, the A
-// fragments come straight from global memory, and the result lands in the same accumulator layout that
-// seeds GEMM2 (fp32 residual) and, as f16, in the X staging tile.
-//
+// sub-layers never travel through HBM: Wo (128 KB, optionally a hi / lo f16 pair) passes through the still-unused
+// weight buffers in two halves, the A rows are fetched once per tile and shared through the X staging region, and
+// the result lands in the same accumulator layout that seeds GEMM2 (fp32 residual) and, as f16, in the X staging tile.
 
 template <int ACT, int EPI, int MODE>
 __global__ __launch_bounds__(NT)
@@ -401,212 +293,129 @@ void ffn_fused_kernel(const FfnParams p) {
             *(u32x4*)(Xst + (c32 >> 3) * (BM * 128) + swz128(row, c32 & 7)) = v;
         }
     } else {
-        // ---- projection + residual + LayerNorm phase: x = LN(A Wo^T + bo + res)
-        //   SRC_LDS: the A operand is the f16 tile in the staging region (else fragments come from global p.A)
-        //   LAST:    x feeds the FFN (f16 -> staging tile, fp32 + b2 -> GEMM2 seed, W1 slices 0/1 requested);
-        //            otherwise x feeds the speaker attention (f16 -> staging tile, fp32 -> out32 stream,
-        //            attention weight slices 0/1 requested)
+        // ---- projection + residual + LayerNorm phase: x = LN1(A Wo^T + bo + res); x feeds the FFN (f16 -> staging tile,
+        // fp32 / alpha + b2 -> GEMM2 seed, W1 slices 0/1 requested).
+        // The A rows are fetched ONCE (compact, 8 x 16 B per thread) and shared through the staging tile, and Wo arrives in
+        // two halves -- k-tiles 0/1 with the inputs, k-tiles 2/3 (whose LDS image overlaps the staging tile) behind the
+        // fragment reads, under the first half of the GEMM.  The input wait of a tile is ingest-bound (~12 B/clk/CU with
+        // every CU fetching at once: s_memtime trace, tools/ffn_trace.py); this form ingests 320 KB per tile, where every
+        // n-wave fetching its own A fragments from global ingested 512 KB.
         const int N0 = g2n + fkg * 4;
-        float* red = (float*)(smem + 131072);
-        const int wn = wave & 3;
-        auto block_rowsum = [&](float (&part)[4]) __attribute__((always_inline)) {
+        f16x8 af[8][4];                                  // A fragments [k-step][token frag]
+        const __amdgpu_buffer_rsrc_t rso = __builtin_amdgcn_make_buffer_rsrc((void*)p.Wo, 0, KD * KD * 2, 0x00020000);
+        auto dma_wo_piece = [&](int piece) __attribute__((always_inline)) {      // Wo -> LDS [4 k-tiles][256 n][128 B], 128 pieces of 1 KB
+            const int kt = piece >> 5, row = (piece & 31) * 8 + drow;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rso, (lds_char*)(smem + piece * 1024), 16,
+                                                     (row * KD + kt * 64 + (dslot ^ ((row >> 1) & 7)) * 8) * 2, 0, 0, 0);
+        };
+        u32x4 ar[8];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                part[j] = wave_xor_add(part[j], 16);
-                part[j] = wave_xor_add(part[j], 32);
-            }
-            __syncthreads();
-            if (fkg == 0) {
+        for (int i = 0; i < 8; ++i) dma_wo_piece(wave * 8 + i);              // k-tiles 0, 1
+        const _Float16* __restrict__ A = (const _Float16*)p.A;
 #pragma unroll
-                for (int j = 0; j < 4; ++j) red[wn * BM + g2m + j * 16 + frow] = part[j];
+        for (int i = 0; i < 8; ++i) {
+            const int q = tid + i * NT;
+            ar[i] = *(const u32x4*)(A + (size_t)rowclamp(q >> 5) * p.lda + (q & 31) * 8);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {                    // accumulators start at bo + res
+            const long m = rowmap(g2m + j * 16 + frow);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const float4 b4 = *(const float4*)(p.bo + N0 + i * 16);
+                float4 r = make_float4(0, 0, 0, 0);
+                if (m >= 0) {
+                    if (p.res) r = *(const float4*)(p.res + (size_t)m * KD + N0 + i * 16);
+                    else if (p.res16) {
+                        const f16x4 h = *(const f16x4*)((const _Float16*)p.res16 + (size_t)m * KD + N0 + i * 16);
+                        r = make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]);
+                    }
+                }
+                acc[i][j] = f32x4{r.x + b4.x, r.y + b4.y, r.z + b4.z, r.w + b4.w};
             }
+        }
+        auto gemm_ks = [&](auto KS) __attribute__((always_inline)) {
+            constexpr int ks = decltype(KS)::value;
+            f16x8 a[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                a[i] = *(const f16x8*)(smem + (ks >> 1) * (KD * 128) + swz128(g2n + i * 16 + frow, (ks & 1) * 4 + fkg));
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[i], af[ks][j], acc[i][j], 0, 0, 0);
+        };
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int q = tid + i * NT;
+            *(u32x4*)(Xst + ((q & 31) >> 3) * (BM * 128) + swz128(q >> 5, q & 7)) = ar[i];
+        }
+        FFN_STAMP(1);
+        __syncthreads();                             // A tile visible; Wo k-tiles 0/1 and the residual have landed
+        FFN_STAMP(2);
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                af[ks][j] = *(const f16x8*)(Xst + (ks >> 1) * (BM * 128) + swz128(g2m + j * 16 + frow, (ks & 1) * 4 + fkg));
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // staging tile free: Wo k-tiles 2/3 land there
+#pragma unroll
+        for (int i = 0; i < 8; ++i) dma_wo_piece(64 + wave * 8 + i);
+        FFN_STAMP(3);
+        static_for<4>([&](auto KS) __attribute__((always_inline)) { gemm_ks(KS); });
+        FFN_STAMP(4);
+        __syncthreads();                             // (vmcnt(0): k-tiles 2/3 complete in every wave)
+        FFN_STAMP(5);
+        // Wo as a hi / lo f16 pair (LS-EEND decoder, round 5: the f16 rounding of the speaker-attention out-projection weight was
+        // the largest single contributor to the worst logit of the 12-slot golden): the lo part's k-tiles follow the hi
+        // part's through the same two LDS halves, each requested as soon as every wave is done with the half it overwrites --
+        // the second product costs its 32 MFMAs per wave and half a DMA latency, the A fragments stay in registers
+        const bool lo = p.Wo_lo != nullptr;
+        const __amdgpu_buffer_rsrc_t rsl = __builtin_amdgcn_make_buffer_rsrc((void*)(lo ? p.Wo_lo : p.Wo), 0, KD * KD * 2, 0x00020000);
+        auto dma_wl_piece = [&](int piece) __attribute__((always_inline)) {
+            const int kt = piece >> 5, row = (piece & 31) * 8 + drow;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsl, (lds_char*)(smem + piece * 1024), 16,
+                                                     (row * KD + kt * 64 + (dslot ^ ((row >> 1) & 7)) * 8) * 2, 0, 0, 0);
+        };
+        if (lo) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) dma_wl_piece(wave * 8 + i);          // lo k-tiles 0, 1 (every wave is past the hi ones: barrier above)
+        }
+        static_for<4>([&](auto KS) __attribute__((always_inline)) { gemm_ks(std::integral_constant<int, decltype(KS)::value + 4>{}); });
+        if (lo) {
+            __syncthreads();                         // lo k-tiles 0 / 1 complete in every wave; every wave past the hi k-tiles 2 / 3
+#pragma unroll
+            for (int i = 0; i < 8; ++i) dma_wl_piece(64 + wave * 8 + i);
+            static_for<4>([&](auto KS) __attribute__((always_inline)) { gemm_ks(KS); });
             __syncthreads();
+            static_for<4>([&](auto KS) __attribute__((always_inline)) { gemm_ks(std::integral_constant<int, decltype(KS)::value + 4>{}); });
+        }
+        // LayerNorm1 statistics (row_epilogue.h).  Behind the first row sum every wave is past its Wo reads: the FFN's first two
+        // weight slices can land in the first 64 KB (the barrier in front of the X fragment reads, with its vmcnt(0), is the
+        // completion wait); the second row sum's barriers retire every wave's reads of the LN scratch
+        float mean[4], rstd[4];
+        row_stats<true, 4, false>(acc, 1.0f / KD, p.eps1, mean, rstd, (float*)(smem + 131072), BM, wave & 3, g2m + frow, fkg,
+                                  [&]() __attribute__((always_inline)) { dma_w1(0, 0); if (nF > 1) dma_w1(FC, 1); });
+        // x as f16 into the X staging tile (the k-tiled operand image GEMM1's fragments are read from, not a row-store image:
+        // its own addresses), x / alpha + b2 into the accumulators: the GEMM2 seed
+        const float ralpha = 1.0f / p.alpha;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int n = N0 + i * 16;
+            const float4 gg = *(const float4*)(p.g1 + n), bb = *(const float4*)(p.be1 + n), b4 = *(const float4*)(p.b2 + n);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int row = g2m + j * 16 + frow;
-                part[j] = red[row] + red[BM + row] + red[2 * BM + row] + red[3 * BM + row];
+                const float v0 = (acc[i][j][0] - mean[j]) * rstd[j] * gg.x + bb.x;
+                const float v1 = (acc[i][j][1] - mean[j]) * rstd[j] * gg.y + bb.y;
+                const float v2 = (acc[i][j][2] - mean[j]) * rstd[j] * gg.z + bb.z;
+                const float v3 = (acc[i][j][3] - mean[j]) * rstd[j] * gg.w + bb.w;
+                f16x4 o;
+                o[0] = to_f16_sat(v0); o[1] = to_f16_sat(v1); o[2] = to_f16_sat(v2); o[3] = to_f16_sat(v3);
+                *(f16x4*)(Xst + (n >> 6) * (BM * 128) + swz128(row, (n & 63) >> 3) + ((n >> 2) & 1) * 8) = o;
+                acc[i][j] = f32x4{v0 * ralpha + b4.x, v1 * ralpha + b4.y, v2 * ralpha + b4.z, v3 * ralpha + b4.w};
             }
-        };
-        // SRC: 0 = A fragments straight from global (each of the 4 n-waves of a token group fetches the same rows),
-        //      1 = A is the f16 tile already in the staging region (the round-2 whole-layer form; no caller left),
-        //      2 = plain PRE tiles: A rows are fetched ONCE (compact, 8 x 16 B per thread) and shared through the staging
-        //          tile, and Wo arrives in two halves -- k-tiles 0/1 with the inputs, k-tiles 2/3 (whose LDS image
-        //          overlaps the staging tile) behind the fragment reads, under the first half of the GEMM.  The input
-        //          wait of a tile is ingest-bound (~12 B/clk/CU with every CU fetching at once: s_memtime trace,
-        //          tools/ffn_trace.py); this form ingests 320 KB per tile instead of 512 KB.
-        auto proj_ln_phase = [&](const void* Wo, const float* bo, const float* g, const float* be, const float eps,
-                                 const float* resp, auto SRC, auto LAST) __attribute__((always_inline)) {
-            constexpr int src = decltype(SRC)::value;
-            constexpr bool src_lds = src == 1, compact = src == 2, last = decltype(LAST)::value;
-            f16x8 af[8][4];                                  // A fragments [k-step][token frag]
-            const __amdgpu_buffer_rsrc_t rso = __builtin_amdgcn_make_buffer_rsrc((void*)Wo, 0, KD * KD * 2, 0x00020000);
-            auto dma_wo_piece = [&](int piece) __attribute__((always_inline)) {      // Wo -> LDS [4 k-tiles][256 n][128 B], 128 pieces of 1 KB
-                const int kt = piece >> 5, row = (piece & 31) * 8 + drow;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rso, (lds_char*)(smem + piece * 1024), 16,
-                                                         (row * KD + kt * 64 + (dslot ^ ((row >> 1) & 7)) * 8) * 2, 0, 0, 0);
-            };
-            u32x4 ar[compact ? 8 : 1];
-            if constexpr (src_lds) {
-#pragma unroll
-                for (int ks = 0; ks < 8; ++ks)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        af[ks][j] = *(const f16x8*)(Xst + (ks >> 1) * (BM * 128) + swz128(g2m + j * 16 + frow, (ks & 1) * 4 + fkg));
-                asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // every wave holds its fragments: the tile may be overwritten
-            }
-            if constexpr (compact) {
-#pragma unroll
-                for (int i = 0; i < 8; ++i) dma_wo_piece(wave * 8 + i);              // k-tiles 0, 1
-                const _Float16* __restrict__ A = (const _Float16*)p.A;
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const int q = tid + i * NT;
-                    ar[i] = *(const u32x4*)(A + (size_t)rowclamp(q >> 5) * p.lda + (q & 31) * 8);
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) dma_wo_piece(wave * 16 + i);
-            }
-            if constexpr (src == 0) {
-                const _Float16* __restrict__ A = (const _Float16*)p.A;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const long m = rowclamp(g2m + j * 16 + frow);
-#pragma unroll
-                    for (int ks = 0; ks < 8; ++ks) af[ks][j] = *(const f16x8*)(A + (size_t)m * p.lda + ks * 32 + fkg * 8);
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {                    // accumulators start at bo + res
-                const long m = rowmap(g2m + j * 16 + frow);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const float4 b4 = *(const float4*)(bo + N0 + i * 16);
-                    float4 r = make_float4(0, 0, 0, 0);
-                    if (m >= 0) {
-                        if (resp) r = *(const float4*)(resp + (size_t)m * KD + N0 + i * 16);
-                        else if (src != 1 && p.res16) {          // (the second out-projection of the layer tail reads its own out32 stream)
-                            const f16x4 h = *(const f16x4*)((const _Float16*)p.res16 + (size_t)m * KD + N0 + i * 16);
-                            r = make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]);
-                        }
-                    }
-                    acc[i][j] = f32x4{r.x + b4.x, r.y + b4.y, r.z + b4.z, r.w + b4.w};
-                }
-            }
-            auto gemm_ks = [&](auto KS) __attribute__((always_inline)) {
-                constexpr int ks = decltype(KS)::value;
-                f16x8 a[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    a[i] = *(const f16x8*)(smem + (ks >> 1) * (KD * 128) + swz128(g2n + i * 16 + frow, (ks & 1) * 4 + fkg));
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[i], af[ks][j], acc[i][j], 0, 0, 0);
-            };
-            if constexpr (compact) {
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const int q = tid + i * NT;
-                    *(u32x4*)(Xst + ((q & 31) >> 3) * (BM * 128) + swz128(q >> 5, q & 7)) = ar[i];
-                }
-                FFN_STAMP(1);
-                __syncthreads();                             // A tile visible; Wo k-tiles 0/1 and the residual have landed
-                FFN_STAMP(2);
-#pragma unroll
-                for (int ks = 0; ks < 8; ++ks)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        af[ks][j] = *(const f16x8*)(Xst + (ks >> 1) * (BM * 128) + swz128(g2m + j * 16 + frow, (ks & 1) * 4 + fkg));
-                asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // staging tile free: Wo k-tiles 2/3 land there
-#pragma unroll
-                for (int i = 0; i < 8; ++i) dma_wo_piece(64 + wave * 8 + i);
-                FFN_STAMP(3);
-                static_for<4>([&](auto KS) __attribute__((always_inline)) { gemm_ks(KS); });
-                FFN_STAMP(4);
-                __syncthreads();                             // (vmcnt(0): k-tiles 2/3 complete in every wave)
-                FFN_STAMP(5);
-                // Wo as a hi / lo f16 pair (LS-EEND decoder, round 5: the f16 rounding of the speaker-attention out-projection weight was
-                // the largest single contributor to the worst logit of the 12-slot golden): the lo part's k-tiles follow the hi
-                // part's through the same two LDS halves, each requested as soon as every wave is done with the half it overwrites --
-                // the second product costs its 32 MFMAs per wave and half a DMA latency, the A fragments stay in registers
-                const bool lo = p.Wo_lo != nullptr && Wo == p.Wo;
-                const __amdgpu_buffer_rsrc_t rsl = __builtin_amdgcn_make_buffer_rsrc((void*)(lo ? p.Wo_lo : Wo), 0, KD * KD * 2, 0x00020000);
-                auto dma_wl_piece = [&](int piece) __attribute__((always_inline)) {
-                    const int kt = piece >> 5, row = (piece & 31) * 8 + drow;
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsl, (lds_char*)(smem + piece * 1024), 16,
-                                                             (row * KD + kt * 64 + (dslot ^ ((row >> 1) & 7)) * 8) * 2, 0, 0, 0);
-                };
-                if (lo) {
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) dma_wl_piece(wave * 8 + i);          // lo k-tiles 0, 1 (every wave is past the hi ones: barrier above)
-                }
-                static_for<4>([&](auto KS) __attribute__((always_inline)) { gemm_ks(std::integral_constant<int, decltype(KS)::value + 4>{}); });
-                if (lo) {
-                    __syncthreads();                         // lo k-tiles 0 / 1 complete in every wave; every wave past the hi k-tiles 2 / 3
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) dma_wl_piece(64 + wave * 8 + i);
-                    static_for<4>([&](auto KS) __attribute__((always_inline)) { gemm_ks(KS); });
-                    __syncthreads();
-                    static_for<4>([&](auto KS) __attribute__((always_inline)) { gemm_ks(std::integral_constant<int, decltype(KS)::value + 4>{}); });
-                }
-            } else {
-                __syncthreads();
-                static_for<8>([&](auto KS) __attribute__((always_inline)) { gemm_ks(KS); });
-            }
-            float part[4], mean[4], rstd[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                float sum = 0.f;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) sum += acc[i][j][0] + acc[i][j][1] + acc[i][j][2] + acc[i][j][3];
-                part[j] = sum;
-            }
-            block_rowsum(part);
-            // every wave is past its Wo reads: the next phase's first two weight slices can land in the first
-            // 64 KB now (the staging barrier below, with its vmcnt(0), is the completion wait)
-            dma_w1(0, 0);
-            if (nF > 1) dma_w1(FC, 1);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) mean[j] = part[j] * (1.0f / KD);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                float sum = 0.f;
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) { const float d = acc[i][j][r] - mean[j]; sum += d * d; }
-                part[j] = sum;
-            }
-            block_rowsum(part);                              // (its barriers also retire every wave's Wo reads)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) rstd[j] = 1.0f / __builtin_sqrtf(part[j] * (1.0f / KD) + eps);
-            const float ralpha = 1.0f / p.alpha;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int n = N0 + i * 16;
-                const float4 gg = *(const float4*)(g + n), bb = *(const float4*)(be + n), b4 = *(const float4*)(p.b2 + n);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int row = g2m + j * 16 + frow;
-                    const float v0 = (acc[i][j][0] - mean[j]) * rstd[j] * gg.x + bb.x;
-                    const float v1 = (acc[i][j][1] - mean[j]) * rstd[j] * gg.y + bb.y;
-                    const float v2 = (acc[i][j][2] - mean[j]) * rstd[j] * gg.z + bb.z;
-                    const float v3 = (acc[i][j][3] - mean[j]) * rstd[j] * gg.w + bb.w;
-                    f16x4 o;
-                    o[0] = to_f16_sat(v0); o[1] = to_f16_sat(v1); o[2] = to_f16_sat(v2); o[3] = to_f16_sat(v3);
-                    *(f16x4*)(Xst + (n >> 6) * (BM * 128) + swz128(row, (n & 63) >> 3) + ((n >> 2) & 1) * 8) = o;
-                    if constexpr (last) {
-                        acc[i][j] = f32x4{v0 * ralpha + b4.x, v1 * ralpha + b4.y, v2 * ralpha + b4.z, v3 * ralpha + b4.w};   // GEMM2 seed
-                    } else {
-                        const long m = rowmap(row);
-                        if (m >= 0) *(float4*)(p.out32 + (size_t)m * KD + n) = make_float4(v0, v1, v2, v3);
-                    }
-                }
-            }
-        };
-
-        proj_ln_phase(p.Wo, p.bo, p.g1, p.be1, p.eps1, p.res, std::integral_constant<int, EEND_FFN_PRE_SRC>{}, std::true_type{});
+        }
     }
     FFN_STAMP(6);
     float4 bcur[2] = {make_float4(0, 0, 0, 0), make_float4(0, 0, 0, 0)};

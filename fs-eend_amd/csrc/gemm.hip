@@ -15,19 +15,10 @@
 // into the producer's epilogue instead of being a kernel of its own.
 #include "common.h"
 #include "kernels.h"
+#include "row_epilogue.h"
 #include <stdlib.h>
-#include <type_traits>
-#include <utility>
 
 namespace {
-
-// Compile-time loop: f(std::integral_constant<int, I>{}) for I in [0, N).  Register arrays
-// indexed through it have constant indices at IR-generation time (a `#pragma unroll` loop
-// variable is only constant after unrolling, too late for SROA -> the array lands in scratch).
-template <class F, int... I>
-DEV void static_for_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, class F>
-DEV void static_for(F&& f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
 
 enum { ALOAD_PLAIN = 0, ALOAD_CONV = 1 };
 
@@ -393,26 +384,6 @@ void gemm_f16_kernel(const GemmParams p) {
             }
         }
         float mean[FL], scale[FL];
-        auto block_rowsum = [&](float (&part)[FL]) __attribute__((always_inline)) {
-#pragma unroll
-            for (int j = 0; j < FL; ++j) {
-                part[j] = wave_xor_add(part[j], 16);
-                part[j] = wave_xor_add(part[j], 32);
-            }
-            __syncthreads();
-            if (fkg == 0) {
-#pragma unroll
-                for (int j = 0; j < FL; ++j) red[wn * BM + j * 16 + frow] = part[j];
-            }
-            __syncthreads();
-#pragma unroll
-            for (int j = 0; j < FL; ++j) {
-                float s = 0.f;
-#pragma unroll
-                for (int w = 0; w < WGN; ++w) s += red[w * BM + j * 16 + frow];
-                part[j] = s;
-            }
-        };
         // EPI_RES_LNBWD: the LayerNorm backward of the post-norm site in front of the branch, in the epilogue (train_rows.hip ln_bwd_kernel,
         // same algebra).  acc = g, the gradient w.r.t. the LayerNorm output (the data-gradient GEMM's result + the incoming stream):
         //   dz = rstd * (g gamma - mean(g gamma) - x_hat mean(g gamma x_hat))  -> out32 (the residual stream's gradient, unmasked)
@@ -453,7 +424,7 @@ void gemm_f16_kernel(const GemmParams p) {
                     if (frow == 0) { cp[R0 + i * 16 + r - n0] = a; cp[256 + R0 + i * 16 + r - n0] = b; }
                 }
             }
-            // both row sums in ONE exchange (red: [2][WGN][BM] floats = the 2 KB in front of the staging tile); the rows' 1/sigma travel under it
+            // both row sums in ONE exchange, so not block_rowsum (red: [2][WGN][BM] floats = the 2 KB in front of the staging tile); the rows' 1/sigma travel under it
             float rsv[FL];
 #pragma unroll
             for (int j = 0; j < FL; ++j) {
@@ -493,37 +464,8 @@ void gemm_f16_kernel(const GemmParams p) {
         } else if constexpr (EPI == EPI_RES_SCALE) {
 #pragma unroll
             for (int j = 0; j < FL; ++j) { mean[j] = 0.f; scale[j] = 1.f; }
-        } else {
-            const float invN = 1.0f / (float)p.N;
-            float part[FL];
-            if constexpr (LNK) {
-#pragma unroll
-                for (int j = 0; j < FL; ++j) {
-                    float s = 0.f;
-#pragma unroll
-                    for (int i = 0; i < FR; ++i) s += acc[i][j][0] + acc[i][j][1] + acc[i][j][2] + acc[i][j][3];
-                    part[j] = s;
-                }
-                block_rowsum(part);
-#pragma unroll
-                for (int j = 0; j < FL; ++j) mean[j] = part[j] * invN;
-            } else {
-#pragma unroll
-                for (int j = 0; j < FL; ++j) mean[j] = 0.f;
-            }
-#pragma unroll
-            for (int j = 0; j < FL; ++j) {
-                float s = 0.f;
-#pragma unroll
-                for (int i = 0; i < FR; ++i)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) { const float d = acc[i][j][r] - mean[j]; s += d * d; }
-                part[j] = s;
-            }
-            block_rowsum(part);
-#pragma unroll
-            for (int j = 0; j < FL; ++j)
-                scale[j] = L2K ? 1.0f / __builtin_sqrtf(part[j]) : 1.0f / __builtin_sqrtf(part[j] * invN + p.eps);
+        } else {                                          // two-pass LayerNorm / L2-norm statistics (red: [WGN][BM])
+            row_stats<LNK, WGN, true>(acc, 1.0f / (float)p.N, p.eps, mean, scale, red, BM, wn, frow, fkg);
         }
         float* __restrict__ o32 = (float*)p.out32;
         ET* __restrict__ o16 = (ET*)p.out16;
@@ -535,120 +477,105 @@ void gemm_f16_kernel(const GemmParams p) {
                     if (L0 + j * 16 < p.M) p.rstat[L0 + j * 16] = scale[j];
             }
         }
-        if constexpr (BM == 64 && BN == 256 && WGN == 4 && 2 * TILE_BYTES >= 2048 + BM * BN * 4) {
-            // Staged stores (as ffn.hip): the direct form writes 64-byte (fp32) / 32-byte (f16) pieces of 16 rows per
-            // instruction -- PMC WRITE_SIZE showed 1.5x the algorithmic bytes for this kernel.  Through LDS every
-            // store instruction writes one whole 1 KB row (fp32) or two 512 B rows (f16).
-            char* stg = smem + 2048;                          // clear of the row-statistics scratch
-            if constexpr (EPI == EPI_RES_SCALE || LNB) __syncthreads();   // (no statistics pass / its scratch was just read: fence before the staging writes)
-            O16 h16[LNB ? 1 : FR][LNB ? 1 : FL];
-            O16 xh16[TRAINK && LNK ? FR : 1][TRAINK && LNK ? FL : 1];
+        // Staged stores (row_epilogue.h's staging images, as ffn.hip; the passes are this kernel's own text): the direct form writes 64-byte (fp32) / 32-byte (f16) pieces of 16 rows per
+        // instruction -- PMC WRITE_SIZE showed 1.5x the algorithmic bytes for this kernel.  Through LDS every
+        // store instruction writes one whole 1 KB row (fp32) or two 512 B rows (f16).
+        static_assert(BM == 64 && BN == 256 && WGN == 4 && 2 * TILE_BYTES >= 2048 + BM * BN * 4,
+                      "64 x 256 tile, four n-waves: the f32 staging image sits behind the 2 KB of row-statistics scratch");
+        char* stg = smem + 2048;                          // clear of the row-statistics scratch
+        const int nl0 = R0 - n0;
+        if constexpr (EPI == EPI_RES_SCALE || LNB) __syncthreads();   // (no statistics pass / its scratch was just read: fence before the staging writes)
+        O16 h16[LNB ? 1 : FR][LNB ? 1 : FL];
+        O16 xh16[TRAINK && LNK ? FR : 1][TRAINK && LNK ? FL : 1];
 #pragma unroll
-            for (int i = 0; i < FR; ++i) {
-                const int n = R0 + i * 16, nl = n - n0;
-                float4 g = make_float4(1, 1, 1, 1), be = make_float4(0, 0, 0, 0);
-                if (LNK && p.gamma) { g = *(const float4*)(p.gamma + n); be = *(const float4*)(p.beta + n); }
+        for (int i = 0; i < FR; ++i) {
+            const int n = R0 + i * 16, nl = n - n0;
+            float4 g = make_float4(1, 1, 1, 1), be = make_float4(0, 0, 0, 0);
+            if (LNK && p.gamma) { g = *(const float4*)(p.gamma + n); be = *(const float4*)(p.beta + n); }
 #pragma unroll
-                for (int j = 0; j < FL; ++j) {
-                    const int row = j * 16 + frow;
-                    f32x4 v;
-                    v[0] = (acc[i][j][0] - mean[j]) * scale[j] * g.x + be.x;
-                    v[1] = (acc[i][j][1] - mean[j]) * scale[j] * g.y + be.y;
-                    v[2] = (acc[i][j][2] - mean[j]) * scale[j] * g.z + be.z;
-                    v[3] = (acc[i][j][3] - mean[j]) * scale[j] * g.w + be.w;
-                    if constexpr (!LNB) h16[i][j] = OutCvt<ET>::cvt(v[0], v[1], v[2], v[3]);      // (LNB: made in the 2-byte staging pass below)
-                    if constexpr (TRAINK && LNK)            // normalised, pre-affine row: what LayerNorm backward needs
-                        xh16[i][j] = OutCvt<ET>::cvt((acc[i][j][0] - mean[j]) * scale[j], (acc[i][j][1] - mean[j]) * scale[j],
-                                                     (acc[i][j][2] - mean[j]) * scale[j], (acc[i][j][3] - mean[j]) * scale[j]);
-                    *(f32x4*)(stg + row * 1024 + (((nl >> 2) ^ (row & 7)) << 4)) = PRENORM ? acc[i][j] : v;
+            for (int j = 0; j < FL; ++j) {
+                const int row = j * 16 + frow;
+                f32x4 v;
+                v[0] = (acc[i][j][0] - mean[j]) * scale[j] * g.x + be.x;
+                v[1] = (acc[i][j][1] - mean[j]) * scale[j] * g.y + be.y;
+                v[2] = (acc[i][j][2] - mean[j]) * scale[j] * g.z + be.z;
+                v[3] = (acc[i][j][3] - mean[j]) * scale[j] * g.w + be.w;
+                if constexpr (!LNB) h16[i][j] = OutCvt<ET>::cvt(v[0], v[1], v[2], v[3]);      // (LNB: made in the 2-byte staging pass below)
+                if constexpr (TRAINK && LNK)            // normalised, pre-affine row: what LayerNorm backward needs
+                    xh16[i][j] = OutCvt<ET>::cvt((acc[i][j][0] - mean[j]) * scale[j], (acc[i][j][1] - mean[j]) * scale[j],
+                                                 (acc[i][j][2] - mean[j]) * scale[j], (acc[i][j][3] - mean[j]) * scale[j]);
+                *(f32x4*)(stg + stage32_frag(row, nl)) = PRENORM ? acc[i][j] : v;
+            }
+        }
+        __syncthreads();
+        if (o32) {
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                const int row = k * 4 + wave;
+                const f32x4 v = *(const f32x4*)(stg + stage32_row(row, lane));
+                if (m0 + row < p.M) *(f32x4*)(o32 + (size_t)(m0 + row) * p.ldo + n0 + lane * 4) = v;
+            }
+        }
+        if (o16) {
+            __syncthreads();
+            if constexpr (LNB) {
+                // the branch gradient carries the forward's (row, column) dropout mask; the masked values' column sums leave per feature fragment
+#pragma unroll
+                for (int i = 0; i < FR; ++i) {
+                    const int nl = nl0 + i * 16;
+                    float cds[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int j = 0; j < FL; ++j) {
+                        const unsigned mm = (unsigned)(L0 + j * 16), nn = (unsigned)(R0 + i * 16);
+                        const float k0 = drop_apply(p.drop, acc[i][j][0], mm, nn), k1 = drop_apply(p.drop, acc[i][j][1], mm, nn + 1);
+                        const float k2 = drop_apply(p.drop, acc[i][j][2], mm, nn + 2), k3 = drop_apply(p.drop, acc[i][j][3], mm, nn + 3);
+                        if (L0 + j * 16 < p.M) { cds[0] += k0; cds[1] += k1; cds[2] += k2; cds[3] += k3; }
+                        *(O16*)(stg + stage16_frag(j * 16 + frow, nl)) = OutCvt<ET>::cvt(k0, k1, k2, k3);
+                    }
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const float c = row16_allreduce_add(cds[r]);
+                        if (frow == 0) cp[512 + nl + r] = c;
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < FR; ++i) {
+                    const int nl = R0 + i * 16 - n0;
+#pragma unroll
+                    for (int j = 0; j < FL; ++j) {
+                        const int row = j * 16 + frow;
+                        *(O16*)(stg + stage16_frag(row, nl)) = h16[i][j];
+                    }
                 }
             }
             __syncthreads();
-            if (o32) {
 #pragma unroll
-                for (int k = 0; k < 16; ++k) {
-                    const int row = k * 4 + wave;
-                    const f32x4 v = *(const f32x4*)(stg + row * 1024 + ((lane ^ (row & 7)) << 4));
-                    if (m0 + row < p.M) *(f32x4*)(o32 + (size_t)(m0 + row) * p.ldo + n0 + lane * 4) = v;
-                }
+            for (int k = 0; k < 8; ++k) {
+                const int row = (k * 4 + wave) * 2 + (lane >> 5), c = lane & 31;
+                const u32x4 v = *(const u32x4*)(stg + stage16_row(row, c));
+                if (m0 + row < p.M) *(u32x4*)(o16 + (size_t)(m0 + row) * p.ldo + n0 + c * 8) = v;
             }
-            if (o16) {
+        }
+        if constexpr (TRAINK && LNK) {
+            if (p.xhat16) {                                     // third staged tile: x_hat (same 2-byte staging as out16)
                 __syncthreads();
 #pragma unroll
                 for (int i = 0; i < FR; ++i) {
                     const int nl = R0 + i * 16 - n0;
-                    float cds[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                     for (int j = 0; j < FL; ++j) {
                         const int row = j * 16 + frow;
-                        O16 hv;
-                        if constexpr (LNB) {                 // the branch gradient carries the forward's (row, column) dropout mask
-                            const unsigned mm = (unsigned)(L0 + j * 16), nn = (unsigned)(R0 + i * 16);
-                            const float k0 = drop_apply(p.drop, acc[i][j][0], mm, nn), k1 = drop_apply(p.drop, acc[i][j][1], mm, nn + 1);
-                            const float k2 = drop_apply(p.drop, acc[i][j][2], mm, nn + 2), k3 = drop_apply(p.drop, acc[i][j][3], mm, nn + 3);
-                            hv = OutCvt<ET>::cvt(k0, k1, k2, k3);
-                            if (L0 + j * 16 < p.M) { cds[0] += k0; cds[1] += k1; cds[2] += k2; cds[3] += k3; }
-                        } else {
-                            hv = h16[i][j];
-                        }
-                        *(O16*)(stg + row * 512 + (((nl >> 3) ^ ((row >> 1) & 7)) << 4) + ((nl >> 2) & 1) * 8) = hv;
-                    }
-                    if constexpr (LNB) {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const float c = row16_allreduce_add(cds[r]);
-                            if (frow == 0) cp[512 + nl + r] = c;
-                        }
+                        *(O16*)(stg + stage16_frag(row, nl)) = xh16[i][j];
                     }
                 }
                 __syncthreads();
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
                     const int row = (k * 4 + wave) * 2 + (lane >> 5), c = lane & 31;
-                    const u32x4 v = *(const u32x4*)(stg + row * 512 + ((c ^ ((row >> 1) & 7)) << 4));
-                    if (m0 + row < p.M) *(u32x4*)(o16 + (size_t)(m0 + row) * p.ldo + n0 + c * 8) = v;
+                    const u32x4 v = *(const u32x4*)(stg + stage16_row(row, c));
+                    if (m0 + row < p.M) *(u32x4*)((ET*)p.xhat16 + (size_t)(m0 + row) * p.ldo + n0 + c * 8) = v;
                 }
-            }
-            if constexpr (TRAINK && LNK) {
-                if (p.xhat16) {                                     // third staged tile: x_hat (same 2-byte staging as out16)
-                    ET* __restrict__ xo = (ET*)p.xhat16;
-                    __syncthreads();
-#pragma unroll
-                    for (int i = 0; i < FR; ++i) {
-                        const int nl = R0 + i * 16 - n0;
-#pragma unroll
-                        for (int j = 0; j < FL; ++j) {
-                            const int row = j * 16 + frow;
-                            *(O16*)(stg + row * 512 + (((nl >> 3) ^ ((row >> 1) & 7)) << 4) + ((nl >> 2) & 1) * 8) = xh16[i][j];
-                        }
-                    }
-                    __syncthreads();
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) {
-                        const int row = (k * 4 + wave) * 2 + (lane >> 5), c = lane & 31;
-                        const u32x4 v = *(const u32x4*)(stg + row * 512 + ((c ^ ((row >> 1) & 7)) << 4));
-                        if (m0 + row < p.M) *(u32x4*)(xo + (size_t)(m0 + row) * p.ldo + n0 + c * 8) = v;
-                    }
-                }
-            }
-        } else
-#pragma unroll
-        for (int i = 0; i < FR; ++i) {
-            const int n = R0 + i * 16;
-            float4 g = make_float4(1, 1, 1, 1), be = make_float4(0, 0, 0, 0);
-            if (LNK && p.gamma) { g = *(const float4*)(p.gamma + n); be = *(const float4*)(p.beta + n); }
-#pragma unroll
-            for (int j = 0; j < FL; ++j) {
-                const int m = L0 + j * 16;
-                if (m >= p.M) continue;
-                const float v0 = (acc[i][j][0] - mean[j]) * scale[j] * g.x + be.x;
-                const float v1 = (acc[i][j][1] - mean[j]) * scale[j] * g.y + be.y;
-                const float v2 = (acc[i][j][2] - mean[j]) * scale[j] * g.z + be.z;
-                const float v3 = (acc[i][j][3] - mean[j]) * scale[j] * g.w + be.w;
-                if (PRENORM) {                             // residual stream stays un-normalised
-                    if (o32) *(float4*)(o32 + (size_t)m * p.ldo + n) = make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
-                } else if (o32) *(float4*)(o32 + (size_t)m * p.ldo + n) = make_float4(v0, v1, v2, v3);
-                if (o16) *(O16*)(o16 + (size_t)m * p.ldo + n) = OutCvt<ET>::cvt(v0, v1, v2, v3);
             }
         }
     } else if constexpr (EPI == EPI_F32_ROWMASK) {

@@ -1,7 +1,9 @@
 """SHA-256 of every output tensor of the weight-stream entries at small fixed-seed shapes that reach each tiling, the phantom-slot
 forms, a ragged last tile, both tile sizes and a second grid round, and of the forward entries that reach the flash and retention tile
 loops (flash_tile.h): resident / tiled / packed / long / training attention, chunk-resident / tiled / fused retention; and of every
-streaming state entry (decode_tile.h, ls_rows.h) with the state it leaves: K/V caches, partials, retention state, conv cache, windows.
+streaming state entry (decode_tile.h, ls_rows.h) with the state it leaves: K/V caches, partials, retention state, conv cache, windows;
+and of every epilogue family of the tiled GEMM (gemm.hip) through its public entries and every launch of the fused FFN family (ffn.hip),
+row statistics, x_hat and column partials included (row_epilogue.h).
 Two builds of the library compute the same bits exactly when their listings are identical:   python tools/stream_hash.py > a.txt;  EEND_HIP_LIB=<other .so> python tools/stream_hash.py > b.txt"""
 import ctypes, hashlib, importlib, math, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -278,3 +280,150 @@ c16, c32 = r(S * nmax, ktap * D).half(), r(S * nmax, ktap * D)
 ops.window_chunk(w16, x, c16, npush, ndummy, ndec, nmax)
 ops.window_chunk_f32(w32, x, c32, npush, ndummy, ndec, nmax)
 show("window_chunk", win16=w16, cols16=c16, win32=w32, cols32=c32)
+
+# ---- the tiled GEMM's epilogue families (gemm.hip, row_epilogue.h) through the public entries.  Rows: just above the skinny routes (17),
+# one tile minus a tail (77), a ragged second tile (130 on the 128-row tile, 70 on the 64-row one); K on both sides of the launcher's
+# straight-line / looped choice.  Weight rows are padded (ldw = K + 8) and N = 384 where packed rows or whole 256-feature groups would send
+# the call to proj.hip; every routed entry asserts the route it is on.  The head-row and Conv1d entries take whole 64-frame slabs.
+call = train._call
+z32 = lambda *s: torch.zeros(*s, device="cuda")
+zb16 = lambda *s: torch.zeros(*s, dtype=torch.bfloat16, device="cuda")
+drop2 = lambda: ((0.0, None), (0.1, ctypes.byref(lib.Dropout(4242, int(round(0.1 * (1 << 24))), 1.0 / 0.9))))
+
+
+def on_tile(entry, want, **f):
+    got = lib.linear_route(entry, **f)
+    assert got in want, (entry, f, got)
+    return got
+
+
+for K in (256, 2048):
+    ldw = K + 8
+    w384, w256 = r(384, ldw, sc=1 / math.sqrt(K)).half(), r(256, ldw, sc=1 / math.sqrt(K)).half()
+    wb384, wb256 = w384.bfloat16(), w256.bfloat16()
+    bias384, bias256, gam, bet = v(384, sc=0.3), v(256, sc=0.3), v(256, 1.0), v(256)
+    tile128 = ("gemm128_straight",) if K == 256 else ("gemm128_looped",)
+    for M in (17, 77, 130):
+        a = r(M, K).half()
+        for act, name in ((ops.ACT_NONE, "none"), (ops.ACT_RELU, "relu"), (ops.ACT_SWISH, "swish")):
+            on_tile("linear_f16", tile128, M=M, N=384, K=K, lda=K, ldw=ldw, ldo=384, act=act)
+            o = z16(M, 384)
+            call("eend_linear_f16", a, K, w384, ldw, bias384, o, 384, M, 384, K, act)
+            show(f"linear_f16 M={M} K={K} {name}", out16=o)
+        on_tile("linear_glu_f16", tile128, M=M, N=384, K=K, lda=K, ldw=ldw, ldo=192)
+        o = z16(M, 192)
+        call("eend_linear_glu_f16", a, K, w384, ldw, bias384, o, 192, M, 384, K)
+        show(f"linear_glu_f16 M={M} K={K}", out16=o)
+        for pdrop, dr in drop2():
+            o = z16(M, 384)
+            call("eend_linear_relu_train_f16", a, K, w384, ldw, bias384, o, 384, M, 384, K, dr)
+            show(f"linear_relu_train M={M} K={K} p={pdrop}", out16=o)
+        ab, act16 = a.bfloat16(), (r(M, 384) * (r(M, 384) > 0)).half()
+        o = zb16(M, 384)
+        call("eend_gemm_bf16", ab, K, wb384, ldw, bias384, o, 384, M, 384, K)
+        show(f"gemm_bf16 M={M} K={K}", out=o)
+        o = zb16(M, 384)
+        call("eend_gemm_relu_bwd_bf16", ab, K, wb384, ldw, act16, 384, o, 384, M, 384, K, 1.0 / 0.9)
+        show(f"gemm_relu_bwd_bf16 M={M} K={K}", out=o)
+    for M in (17, 77, 70):
+        a, res = r(M, K).half(), r(M, 256)
+        f = dict(M=M, N=256, K=K, lda=K, ldw=ldw, ldo=256)
+        for entry, rr in (("linear_res_ln_f16", res), ("linear_res16_ln_f16", res.half())):
+            on_tile(entry, ("gemm64x256",), **f)
+            o32, o16 = z32(M, 256), z16(M, 256)
+            call("eend_" + entry, a, K, w256, ldw, bias256, rr, 0.5, gam, bet, 1e-5, o32, o16, M, K)
+            show(f"{entry} M={M} K={K}", out32=o32, out16=o16)
+        on_tile("linear_res_scale_f16", ("gemm64x256",), **f)
+        o32, o16 = z32(M, 256), z16(M, 256)
+        call("eend_linear_res_scale_f16", a, K, w256, ldw, bias256, res, 0.5, o32, o16, M, K)
+        show(f"linear_res_scale_f16 M={M} K={K}", out32=o32, out16=o16)
+        on_tile("linear_res_scale_ln16_f16", ("gemm64x256",), **f)
+        o32, o16 = z32(M, 256), z16(M, 256)
+        call("eend_linear_res_scale_ln16_f16", a, K, w256, ldw, bias256, res, 0.5, gam, bet, 1e-5, o32, o16, M, K)
+        show(f"linear_res_scale_ln16_f16 M={M} K={K}", out32=o32, out16=o16)
+        for entry in ("eend_linear_res_ln_train_f16", "eend_linear_res_scale_ln_train_f16"):
+            for pdrop, dr in drop2():
+                o32, o16, xh, rs = z32(M, 256), z16(M, 256), z16(M, 256), z32(M)
+                call(entry, a, K, w256, ldw, bias256, res, 0.5, gam, bet, 1e-5, o32, o16, xh, rs, M, K, dr)
+                show(f"{entry[5:]} M={M} K={K} p={pdrop}", out32=o32, out16=o16, xhat16=xh, rstd=rs)
+        ab, gq = a.bfloat16(), r(M, 256, sc=1e-2)
+        o32, o16 = z32(M, 256), zb16(M, 256)
+        call("eend_gemm_acc_bf16", ab, K, wb256, ldw, gq, 1.0, o32, o16, M, K)
+        show(f"gemm_acc_bf16 M={M} K={K}", out32=o32, out=o16)
+        xh, rs = r(M, 256).half(), v(M, 1.0).abs()
+        for pdrop, dr in drop2():
+            nb = (M + 63) // 64
+            ds32, ds16, ws = z32(M, 256), zb16(M, 256), z32(nb * 768)
+            dg, db, dbias = z32(256), z32(256), z32(256)
+            call("eend_gemm_acc_lnbwd_bf16", ab, K, wb256, ldw, gq, xh, rs, gam, ds32, ds16, ws, nb * 768, dg, db, dbias, M, K, dr)
+            show(f"gemm_acc_lnbwd_bf16 M={M} K={K} p={pdrop}", ds32=ds32, ds=ds16, colpart=ws, dgamma=dg, dbeta=db, dbias=dbias)
+    for nseq in (1, 2, 3):                         # head rows: 64, 128 (one tile), 192 rows (a half-filled second tile)
+        Tp, M = 64, nseq * 64
+        a, w768, w1024 = r(M, K).half(), r(768, ldw, sc=1 / math.sqrt(K)).half(), r(1024, ldw, sc=1 / math.sqrt(K)).half()
+        on_tile("inproj_heads_bf16", tile128, nseq=nseq, Tp=Tp, H=4, dh=64, K=K, lda=K, ldw=ldw)
+        q, k, vt = (zb16(M * 256) for _ in range(3))
+        call("eend_inproj_heads_bf16", a, K, w768, ldw, v(768, sc=0.3), q, k, vt, nseq, Tp, 4, 64, K)
+        show(f"inproj_heads_bf16 nseq={nseq} K={K}", q=q, k=k, vt=vt)
+        on_tile("retention_proj_f16", tile128, nseq=nseq, Tp=Tp, H=4, dh=64, K=K, lda=K, ldw=ldw)
+        q, k, kt, vt, gg = (z16(M * 256) for _ in range(5))
+        call("eend_retention_proj_f16", a, K, w1024, ldw, v(1024, sc=0.3), q, k, kt, vt, gg, nseq, Tp, 4, 64, K)
+        show(f"retention_proj_f16 nseq={nseq} K={K}", q=q, k=k, kt=kt, vt=vt, g=gg)
+for nseq, lens in ((1, (64,)), (3, (64, 17, 1))):  # the implicit-GEMM loads: Conv1d + L2 norm, its training form, the Conv1d data gradient
+    Tp, ktaps, pad = 64, 3, 1
+    x, wr, bias, il = r(nseq * Tp, 256).half(), r(256, ktaps * 256, sc=1 / 28).half(), v(256), i32(*lens)
+    o32, o16 = z32(nseq * Tp, 256), z16(nseq * Tp, 256)
+    call("eend_conv1d_l2norm_f16", x, wr, bias, il, o32, o16, nseq, Tp, 256, ktaps, pad)
+    show(f"conv1d_l2norm_f16 nseq={nseq}", out32=o32, out16=o16)
+    o32, o16, inv = z32(nseq * Tp, 256), z16(nseq * Tp, 256), z32(nseq * Tp)
+    call("eend_conv1d_l2norm_train_f16", x, wr, bias, il, o32, o16, inv, nseq, Tp, 256, ktaps, pad)
+    show(f"conv1d_l2norm_train_f16 nseq={nseq}", out32=o32, out16=o16, inv_norm=inv)
+    o32 = z32(nseq * Tp, 256)
+    call("eend_conv1d_dgrad_bf16", x.bfloat16(), wr.bfloat16(), il, il, o32, nseq, Tp, 256, ktaps, pad)
+    show(f"conv1d_dgrad_bf16 nseq={nseq}", out32=o32)
+for Bc, Tp, C in ((1, 17, 33), (2, 35, 33)):       # more than 32 slots: the fan-out stays on the GEMM tile (17 rows, 70 rows)
+    on_tile("convert_fanout_f16", ("gemm64x256",), nseq=Bc, Tp=Tp, C=C)
+    e, w1c, pc = r(Bc * Tp, 256).half(), r(256, 256, sc=1 / 16).half(), r(C, 256, sc=0.3)
+    for with32 in (True, False):
+        o32, o16 = z32(Bc * C * Tp, 256) if with32 else None, z16(Bc * C * Tp, 256)
+        call("eend_convert_fanout_f16", e, w1c, pc, o32, o16, Bc, Tp, C)
+        show(f"convert_fanout_f16 B={Bc} Tp={Tp} C={C} out32={int(with32)}", out16=o16, **({"out32": o32} if with32 else {}))
+
+# ---- every launch of the fused FFN family (ffn.hip): a tile with a tail, a few tiles, and (F = 64) one row tile past a full grid round
+ncu = torch.cuda.get_device_properties(0).multi_processor_count
+for Fh in (64, 1024):
+    w1, w2, b1 = r(Fh, 256, sc=0.08).half(), r(256, Fh, sc=1 / math.sqrt(Fh)).half(), v(Fh, sc=0.3)
+    w2t, w1t = w2.t().contiguous().bfloat16(), w1.t().contiguous().bfloat16()
+    for M in (77, 300) + ((ncu * 128 + 77,) if Fh == 64 else ()):
+        x, a, res = r(M, 256).half(), r(M, 256).half(), r(M, 256)
+        for act, name in ((ops.ACT_RELU, "relu"), (ops.ACT_SWISH, "swish")):
+            for unnorm in (False, True):
+                o32, o16 = z32(M, 256), z16(M, 256)
+                ops.ffn_fused(x, w1, b1, w2, b2, res, g22, be22, o32, o16, act=act, alpha=0.5, residual_unnormalised=unnorm)
+                show(f"ffn_fused M={M} F={Fh} {name} unnormalised={int(unnorm)}", out32=o32, out16=o16)
+        for wl in (None, wo_lo):
+            for with_lo in (False, True):
+                o32, o16, lo = z32(M, 256), z16(M, 256), z16(M, 256) if with_lo else None
+                ops.attnout_ffn_fused(a, wo2, bo2, res, g21, be21, 1e-5, w1, b1, w2, b2, g22, be22, 1e-5, o32, o16, out16lo=lo, wo_lo=wl)
+                show(f"attnout_ffn_fused M={M} F={Fh} wo_lo={int(wl is not None)} lo={int(with_lo)}", out32=o32, out16=o16, **({"out16lo": lo} if with_lo else {}))
+        o16 = z16(M, 256)
+        ops.attnout_ffn_fused(a, wo2, bo2, res, g21, be21, 1e-5, w1, b1, w2, b2, g22, be22, 1e-5, None, o16)
+        show(f"attnout_ffn_fused M={M} F={Fh} out32=NULL", out16=o16)
+        o32, o16 = z32(M, 256), z16(M, 256)
+        ops.attnout_ffn_fused_res16(a, wo2, bo2, res.half(), g21, be21, 1e-5, w1, b1, w2, b2, g22, be22, 1e-5, o32, o16)
+        show(f"attnout_ffn_fused_res16 M={M} F={Fh}", out32=o32, out16=o16)
+        for pdrop in (0.0, 0.1):
+            if pdrop > 0:
+                s1, s2 = lib.Dropout(12345, int(round(pdrop * (1 << 24))), 1.0 / (1.0 - pdrop)), lib.Dropout(54321, int(round(pdrop * (1 << 24))), 1.0 / (1.0 - pdrop))
+                r1, r2 = ctypes.byref(s1), ctypes.byref(s2)
+            else:
+                r1 = r2 = None
+            o32, o16, hid, xh, rs = z32(M, 256), z16(M, 256), z16(M, Fh), z16(M, 256), z32(M)
+            call("eend_ffn_train_f16", x, 256, w1, b1, w2, b2, res, 1.0, g22, be22, 1e-5, o32, o16, hid, xh, rs, M, Fh, r1, r2)
+            show(f"ffn_train M={M} F={Fh} p={pdrop}", out32=o32, out16=o16, hid=hid, xhat16=xh, rstd=rs)
+            for unnorm in (0, 1):
+                o32, o16, zz, aa, xh, rs = z32(M, 256), z16(M, 256), z16(M, Fh), z16(M, Fh), z16(M, 256), z32(M)
+                call("eend_ffn_swish_train_f16", x, 256, w1, b1, w2, b2, res, 0.5, g22, be22, 1e-5, o32, o16, zz, aa, xh, rs, M, Fh, unnorm, r1, r2)
+                show(f"ffn_swish_train M={M} F={Fh} p={pdrop} unnormalised={unnorm}", out32=o32, out16=o16, z=zz, a=aa, xhat16=xh, rstd=rs)
+        dy, g32, dh = r(M, 256, sc=1e-2).bfloat16(), r(M, 256, sc=1e-2), zb16(M, Fh)
+        call("eend_ffn_bwd_data_bf16", dy, 256, w2t, hid, w1t, 1.0 / 0.9, dh, g32, M, Fh)      # the mask: the dropout forward's hidden rows
+        show(f"ffn_bwd_data M={M} F={Fh}", dH=dh, g=g32)
