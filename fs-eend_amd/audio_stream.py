@@ -289,6 +289,10 @@ class AudioStreamSession:
 
     def __init__(self, session, input_transform=None, context_size: int = 7, subsampling: int = 10):
         self.ses, self.C = session, session.C
+        if getattr(session, "sad", False):
+            raise ValueError("AudioStreamSession over a SegmentSession with sad=True: the session wants one speech-activity flag "
+                             "per model frame, and this wrapper cuts audio into frames itself, so a sample-rate mask has no way "
+                             "through it yet; push features and flags to the SegmentSession directly")
         if input_transform is None:
             input_transform = session.input_transform
         self.fe = AudioFrontEnd(session.S, input_transform, context_size, subsampling, device=session.dev)

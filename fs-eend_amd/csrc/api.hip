@@ -473,6 +473,17 @@ int eend_segtrack_feed_f32(const long* desc, const int* counts, const int* ends,
                                 (hipStream_t)stream);
 }
 
+int eend_sad_fuse_f32(const float* pred, int ld, int T, int S, float threshold, const unsigned char* sad, float* out, void* stream) {
+    return eend_launch_sad_fuse(pred, ld, T, S, threshold, sad, out, (hipStream_t)stream);
+}
+
+int eend_segtrack_feed_sad_f32(const long* desc, const int* counts, const int* ends, const long* sad_desc, int n, int ld, int col0,
+                               int ntracks, float threshold, int median, int is_prob, unsigned long long* hist, int* open, int* box,
+                               int slots, int cap, void* stream) {
+    return eend_launch_segtrack_sad(desc, counts, ends, sad_desc, n, ld, col0, ntracks, threshold, median, is_prob, hist, open, box,
+                                    slots, cap, (hipStream_t)stream);
+}
+
 int eend_der_counters_u64(const float* pred, int ldp, const float* label, int ldl, int T, int C, int label_delay,
                           unsigned long long* counters, void* stream) {
     return eend_launch_der_counters(pred, ldp, label, ldl, T, C, label_delay, counters, (hipStream_t)stream);

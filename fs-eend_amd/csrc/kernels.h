@@ -95,11 +95,15 @@ int eend_launch_emb_consistency(const float* emb, const float* tgt, const int* l
                                 int B, int T, int Tp, int D, int C, hipStream_t stream);
 
 int eend_launch_activity_median(const float* pred, int ld, int T, int S, float thr, int k, unsigned char* out, hipStream_t stream);
+int eend_launch_sad_fuse(const float* pred, int ld, int T, int S, float thr, const unsigned char* sad, float* out, hipStream_t stream);
 int eend_launch_segments(const unsigned char* act, int T, int S, int* changes, int* counts, int cap, hipStream_t stream);
 // live segments (segtrack.hip): per-slot header {frames, count, overflow, 0} in front of the ring of closed segments
 #define SEGTRACK_HDR 4
 int eend_launch_segtrack(const long* desc, const int* counts, const int* ends, int n, int ld, int col0, int ntracks, float thr, int k,
                          int is_prob, unsigned long long* hist, int* open, int* box, int S, int cap, hipStream_t stream);
+int eend_launch_segtrack_sad(const long* desc, const int* counts, const int* ends, const long* sad_desc, int n, int ld, int col0,
+                             int ntracks, float thr, int k, int is_prob, unsigned long long* hist, int* open, int* box, int S, int cap,
+                             hipStream_t stream);
 int eend_launch_der_counters(const float* pred, int ldp, const float* label, int ldl, int T, int C, int delay,
                              unsigned long long* counters, hipStream_t stream);
 

@@ -25,6 +25,34 @@ void activity_median_kernel(const float* __restrict__ pred, int ld, int T, int S
     out[idx] = cnt >= h + 1 ? 1 : 0;
 }
 
+// External speech-activity mask (LS-EEND/sad_post_process.py:23-33): row t keeps its decisions pred > thr only where the mask
+// calls it speech, and a speech row in which nobody passed the threshold gets its largest posterior (lowest index on ties, as
+// torch.argmax; NaN is never active and never wins).  One thread per row; out f32 (T, S) of 0 / 1, which
+// activity_median_kernel reads with threshold 0.5.
+__global__ __launch_bounds__(256)
+void sad_fuse_kernel(const float* __restrict__ pred, int ld, int T, int S, float thr, const unsigned char* __restrict__ sad,
+                     float* __restrict__ out) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= T) return;
+    const float* __restrict__ p = pred + t * ld;
+    float* __restrict__ o = out + t * S;
+    const bool g = sad[t] != 0;
+    bool any = false;
+    int best = -1;
+    float top = 0.f;
+    for (int s = 0; s < S; ++s) {
+        const float v = p[s];
+        const bool d = g && v > thr;
+        any |= d;
+        o[s] = d ? 1.0f : 0.0f;
+        if (v == v && (best < 0 || v > top)) {
+            best = s;
+            top = v;
+        }
+    }
+    if (g && !any && best >= 0) o[best] = 1.0f;
+}
+
 // one wave per speaker: indices i in [0, T] where the zero-padded track changes (padded[i+1] != padded[i]),
 // in increasing order (ballot + prefix popcount compaction); even entries are segment starts, odd ones ends.
 __global__ __launch_bounds__(64)
@@ -92,6 +120,12 @@ int eend_launch_activity_median(const float* pred, int ld, int T, int S, float t
     if (!pred || !out || T <= 0 || S <= 0 || ld < S || k < 1 || (k & 1) == 0 || k > 255) return EEND_EINVAL;
     const long n = (long)T * S;
     hipLaunchKernelGGL(activity_median_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, pred, ld, T, S, thr, k, out);
+    return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
+}
+
+int eend_launch_sad_fuse(const float* pred, int ld, int T, int S, float thr, const unsigned char* sad, float* out, hipStream_t stream) {
+    if (!pred || !sad || !out || T <= 0 || S <= 0 || ld < S) return EEND_EINVAL;
+    hipLaunchKernelGGL(sad_fuse_kernel, dim3((unsigned)(((long)T + 255) / 256)), dim3(256), 0, stream, pred, ld, T, S, thr, sad, out);
     return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
 }
 

@@ -5,6 +5,9 @@
 // the open segment (-1: none, which is also the last finalised filtered decision); per slot a header {frames, count, overflow}
 // and a ring of closed segments {track, start, end}.  Every feed of a stream with its end flag set therefore yields exactly
 // the segments of make_rttm over the concatenated rows, however the rows were cut.
+// The SAD instantiation gates the raw decisions with an external speech-activity mask (one uint8 flag per row), as
+// sad_fuse_kernel of postproc.hip does for a whole file: a non-speech row is cleared, a speech row in which no track passed the
+// threshold gets the track with the largest value.  Everything behind the raw decision bit is shared.
 #include "common.h"
 #include "kernels.h"
 
@@ -14,10 +17,12 @@ constexpr int kBatch = 16;       // rows whose loads / decisions are issued toge
 
 // frames == 0 means "empty stream": the slot's words are not read (a reopened slot computes what a fresh one does).
 // One wave per descriptor entry, lane = track.  desc i64 [n][2] = {address of the entry's first row, slot}.
+// SAD: sad_desc i64 [n] = address of the entry's counts[e] flags, read only for the rows the entry brings.
+template <bool SAD>
 __global__ __launch_bounds__(64)
-void segtrack_kernel(const long* __restrict__ desc, const int* __restrict__ counts, const int* __restrict__ ends, int ld, int col0,
-                     int ntracks, float thr, int k, int is_prob, unsigned long long* __restrict__ hist_all, int* __restrict__ open_all,
-                     int* __restrict__ box, int S, int cap) {
+void segtrack_kernel(const long* __restrict__ desc, const int* __restrict__ counts, const int* __restrict__ ends,
+                     const long* __restrict__ sad_desc, int ld, int col0, int ntracks, float thr, int k, int is_prob,
+                     unsigned long long* __restrict__ hist_all, int* __restrict__ open_all, int* __restrict__ box, int S, int cap) {
     const int lane = threadIdx.x;
     const int e = blockIdx.x;
     const int slot = (int)desc[2 * e + 1];
@@ -36,6 +41,10 @@ void segtrack_kernel(const long* __restrict__ desc, const int* __restrict__ coun
     unsigned long long hist = n0 > 0 ? hist_all[(size_t)slot * 64 + lane] : 0ull;
     int st = n0 > 0 ? open_all[(size_t)slot * 64 + lane] : -1;
     const unsigned long long lt = (1ull << lane) - 1ull;
+    const unsigned char* __restrict__ flags = nullptr;
+    if constexpr (SAD) {
+        if (cnt > 0) flags = (const unsigned char*)sad_desc[e];
+    }
 
     // filtered decision f of frame u (final): a segment opens at u or the open one closes at u (exclusive end); closes are
     // appended in track order (ballot + prefix popcount), so the ring is ordered by end frame, then track.
@@ -62,9 +71,31 @@ void segtrack_kernel(const long* __restrict__ desc, const int* __restrict__ coun
 #pragma unroll
         for (int i = 0; i < kBatch; ++i) {
             const int j = j0 + i;
-            if (on && j < cnt) {
-                const float v = x[(size_t)j * ld + col0 + lane];
-                const bool d = is_prob ? v > thr : 1.0f / (1.0f + expf(-v)) > thr;     // NaN: inactive
+            if constexpr (!SAD) {
+                if (on && j < cnt) {
+                    const float v = x[(size_t)j * ld + col0 + lane];
+                    const bool d = is_prob ? v > thr : 1.0f / (1.0f + expf(-v)) > thr; // NaN: inactive
+                    dec |= (unsigned)d << i;
+                }
+            } else {
+                float v = 0.f;
+                bool d = false;
+                if (on && j < cnt) {
+                    v = x[(size_t)j * ld + col0 + lane];
+                    d = is_prob ? v > thr : 1.0f / (1.0f + expf(-v)) > thr;
+                }
+                if (j < cnt) {                                                         // wave-uniform, as is the row's flag
+                    if (__builtin_amdgcn_readfirstlane((int)flags[j]) == 0) {
+                        d = false;
+                    } else if (__builtin_amdgcn_ballot_w64(d) == 0ull) {               // speech, nobody active: the largest value
+                        const bool cand = on && j < cnt && v == v;                     // (raw logits order as their sigmoids do)
+                        float top = cand ? v : -INFINITY;
+#pragma unroll
+                        for (int m = 1; m < 64; m <<= 1) top = fmaxf(top, __shfl_xor(top, m, 64));
+                        const unsigned long long w = __builtin_amdgcn_ballot_w64(cand && v == top);
+                        d = w != 0ull && lane == __builtin_ctzll(w);                   // ties: the lowest track, as torch.argmax
+                    }
+                }
                 dec |= (unsigned)d << i;
             }
         }
@@ -99,13 +130,27 @@ void segtrack_kernel(const long* __restrict__ desc, const int* __restrict__ coun
 
 }  // namespace
 
-int eend_launch_segtrack(const long* desc, const int* counts, const int* ends, int n, int ld, int col0, int ntracks, float thr, int k,
-                         int is_prob, unsigned long long* hist, int* open, int* box, int S, int cap, hipStream_t stream) {
+template <bool SAD>
+static int launch_segtrack(const long* desc, const int* counts, const int* ends, const long* sad_desc, int n, int ld, int col0,
+                           int ntracks, float thr, int k, int is_prob, unsigned long long* hist, int* open, int* box, int S, int cap,
+                           hipStream_t stream) {
     if (!desc || !counts || !hist || !open || !box || n < 0 || n > S || S <= 0 || cap <= 0 || ntracks < 1 || ntracks > 64 ||
         col0 < 0 || ld < col0 + ntracks || k < 1 || k > 63 || (k & 1) == 0 || (long)S * (SEGTRACK_HDR + 3L * cap) > 0x7fffffffL)
         return EEND_EINVAL;
     if (n == 0) return EEND_OK;
-    hipLaunchKernelGGL(segtrack_kernel, dim3(n), dim3(64), 0, stream, desc, counts, ends, ld, col0, ntracks, thr, k, is_prob, hist, open,
-                       box, S, cap);
+    hipLaunchKernelGGL(segtrack_kernel<SAD>, dim3(n), dim3(64), 0, stream, desc, counts, ends, sad_desc, ld, col0, ntracks, thr, k,
+                       is_prob, hist, open, box, S, cap);
     return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
+}
+
+int eend_launch_segtrack(const long* desc, const int* counts, const int* ends, int n, int ld, int col0, int ntracks, float thr, int k,
+                         int is_prob, unsigned long long* hist, int* open, int* box, int S, int cap, hipStream_t stream) {
+    return launch_segtrack<false>(desc, counts, ends, nullptr, n, ld, col0, ntracks, thr, k, is_prob, hist, open, box, S, cap, stream);
+}
+
+int eend_launch_segtrack_sad(const long* desc, const int* counts, const int* ends, const long* sad_desc, int n, int ld, int col0,
+                             int ntracks, float thr, int k, int is_prob, unsigned long long* hist, int* open, int* box, int S, int cap,
+                             hipStream_t stream) {
+    if (!sad_desc) return EEND_EINVAL;
+    return launch_segtrack<true>(desc, counts, ends, sad_desc, n, ld, col0, ntracks, thr, k, is_prob, hist, open, box, S, cap, stream);
 }

@@ -75,6 +75,8 @@ PROTOTYPES = {
     "eend_feature_meannorm_f32": [_vp, _vp, _i, _i, _i, _vp],
     "eend_splice_subsample_f32": [_vp, _i, _i, _i, _i, _vp, _vp],
     "eend_segtrack_feed_f32": [_vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _i, _i, _vp],
+    "eend_sad_fuse_f32": [_vp, _i, _i, _i, _f, _vp, _vp, _vp],
+    "eend_segtrack_feed_sad_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _i, _i, _vp],
     "eend_audio_feed_f32": [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp],
     "eend_pit_cost_f64": [_vp, _vp, _i, _i, _i, _vp, _vp],
     "eend_pit_assign_i32": [_vp, _vp, _i, _i, _vp, _vp, _vp],

@@ -11,6 +11,11 @@ over the concatenated rows, however the rows were cut and whatever the other slo
 
 One `feed` is one launch (and one small descriptor copy for the ragged form); `feed_rows` reads the per-slot row counts from
 device memory, so a session's own decoder-append mask drives it with no host work.  `poll` is one device-to-host copy.
+
+With `sad=True` the raw decisions are first fused with an external speech-activity mask, one flag per row, as
+`postproc.sad_func` / `make_rttm(sad=)` do for a whole file (LS-EEND/sad_post_process.py:23-33): rows the mask calls non-speech
+are cleared, and a speech row in which no track passed the threshold gets the track with the largest value.  The flags of a
+`feed` travel in its descriptor block; a `SegmentSession` keeps, per slot, the flags of the frames pushed but not yet emitted.
 """
 
 import torch
@@ -20,7 +25,7 @@ from . import ops
 from .multistream import SlotError, check_parts
 from .postproc import rttm_lines
 
-F32, I32, I64 = torch.float32, torch.int32, torch.int64
+F32, I32, I64, U8 = torch.float32, torch.int32, torch.int64, torch.uint8
 HDR = ops.SEGTRACK_HDR                          # box row: frames, count, overflow, 0, then cap x (track, start, end)
 MAX_MEDIAN, MAX_TRACKS = 63, 64
 
@@ -39,6 +44,84 @@ def check_params(ntracks, col0, threshold, median, capacity):
         raise ValueError(f"capacity must be a positive int, got {capacity!r}")
     if not isinstance(threshold, (int, float)) or threshold != threshold:
         raise ValueError(f"threshold must be a number, got {threshold!r}")
+
+
+def host_flags(flags, n, what):
+    """Speech-activity flags given as a host sequence, a scalar (n = 1) or a tensor -> a list of n ints 0 / 1 (non-zero:
+    speech); SlotError when there are not exactly n."""
+    if torch.is_tensor(flags):
+        flags = flags.reshape(-1).tolist()
+    elif isinstance(flags, (bool, int, float)):
+        flags = [flags]
+    try:
+        out = [1 if f != 0 else 0 for f in flags]
+    except TypeError:
+        raise SlotError(f"{what}: expected {n} speech-activity flag(s), got {flags!r}") from None
+    if len(out) != n:
+        raise SlotError(f"{what}: {n} row(s) need {n} speech-activity flag(s), got {len(out)}")
+    return out
+
+
+def tracker_config(ntracks, col0, threshold, median, is_prob, capacity, sad=False):
+    """The "config" of a tracker's snapshot part.  A plain tracker's keeps the keys it always had, so parts saved before the
+    speech-activity mask existed still fit; a tracker with the mask adds "sad": True, and neither resumes the other's."""
+    cfg = {"ntracks": ntracks, "col0": col0, "threshold": threshold, "median": median, "is_prob": is_prob, "capacity": capacity}
+    if sad:
+        cfg["sad"] = True
+    return cfg
+
+
+class FlagFifo:
+    """Host side of a SegmentSession with a speech-activity mask (pure Python, no device): per slot, the flags of the frames
+    pushed whose output rows the session has not emitted yet, oldest first.  `check` validates a step's flags without changing
+    anything; `push` and `pop` run after the wrapped step has."""
+
+    def __init__(self, slots):
+        self.S = slots
+        self.q = [[] for _ in range(slots)]
+
+    def clear(self, s):
+        self.q[s] = []
+
+    def check(self, frames, sad):
+        """frames: {slot: frames it pushes in this step}, sad: {slot: their flags} -> {slot: flags as a list of 0 / 1}.
+        SlotError unless every slot that pushes frames has one flag per frame and no other slot has any."""
+        sad = dict(sad or {})
+        extra = sorted(s for s in sad if s not in frames)
+        if extra:
+            raise SlotError(f"speech-activity flags for slot(s) {extra}, which bring no frames in this call")
+        out = {}
+        for s, n in frames.items():
+            if s not in sad:
+                if n:
+                    raise SlotError(f"slot {s}: {n} frame(s) without speech-activity flags")
+                continue
+            out[s] = host_flags(sad[s], n, f"slot {s}")
+        return out
+
+    def push(self, flags):
+        for s, f in flags.items():
+            self.q[s] += f
+
+    def pop(self, emitted):
+        """emitted: {slot: rows it emitted} -> {slot: the flags of those rows}, which leave the queue."""
+        for s, m in emitted.items():
+            assert len(self.q[s]) >= m, f"slot {s} emitted {m} row(s) with {len(self.q[s])} flag(s) waiting"
+        out = {}
+        for s, m in emitted.items():
+            out[s] = self.q[s][:m]
+            del self.q[s][:m]
+        return out
+
+    def export(self, s):
+        return list(self.q[s])
+
+    @staticmethod
+    def fits(v):
+        return isinstance(v, (list, tuple)) and all(isinstance(f, int) and f in (0, 1) for f in v)
+
+    def adopt(self, s, v):
+        self.q[s] = [int(f) for f in v]
 
 
 class SegmentLog:
@@ -144,11 +227,18 @@ class SegmentTracker:
         tr.rttm(s, "rec")                              # make_rttm's dict of every line of the stream so far
 
     Slots start open and empty.  `threshold` and `is_prob` follow make_rttm(rec, sigmoid(L[:, col0:col0 + ntracks])):
-    logits are thresholded as torch.sigmoid(x) > threshold, probabilities (is_prob) as x > threshold."""
+    logits are thresholded as torch.sigmoid(x) > threshold, probabilities (is_prob) as x > threshold.
+
+    With sad=True every row comes with a flag of an external speech-activity mask (non-zero: speech), and the stream's segments
+    are those of make_rttm(..., sad=flags): `feed(rows, end, sad={slot: flags})`, one flag per row of every slot that brings
+    rows (a host sequence or a tensor), or `feed_rows(..., sad=flags_dev)`.  In logits mode the largest value of a row is taken
+    over the raw logits of the tracked columns."""
 
     def __init__(self, slots: int, ntracks: int, col0: int = 1, threshold: float = 0.5, median: int = 11, capacity: int = 256,
-                 is_prob: bool = False, device=None):
+                 is_prob: bool = False, device=None, sad: bool = False):
         check_params(ntracks, col0, threshold, median, capacity)
+        self.sad = bool(sad)
+        self.fifo = FlagFifo(slots) if self.sad else None               # a SegmentSession's flags pushed but not yet emitted
         self.log = SegmentLog(slots, ntracks, capacity)
         self.S, self.ntracks, self.col0, self.cap = slots, ntracks, col0, capacity
         self.threshold, self.median, self.is_prob = float(threshold), median, bool(is_prob)
@@ -159,6 +249,7 @@ class SegmentTracker:
         self.open_ = torch.full((slots, 64), -1, dtype=I32, device=self.dev)
         self.box = torch.zeros(slots, HDR + 3 * capacity, dtype=I32, device=self.dev)
         self._rows = None                       # (data_ptr, ld, desc) of the last feed_rows matrix
+        self._sad_rows = None                   # (data_ptr, rows_per_slot, desc) of the last feed_rows flags
 
     @property
     def lookahead(self) -> int:
@@ -170,25 +261,30 @@ class SegmentTracker:
         """Start an empty stream in slot s (any state); its unpolled segments are dropped."""
         self.log.reset(s)
         self.box[s, :3] = 0
+        if self.sad:
+            self.fifo.clear(s)
 
     def close(self, s: int):
         """Drop slot s's stream: its device state, its unpolled segments and the lines collected so far."""
         self.log.close(s)
         self.box[s, :3] = 0
+        if self.sad:
+            self.fifo.clear(s)
 
     def state(self, s: int) -> str:
         return self.log.state[s]
 
     # ---- a slot's stream leaves / comes back (the "tracker" part of a multistream.StreamSnapshot)
     def _config(self):
-        return {"ntracks": self.ntracks, "col0": self.col0, "threshold": self.threshold, "median": self.median,
-                "is_prob": self.is_prob, "capacity": self.cap}
+        return tracker_config(self.ntracks, self.col0, self.threshold, self.median, self.is_prob, self.cap, self.sad)
 
     def export(self, s: int) -> dict:
         """Slot s's tracker state as plain values and tensors: its device rows (copies; the segments no poll has taken yet
-        travel in the box row) and its host fields."""
+        travel in the box row) and its host fields; with sad, also the flags pushed but not yet emitted ("fifo")."""
         part = self.log.export(s)
         part.update(config=self._config(), hist=self.hist[s].clone(), open=self.open_[s].clone(), box=self.box[s].clone())
+        if self.sad:
+            part["fifo"] = self.fifo.export(s)
         return part
 
     def check_part(self, part):
@@ -197,6 +293,8 @@ class SegmentTracker:
               and all(isinstance(part.get(k), (list, tuple)) for k in ("segs", "pending"))
               and all(torch.is_tensor(part.get(k)) and part[k].shape == row.shape[1:] and part[k].dtype == row.dtype
                       for k, row in (("hist", self.hist), ("open", self.open_), ("box", self.box))))
+        if ok and self.sad:
+            ok = FlagFifo.fits(part.get("fifo"))
         if not ok:
             raise SlotError("resume: the snapshot's tracker part does not fit this tracker "
                             f"(here {self._config()}, there {part.get('config') if isinstance(part, dict) else part!r})")
@@ -206,11 +304,21 @@ class SegmentTracker:
         self.log.adopt(s, part)
         for k, rows in (("hist", self.hist), ("open", self.open_), ("box", self.box)):
             rows[s].copy_(part[k], non_blocking=True)
+        if self.sad:
+            self.fifo.adopt(s, part["fifo"])
 
     # ---- feeding
-    def _launch(self, desc, counts, ends, n, ld):
+    def _launch(self, desc, counts, ends, n, ld, sad_desc=None):
         ops.segtrack_feed(desc, counts, ends, n, ld, self.col0, self.ntracks, self.threshold, self.median, self.is_prob, self.hist,
-                          self.open_, self.box, self.cap)
+                          self.open_, self.box, self.cap, sad_desc)
+
+    def _check_sad(self, rows, sad):
+        """The flags of a feed: {slot: n flags as a list} for every slot that brings n > 0 rows; SlotError otherwise."""
+        if not self.sad:
+            if sad is not None:
+                raise SlotError("speech-activity flags given to a tracker built without sad=True")
+            return None
+        return self.fifo.check({s: x.shape[0] for s, x in rows.items()}, sad)
 
     def _rows_f32(self, s, x):
         if not isinstance(x, torch.Tensor) or not x.is_cuda:
@@ -222,12 +330,14 @@ class SegmentTracker:
         return x.to(F32).contiguous()
 
     @torch.no_grad()
-    def feed(self, rows=None, end=()):
+    def feed(self, rows=None, end=(), sad=None):
         """rows: {slot: (n, C) device tensor of its next rows}; end: slots whose stream ends after these rows.  Every tensor of a
-        call has the same C >= col0 + ntracks.  One descriptor copy, one launch; nothing waits for the device."""
+        call has the same C >= col0 + ntracks.  One descriptor copy, one launch; nothing waits for the device.  A tracker built
+        with sad=True also takes sad: {slot: n flags} for every slot that brings rows; they travel in the descriptor block."""
         rows = {s: self._rows_f32(s, x) for s, x in dict(rows or {}).items()}
         end = list(end)
         self.log.check_feed(rows.keys(), end)
+        sad = self._check_sad(rows, sad)
         slots = sorted(set(rows) | set(end))
         if not slots:
             return
@@ -239,6 +349,9 @@ class SegmentTracker:
         ld = next(iter(cols)) if cols else self.col0 + self.ntracks
         n = len(slots)
         desc = [[rows[s].data_ptr() if s in rows and rows[s].shape[0] else self.box.data_ptr(), s] for s in slots]
+        if self.sad:
+            self._feed_sad(rows, end, sad, slots, desc, ld)
+            return
         stage = torch.empty(4 * n + 2 * n, dtype=I32, pin_memory=True)   # a fresh pinned block per call (copied asynchronously)
         stage[:4 * n].view(I64).copy_(torch.tensor(desc, dtype=I64).reshape(-1))
         stage[4 * n:5 * n].copy_(torch.tensor([rows[s].shape[0] if s in rows else 0 for s in slots], dtype=I32))
@@ -248,15 +361,43 @@ class SegmentTracker:
         self._launch(dbuf[:4 * n].view(I64), dbuf[4 * n:5 * n], dbuf[5 * n:], n, ld)
         self.log.ended(end)
 
+    def _feed_sad(self, rows, end, sad, slots, desc, ld):
+        """feed's block with the flags behind it: int32 words [desc 4n | flag addresses 2n | counts n | ends n | flags, one byte
+        per row, each slot's run after the other].  Still one copy and one launch."""
+        n = len(slots)
+        flags, off = [], []
+        for s in slots:
+            off.append(len(flags))
+            flags += sad.get(s, [])
+        words = 8 * n + (len(flags) + 3) // 4
+        dbuf = torch.empty(words, dtype=I32, device=self.dev)
+        base = dbuf.data_ptr() + 32 * n
+        stage = torch.zeros(words, dtype=I32, pin_memory=True)
+        stage[:4 * n].view(I64).copy_(torch.tensor(desc, dtype=I64).reshape(-1))
+        stage[4 * n:6 * n].view(I64).copy_(torch.tensor([base + o for o in off], dtype=I64))
+        stage[6 * n:7 * n].copy_(torch.tensor([rows[s].shape[0] if s in rows else 0 for s in slots], dtype=I32))
+        stage[7 * n:8 * n].copy_(torch.tensor([1 if s in end else 0 for s in slots], dtype=I32))
+        if flags:
+            stage[8 * n:].view(U8)[:len(flags)].copy_(torch.tensor(flags, dtype=U8))
+        dbuf.copy_(stage, non_blocking=True)
+        self._launch(dbuf[:4 * n].view(I64), dbuf[6 * n:7 * n], dbuf[7 * n:8 * n], n, ld, dbuf[4 * n:6 * n].view(I64))
+        self.log.ended(end)
+
     @torch.no_grad()
-    def feed_rows(self, x, counts_dev, rows_per_slot=1):
+    def feed_rows(self, x, counts_dev, rows_per_slot=1, sad=None):
         """The session form: row s of x ((S, C) or (S, 1, C) f32 device tensor, rows contiguous) is slot s's next row when
         counts_dev[s] (device int32 [S]) is 1.  With rows_per_slot = n, x is (S, n, C) and slot s takes its first counts_dev[s]
-        (0..n) rows.  No host data, one launch; the host does not check slot states here."""
+        (0..n) rows.  No host data, one launch; the host does not check slot states here.  A tracker built with sad=True also
+        takes sad: a contiguous uint8 (S, rows_per_slot) device tensor, the flag of row j of slot s at [s, j]."""
         if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != F32 or not x.is_contiguous():
             raise _lib.EendHipError("feed_rows: expected a contiguous f32 GPU tensor")
         if not isinstance(rows_per_slot, int) or rows_per_slot < 1:
             raise ValueError(f"feed_rows: rows_per_slot must be a positive int, got {rows_per_slot!r}")
+        if self.sad != (sad is not None):
+            raise SlotError("feed_rows: speech-activity flags go with a tracker built with sad=True, and only with it")
+        if self.sad and (not isinstance(sad, torch.Tensor) or not sad.is_cuda or sad.dtype != U8 or not sad.is_contiguous()
+                         or sad.numel() != self.S * rows_per_slot):
+            raise SlotError(f"feed_rows: sad must be a contiguous uint8 GPU tensor of {self.S} x {rows_per_slot} flags")
         x2 = x.reshape(x.shape[0] * rows_per_slot, -1) if x.shape[0] == self.S else x.reshape(x.shape[0], -1)
         if x2.shape[0] != self.S * rows_per_slot:
             raise ValueError(f"feed_rows: {rows_per_slot} row(s) per slot ({self.S}), got {x2.shape[0]}")
@@ -267,6 +408,12 @@ class SegmentTracker:
         if self._rows is None or self._rows[0] != key:
             desc = torch.tensor([[key[0] + 4 * rows_per_slot * ld * s, s] for s in range(self.S)], dtype=I64).to(self.dev)
             self._rows = (key, desc)
+        if self.sad:
+            skey = (sad.data_ptr(), rows_per_slot)
+            if self._sad_rows is None or self._sad_rows[0] != skey:
+                self._sad_rows = (skey, torch.tensor([skey[0] + rows_per_slot * s for s in range(self.S)], dtype=I64).to(self.dev))
+            self._launch(self._rows[1], counts_dev, None, self.S, ld, self._sad_rows[1])
+            return
         self._launch(self._rows[1], counts_dev, None, self.S, ld)
 
     def end(self, slots):
@@ -325,16 +472,24 @@ class SegmentSession:
 
     After a step that emitted logits, one tracker launch reads the rows the session emitted (`emitted()`: its logits rows
     with the per-slot emitted row counts on the device, no host work); slots that turned done in a step are ended.
-    tracker_kw go to SegmentTracker (col0 = 1 and ntracks = C - col0 by default)."""
+    tracker_kw go to SegmentTracker (col0 = 1 and ntracks = C - col0 by default).
 
-    def __init__(self, session, **tracker_kw):
+    With sad=True every pushed frame comes with a flag of an external speech-activity mask: `step(push, flush, sad={slot:
+    flag})`, `step_frames(push, flush, sad={slot: flags of its pushed frames})`, `prefill(s, feats, sad=flags)`.  Output row u
+    of a slot belongs to its input frame u and is emitted conv_delay pushes later, so the flags wait in a per-slot host FIFO;
+    after a step each slot's emitted rows take the oldest flags (one asynchronous copy of an (S, n) uint8 block, then the
+    tracker's launch).  The stream's lines are make_rttm(rec, sigmoid(L[:, 1:]), sad=flags) over its logits L."""
+
+    def __init__(self, session, sad: bool = False, **tracker_kw):
         self.ses = session
+        self.sad = bool(sad)
+        self._flags = {}                        # rows per slot -> the (S, n) uint8 device block the tracker reads
         self.S, self.C, self.dev, self.m = session.S, session.C, session.dev, session.m
         self.max_frames, self.input_transform = session.max_frames, session.input_transform
         kw = dict(tracker_kw)
         col0 = kw.setdefault("col0", 1)
         kw.setdefault("ntracks", self.C - col0)
-        self.tracker = SegmentTracker(self.S, device=self.dev, **kw)
+        self.tracker = SegmentTracker(self.S, device=self.dev, sad=self.sad, **kw)
 
     def open(self) -> int:
         s = self.ses.open()
@@ -378,36 +533,88 @@ class SegmentSession:
         self.tracker.adopt(s, snap.parts["tracker"])
         return s
 
-    def _step(self, step, push, flush):
+    def _pushed_flags(self, frames, sad):
+        """frames: {slot: frames it pushes in this step}; -> {slot: their flags as a list}.  SlotError, before anything ran,
+        unless every pushing slot has one flag per frame and no other slot has any (a plain session takes none at all)."""
+        if not self.sad:
+            if sad is not None:
+                raise SlotError("speech-activity flags given to a session built without sad=True")
+            return None
+        return self.tracker.fifo.check(frames, sad)
+
+    def _emitted_flags(self, out, n):
+        """The flags of the rows a step emitted (out: its result), oldest first per slot, as the (S, n) uint8 device block of
+        that row count: one asynchronous copy from a fresh pinned block."""
+        rows = [[0] * n for _ in range(self.S)]
+        for s, f in self.tracker.fifo.pop({s: v.shape[1] for s, v in out.items()}).items():
+            rows[s][:len(f)] = f
+        stage = torch.empty(self.S, n, dtype=U8, pin_memory=self.dev.type == "cuda")
+        stage.copy_(torch.tensor(rows, dtype=U8))
+        if n not in self._flags:
+            self._flags[n] = torch.zeros(self.S, n, dtype=U8, device=self.dev)
+        self._flags[n].copy_(stage, non_blocking=True)
+        return self._flags[n]
+
+    def _step(self, step, push, flush, flags=None):
         before = [self.ses.state(s) for s in range(self.S)]
         out = step(push=push, flush=flush)
+        if self.sad:
+            self.tracker.fifo.push(flags)
         if out:                                 # a replay happened: the tracker reads its emitted rows
             logits, counts, n = self.ses.emitted()
-            self.tracker.feed_rows(logits, counts, rows_per_slot=n)
+            if self.sad:
+                self.tracker.feed_rows(logits, counts, rows_per_slot=n, sad=self._emitted_flags(out, n))
+            else:
+                self.tracker.feed_rows(logits, counts, rows_per_slot=n)
         done = [s for s in range(self.S) if before[s] != "done" and self.ses.state(s) == "done"]
         if done:
+            if self.sad:
+                assert not any(self.tracker.fifo.q[s] for s in done), "a finished stream has flags left"
             self.tracker.end(done)
         return out
 
     @torch.no_grad()
-    def step(self, push=None, flush=()):
-        return self._step(self.ses.step, push, flush)
+    def step(self, push=None, flush=(), sad=None):
+        flags = self._pushed_flags({s: 1 for s in dict(push or {})}, sad)
+        return self._step(self.ses.step, push, flush, flags)
 
     @torch.no_grad()
-    def step_frames(self, push=None, flush=()):
-        return self._step(self.ses.step_frames, push, flush)
+    def step_frames(self, push=None, flush=(), sad=None):
+        frames = {}
+        if self.sad:
+            for s, x in dict(push or {}).items():
+                if not torch.is_tensor(x):
+                    raise SlotError(f"push to slot {s}: expected a tensor of features")
+                frames[s] = x.numel() // self.m._in_size
+        flags = self._pushed_flags(frames, sad)
+        return self._step(self.ses.step_frames, push, flush, flags)
 
     @torch.no_grad()
-    def prefill(self, s: int, feats):
-        """The session's prefill of slot s; the rows it emitted go to the slot's tracker in one feed."""
+    def prefill(self, s: int, feats, sad=None):
+        """The session's prefill of slot s; the rows it emitted go to the slot's tracker in one feed.  With sad=True, `sad` holds
+        one flag per frame of feats."""
+        flags = None
+        if self.sad or sad is not None:
+            if not torch.is_tensor(feats):
+                raise SlotError(f"prefill of slot {s}: expected a tensor of features")
+            flags = self._pushed_flags({s: feats.numel() // self.m._in_size}, None if sad is None else {s: sad})
         out = self.ses.prefill(s, feats)
-        if out.shape[1]:
+        m = out.shape[1]
+        if self.sad:
+            self.tracker.fifo.push(flags)
+            f = self.tracker.fifo.pop({s: m})[s]
+            if m:
+                self.tracker.feed({s: out[0]}, sad={s: f})
+        elif m:
             self.tracker.feed({s: out[0]})
         return out
 
     def seek(self, s: int, t: int):
         """The session's benchmarking aid (FsMultiStreamSession.seek).  The tracker is not moved: the slot's segment frames keep
-        counting the rows the session emits, from 0 at open()."""
+        counting the rows the session emits, from 0 at open().  Not with sad=True: the flags waiting for their rows would no
+        longer belong to them."""
+        if self.sad:
+            raise SlotError("seek on a session with a speech-activity mask would misalign its flags")
         self.ses.seek(s, t)
 
     def poll(self):

@@ -692,10 +692,12 @@ def counter_add_masked(len_i32, mask_i32):
 SEGTRACK_HDR = 4                                  # per-slot header of the segment box: frames, count, overflow, 0
 
 
-def segtrack_feed(desc_i64, counts_i32, ends_i32, n, ld, col0, ntracks, threshold, median, is_prob, hist, open_i32, box, cap):
+def segtrack_feed(desc_i64, counts_i32, ends_i32, n, ld, col0, ntracks, threshold, median, is_prob, hist, open_i32, box, cap,
+                  sad_desc_i64=None):
     """Advance n slots of a segment tracker in one launch: entry e feeds counts[e] rows from the address desc[e][0] (row stride
     ld floats) to slot desc[e][1]; ends[e] != 0 (ends may be None) ends that stream.  State: hist int64 (S, 64), open int32
-    (S, 64), box int32 (S, SEGTRACK_HDR + 3 cap) (include/eend_hip.h eend_segtrack_feed_f32)."""
+    (S, 64), box int32 (S, SEGTRACK_HDR + 3 cap) (include/eend_hip.h eend_segtrack_feed_f32).  sad_desc_i64 (n addresses of
+    uint8 flags, one per row of the entry) gates the decisions with a speech-activity mask (eend_segtrack_feed_sad_f32)."""
     L = _lib.load()
     _chk(desc_i64, torch.int64, "desc"); _chk(counts_i32, torch.int32, "counts"); _chk(ends_i32, torch.int32, "ends")
     _chk(hist, torch.int64, "hist"); _chk(open_i32, torch.int32, "open"); _chk(box, torch.int32, "box")
@@ -703,6 +705,14 @@ def segtrack_feed(desc_i64, counts_i32, ends_i32, n, ld, col0, ntracks, threshol
     if (desc_i64.numel() < 2 * n or counts_i32.numel() < n or (ends_i32 is not None and ends_i32.numel() < n) or hist.shape != (S, 64)
             or open_i32.shape != (S, 64) or box.shape[1] != SEGTRACK_HDR + 3 * cap):
         raise _lib.EendHipError("segtrack_feed: shape mismatch")
+    if sad_desc_i64 is not None:
+        _chk(sad_desc_i64, torch.int64, "sad_desc")
+        if sad_desc_i64.numel() < n:
+            raise _lib.EendHipError("segtrack_feed: one flag address per entry")
+        _lib.check(L.eend_segtrack_feed_sad_f32(_p(desc_i64), _p(counts_i32), _p(ends_i32), _p(sad_desc_i64), n, ld, col0, ntracks,
+                                                float(threshold), median, int(bool(is_prob)), _p(hist), _p(open_i32), _p(box), S, cap,
+                                                _stream()), "eend_segtrack_feed_sad_f32")
+        return
     _lib.check(L.eend_segtrack_feed_f32(_p(desc_i64), _p(counts_i32), _p(ends_i32), n, ld, col0, ntracks, float(threshold), median,
                                         int(bool(is_prob)), _p(hist), _p(open_i32), _p(box), S, cap, _stream()), "eend_segtrack_feed_f32")
 

@@ -4,6 +4,8 @@ csrc/postproc.hip (no CPU fallback: tensors must live on the GPU).
     make_rttm                  FS-EEND/train/utils/make_rttm.py:10-28 (LS-EEND copy identical)
     calc_diarization_error     FS-EEND/train/utils/loss.py:198-236   (LS-EEND train/utils/loss.py:215-257)
     report_diarization_error   FS-EEND/train/utils/loss.py:239-254
+    sad_func                   LS-EEND/sad_post_process.py:23-33     (external speech-activity mask; also `sad=` of
+                               activity / make_rttm, which the reference applies before its median filter)
 
 Same names, arguments and return structure as the reference, so `dia_pred.py` / `streaming_infer_dia.py` /
 the Lightning validation step can import them from the drop-in `train.utils` shims.
@@ -44,11 +46,50 @@ def _to_device(t, name):
     return t.to(torch.device("cuda", torch.cuda.current_device()))
 
 
-def activity(pred, threshold=0.5, median=11):
-    """(T, S) probabilities -> uint8 (T, S): threshold, then median filter along time (make_rttm.py:12-15)."""
+def _sad_u8(sad, T, device):
+    """A speech-activity mask of shape (T,) or (T, 1), any dtype (non-zero: speech) -> contiguous uint8 (T,) on `device`."""
+    if not isinstance(sad, torch.Tensor):
+        sad = torch.as_tensor(sad)
+    if sad.dim() == 2 and sad.shape[1] == 1:
+        sad = sad[:, 0]
+    if sad.dim() != 1 or sad.shape[0] != T:
+        raise ValueError(f"sad: expected one flag per frame, shape ({T},) or ({T}, 1), got {tuple(sad.shape)}")
+    return (sad.to(device) != 0).to(_U8).contiguous()
+
+
+def sad_fuse(pred, sad, threshold=0.5):
+    """(T, S) probabilities and a speech-activity mask -> float32 (T, S) of 0 / 1 (csrc/postproc.hip sad_fuse_kernel): the
+    decisions pred > threshold where the mask says speech, none elsewhere, and in a speech frame with no decision the speaker
+    with the largest probability (the lowest index on ties).  NaN is never active and never the largest."""
     L = _lib.load()
     pred = _gpu_f32(pred, "pred")
     T, S = pred.shape
+    flags = _sad_u8(sad, T, pred.device)
+    out = torch.empty(T, S, dtype=_F32, device=pred.device)
+    if T and S:
+        _lib.check(L.eend_sad_fuse_f32(pred.data_ptr(), pred.stride(0), T, S, float(threshold), flags.data_ptr(), out.data_ptr(),
+                                       _stream()), "eend_sad_fuse_f32")
+    return out
+
+
+def sad_func(decision, sad, posterior, threshold=0.5):
+    """Drop-in for LS-EEND/sad_post_process.py sad_func(decision, sad, posterior): float32 (T, C) on the posterior's device (a
+    CPU posterior is moved to the GPU, and so is the result).  `decision` is accepted for signature compatibility only: it is
+    recomputed on the device as posterior > threshold, which is what the reference's caller passes (:69)."""
+    posterior = _to_device(posterior, "posterior")
+    if decision is not None and tuple(decision.shape) != tuple(posterior.shape):
+        raise ValueError(f"decision {tuple(decision.shape)} and posterior {tuple(posterior.shape)} differ in shape")
+    return sad_fuse(posterior, sad, threshold)
+
+
+def activity(pred, threshold=0.5, median=11, sad=None):
+    """(T, S) probabilities -> uint8 (T, S): threshold, then median filter along time (make_rttm.py:12-15).  With `sad` ((T,)
+    or (T, 1), non-zero: speech) the thresholded decisions are fused with that mask first (sad_fuse), as the reference does."""
+    L = _lib.load()
+    pred = _gpu_f32(pred, "pred")
+    T, S = pred.shape
+    if sad is not None:
+        pred, threshold = sad_fuse(pred, sad, threshold), 0.5
     out = torch.empty(T, S, dtype=_U8, device=pred.device)
     _lib.check(L.eend_activity_median_u8(pred.data_ptr(), pred.stride(0), T, S, float(threshold), int(median) if median > 1 else 1,
                                          out.data_ptr(), _stream()), "eend_activity_median_u8")
@@ -89,9 +130,9 @@ def rttm_lines(rec, segs, frame_shift=80, subsampling=10, sampling_rate=8000):
     return rttm
 
 
-def make_rttm(rec, pred, frame_shift=80, threshold=0.5, median=11, subsampling=10, sampling_rate=8000):
+def make_rttm(rec, pred, frame_shift=80, threshold=0.5, median=11, subsampling=10, sampling_rate=8000, sad=None):
     pred = _to_device(pred, "pred")
-    return rttm_lines(rec, segments(activity(pred, threshold, median)), frame_shift, subsampling, sampling_rate)
+    return rttm_lines(rec, segments(activity(pred, threshold, median, sad)), frame_shift, subsampling, sampling_rate)
 
 
 def der_counters(pred, label, label_delay=0):

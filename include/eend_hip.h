@@ -310,6 +310,22 @@ int eend_activity_segments_i32(const unsigned char* act, int T, int S, int* chan
 int eend_segtrack_feed_f32(const long* desc, const int* counts, const int* ends, int n, int ld, int col0, int ntracks, float threshold,
                            int median, int is_prob, unsigned long long* hist, int* open, int* box, int slots, int cap, void* stream);
 
+/* External speech-activity mask, whole file (LS-EEND/sad_post_process.py:23-33; additive to ABI version 5).  pred f32 [T][ld]
+ * (S <= ld columns used), sad u8 [T] (non-zero: speech) -> out f32 [T][S] of 0 / 1: out[t][s] = pred[t][s] > threshold where
+ * sad[t] is set and 0 elsewhere; a speech row with no column above the threshold gets a 1 at its largest value (the lowest
+ * column on ties, as torch.argmax; -inf and 0 are ordinary values).  NaN is never above the threshold and never the largest; a
+ * speech row of NaN only stays 0.  eend_activity_median_u8(out, S, T, S, 0.5f, median, ...) then filters it as usual. */
+int eend_sad_fuse_f32(const float* pred, int ld, int T, int S, float threshold, const unsigned char* sad, float* out, void* stream);
+
+/* eend_segtrack_feed_f32 behind an external speech-activity mask (additive to ABI version 5): the same arguments and state, plus
+ * sad_desc i64 [n]: entry e's address of counts[e] u8 flags, one per row it brings (never read when counts[e] <= 0).  The raw
+ * decision of a row is gated as eend_sad_fuse_f32 gates it, over the tracked columns col0 .. col0 + ntracks - 1 only; without
+ * is_prob the largest value is taken over the raw logits.  The median, the segments and the end of a stream are unchanged, so a
+ * stream's segments are those of eend_sad_fuse_f32 + eend_activity_median_u8 + eend_activity_segments_i32 over its rows. */
+int eend_segtrack_feed_sad_f32(const long* desc, const int* counts, const int* ends, const long* sad_desc, int n, int ld, int col0,
+                               int ntracks, float threshold, int median, int is_prob, unsigned long long* hist, int* open, int* box,
+                               int slots, int cap, void* stream);
+
 /* Frame-level DER counters of pre-activations pred f32 [T][ldp] against 0/1 labels f32 [T][ldl], C columns,
  * label_delay as in the reference: counters u64 [8] = speech_scored, speech_miss, speech_falarm,
  * speaker_scored, speaker_miss, speaker_falarm, speaker_error, #(label == decision).  Zeroed by the call. */

@@ -2,12 +2,13 @@
 
   session : per-frame wall time of FsMultiStreamSession (C = 6) and LsMultiStreamSession (C = 10) with and without the
             SegmentSession wrapper at S = 1, 8, 64, all slots pushing every frame; the two are timed alternately on the same
-            box, --rounds times, and the median of each is kept.
+            box, --rounds times, and the median of each is kept.  With --sad a third session, SegmentSession(sad=True)
+            with one speech-activity flag per pushed frame (runs of 0 and 1), joins the alternation.
   poll    : SegmentSession.poll at S = 64 with a poll every 100 frames: ms per poll (host wall, the sync included) and per frame.
   hour    : one hour (36 000 rows, 11 tracks) of one stream fed to a tracker in one call, end included, against
             postproc.make_rttm on the same logits (device-event time of each; make_rttm's includes its two host reads).
 
-    python tools/segment_stream_bench.py [--slots 1,8,64] [--steps 200] [--warmup 20] [--rounds 3] [--skip-session]
+    python tools/segment_stream_bench.py [--slots 1,8,64] [--steps 200] [--warmup 20] [--rounds 3] [--skip-session] [--sad]
 
 Kernel times come from a separate `rocprofv3 --kernel-trace --stats` run of this tool."""
 import argparse
@@ -62,24 +63,34 @@ def sessions(args, torch, dev, sm, lm):
             x = (torch.randn(S, 345, generator=g) * 2 - 3).to(dev)
             push = {s: x[s] for s in range(S)}
             bare, wrapped = mk(S), SegmentSession(mk(S))
-            for ses in (bare, wrapped):
+            masked = SegmentSession(mk(S), sad=True) if args.sad else None
+            flags = [{s: ((i + 3 * s) // 7) & 1 for s in range(S)} for i in range(14)]    # runs of 7 frames, staggered by slot
+            for ses in (bare, wrapped, masked):
+                if ses is None:
+                    continue
                 for _ in range(S):
                     ses.open()
-                for _ in range(args.warmup + 20):                          # past the look-ahead, graph captured, warm
-                    ses.step(push=push)
-            t_bare, t_wrap = [], []
+                for i in range(args.warmup + 20):                          # past the look-ahead, graph captured, warm
+                    ses.step(push=push, **({"sad": flags[i % 14]} if ses is masked else {}))
+            t_bare, t_wrap, t_sad = [], [], []
             for _ in range(args.rounds):
                 t_bare.append(timed(lambda i: bare.step(push=push), args.steps, torch))
                 t_wrap.append(timed(lambda i: wrapped.step(push=push), args.steps, torch))
                 wrapped.poll()
+                if masked is not None:
+                    t_sad.append(timed(lambda i: masked.step(push=push, sad=flags[i % 14]), args.steps, torch))
+                    masked.poll()
             b, w = statistics.median(t_bare), statistics.median(t_wrap)
             out.append(dict(model=name, slots=S, C=C, steps=args.steps, rounds=args.rounds, bare_ms_per_frame=b,
                             segments_ms_per_frame=w, added=(w - b) / b, bare_all=t_bare, segments_all=t_wrap))
+            if masked is not None:
+                m = statistics.median(t_sad)
+                out[-1].update(sad_ms_per_frame=m, sad_added=(m - b) / b, sad_over_segments=(m - w) / w, sad_all=t_sad)
             print(json.dumps(out[-1]), file=sys.stderr, flush=True)
             if S == 64 and name == "FS":
                 out.append(poll_cost(args, torch, wrapped, push))
                 print(json.dumps(out[-1]), file=sys.stderr, flush=True)
-            del bare, wrapped
+            del bare, wrapped, masked
             torch.cuda.synchronize()
             torch.cuda.empty_cache()
     return out
@@ -134,6 +145,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--skip-session", action="store_true")
+    ap.add_argument("--sad", action="store_true", help="also time SegmentSession(sad=True) with a flag per pushed frame")
+    ap.add_argument("--skip-hour", action="store_true")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -143,8 +156,9 @@ def main():
     if not args.skip_session:
         sm, lm = models(torch, dev)
         r["session"] = sessions(args, torch, dev, sm, lm)
-    r["hour"] = hour(args, torch, dev)
-    print(json.dumps(r["hour"]), file=sys.stderr, flush=True)
+    if not args.skip_hour:
+        r["hour"] = hour(args, torch, dev)
+        print(json.dumps(r["hour"]), file=sys.stderr, flush=True)
     r["timing"] = "events around the timed calls (host gaps included); session: median of alternating rounds; hour: best of 5"
     print(json.dumps(r))
 
