@@ -489,6 +489,20 @@ int eend_der_counters_u64(const float* pred, int ldp, const float* label, int ld
     return eend_launch_der_counters(pred, ldp, label, ldl, T, C, label_delay, counters, (hipStream_t)stream);
 }
 
+int eend_collar_der_u64(const unsigned char* ref, const int* ref_off, int Cr, const unsigned char* hyp, const int* hyp_off, int Ch, int B,
+                        int subsampling, int half_collar, int skip_overlap, unsigned long long* counters, unsigned long long* cooc,
+                        int* mapping, void* stream) {
+    return eend_launch_collar_der(ref, ref_off, Cr, hyp, hyp_off, Ch, B, subsampling, half_collar, skip_overlap, counters, cooc, mapping,
+                                  (hipStream_t)stream);
+}
+
+int eend_collar_der_limits(int* tile, int* max_half_collar) {
+    if (!tile || !max_half_collar) return EEND_EINVAL;
+    *tile = DER_TILE;
+    *max_half_collar = DER_HMAX;
+    return EEND_OK;
+}
+
 int eend_stft_logmel23_f32(const float* y, long len, long first, int n_frames, const float* dft, const float* melT,
                            float* out, void* stream) {
     return eend_launch_stft_logmel(y, len, first, n_frames, dft, melT, out, (hipStream_t)stream);

@@ -106,6 +106,16 @@ int eend_launch_segtrack_sad(const long* desc, const int* counts, const int* end
                              hipStream_t stream);
 int eend_launch_der_counters(const float* pred, int ldp, const float* label, int ldl, int T, int C, int delay,
                              unsigned long long* counters, hipStream_t stream);
+// collar DER (der_collar.hip): speakers per side, reference frames per tile, largest half collar, tile groups per recording,
+// longest recording in reference frames
+#define DER_CMAX 16
+#define DER_TILE 1024
+#define DER_HMAX 2048
+#define DER_MAX_GROUPS 512
+#define DER_MAX_FRAMES 0x7fff0000L
+int eend_launch_collar_der(const unsigned char* ref, const int* roff, int Cr, const unsigned char* hyp, const int* hoff, int Ch, int B,
+                           int sub, int h, int skip, unsigned long long* counters, unsigned long long* cooc, int* mapping,
+                           hipStream_t stream);
 
 int eend_launch_stft_logmel(const float* y, long len, long first, int n_frames, const float* dft, const float* melT, float* out,
                             hipStream_t stream);

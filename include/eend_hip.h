@@ -332,6 +332,43 @@ int eend_segtrack_feed_sad_f32(const long* desc, const int* counts, const int* e
 int eend_der_counters_u64(const float* pred, int ldp, const float* label, int ldl, int T, int C, int label_delay,
                           unsigned long long* counters, void* stream);
 
+/* Collar DER with the optimal speaker mapping, as the papers report it (LS-EEND/metrics.py:41-108: pyannote's
+ * DiarizationErrorRate(collar=50) over the label runs and the thresholded, median-filtered predictions; additive to ABI
+ * version 5).  A ragged batch of B recordings (1 <= B <= 65535), rows concatenated: recording b has the reference rows
+ * ref_off[b] .. ref_off[b + 1] - 1 of ref u8 [.][Cr] (label rate) and the hypothesis rows hyp_off[b] .. hyp_off[b + 1] - 1 of
+ * hyp u8 [.][Ch] (model rate); the i32 [B + 1] offsets live on the device and do not decrease; non-zero is active; Cr and Ch are
+ * independent, each in 1 .. 16.  Hypothesis frame k covers the reference frames [k * subsampling, (k + 1) * subsampling).  With
+ * Tr and Th the two row counts, T = max(Tr, Th * subsampling); a side is zero beyond its own end, an empty side is legal, and
+ * everything is counted in reference frames.
+ *   1. Collar: half_collar = collar / 2 for pyannote's collar (the total width centred on a boundary).  Reference speaker s
+ *      has a boundary at b in 0 .. Tr where ref[b - 1][s] != ref[b][s] (zeros outside [0, Tr), so a speaker active in frame 0 or
+ *      Tr - 1 has one at 0 or Tr).  Frame t is removed iff some speaker has a boundary b with t - h < b <= t + h; the collar of
+ *      the boundary at Tr reaches into a hypothesis-only tail.  Collars come from the reference only.  On the frame grid this is
+ *      pyannote's interval arithmetic (collars [b - collar / 2, b + collar / 2) taken out of the union extent).
+ *   2. skip_overlap != 0: frames with two or more active reference speakers are removed as well.
+ *   3. cooc[i][j] = kept frames in which reference speaker i and hypothesis speaker j are both active.
+ *   4. Mapping hypothesis j -> reference i, one-to-one and partial, maximising the sum of cooc; pairs with cooc = 0 are not
+ *      mapped.  Where several mappings are optimal any one of them is returned; the counters do not depend on the choice.
+ *   5. Per kept frame with nr reference and nh hypothesis speakers: total += nr, miss += max(0, nr - nh), false alarm +=
+ *      max(0, nh - nr), correct += mapped pairs active on both sides, confusion += min(nr, nh) - those.  Summed over the
+ *      frames, correct is the value of the optimal mapping, so one pass over the frames and one assignment do it.
+ *      DER = (miss + false alarm + confusion) / total.
+ * counters u64 [B][8] = total, miss, false alarm, confusion, correct, frames kept, frames removed within [0, T) (by a collar or
+ * as overlap), sum of min(nr, nh); cooc u64 [B][16][16] (rows and columns beyond Cr and Ch are 0); mapping i32 [B][16],
+ * hypothesis -> reference, -1 = unmapped.  All three are written by the call: a clearing launch, one pass over the rows (workgroups
+ * walk tiles of reference frames, at most 512 tile groups per recording, 64-bit integer atomics only, so every run gives the
+ * same bits) and one assignment launch; nothing is allocated and the host is not waited for.  EEND_EINVAL: a NULL pointer, Cr
+ * or Ch outside 1 .. 16, B outside 1 .. 65535, subsampling < 1, half_collar < 0 or above the cap eend_collar_der_limits reports.
+ * A recording with T > 2^31 - 2^16, or with decreasing offsets, is out of scope: it is not read, its counters are all ~0 and its
+ * mapping is -1.  One quirk of the reference's script is not reproduced: there a second speaker with the very same run (s, e)
+ * overwrites the first (`reference[Segment(s, e)] = str(spkid)`); here both count. */
+int eend_collar_der_u64(const unsigned char* ref, const int* ref_off, int Cr, const unsigned char* hyp, const int* hyp_off, int Ch, int B,
+                        int subsampling, int half_collar, int skip_overlap, unsigned long long* counters, unsigned long long* cooc,
+                        int* mapping, void* stream);
+
+/* The reference frames per tile of eend_collar_der_u64's pass and the largest half_collar it takes (host arithmetic only). */
+int eend_collar_der_limits(int* tile, int* max_half_collar);
+
 /* ---- feature front-end ({LS,FS}-EEND/datasets/feature.py: stft :166-191, transform :43-131, splice :141-163,
  * subsample :133-138, extract_fbank :324-336); fp32 throughout.  ---- */
 
