@@ -17,10 +17,15 @@ splice of the next model frame reads; the host keeps the counters, which depend 
 sum strictly in frame order, so its features do not depend on how the audio was cut, and differ from the batch path (which
 sums in another order) by about one float ulp of the mean.  One `feed` costs three launches and one host-to-device copy,
 whatever the number of slots or the chunk sizes, and never waits for the device.
+
+Audio that is not 8 kHz float goes through `audio_ingest.AudioIngest` first (`sample_rate=`, `encoding=`: G.711 mu-law / A-law,
+16-bit PCM or float at 8 .. 48 kHz): the raw chunks travel at their own width in the same staging block, two more launches
+decode and convert them on the device into a packed f32 buffer, and the feed descriptors point at that buffer.  The converted
+samples do not depend on how the audio was cut either, so the contract above starts at the wire.
 """
 import torch
 
-from . import feature
+from . import audio_ingest, feature
 from . import lib as _lib
 from .multistream import SlotError, check_parts
 
@@ -128,7 +133,8 @@ class FrontEndTable:
 
 
 class AudioFrontEnd:
-    """Incremental `extract_fbank_wave` for `slots` concurrent 8 kHz streams:
+    """Incremental `extract_fbank_wave` for `slots` concurrent streams (8 kHz float, or any `sample_rate` / `encoding` of
+    `audio_ingest`, decoded and converted on the device):
 
         fe = AudioFrontEnd(64, "logmel23_cummn")
         fe.reset(s)                                   # an empty stream in slot s
@@ -139,7 +145,7 @@ class AudioFrontEnd:
     for bit with logmel23), however the audio was cut."""
 
     def __init__(self, slots: int, input_transform: str, context_size: int = 7, subsampling: int = 10, device=None,
-                 pad_mode: str = "constant"):
+                 pad_mode: str = "constant", sample_rate: int = 8000, encoding: str = "f32"):
         if input_transform == "logmel23_mn":
             raise ValueError("logmel23_mn normalises by the mean of the whole recording and cannot be computed incrementally; "
                              "use logmel23 or logmel23_cummn")
@@ -148,6 +154,8 @@ class AudioFrontEnd:
         if pad_mode != "constant":
             raise ValueError("the incremental front-end supports pad_mode='constant' only (reflect padding needs the samples past "
                              "the end of the stream)")
+        audio_ingest.check_encoding(encoding)
+        audio_ingest.ratio(sample_rate)
         self.table = FrontEndTable(slots, context_size, subsampling)
         self.S, self.ctx, self.sub = slots, context_size, subsampling
         self.mode = MODES[input_transform]
@@ -161,13 +169,21 @@ class AudioFrontEnd:
         self.ring = z(slots, RING, NMEL)
         self.sums = z(slots, NMEL, dt=torch.float64)
         self.dft, self.melT = feature._tables(self.dev)
+        self.sample_rate, self.encoding = sample_rate, encoding
+        self.ingest = None                      # 8 kHz float needs none: feed is the three launches alone
+        if (sample_rate, encoding) != (audio_ingest.OUT_RATE, "f32"):
+            self.ingest = audio_ingest.AudioIngest(slots, sample_rate, encoding, device=self.dev)
 
     def reset(self, s: int):
         """Start an empty stream in slot s (any state): its device state is ignored until overwritten."""
         self.table.reset(s)
+        if self.ingest is not None:
+            self.ingest.reset(s)
 
     def close(self, s: int):
         self.table.close(s)
+        if self.ingest is not None:
+            self.ingest.close(s)
 
     def state(self, s: int) -> str:
         return self.table.state[s]
@@ -182,8 +198,11 @@ class AudioFrontEnd:
         if self.table.state[s] == FREE:
             raise SlotError(f"slot {s} is not open (reset it first)")
         t = self.table
-        return {"config": self._config(), "tail": self.tail[s].clone(), "ring": self.ring[s].clone(), "sums": self.sums[s].clone(),
+        part = {"config": self._config(), "tail": self.tail[s].clone(), "ring": self.ring[s].clone(), "sums": self.sums[s].clone(),
                 "state": t.state[s], "recv": t.recv[s], "frames": t.frames[s], "mframes": t.mframes[s]}
+        if self.ingest is not None:             # config, history row and counters of the stage in front
+            part["ingest"] = self.ingest.export(s)
+        return part
 
     def check_part(self, part):
         """SlotError unless `part` is an export of a front-end configured like this one."""
@@ -194,6 +213,12 @@ class AudioFrontEnd:
         if not ok:
             raise SlotError("resume: the snapshot's front-end part does not fit this front-end "
                             f"(here {self._config()}, there {part.get('config') if isinstance(part, dict) else part!r})")
+        if self.ingest is not None:
+            self.ingest.check_part(part.get("ingest"))
+        elif "ingest" in part:
+            raise SlotError("resume: the snapshot's audio was ingested as "
+                            f"{part['ingest'].get('config') if isinstance(part['ingest'], dict) else part['ingest']!r}, this "
+                            "front-end takes 8 kHz float samples")
 
     def adopt(self, s: int, part):
         """Slot s goes on from an exported `part` (checked by check_part): ordinary row copies on the current stream."""
@@ -202,6 +227,8 @@ class AudioFrontEnd:
             rows[s].copy_(part[k], non_blocking=True)
         t = self.table
         t.state[s], t.recv[s], t.frames[s], t.mframes[s] = part["state"], part["recv"], part["frames"], part["mframes"]
+        if self.ingest is not None:
+            self.ingest.adopt(s, part["ingest"], part["state"])
 
     @staticmethod
     def _samples(s, w):
@@ -215,8 +242,10 @@ class AudioFrontEnd:
 
     @torch.no_grad()
     def feed(self, waves=None, end=()):
-        """waves: {slot: 1-D float tensor (CPU or GPU) of its next samples}; end: slots whose audio ends here.
-        -> {slot: (n, width) f32 device tensor of its new model frames} for every slot named."""
+        """waves: {slot: 1-D tensor (CPU or GPU) of its next samples, float at 8 kHz or as sample_rate / encoding say}; end: slots
+        whose audio ends here.  -> {slot: (n, width) f32 device tensor of its new model frames} for every slot named."""
+        if self.ingest is not None:
+            return self._feed_ingest(waves, end)
         waves = {s: self._samples(s, w) for s, w in dict(waves or {}).items()}
         plan = self.table.plan({s: int(w.numel()) for s, w in waves.items()}, end)
         if not plan:
@@ -271,6 +300,46 @@ class AudioFrontEnd:
         del keep
         return {s: out[o:o + n] for s, (o, n) in rows.items()}
 
+    def _feed_ingest(self, waves, end):
+        """feed with the ingest in front: both tables planned, the raw chunks at their own width behind both descriptor sets in
+        one staging block, the ingest launched into a packed f32 buffer that the feed descriptors point at, both tables
+        committed after both calls returned."""
+        ing = self.ingest
+        waves = {s: ing.samples(s, w) for s, w in dict(waves or {}).items()}
+        iplan = ing.table.plan({s: int(w.numel()) for s, w in waves.items()}, end)
+        plan = self.table.plan({p.slot: p.out1 - p.out0 for p in iplan}, end)      # the front-end is fed what the ingest makes
+        if not plan:
+            return {}
+        dev, W = self.dev, self.width
+        staging = audio_ingest.Staging(dev, ing.dtype, ing.every)
+        iwords, ichunk_at, n_itiles, x_at, n_x = ing.stage(iplan, waves, staging)
+        x8 = torch.empty(max(n_x, 1), dtype=F32, device=dev)
+        desc, stft, splice = [], [], []
+        y_rows = o_rows = 0
+        rows = {}
+        for i, p in enumerate(plan):
+            desc.append([x8.data_ptr() + 4 * x_at[p.slot][0], p.recv0, p.recv1, p.f0, p.f1, p.rb0, p.rb1, y_rows, p.slot])
+            stft += [[i, f, min(FB, p.f1 - f)] for f in range(p.f0, p.f1, FB)]
+            splice += [[i, j, min(SPL_ROWS, p.j1 - j), o_rows + j - p.j0] for j in range(p.j0, p.j1, SPL_ROWS)]
+            rows[p.slot] = (o_rows, p.j1 - p.j0)
+            y_rows += p.f1 - p.rb0
+            o_rows += p.j1 - p.j0
+        words = [v for d in desc for v in d] + [v for t in stft for v in t] + [v for t in splice for v in t]
+        n_words = len(words)
+        _dbuf, base = staging.upload(words + iwords, [n_words + i for i in ichunk_at])
+        Y = torch.empty(max(y_rows, 1), NMEL, dtype=F32, device=dev)
+        out = torch.empty(o_rows, W, dtype=F32, device=dev)
+        ing.launch(base + 8 * n_words, len(iplan), n_itiles, x8)
+        _lib.check(_lib.load().eend_audio_feed_f32(base, len(desc), base + 8 * FEED_N * len(desc), len(stft),
+                                                   base + 8 * (FEED_N * len(desc) + 3 * len(stft)), len(splice),
+                                                   self.tail.data_ptr(), self.ring.data_ptr(), self.sums.data_ptr(), Y.data_ptr(),
+                                                   out.data_ptr() if o_rows else None, self.mode, self.ctx, self.sub,
+                                                   self.dft.data_ptr(), self.melT.data_ptr(),
+                                                   torch.cuda.current_stream(dev).cuda_stream), "eend_audio_feed_f32")
+        self.table.commit(plan)
+        ing.table.commit(iplan)
+        return {s: out[o:o + n] for s, (o, n) in rows.items()}
+
 
 class AudioStreamSession:
     """Audio in, logits out: an `AudioFrontEnd` in front of an `FsMultiStreamSession` or `LsMultiStreamSession`, slot for slot.
@@ -285,9 +354,11 @@ class AudioStreamSession:
     `push` runs the front-end once for all slots named, then steps the session with step_frames, each step pushing the next
     max_frames feature frames of every slot that still has some (the other slots pause); `end` flushes with the last of
     them; `prefill` gives one slot a backlog of audio through the session's prefill.  `input_transform` defaults to the session's (the reference configs': logmel23 for FS-EEND, logmel23_cummn for
-    LS-EEND)."""
+    LS-EEND).  `sample_rate` / `encoding` say how the audio of push, prefill and end arrives (`audio_ingest`): by default float
+    samples at 8 kHz, else e.g. 8000 / "mulaw" from a telephone trunk or 48000 / "s16" from a meeting client."""
 
-    def __init__(self, session, input_transform=None, context_size: int = 7, subsampling: int = 10):
+    def __init__(self, session, input_transform=None, context_size: int = 7, subsampling: int = 10, sample_rate: int = 8000,
+                 encoding: str = "f32"):
         self.ses, self.C = session, session.C
         if getattr(session, "sad", False):
             raise ValueError("AudioStreamSession over a SegmentSession with sad=True: the session wants one speech-activity flag "
@@ -295,7 +366,8 @@ class AudioStreamSession:
                              "through it yet; push features and flags to the SegmentSession directly")
         if input_transform is None:
             input_transform = session.input_transform
-        self.fe = AudioFrontEnd(session.S, input_transform, context_size, subsampling, device=session.dev)
+        self.fe = AudioFrontEnd(session.S, input_transform, context_size, subsampling, device=session.dev, sample_rate=sample_rate,
+                                encoding=encoding)
         in_size = session.m._in_size
         if in_size != self.fe.width:
             raise ValueError(f"the model takes {in_size} features per frame, the front-end makes {self.fe.width} "
@@ -371,7 +443,8 @@ class AudioStreamSession:
 
     @torch.no_grad()
     def push(self, waves):
-        """waves: {slot: 1-D float tensor of its next samples} -> {slot: (k, C) logits} of the frames completed."""
+        """waves: {slot: 1-D tensor of its next samples (float at 8 kHz, or as sample_rate / encoding say)} -> {slot: (k, C)
+        logits} of the frames completed."""
         waves = dict(waves)
         self._check_open(waves, "push to")
         feats = self.fe.feed(waves)

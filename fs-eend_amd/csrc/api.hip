@@ -523,6 +523,11 @@ int eend_audio_feed_f32(const long* desc, int n_desc, const long* stft_tiles, in
                                   dft, melT, (hipStream_t)stream);
 }
 
+int eend_audio_ingest(const long* desc, int n_desc, const long* tiles, int n_tiles, float* hist, const float* table,
+                      const float* decode, int L, int M, int H, int P, int encoding, float* out, void* stream) {
+    return eend_launch_audio_ingest(desc, n_desc, tiles, n_tiles, hist, table, decode, L, M, H, P, encoding, out, (hipStream_t)stream);
+}
+
 int eend_pit_cost_f64(const float* y, const float* labels, int B, int T, int C, double* cost, void* stream) {
     return eend_launch_pit_cost(y, labels, B, T, C, cost, (hipStream_t)stream);
 }

@@ -125,6 +125,11 @@ int eend_launch_audio_feed(const long* desc, int n_desc, const long* stft_tiles,
                            float* tail, float* ring, double* sums, float* Y, float* out, int mode, int ctx, int sub,
                            const float* dft, const float* melT, hipStream_t stream);
 
+// audio ingest (resample.hip): LDS floats of a tile's input span, at least 255 M / L + P + 2
+#define INGEST_SPAN 2048
+int eend_launch_audio_ingest(const long* desc, int n_desc, const long* tiles, int n_tiles, float* hist, const float* table,
+                             const float* decode, int L, int M, int H, int P, int encoding, float* out, hipStream_t stream);
+
 int eend_launch_pit_cost(const float* y, const float* lab, int B, int T, int C, double* cost, hipStream_t stream);
 int eend_launch_pit_assign(const double* cost, const int* nspk, int B, int C, int* perm, double* loss, hipStream_t stream);
 

@@ -127,10 +127,15 @@ def subsample(Y, T, subsampling=1):
 
 
 def extract_fbank_wave(data, context_size=7, frame_size=200, frame_shift=80, input_transform=None, subsampling=10,
-                       pad_mode="constant"):
-    """extract_fbank (feature.py:324-336) from the decoded waveform on: (ceil(n_frames / subsampling), 23 * 15)."""
+                       pad_mode="constant", sample_rate=8000, encoding="f32"):
+    """extract_fbank (feature.py:324-336) from the decoded waveform on: (ceil(n_frames / subsampling), 23 * 15).
+    `data` is float at 8 kHz, or a recording at another `sample_rate` / `encoding` (audio_ingest: "f32", "s16", "mulaw",
+    "alaw"), which the ingest kernel decodes and converts first: the samples a stream of the same audio gets, bit for bit."""
     if not input_transform:
         raise NotImplementedError("only the log-mel-23 transforms are implemented on the GPU")
+    if (sample_rate, encoding) != (8000, "f32"):
+        from . import audio_ingest
+        data = audio_ingest.convert(data, sample_rate, encoding)
     return splice_subsample(logmel(data, frame_size, frame_shift, input_transform, pad_mode), context_size, subsampling)
 
 

@@ -404,6 +404,24 @@ int eend_audio_feed_f32(const long* desc, int n_desc, const long* stft_tiles, in
                         float* tail, float* ring, double* sums, float* Y, float* out, int mode, int ctx, int sub,
                         const float* dft, const float* melT, void* stream);
 
+/* Audio ingest in front of eend_audio_feed_f32: many streams ("slots"), each fed raw audio at one sample rate and encoding in
+ * chunks of any size, decoded and converted to f32 samples at 8 kHz.  encoding 0 = f32 (the value itself), 1 = 16-bit PCM
+ * (v / 32768), 2 = G.711 mu-law, 3 = G.711 A-law (decode f32 [2][256]: the value of every mu-law, then every A-law byte).
+ * With g = gcd(rate, 8000), L = 8000 / g, M = rate / g and a low-pass prototype h[-H..H] on the rate * L grid, output n of a
+ * stream is  y[n] = sum_k h[n M - k L] x[k]  over k = ceil((n M - H) / L) .. floor((n M + H) / L), x zero outside the stream,
+ * accumulated in f32 with fmaf from zero in ascending k: its bits do not depend on how the audio was cut.  table f32 [L][P],
+ * P = 2 H / L + 1 <= 255: row (n M) mod L holds the taps of output n in that order, zero-padded (L = M = 1, H = 0, table {1}
+ * decodes only).  Per-slot device state: hist f32 [slots][256], the decoded samples max(0, ceil((n M - H) / L)) .. received
+ * - 1 that the slot's next output n still reads (fewer than P).  desc i64 [n_desc][8], one row per slot in the call: {device
+ * address of its raw chunk, input samples received before / after, outputs made before / after, index in out of its first
+ * new output, 1 if the stream ends with this call, slot}.  tiles i64 [n_tiles][3]: {desc row, first output, outputs <= 256}.
+ * out f32: the new outputs of every slot, packed.  Two launches: the tiles (one workgroup each, the input span staged in LDS),
+ * then the new history rows (one workgroup per desc row; a later launch because the tiles read the rows it overwrites).
+ * The host owns all counters (see fs-eend_amd/audio_ingest.py).  EEND_EINVAL: a NULL pointer that is needed, M < L (a rate
+ * below 8 kHz), P outside 1 .. 255 or unlike 2 H / L + 1, an unknown encoding, or a tile span 255 M / L + P + 2 above 2048. */
+int eend_audio_ingest(const long* desc, int n_desc, const long* tiles, int n_tiles, float* hist, const float* table,
+                      const float* decode, int L, int M, int H, int P, int encoding, float* out, void* stream);
+
 /* ---- permutation-invariant label assignment (FS-EEND/train/utils/loss.py:257-327 batch_pit_n_speaker_loss;
  * LS-EEND/train/utils/loss.py:350-379 pit_loss_multispk) ---- */
 
