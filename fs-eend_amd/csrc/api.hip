@@ -523,6 +523,14 @@ int eend_audio_feed_f32(const long* desc, int n_desc, const long* stft_tiles, in
                                   dft, melT, (hipStream_t)stream);
 }
 
+int eend_chunk_batch_f32(const void* corpus, int storage, const int* segments, const long* desc, int n_chunks,
+                         const long* stft_tiles, int n_stft, const long* splice_tiles, int n_splice, float* Y, float* Yn,
+                         float* feats, float* labels, int S_max, int mode, int ctx, int sub, const float* dft, const float* melT,
+                         void* stream) {
+    return eend_launch_chunk_batch(corpus, storage, segments, desc, n_chunks, stft_tiles, n_stft, splice_tiles, n_splice, Y, Yn, feats,
+                                   labels, S_max, mode, ctx, sub, dft, melT, (hipStream_t)stream);
+}
+
 int eend_audio_ingest(const long* desc, int n_desc, const long* tiles, int n_tiles, float* hist, const float* table,
                       const float* decode, int L, int M, int H, int P, int encoding, float* out, void* stream) {
     return eend_launch_audio_ingest(desc, n_desc, tiles, n_tiles, hist, table, decode, L, M, H, P, encoding, out, (hipStream_t)stream);

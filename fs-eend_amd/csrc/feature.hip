@@ -107,12 +107,13 @@ void stft_logmel_kernel(const float* __restrict__ y, long len, long first, int n
 // Mean normalisations of a (T, F) map, one block per column, the running column sum carried in fp64:
 //   mode 1 (logmel23_mn)    out = Y - mean over all frames
 //   mode 2 (logmel23_cummn) out[t] = Y[t] - (Y[0] + .. + Y[t]) / (t + 1)
+// colnorm_column is the whole body, one block of NT2 threads per column of one map (wsum: NT2 / 64 doubles and carry: one
+// double of LDS): the single-waveform and the batched kernel both call it, so their sums are added in the same order.
 constexpr int NT2 = 1024, PER = 4;
-__global__ __launch_bounds__(NT2)
-void colnorm_kernel(const float* __restrict__ Y, float* __restrict__ out, int T, int F, int mode) {
-    __shared__ double wsum[NT2 / 64];
-    __shared__ double carry_s;
-    const int col = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+__device__ __forceinline__ void colnorm_column(const float* __restrict__ Y, float* __restrict__ out, int T, int F, int col, int mode,
+                                               double* wsum, double* carry) {
+    double& carry_s = *carry;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (tid == 0) carry_s = 0.0;
     __syncthreads();
     if (mode == 1) {
@@ -160,6 +161,13 @@ void colnorm_kernel(const float* __restrict__ Y, float* __restrict__ out, int T,
         if (tid == NT2 - 1) carry_s = pre + s;
         __syncthreads();
     }
+}
+
+__global__ __launch_bounds__(NT2)
+void colnorm_kernel(const float* __restrict__ Y, float* __restrict__ out, int T, int F, int mode) {
+    __shared__ double wsum[NT2 / 64];
+    __shared__ double carry_s;
+    colnorm_column(Y, out, T, F, blockIdx.x, mode, wsum, &carry_s);
 }
 
 // out[j][c * F + m] = Y[j * sub + c - ctx][m] (zero outside [0, T)): splice of 2 ctx + 1 frames, every sub-th row
@@ -286,6 +294,82 @@ void feed_splice_kernel(const long* __restrict__ desc, const long* __restrict__ 
     }
 }
 
+// ---- labelled training batches from resident audio (eend_chunk_batch_f32): many chunks of a device-resident corpus, each ----
+// treated as a file of its own (LS-EEND/datasets/diarization_dataset_on_the_fly.py:87-131, datasets/feature.py:255-322).  The
+// host builds one descriptor per chunk (CHUNK_* fields) and the two tile tables; Y / Yn hold the chunks' log-mel rows back to back.
+enum { CHUNK_OFF, CHUNK_LEN, CHUNK_FRAMES, CHUNK_YBASE, CHUNK_START, CHUNK_END, CHUNK_SEG0, CHUNK_SEG1, CHUNK_N };
+
+__device__ __forceinline__ float sample_f32(float v) { return v; }
+__device__ __forceinline__ float sample_f32(short v) { return (float)v * (1.f / 32768.f); }       // exact: a power of two
+
+// One block per tile of up to FB log-mel frames of one chunk (tile = {descriptor, first frame, rows}): the third gather of
+// stft_logmel_tile, corpus[off + i] for 0 <= i < len and zero outside, i.e. stft_logmel_kernel's with first = -100 per chunk.
+template <class S>
+__global__ __launch_bounds__(256)
+void chunk_stft_kernel(const S* __restrict__ corpus, const long* __restrict__ desc, const long* __restrict__ tiles,
+                       const float* __restrict__ dft, const float* __restrict__ melT, float* __restrict__ Y) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const long* t = tiles + 3 * (long)blockIdx.x;
+    const long* d = desc + CHUNK_N * t[0];
+    const S* x = corpus + d[CHUNK_OFF];
+    const long len = d[CHUNK_LEN], f_a = t[1];
+    const long base = f_a * HOP - 100;
+    auto gather = [=](int i) {
+        const long idx = base + i;
+        return (idx >= 0 && idx < len) ? sample_f32(x[idx]) : 0.f;
+    };
+    stft_logmel_tile(smem, gather, dft, melT, Y + (d[CHUNK_YBASE] + f_a) * NMEL, (int)t[2]);
+}
+
+// grid (NMEL, chunks): colnorm_kernel on every chunk's own rows
+__global__ __launch_bounds__(NT2)
+void chunk_colnorm_kernel(const long* __restrict__ desc, const float* __restrict__ Y, float* __restrict__ out, int mode) {
+    __shared__ double wsum[NT2 / 64];
+    __shared__ double carry_s;
+    const long* d = desc + CHUNK_N * (long)blockIdx.y;
+    const int T = (int)d[CHUNK_FRAMES];
+    if (T <= 0) return;
+    const long at = d[CHUNK_YBASE] * NMEL;
+    colnorm_column(Y + at, out + at, T, NMEL, blockIdx.x, mode, wsum, &carry_s);
+}
+
+// One block per tile of up to SPL_ROWS model frames of one chunk (tile = {descriptor, first model frame j, rows, output row}):
+// the feature rows as feed_splice_kernel (frames j sub - ctx .. j sub + ctx, zero outside [0, n)), and the label rows of frames
+// j sub, rasterised from the recording's segments {start_frame, end_frame, speaker} by the reference's rule (feature.py:301-317).
+__global__ __launch_bounds__(256)
+void chunk_splice_label_kernel(const long* __restrict__ desc, const long* __restrict__ tiles, const int* __restrict__ segs,
+                               const float* __restrict__ Y, float* __restrict__ feats, float* __restrict__ labels, int S_max,
+                               int ctx, int sub) {
+    const long* t = tiles + 4 * (long)blockIdx.x;
+    const long* d = desc + CHUNK_N * t[0];
+    const long j0 = t[1], n = d[CHUNK_FRAMES];
+    const int rows = (int)t[2], W = NMEL * (2 * ctx + 1);
+    const float* Ys = Y + d[CHUNK_YBASE] * NMEL;
+    float* o = feats + t[3] * W;
+    for (int i = threadIdx.x; i < rows * W; i += 256) {
+        const int r = i / W, e = i - r * W, c = e / NMEL, m = e - c * NMEL;
+        const long f = (j0 + r) * sub + c - ctx;
+        o[i] = (f >= 0 && f < n) ? Ys[f * NMEL + m] : 0.f;
+    }
+    const long start = d[CHUNK_START], end = d[CHUNK_END], seg0 = d[CHUNK_SEG0], seg1 = d[CHUNK_SEG1];
+    float* lab = labels + t[3] * S_max;
+    for (int i = threadIdx.x; i < rows * S_max; i += 256) {
+        const int r = i / S_max, s = i - r * S_max;
+        const long f = (j0 + r) * sub;                              // < n: the tile's rows are model frames of the chunk
+        float v = 0.f;
+        for (long g = seg0; g < seg1; ++g) {
+            const int* sg = segs + 3 * g;
+            if (sg[2] != s) continue;
+            const long sf = sg[0], ef = sg[1];
+            const bool has_a = start <= sf && sf < end, has_b = start < ef && ef <= end;
+            if (!has_a && !has_b) continue;                         // also a segment that covers the whole chunk
+            const long lo = has_a ? sf - start : 0, hi = has_b ? ef - start : n;
+            if (f >= lo && f < hi) v = 1.f;
+        }
+        lab[i] = v;
+    }
+}
+
 }  // namespace
 
 int eend_launch_stft_logmel(const float* y, long len, long first, int n_frames, const float* dft, const float* melT, float* out,
@@ -327,5 +411,39 @@ int eend_launch_audio_feed(const long* desc, int n_desc, const long* stft_tiles,
     hipLaunchKernelGGL(feed_state_kernel, dim3(n_desc), dim3(256), 0, stream, desc, tail, ring, sums, Y, mode);
     if (n_splice)
         hipLaunchKernelGGL(feed_splice_kernel, dim3(n_splice), dim3(256), 0, stream, desc, splice_tiles, Y, out, ctx, sub);
+    return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
+}
+
+namespace {
+template <class S>
+bool launch_chunk_stft(const void* corpus, const long* desc, const long* tiles, int n_tiles, const float* dft, const float* melT,
+                       float* Y, hipStream_t stream) {
+    static EendOncePerDevice attr_once;                          // one per instantiation
+    if (!eend_set_dynamic_lds(attr_once, (const void*)chunk_stft_kernel<S>, SM_BYTES)) return false;
+    hipLaunchKernelGGL(chunk_stft_kernel<S>, dim3(n_tiles), dim3(256), SM_BYTES, stream, (const S*)corpus, desc, tiles, dft, melT, Y);
+    return true;
+}
+}  // namespace
+
+int eend_launch_chunk_batch(const void* corpus, int storage, const int* segments, const long* desc, int n_chunks,
+                            const long* stft_tiles, int n_stft, const long* splice_tiles, int n_splice, float* Y, float* Yn,
+                            float* feats, float* labels, int S_max, int mode, int ctx, int sub, const float* dft, const float* melT,
+                            hipStream_t stream) {
+    if (n_chunks < 0 || n_chunks > 65535 || n_stft < 0 || n_splice < 0 || storage < 0 || storage > 1 || mode < 0 || mode > 2 ||
+        ctx < 0 || ctx > 64 || sub < 1 || sub > 4096 || S_max < 1 || S_max > 64)
+        return EEND_EINVAL;
+    if (n_chunks == 0) return (n_stft || n_splice) ? EEND_EINVAL : EEND_OK;
+    if (!desc || !segments || (n_stft && (!corpus || !stft_tiles || !Y || !dft || !melT || (mode && !Yn))) ||
+        (n_splice && (!n_stft || !splice_tiles || !feats || !labels)))
+        return EEND_EINVAL;
+    if (n_stft) {
+        const bool ok = storage == 0 ? launch_chunk_stft<float>(corpus, desc, stft_tiles, n_stft, dft, melT, Y, stream)
+                                     : launch_chunk_stft<short>(corpus, desc, stft_tiles, n_stft, dft, melT, Y, stream);
+        if (!ok) return EEND_ELAUNCH;
+        if (mode) hipLaunchKernelGGL(chunk_colnorm_kernel, dim3(NMEL, n_chunks), dim3(NT2), 0, stream, desc, Y, Yn, mode);
+    }
+    if (n_splice)
+        hipLaunchKernelGGL(chunk_splice_label_kernel, dim3(n_splice), dim3(256), 0, stream, desc, splice_tiles, segments,
+                           mode ? Yn : Y, feats, labels, S_max, ctx, sub);
     return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
 }

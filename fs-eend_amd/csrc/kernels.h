@@ -124,6 +124,10 @@ int eend_launch_splice_subsample(const float* Y, int T, int F, int ctx, int sub,
 int eend_launch_audio_feed(const long* desc, int n_desc, const long* stft_tiles, int n_stft, const long* splice_tiles, int n_splice,
                            float* tail, float* ring, double* sums, float* Y, float* out, int mode, int ctx, int sub,
                            const float* dft, const float* melT, hipStream_t stream);
+int eend_launch_chunk_batch(const void* corpus, int storage, const int* segments, const long* desc, int n_chunks,
+                            const long* stft_tiles, int n_stft, const long* splice_tiles, int n_splice, float* Y, float* Yn,
+                            float* feats, float* labels, int S_max, int mode, int ctx, int sub, const float* dft, const float* melT,
+                            hipStream_t stream);
 
 // audio ingest (resample.hip): LDS floats of a tile's input span, at least 255 M / L + P + 2
 #define INGEST_SPAN 2048

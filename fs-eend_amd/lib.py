@@ -80,6 +80,7 @@ PROTOTYPES = {
     "eend_sad_fuse_f32": [_vp, _i, _i, _i, _f, _vp, _vp, _vp],
     "eend_segtrack_feed_sad_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _i, _i, _vp],
     "eend_audio_feed_f32": [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp],
+    "eend_chunk_batch_f32": [_vp, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp],
     "eend_audio_ingest": [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp],
     "eend_pit_cost_f64": [_vp, _vp, _i, _i, _i, _vp, _vp],
     "eend_pit_assign_i32": [_vp, _vp, _i, _i, _vp, _vp, _vp],
@@ -265,6 +266,8 @@ def load():
         raise EendHipError(
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950). There is no fallback path.")
+    import torch  # noqa: F401  -- first: a torch wheel brings its own HIP runtime, and the library must bind to the one torch's
+    #                              streams and allocations come from, not load a second copy from the toolkit's directory before it
     lib = ctypes.CDLL(LIB_PATH)
     for protos, restype in ((PROTOTYPES, ctypes.c_int), (LONG_PROTOTYPES, ctypes.c_long)):
         for name, argtypes in protos.items():

@@ -404,6 +404,33 @@ int eend_audio_feed_f32(const long* desc, int n_desc, const long* stft_tiles, in
                         float* tail, float* ring, double* sums, float* Y, float* out, int mode, int ctx, int sub,
                         const float* dft, const float* melT, void* stream);
 
+/* Labelled training batches from resident audio: what LS-EEND/datasets/diarization_dataset_on_the_fly.py:87-131 (__getitem__:
+ * get_labeledSTFT -> transform -> splice -> subsample) and datasets/feature.py:255-322 (get_labeledSTFT) do per item on one CPU
+ * core, for a whole batch of chunks in three launches.  corpus: the samples of every recording back to back, storage 0 = f32,
+ * 1 = 16-bit PCM decoded as v / 32768 (what soundfile returns for such a file with dtype='float32').  A chunk is treated as a
+ * file of its own: its log-mel frames are those of eend_stft_logmel23_f32 on corpus[off .. off + len) with first = -100, its
+ * normalisation (mode 0 = logmel23, 1 = logmel23_mn, 2 = logmel23_cummn) that of eend_feature_meannorm_f32 with the fp64 sums
+ * added in the same order, its rows those of eend_splice_subsample_f32: all three bit for bit.
+ * desc i64 [n_chunks][8], one row per chunk: {off = index in corpus of its first sample, len = its samples (already clipped at
+ * the end of the recording), n = its log-mel frames (1 + len / 80, minus one when len % 80 == 0), row of its first frame in Y,
+ * start, end = the chunk in STFT frames of its recording as the dataset row names it (end not clipped), seg0, seg1 = its
+ * recording's range of rows in segments}.  stft_tiles i64 [n_stft][3]: {desc row, first frame, frames <= 64}; splice_tiles i64
+ * [n_splice][4]: {desc row, first model frame j, frames <= 16, output row}.  segments i32 [rows][3]: {start_frame, end_frame,
+ * speaker index}, CSR by recording, frames rounded on the host (feature.py:305-308).  Label rule (feature.py:301-317) for a
+ * chunk [start, end) of n frames: a = start_frame - start if start <= start_frame < end, b = end_frame - start if start <
+ * end_frame <= end; a segment with neither is skipped (also one that covers the whole chunk); else frames [a or 0, min(b or n,
+ * n)) of its speaker are 1.  Y, Yn f32 scratch [sum n][23] (Yn unused with mode 0); feats f32 [sum ceil(n / sub)][23 (2 ctx +
+ * 1)], labels f32 [sum ceil(n / sub)][S_max] (0.0 / 1.0; columns of speakers without a segment stay 0), both fully written.
+ * Stateless, stream-ordered, nothing allocated, the host not waited for; the descriptors are trusted (the host checks off + len
+ * against the corpus, see fs-eend_amd/device_data.py).  EEND_EINVAL: a NULL pointer that is needed, storage outside 0 .. 1,
+ * mode outside 0 .. 2, ctx outside 0 .. 64, sub outside 1 .. 4096, S_max outside 1 .. 64, n_chunks above 65535.  Limits: frame
+ * size 200 and shift 80 at 8 kHz only; at most 2^31 - 1 frames and output rows per call; speaker-id targets (use_speaker_id),
+ * frame shuffling and reflect padding are not covered. */
+int eend_chunk_batch_f32(const void* corpus, int storage, const int* segments, const long* desc, int n_chunks,
+                         const long* stft_tiles, int n_stft, const long* splice_tiles, int n_splice, float* Y, float* Yn,
+                         float* feats, float* labels, int S_max, int mode, int ctx, int sub, const float* dft, const float* melT,
+                         void* stream);
+
 /* Audio ingest in front of eend_audio_feed_f32: many streams ("slots"), each fed raw audio at one sample rate and encoding in
  * chunks of any size, decoded and converted to f32 samples at 8 kHz.  encoding 0 = f32 (the value itself), 1 = 16-bit PCM
  * (v / 32768), 2 = G.711 mu-law, 3 = G.711 A-law (decode f32 [2][256]: the value of every mu-law, then every A-law byte).
