@@ -14,27 +14,26 @@ is computed in float64 and rounded to f32; L == M == 1 has no filter (H = 0, h =
     y[n] = sum over k = ceil((n M - H) / L) .. floor((n M + H) / L) of h[n M - k L] x[k],   x zero outside [0, n_in)
 
 accumulated in f32 with fmaf from zero in ascending k, so a sample's bits do not depend on how the audio was cut.  The
-counters are host integers (`IngestTable`): while a stream is open, recv samples make max(0, ceil((recv L - H) / M)) outputs
-ready; at its end all ceil(n_in L / M) exist; after n outputs the oldest sample still needed is max(0, ceil((n M - H) / L)),
+counters are host integers (`IngestTable`, an `audio_plan.SlotTable`): while a stream is open, recv samples make
+max(0, ceil((recv L - H) / M)) outputs ready; at its end all ceil(n_in L / M) exist; after n outputs the oldest sample still needed is max(0, ceil((n M - H) / L)),
 so a slot's history is fewer than P <= 255 samples.  The latency is `zeros` output samples (2 ms with the default 16).
 Supported: rate >= 8000 with P <= 255 (with the defaults 8000, 11025, 12000, 16000, 22050, 24000, 32000, 44100, 48000 Hz).
 """
 import math
+from dataclasses import dataclass
 from functools import lru_cache
 
 import numpy as np
 import torch
 
 from . import lib as _lib
+from .audio_plan import DESC_N, F32, HIST, OPEN, TILE, SlotTable, Staging, there
 from .multistream import SlotError
 
-F32 = torch.float32
 OUT_RATE = 8000
 MAX_TAPS = 255
-HIST, TILE, DESC_N = 256, 256, 8           # history row and outputs per tile of csrc/resample.hip, descriptor fields
-ENCODINGS = {"f32": 0, "s16": 1, "mulaw": 2, "alaw": 3}
+ENCODINGS = {"f32": 0, "s16": 1, "mulaw": 2, "alaw": 3}     # enum ENC_* of csrc/resample.hip
 DTYPES = {"f32": torch.float32, "s16": torch.int16, "mulaw": torch.uint8, "alaw": torch.uint8}
-FREE, OPEN, ENDED = "free", "open", "ended"
 
 
 def _cdiv(a: int, b: int) -> int:
@@ -161,131 +160,63 @@ def launch(d: Design, encoding: str, desc, n_desc, tiles, n_tiles, hist, out, de
                "eend_audio_ingest")
 
 
+@dataclass(slots=True)
+class SlotIngest:
+    """What one feed does to one slot: input samples recv0 -> recv1, outputs out0 -> out1."""
+    slot: int
+    recv0: int
+    recv1: int
+    out0: int
+    out1: int
+    ended: bool
+
+
+class IngestTable(SlotTable):
+    """Host bookkeeping of the ingest (`audio_plan.SlotTable`, like `audio_stream.FrontEndTable`): per slot the input samples
+    received and the 8 kHz samples made."""
+
+    counters = {"recv": "recv1", "outs": "out1"}
+
+    def __init__(self, slots: int, d: Design):
+        super().__init__(slots, "an ingest")
+        self.d = d
+
+    def advance(self, s, recv1, ended):
+        return SlotIngest(s, self.recv[s], recv1, self.outs[s], self.d.ready(recv1, ended), ended)
+
+
+def stage(plan, waves, staging):
+    """The ingest's words for `plan` (chunks placed through `staging`): -> (words, indices of the chunk addresses in it,
+    number of tiles, {slot: (first index in the packed output, new outputs)}, outputs in all)."""
+    desc, tiles, rows = [], [], {}
+    n_out = 0
+    for i, p in enumerate(plan):
+        desc.append([staging.place(waves.get(p.slot)), p.recv0, p.recv1, p.out0, p.out1, n_out, int(p.ended), p.slot])
+        tiles += [[i, n, min(TILE, p.out1 - n)] for n in range(p.out0, p.out1, TILE)]
+        rows[p.slot] = (n_out, p.out1 - p.out0)
+        n_out += p.out1 - p.out0
+    words = [v for d in desc for v in d] + [v for t in tiles for v in t]
+    return words, [DESC_N * i for i in range(len(desc))], len(tiles), rows, n_out
+
+
 def convert(data, sample_rate: int, encoding: str = "f32", zeros: int = 16, beta: float = 9.0, rolloff: float = 0.9):
-    """A whole recording (1-D GPU tensor of the encoding's dtype) -> its f32 samples at 8 kHz, the bits a stream of it gives."""
+    """A whole recording (1-D GPU tensor of the encoding's dtype) -> its f32 samples at 8 kHz, the bits a stream of it gives:
+    one slot fed the recording and its end in one call."""
     check_encoding(encoding)
     d = design(sample_rate, zeros, beta, rolloff)
     data = samples(encoding, "convert", data)
     if not data.is_cuda:
         raise _lib.EendHipError("audio_ingest.convert: expected a GPU tensor (the HIP path has no CPU fallback)")
     dev = data.device
-    data = data.to(DTYPES[encoding]).contiguous()
-    n_in = data.numel()
-    n_out = d.ready(n_in, True)
+    table = IngestTable(1, d)
+    table.reset(0)
+    staging = Staging(dev, DTYPES[encoding])
+    words, chunk_at, n_tiles, _rows, n_out = stage(table.plan({0: data.numel()}, end=[0]), {0: data}, staging)
     out = torch.empty(n_out, dtype=F32, device=dev)
-    if n_out == 0:
-        return out
-    first = torch.arange(0, n_out, TILE, dtype=torch.int64)
-    tiles = torch.stack([torch.zeros_like(first), first, (n_out - first).clamp(max=TILE)], dim=1)
-    words = torch.cat([torch.tensor([data.data_ptr(), 0, n_in, 0, n_out, 0, 1, 0], dtype=torch.int64), tiles.reshape(-1)]).to(dev)
-    hist = torch.zeros(1, HIST, dtype=F32, device=dev)
-    launch(d, encoding, words.data_ptr(), 1, words.data_ptr() + 8 * DESC_N, tiles.shape[0], hist, out, dev)
+    if n_out:
+        _dbuf, base = staging.upload(words, chunk_at)
+        launch(d, encoding, base, 1, base + 8 * DESC_N, n_tiles, torch.zeros(1, HIST, dtype=F32, device=dev), out, dev)
     return out
-
-
-class Staging:
-    """The block a feed sends to the device with one asynchronous copy: i64 words (descriptors and tile tables) first, then the
-    CPU chunks of the call as `dtype`, each starting on a multiple of `every` elements.  `place` returns a chunk's device
-    address, or -1 - (its element offset behind the words) for `upload` to patch."""
-
-    def __init__(self, dev, dtype, every: int):
-        self.dev, self.dtype, self.every = dev, dtype, every
-        self.esize = 8 // every
-        self.keep, self.host, self.n = [], [], 0            # device chunks kept alive; (element offset, CPU chunk); elements placed
-
-    def place(self, w) -> int:
-        if w is None or not w.numel():
-            return 0
-        if w.is_cuda:
-            w = w.to(device=self.dev, dtype=self.dtype).contiguous()
-            self.keep.append(w)
-            return w.data_ptr()
-        off = self.n
-        self.host.append((off, w.to(self.dtype).contiguous()))
-        self.n = -(-(off + w.numel()) // self.every) * self.every
-        return -1 - off
-
-    def upload(self, words, chunk_at):
-        """words: the i64 words; chunk_at: the indices in it of values `place` returned.  -> (device block, its address)."""
-        head = 8 * len(words)
-        nbytes = head + self.esize * self.n
-        dbuf = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
-        base = dbuf.data_ptr()
-        for i in chunk_at:
-            if words[i] < 0:
-                words[i] = base + head + self.esize * (-1 - words[i])
-        stage = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)   # a fresh pinned block per call (copied asynchronously)
-        stage[:head].view(torch.int64).copy_(torch.tensor(words, dtype=torch.int64))
-        if self.n:
-            samples = stage[head:].view(self.dtype)
-            for off, w in self.host:
-                samples[off:off + w.numel()].copy_(w)
-        dbuf.copy_(stage, non_blocking=True)
-        return dbuf, base
-
-
-class SlotIngest:
-    """What one feed does to one slot: input samples recv0 -> recv1, outputs out0 -> out1."""
-
-    __slots__ = ("slot", "recv0", "recv1", "out0", "out1", "ended")
-
-    def __init__(self, **kw):
-        for k, v in kw.items():
-            setattr(self, k, v)
-
-
-class IngestTable:
-    """Host bookkeeping of the ingest (pure Python, no device), like `audio_stream.FrontEndTable`: per slot its state free /
-    open / ended, the input samples received and the 8 kHz samples made."""
-
-    def __init__(self, slots: int, d: Design):
-        if slots <= 0:
-            raise SlotError("an ingest needs at least one slot")
-        self.S, self.d = slots, d
-        self.state = [FREE] * slots
-        self.recv = [0] * slots
-        self.outs = [0] * slots
-
-    def _check(self, s):
-        if not isinstance(s, int) or not 0 <= s < self.S:
-            raise SlotError(f"slot {s!r} out of range 0..{self.S - 1}")
-
-    def reset(self, s):
-        self._check(s)
-        self.state[s] = OPEN
-        self.recv[s] = self.outs[s] = 0
-
-    def close(self, s):
-        self._check(s)
-        self.state[s] = FREE
-
-    def plan(self, counts, end=()):
-        """counts: {slot: new input samples}; end: slots whose audio ends with this call.  -> [SlotIngest] in slot order."""
-        counts, end = dict(counts), list(end)
-        if len(set(end)) != len(end):
-            raise SlotError("a slot is named twice in end")
-        for s in list(counts) + end:
-            self._check(s)
-            if self.state[s] == FREE:
-                raise SlotError(f"slot {s} is not open (reset it first)")
-            if self.state[s] == ENDED:
-                raise SlotError(f"slot {s} was fed its end; reset it to start a new stream")
-        for s, n in counts.items():
-            if not isinstance(n, int) or n < 0:
-                raise ValueError(f"slot {s}: sample count must be a non-negative int, got {n!r}")
-        out = []
-        for s in sorted(set(counts) | set(end)):
-            ended = s in end
-            recv1 = self.recv[s] + counts.get(s, 0)
-            out.append(SlotIngest(slot=s, recv0=self.recv[s], recv1=recv1, out0=self.outs[s], out1=self.d.ready(recv1, ended),
-                                  ended=ended))
-        return out
-
-    def commit(self, plan):
-        for p in plan:
-            self.recv[p.slot], self.outs[p.slot] = p.recv1, p.out1
-            if p.ended:
-                self.state[p.slot] = ENDED
 
 
 class AudioIngest:
@@ -304,7 +235,6 @@ class AudioIngest:
         check_encoding(encoding)
         self.d = design(sample_rate, zeros, beta, rolloff)
         self.encoding, self.dtype = encoding, DTYPES[encoding]
-        self.every = 8 // torch.empty(0, dtype=self.dtype).element_size()       # chunks start 8-byte aligned in the staging block
         self.table = IngestTable(slots, self.d)
         self.S = slots
         self.dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -332,40 +262,17 @@ class AudioIngest:
         return {"rate": d.rate, "encoding": self.encoding, "zeros": d.zeros, "beta": d.beta, "rolloff": d.rolloff}
 
     def export(self, s: int) -> dict:
-        self.table._check(s)
-        if self.table.state[s] == FREE:
-            raise SlotError(f"slot {s} is not open (reset it first)")
-        return {"config": self._config(), "hist": self.hist[s].clone(), "recv": self.table.recv[s], "outs": self.table.outs[s]}
+        return self.table.export(s, self._config(), {"hist": self.hist})
 
     def check_part(self, part):
         """SlotError unless `part` is an export of an ingest configured like this one."""
-        ok = (isinstance(part, dict) and part.get("config") == self._config()
-              and all(isinstance(part.get(k), int) and part[k] >= 0 for k in ("recv", "outs"))
-              and torch.is_tensor(part.get("hist")) and part["hist"].shape == (HIST,) and part["hist"].dtype == F32)
-        if not ok:
+        if not self.table.fits(part, self._config(), {"hist": self.hist}):
             raise SlotError("resume: the snapshot's ingest does not fit this front-end "
-                            f"(here {self._config()}, there {part.get('config') if isinstance(part, dict) else part!r})")
+                            f"(here {self._config()}, there {there(part)!r})")
 
     def adopt(self, s: int, part, state: str = OPEN):
         """Slot s goes on from an exported `part` (checked by check_part) in `state`: a row copy on the current stream."""
-        self.table._check(s)
-        self.hist[s].copy_(part["hist"], non_blocking=True)
-        t = self.table
-        t.state[s], t.recv[s], t.outs[s] = state, part["recv"], part["outs"]
-
-    # ---- one call
-    def stage(self, plan, waves, staging):
-        """The ingest's words for `plan` (chunks placed through `staging`): -> (words, indices of the chunk addresses in it,
-        number of tiles, {slot: (first index in the packed output, new outputs)}, outputs in all)."""
-        desc, tiles, rows = [], [], {}
-        n_out = 0
-        for i, p in enumerate(plan):
-            desc.append([staging.place(waves.get(p.slot)), p.recv0, p.recv1, p.out0, p.out1, n_out, int(p.ended), p.slot])
-            tiles += [[i, n, min(TILE, p.out1 - n)] for n in range(p.out0, p.out1, TILE)]
-            rows[p.slot] = (n_out, p.out1 - p.out0)
-            n_out += p.out1 - p.out0
-        words = [v for d in desc for v in d] + [v for t in tiles for v in t]
-        return words, [DESC_N * i for i in range(len(desc))], len(tiles), rows, n_out
+        self.table.adopt(s, part, {"hist": self.hist}, state)
 
     def launch(self, desc, n_desc, n_tiles, out):
         launch(self.d, self.encoding, desc, n_desc, desc + 8 * DESC_N * n_desc, n_tiles, self.hist, out, self.dev)
@@ -378,8 +285,8 @@ class AudioIngest:
         plan = self.table.plan({s: int(w.numel()) for s, w in waves.items()}, end)
         if not plan:
             return {}
-        staging = Staging(self.dev, self.dtype, self.every)
-        words, chunk_at, n_tiles, rows, n_out = self.stage(plan, waves, staging)
+        staging = Staging(self.dev, self.dtype)
+        words, chunk_at, n_tiles, rows, n_out = stage(plan, waves, staging)
         _dbuf, base = staging.upload(words, chunk_at)
         out = torch.empty(max(n_out, 1), dtype=F32, device=self.dev)
         self.launch(base, len(plan), n_tiles, out)

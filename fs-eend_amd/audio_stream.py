@@ -5,43 +5,42 @@
 the splice pads with zeros past the last frame and `logmel23_cummn` normalises by the running mean of every earlier frame.
 Both shipped transforms are causal, so they can be computed as the audio arrives.  Per slot the device keeps the sample tail
 (fewer than 200 samples), the fp64 column sums of the running mean and a ring of the last normalised log-mel frames that the
-splice of the next model frame reads; the host keeps the counters, which depend on sample counts only
-(`FrontEndTable`).  With pad_mode "constant" (first sample of frame f at 80 f - 100, as `feature.logmel`):
+splice of the next model frame reads; the host keeps the counters, which depend on sample counts only (`FrontEndTable`, an
+`audio_plan.SlotTable`).  With pad_mode "constant" (first sample of frame f at 80 f - 100, as `feature.logmel`):
 
     log-mel frame f is ready once 80 f + 100 samples are in;
     model frame j (frames sub j - ctx .. sub j + ctx) once log-mel frame sub j + ctx exists;
-    at the end of a stream of n samples the rest follow the batch rules: n_frames = 1 + n // 80 - (n % 80 == 0) log-mel
-    frames (zero samples past n) and ceil(n_frames / sub) model frames (zero frames past n_frames).
+    at the end of a stream of n samples the rest follow the batch rules: `audio_plan.stft_frames(n)` log-mel frames, 1 + n // 80
+    less the excess last one (zero samples past n), and ceil(n_frames / sub) model frames (zero frames past n_frames).
 
 `logmel23` frames are bit-identical to the batch front-end (the same STFT tile body); `logmel23_cummn` adds the fp64 running
 sum strictly in frame order, so its features do not depend on how the audio was cut, and differ from the batch path (which
-sums in another order) by about one float ulp of the mean.  One `feed` costs three launches and one host-to-device copy,
-whatever the number of slots or the chunk sizes, and never waits for the device.
+sums in another order) by about one float ulp of the mean.  One `feed` costs three launches and one host-to-device copy
+(`audio_plan.Staging`: the words that `feed_words` builds, then the CPU chunks), whatever the number of slots or the chunk
+sizes, and never waits for the device.
 
 Audio that is not 8 kHz float goes through `audio_ingest.AudioIngest` first (`sample_rate=`, `encoding=`: G.711 mu-law / A-law,
 16-bit PCM or float at 8 .. 48 kHz): the raw chunks travel at their own width in the same staging block, two more launches
 decode and convert them on the device into a packed f32 buffer, and the feed descriptors point at that buffer.  The converted
 samples do not depend on how the audio was cut either, so the contract above starts at the wire.
 """
+from dataclasses import dataclass
+
 import torch
 
 from . import audio_ingest, feature
 from . import lib as _lib
+from .audio_plan import ENDED, F32, FB, FEED_N, FREE, HOP, NMEL, OPEN, RING, SPL_ROWS, TAIL, SlotTable, Staging, stft_frames, there
 from .multistream import SlotError, check_parts
 
-F32 = torch.float32
-HOP, WIN_END = 80, 100                   # frame f reads samples 80 f - 100 .. 80 f + 99
-TAIL, RING, NMEL = 200, 32, 23             # per-slot device state of csrc/feature.hip
-FB, SPL_ROWS, FEED_N = 64, 16, 9           # log-mel frames per STFT tile, model frames per splice tile, descriptor fields
+WIN_END = 100                              # frame f reads samples 80 f - 100 .. 80 f + 99
 MODES = {"logmel23": 0, "logmel23_cummn": 2}
-
-FREE, OPEN, ENDED = "free", "open", "ended"
 
 
 def logmel_frames(n: int, ended: bool) -> int:
     """Log-mel frames computable from n samples: all of them at the end of the stream (feature.logmel's count)."""
     if ended:
-        return 1 + n // HOP - (1 if n % HOP == 0 else 0)
+        return stft_frames(n)
     return (n - WIN_END) // HOP + 1 if n >= WIN_END else 0
 
 
@@ -57,79 +56,59 @@ def ring_start(T: int, j: int, ctx: int, sub: int) -> int:
     return max(0, min(T, sub * j - ctx))
 
 
+@dataclass(slots=True)
 class SlotFeed:
     """What one feed does to one slot: samples recv0 -> recv1, log-mel frames f0 -> f1, model frames j0 -> j1, the ring holding
     frames rb0 .. f0 - 1 before and rb1 .. f1 - 1 after."""
+    slot: int
+    recv0: int
+    recv1: int
+    f0: int
+    f1: int
+    j0: int
+    j1: int
+    rb0: int
+    rb1: int
+    ended: bool
 
-    __slots__ = ("slot", "recv0", "recv1", "f0", "f1", "j0", "j1", "rb0", "rb1", "ended")
 
-    def __init__(self, **kw):
-        for k, v in kw.items():
-            setattr(self, k, v)
+class FrontEndTable(SlotTable):
+    """Host bookkeeping of the incremental front-end (`audio_plan.SlotTable`): per slot the samples received, log-mel frames
+    and model frames emitted."""
 
-
-class FrontEndTable:
-    """Host bookkeeping of the incremental front-end (pure Python, no device): per slot its state free / open / ended and the
-    samples received, log-mel frames and model frames emitted.  reset(s) starts an empty stream in any slot; a slot fed its
-    end accepts no more audio until the next reset."""
+    counters = {"recv": "recv1", "frames": "f1", "mframes": "j1"}
 
     def __init__(self, slots: int, context_size: int = 7, subsampling: int = 10):
-        if slots <= 0:
-            raise SlotError("a front-end needs at least one slot")
+        super().__init__(slots, "a front-end")
         if not 0 <= context_size <= 15:
             raise ValueError(f"context_size must be in 0..15, got {context_size}")
         if not 1 <= subsampling <= 16:
             raise ValueError(f"subsampling must be in 1..16, got {subsampling}")
-        self.S, self.ctx, self.sub = slots, context_size, subsampling
-        self.state = [FREE] * slots
-        self.recv = [0] * slots
-        self.frames = [0] * slots
-        self.mframes = [0] * slots
+        self.ctx, self.sub = context_size, subsampling
 
-    def _check(self, s):
-        if not isinstance(s, int) or not 0 <= s < self.S:
-            raise SlotError(f"slot {s!r} out of range 0..{self.S - 1}")
-
-    def reset(self, s):
-        self._check(s)
-        self.state[s] = OPEN
-        self.recv[s] = self.frames[s] = self.mframes[s] = 0
-
-    def close(self, s):
-        self._check(s)
-        self.state[s] = FREE
-
-    def plan(self, counts, end=()):
-        """counts: {slot: new samples}; end: slots whose audio ends with this call.  -> [SlotFeed] in slot order."""
-        counts, end = dict(counts), list(end)
-        if len(set(end)) != len(end):
-            raise SlotError("a slot is named twice in end")
-        for s in list(counts) + end:
-            self._check(s)
-            if self.state[s] == FREE:
-                raise SlotError(f"slot {s} is not open (reset it first)")
-            if self.state[s] == ENDED:
-                raise SlotError(f"slot {s} was fed its end; reset it to start a new stream")
-        for s, n in counts.items():
-            if not isinstance(n, int) or n < 0:
-                raise ValueError(f"slot {s}: sample count must be a non-negative int, got {n!r}")
+    def advance(self, s, recv1, ended):
         ctx, sub = self.ctx, self.sub
-        out = []
-        for s in sorted(set(counts) | set(end)):
-            ended = s in end
-            recv0, f0, j0 = self.recv[s], self.frames[s], self.mframes[s]
-            recv1 = recv0 + counts.get(s, 0)
-            f1 = logmel_frames(recv1, ended)
-            j1 = model_frames(f1, ended, ctx, sub)
-            out.append(SlotFeed(slot=s, recv0=recv0, recv1=recv1, f0=f0, f1=f1, j0=j0, j1=j1,
-                                rb0=ring_start(f0, j0, ctx, sub), rb1=ring_start(f1, j1, ctx, sub), ended=ended))
-        return out
+        f0, j0 = self.frames[s], self.mframes[s]
+        f1 = logmel_frames(recv1, ended)
+        j1 = model_frames(f1, ended, ctx, sub)
+        return SlotFeed(s, self.recv[s], recv1, f0, f1, j0, j1, ring_start(f0, j0, ctx, sub), ring_start(f1, j1, ctx, sub), ended)
 
-    def commit(self, plan):
-        for p in plan:
-            self.recv[p.slot], self.frames[p.slot], self.mframes[p.slot] = p.recv1, p.f1, p.j1
-            if p.ended:
-                self.state[p.slot] = ENDED
+
+def feed_words(plan, chunks):
+    """The words of one eend_audio_feed_f32 call (host arithmetic only): `plan` a FrontEndTable's, `chunks` the address of each
+    planned slot's new samples, in the plan's order.  -> (desc rows of FEED_N, stft tiles {descriptor, first frame, frames <=
+    FB}, splice tiles {descriptor, first model frame, rows <= SPL_ROWS, output row}, {slot: (first output row, rows)}, y_rows,
+    o_rows).  A slot's region of the scratch Y starts at its y row with its ring frames rb0 .. f0 - 1, then its new frames."""
+    desc, stft, splice, rows = [], [], [], {}
+    y_rows = o_rows = 0
+    for i, (p, ptr) in enumerate(zip(plan, chunks)):
+        desc.append([ptr, p.recv0, p.recv1, p.f0, p.f1, p.rb0, p.rb1, y_rows, p.slot])
+        stft += [[i, f, min(FB, p.f1 - f)] for f in range(p.f0, p.f1, FB)]
+        splice += [[i, j, min(SPL_ROWS, p.j1 - j), o_rows + j - p.j0] for j in range(p.j0, p.j1, SPL_ROWS)]
+        rows[p.slot] = (o_rows, p.j1 - p.j0)
+        y_rows += p.f1 - p.rb0
+        o_rows += p.j1 - p.j0
+    return desc, stft, splice, rows, y_rows, o_rows
 
 
 class AudioFrontEnd:
@@ -192,41 +171,31 @@ class AudioFrontEnd:
     def _config(self):
         return {"mode": self.mode, "context_size": self.ctx, "subsampling": self.sub}
 
+    def _rows(self):
+        return {"tail": self.tail, "ring": self.ring, "sums": self.sums}
+
     def export(self, s: int) -> dict:
         """Slot s's front-end state as plain values and tensors: its device rows (copies) and its table fields."""
-        self.table._check(s)
-        if self.table.state[s] == FREE:
-            raise SlotError(f"slot {s} is not open (reset it first)")
-        t = self.table
-        part = {"config": self._config(), "tail": self.tail[s].clone(), "ring": self.ring[s].clone(), "sums": self.sums[s].clone(),
-                "state": t.state[s], "recv": t.recv[s], "frames": t.frames[s], "mframes": t.mframes[s]}
+        part = self.table.export(s, self._config(), self._rows())
+        part["state"] = self.table.state[s]
         if self.ingest is not None:             # config, history row and counters of the stage in front
             part["ingest"] = self.ingest.export(s)
         return part
 
     def check_part(self, part):
         """SlotError unless `part` is an export of a front-end configured like this one."""
-        ok = (isinstance(part, dict) and part.get("config") == self._config() and part.get("state") in (OPEN, ENDED)
-              and all(isinstance(part.get(k), int) and part[k] >= 0 for k in ("recv", "frames", "mframes"))
-              and all(torch.is_tensor(part.get(k)) and part[k].shape == row.shape[1:] and part[k].dtype == row.dtype
-                      for k, row in (("tail", self.tail), ("ring", self.ring), ("sums", self.sums))))
-        if not ok:
-            raise SlotError("resume: the snapshot's front-end part does not fit this front-end "
-                            f"(here {self._config()}, there {part.get('config') if isinstance(part, dict) else part!r})")
+        if not (self.table.fits(part, self._config(), self._rows()) and part.get("state") in (OPEN, ENDED)):
+            raise SlotError(f"resume: the snapshot's front-end part does not fit this front-end (here {self._config()}, "
+                            f"there {there(part)!r})")
         if self.ingest is not None:
             self.ingest.check_part(part.get("ingest"))
         elif "ingest" in part:
-            raise SlotError("resume: the snapshot's audio was ingested as "
-                            f"{part['ingest'].get('config') if isinstance(part['ingest'], dict) else part['ingest']!r}, this "
-                            "front-end takes 8 kHz float samples")
+            raise SlotError(f"resume: the snapshot's audio was ingested as {there(part['ingest'])!r}, this front-end takes 8 kHz "
+                            "float samples")
 
     def adopt(self, s: int, part):
         """Slot s goes on from an exported `part` (checked by check_part): ordinary row copies on the current stream."""
-        self.table._check(s)
-        for k, rows in (("tail", self.tail), ("ring", self.ring), ("sums", self.sums)):
-            rows[s].copy_(part[k], non_blocking=True)
-        t = self.table
-        t.state[s], t.recv[s], t.frames[s], t.mframes[s] = part["state"], part["recv"], part["frames"], part["mframes"]
+        self.table.adopt(s, part, self._rows(), part["state"])
         if self.ingest is not None:
             self.ingest.adopt(s, part["ingest"], part["state"])
 
@@ -243,93 +212,37 @@ class AudioFrontEnd:
     @torch.no_grad()
     def feed(self, waves=None, end=()):
         """waves: {slot: 1-D tensor (CPU or GPU) of its next samples, float at 8 kHz or as sample_rate / encoding say}; end: slots
-        whose audio ends here.  -> {slot: (n, width) f32 device tensor of its new model frames} for every slot named."""
-        if self.ingest is not None:
-            return self._feed_ingest(waves, end)
-        waves = {s: self._samples(s, w) for s, w in dict(waves or {}).items()}
-        plan = self.table.plan({s: int(w.numel()) for s, w in waves.items()}, end)
-        if not plan:
-            return {}
-        dev, W = self.dev, self.width
-        desc, stft, splice = [], [], []
-        keep, host = [], []                     # device chunks to keep alive; (sample offset, CPU chunk) for the staging block
-        n_host = y_rows = o_rows = 0
-        rows = {}
-        for i, p in enumerate(plan):
-            w = waves.get(p.slot)
-            ptr = 0
-            if w is not None and w.numel():
-                if w.is_cuda:
-                    w = w.to(device=dev, dtype=F32).contiguous()
-                    keep.append(w)
-                    ptr = w.data_ptr()
-                else:
-                    host.append((n_host, w.to(F32).contiguous()))
-                    ptr = -1 - n_host           # patched to the device address below
-                    n_host += w.numel()
-            desc.append([ptr, p.recv0, p.recv1, p.f0, p.f1, p.rb0, p.rb1, y_rows, p.slot])
-            stft += [[i, f, min(FB, p.f1 - f)] for f in range(p.f0, p.f1, FB)]
-            splice += [[i, j, min(SPL_ROWS, p.j1 - j), o_rows + j - p.j0] for j in range(p.j0, p.j1, SPL_ROWS)]
-            rows[p.slot] = (o_rows, p.j1 - p.j0)
-            y_rows += p.f1 - p.rb0
-            o_rows += p.j1 - p.j0
-        n_words = FEED_N * len(desc) + 3 * len(stft) + 4 * len(splice)
-        nbytes = 8 * n_words + 4 * n_host
-        dbuf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        base = dbuf.data_ptr()
-        for d in desc:
-            if d[0] < 0:
-                d[0] = base + 8 * n_words + 4 * (-1 - d[0])
-        words = [v for d in desc for v in d] + [v for t in stft for v in t] + [v for t in splice for v in t]
-        stage = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)   # a fresh pinned block per call (copied asynchronously)
-        stage[:8 * n_words].view(torch.int64).copy_(torch.tensor(words, dtype=torch.int64))
-        if n_host:
-            samples = stage[8 * n_words:].view(F32)
-            for off, w in host:
-                samples[off:off + w.numel()].copy_(w)
-        dbuf.copy_(stage, non_blocking=True)
-        Y = torch.empty(max(y_rows, 1), NMEL, dtype=F32, device=dev)
-        out = torch.empty(o_rows, W, dtype=F32, device=dev)
-        L = _lib.load()
-        _lib.check(L.eend_audio_feed_f32(base, len(desc), base + 8 * FEED_N * len(desc), len(stft),
-                                         base + 8 * (FEED_N * len(desc) + 3 * len(stft)), len(splice),
-                                         self.tail.data_ptr(), self.ring.data_ptr(), self.sums.data_ptr(), Y.data_ptr(),
-                                         out.data_ptr() if o_rows else None, self.mode, self.ctx, self.sub, self.dft.data_ptr(),
-                                         self.melT.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "eend_audio_feed_f32")
-        self.table.commit(plan)
-        del keep
-        return {s: out[o:o + n] for s, (o, n) in rows.items()}
+        whose audio ends here.  -> {slot: (n, width) f32 device tensor of its new model frames} for every slot named.
 
-    def _feed_ingest(self, waves, end):
-        """feed with the ingest in front: both tables planned, the raw chunks at their own width behind both descriptor sets in
-        one staging block, the ingest launched into a packed f32 buffer that the feed descriptors point at, both tables
-        committed after both calls returned."""
-        ing = self.ingest
-        waves = {s: ing.samples(s, w) for s, w in dict(waves or {}).items()}
-        iplan = ing.table.plan({s: int(w.numel()) for s, w in waves.items()}, end)
-        plan = self.table.plan({p.slot: p.out1 - p.out0 for p in iplan}, end)      # the front-end is fed what the ingest makes
+        With an ingest in front both tables are planned, the raw chunks travel at their own width behind both sets of words in
+        the one staging block, the ingest is launched into a packed f32 buffer that the feed descriptors point at, and both
+        tables are committed after both calls returned."""
+        ing, dev = self.ingest, self.dev
+        waves = {s: (self._samples if ing is None else ing.samples)(s, w) for s, w in dict(waves or {}).items()}
+        counts = {s: int(w.numel()) for s, w in waves.items()}
+        if ing is not None:
+            iplan = ing.table.plan(counts, end)
+            counts = {p.slot: p.out1 - p.out0 for p in iplan}      # the front-end is fed what the ingest makes
+        plan = self.table.plan(counts, end)
         if not plan:
             return {}
-        dev, W = self.dev, self.width
-        staging = audio_ingest.Staging(dev, ing.dtype, ing.every)
-        iwords, ichunk_at, n_itiles, x_at, n_x = ing.stage(iplan, waves, staging)
-        x8 = torch.empty(max(n_x, 1), dtype=F32, device=dev)
-        desc, stft, splice = [], [], []
-        y_rows = o_rows = 0
-        rows = {}
-        for i, p in enumerate(plan):
-            desc.append([x8.data_ptr() + 4 * x_at[p.slot][0], p.recv0, p.recv1, p.f0, p.f1, p.rb0, p.rb1, y_rows, p.slot])
-            stft += [[i, f, min(FB, p.f1 - f)] for f in range(p.f0, p.f1, FB)]
-            splice += [[i, j, min(SPL_ROWS, p.j1 - j), o_rows + j - p.j0] for j in range(p.j0, p.j1, SPL_ROWS)]
-            rows[p.slot] = (o_rows, p.j1 - p.j0)
-            y_rows += p.f1 - p.rb0
-            o_rows += p.j1 - p.j0
-        words = [v for d in desc for v in d] + [v for t in stft for v in t] + [v for t in splice for v in t]
+        if ing is None:
+            staging = Staging(dev, F32)
+            chunks, iwords, ichunk_at = [staging.place(waves.get(p.slot)) for p in plan], [], []
+        else:
+            staging = Staging(dev, ing.dtype)
+            iwords, ichunk_at, n_itiles, x_at, n_x = audio_ingest.stage(iplan, waves, staging)
+            x8 = torch.empty(max(n_x, 1), dtype=F32, device=dev)
+            chunks = [x8.data_ptr() + 4 * x_at[p.slot][0] for p in plan]
+        desc, stft, splice, rows, y_rows, o_rows = feed_words(plan, chunks)
+        words = [v for part in (desc, stft, splice) for row in part for v in row]
         n_words = len(words)
-        _dbuf, base = staging.upload(words + iwords, [n_words + i for i in ichunk_at])
+        chunk_at = list(range(0, FEED_N * len(desc), FEED_N)) + [n_words + i for i in ichunk_at]
+        _dbuf, base = staging.upload(words + iwords, chunk_at)
         Y = torch.empty(max(y_rows, 1), NMEL, dtype=F32, device=dev)
-        out = torch.empty(o_rows, W, dtype=F32, device=dev)
-        ing.launch(base + 8 * n_words, len(iplan), n_itiles, x8)
+        out = torch.empty(o_rows, self.width, dtype=F32, device=dev)
+        if ing is not None:
+            ing.launch(base + 8 * n_words, len(iplan), n_itiles, x8)
         _lib.check(_lib.load().eend_audio_feed_f32(base, len(desc), base + 8 * FEED_N * len(desc), len(stft),
                                                    base + 8 * (FEED_N * len(desc) + 3 * len(stft)), len(splice),
                                                    self.tail.data_ptr(), self.ring.data_ptr(), self.sums.data_ptr(), Y.data_ptr(),
@@ -337,7 +250,8 @@ class AudioFrontEnd:
                                                    self.dft.data_ptr(), self.melT.data_ptr(),
                                                    torch.cuda.current_stream(dev).cuda_stream), "eend_audio_feed_f32")
         self.table.commit(plan)
-        ing.table.commit(iplan)
+        if ing is not None:
+            ing.table.commit(iplan)
         return {s: out[o:o + n] for s, (o, n) in rows.items()}
 
 

@@ -170,6 +170,14 @@ void colnorm_kernel(const float* __restrict__ Y, float* __restrict__ out, int T,
     colnorm_column(Y, out, T, F, blockIdx.x, mode, wsum, &carry_s);
 }
 
+// Element e = c * F + m of model frame j, the splice of frames j sub - ctx .. j sub + ctx side by side: Y[f - row0][m] for
+// f = j sub + c - ctx in [lo, hi) (Y's first row is frame row0), zero outside.  The one rule of all three splice kernels.
+__device__ __forceinline__ float splice_at(const float* Y, long lo, long hi, long row0, long j, int e, int F, int ctx, int sub) {
+    const int c = e / F, m = e - c * F;
+    const long f = j * sub + c - ctx;
+    return (f >= lo && f < hi) ? Y[(f - row0) * F + m] : 0.f;
+}
+
 // out[j][c * F + m] = Y[j * sub + c - ctx][m] (zero outside [0, T)): splice of 2 ctx + 1 frames, every sub-th row
 __global__ __launch_bounds__(256)
 void splice_subsample_kernel(const float* __restrict__ Y, int T, int F, int ctx, int sub, int To, float* __restrict__ out) {
@@ -177,9 +185,7 @@ void splice_subsample_kernel(const float* __restrict__ Y, int T, int F, int ctx,
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (long)To * W) return;
     const int j = (int)(idx / W), e = (int)(idx - (long)j * W);
-    const int c = e / F, m = e - c * F;
-    const long t = (long)j * sub + c - ctx;
-    out[idx] = (t >= 0 && t < T) ? Y[t * F + m] : 0.f;
+    out[idx] = splice_at(Y, 0, T, 0, j, e, F, ctx, sub);
 }
 
 
@@ -192,25 +198,26 @@ void splice_subsample_kernel(const float* __restrict__ Y, int T, int F, int ctx,
 constexpr int TAIL = 200, RING = 32;
 enum { FEED_CHUNK, FEED_RECV0, FEED_RECV1, FEED_F0, FEED_F1, FEED_RB0, FEED_RB1, FEED_YBASE, FEED_SLOT, FEED_N };
 
-// One block per tile of up to FB new log-mel frames of one slot (tile = {descriptor, first frame, rows}): the samples
-// come from the slot's tail (received before this call) or from its new chunk, zero before 0 and from recv1 on.
+// Sample idx of a slot's stream during a call: zero before 0 and from recv1 on, from the new chunk from recv0 on, below that
+// from the slot's tail tl (received before this call), whose element 0 is the first sample of log-mel frame f0.
+__device__ __forceinline__ float feed_sample(long idx, const long* __restrict__ d, const float* __restrict__ tl) {
+    if (idx < 0 || idx >= d[FEED_RECV1]) return 0.f;
+    if (idx >= d[FEED_RECV0]) return ((const float*)d[FEED_CHUNK])[idx - d[FEED_RECV0]];
+    const long q = idx - (d[FEED_F0] * HOP - 100);
+    return q < TAIL ? tl[q] : 0.f;
+}
+
+// One block per tile of up to FB new log-mel frames of one slot (tile = {descriptor, first frame, rows}).
 __global__ __launch_bounds__(256)
 void feed_stft_kernel(const long* __restrict__ desc, const long* __restrict__ tiles, const float* __restrict__ tail,
                       const float* __restrict__ dft, const float* __restrict__ melT, float* __restrict__ Y) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const long* t = tiles + 3 * (long)blockIdx.x;
     const long* d = desc + FEED_N * t[0];
-    const float* chunk = (const float*)d[FEED_CHUNK];
-    const long recv0 = d[FEED_RECV0], recv1 = d[FEED_RECV1], f_a = t[1];
-    const long tbase = d[FEED_F0] * HOP - 100;                    // sample index of the tail's element 0
+    const long f_a = t[1];
     const float* tl = tail + (long)d[FEED_SLOT] * TAIL;
     const long base = f_a * HOP - 100;
-    auto gather = [=](int i) {
-        const long idx = base + i;
-        if (idx < 0 || idx >= recv1) return 0.f;
-        if (idx >= recv0) return chunk[idx - recv0];
-        return idx - tbase < TAIL ? tl[idx - tbase] : 0.f;
-    };
+    auto gather = [=](int i) { return feed_sample(base + i, d, tl); };
     float* out = Y + (d[FEED_YBASE] + f_a - d[FEED_RB0]) * NMEL;
     stft_logmel_tile(smem, gather, dft, melT, out, (int)t[2]);
 }
@@ -224,8 +231,7 @@ void feed_state_kernel(const long* __restrict__ desc, float* __restrict__ tail, 
     __shared__ float nr[RING * NMEL];
     const int tid = threadIdx.x;
     const long* d = desc + FEED_N * (long)blockIdx.x;
-    const float* chunk = (const float*)d[FEED_CHUNK];
-    const long recv0 = d[FEED_RECV0], recv1 = d[FEED_RECV1], f0 = d[FEED_F0], f1 = d[FEED_F1];
+    const long f0 = d[FEED_F0], f1 = d[FEED_F1];
     const long rb0 = d[FEED_RB0], rb1 = d[FEED_RB1], slot = d[FEED_SLOT];
     float* Ys = Y + d[FEED_YBASE] * NMEL;
     float* rg = ring + slot * RING * NMEL;
@@ -238,11 +244,7 @@ void feed_state_kernel(const long* __restrict__ desc, float* __restrict__ tail, 
         const long q = rb0 + i / NMEL - rb1;
         if (q >= 0) nr[q * NMEL + i % NMEL] = v;
     }
-    float tv = 0.f;
-    if (tid < TAIL) {
-        const long idx = f1 * HOP - 100 + tid, tbase = f0 * HOP - 100;
-        if (idx >= 0 && idx < recv1) tv = idx >= recv0 ? chunk[idx - recv0] : (idx - tbase < TAIL ? tl[idx - tbase] : 0.f);
-    }
+    const float tv = tid < TAIL ? feed_sample(f1 * HOP - 100 + tid, d, tl) : 0.f;
     float* Yn = Ys + (long)hist * NMEL;
     if (mode == 2) {
         if (tid < NMEL) {
@@ -288,9 +290,8 @@ void feed_splice_kernel(const long* __restrict__ desc, const long* __restrict__ 
     const float* Ys = Y + d[FEED_YBASE] * NMEL;
     float* o = out + t[3] * W;
     for (int i = threadIdx.x; i < rows * W; i += 256) {
-        const int r = i / W, e = i - r * W, c = e / NMEL, m = e - c * NMEL;
-        const long f = (j0 + r) * sub + c - ctx;
-        o[i] = (f >= rb && f < f1) ? Ys[(f - rb) * NMEL + m] : 0.f;
+        const int r = i / W;
+        o[i] = splice_at(Ys, rb, f1, rb, j0 + r, i - r * W, NMEL, ctx, sub);
     }
 }
 
@@ -347,9 +348,8 @@ void chunk_splice_label_kernel(const long* __restrict__ desc, const long* __rest
     const float* Ys = Y + d[CHUNK_YBASE] * NMEL;
     float* o = feats + t[3] * W;
     for (int i = threadIdx.x; i < rows * W; i += 256) {
-        const int r = i / W, e = i - r * W, c = e / NMEL, m = e - c * NMEL;
-        const long f = (j0 + r) * sub + c - ctx;
-        o[i] = (f >= 0 && f < n) ? Ys[f * NMEL + m] : 0.f;
+        const int r = i / W;
+        o[i] = splice_at(Ys, 0, n, 0, j0 + r, i - r * W, NMEL, ctx, sub);
     }
     const long start = d[CHUNK_START], end = d[CHUNK_END], seg0 = d[CHUNK_SEG0], seg1 = d[CHUNK_SEG1];
     float* lab = labels + t[3] * S_max;

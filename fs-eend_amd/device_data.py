@@ -12,8 +12,8 @@ Kaldi `segments` table live on the GPU, and one call turns a list of chunk rows 
 
 Every chunk is treated as a file of its own, so `feats[b]` is `feature.extract_fbank_wave(wave[st * 80:ed * 80], ...)` bit for
 bit (the same STFT tile body, the same order of the fp64 sums) and `labels[b]` is the reference's label matrix, subsampled.
-The host builds per-chunk descriptors and two tile tables (`plan_batch`, numpy only), which travel in one pinned block with
-one asynchronous copy.  Scratch and outputs come from a pool that grows on demand: a repeated batch shape allocates nothing, and
+The host builds per-chunk descriptors and two tile tables (`plan_batch`, numpy only; the frame count and the layout constants
+are `audio_plan`'s), which travel in one pinned block with one asynchronous copy.  Scratch and outputs come from a pool that grows on demand: a repeated batch shape allocates nothing, and
 the tensors a call returns are views of the pool that the next `batch` call of the same corpus overwrites (clone what must
 outlive it; the training step consumes them before the next batch is built).
 
@@ -26,10 +26,8 @@ import torch
 from . import data as _data
 from . import feature
 from . import lib as _lib
+from .audio_plan import CHUNK_N, F32, FB, HOP, NMEL, SPL_ROWS, WIN, stft_frames
 
-F32 = torch.float32
-HOP, WIN, NMEL = 80, 200, 23
-FB, SPL_ROWS, CHUNK_N = 64, 16, 8          # log-mel frames per STFT tile, model frames per splice tile, descriptor fields
 MODES = {"logmel23": 0, "logmel23_mn": 1, "logmel23_cummn": 2}
 STORAGES = {"f32": (0, torch.float32), "s16": (1, torch.int16)}
 MAX_ROWS, MAX_CHUNKS, MAX_SPEAKERS = 2 ** 31 - 1, 65535, 64
@@ -42,9 +40,7 @@ def chunk_samples(n_samples: int, st: int, ed: int, frame_shift: int = HOP):
     return a, min(ed * frame_shift, n_samples) - a
 
 
-def chunk_frames(length: int, frame_shift: int = HOP) -> int:
-    """STFT frames of a chunk of `length` samples (feature.py:166-191: 1 + len // shift, the excess last frame dropped)."""
-    return 1 + length // frame_shift - (1 if length % frame_shift == 0 else 0)
+chunk_frames = stft_frames                 # STFT frames of a chunk of `length` samples: a chunk is a file of its own
 
 
 def _tiles(n, step):
@@ -63,7 +59,7 @@ def plan_batch(off, length, start, end, seg0, seg1, subsampling: int):
     B = len(off)
     if B > MAX_CHUNKS:
         raise ValueError(f"a batch takes at most {MAX_CHUNKS} chunks, got {B}")
-    n = 1 + length // HOP - (length % HOP == 0)
+    n = stft_frames(length)
     T = -(-n // subsampling)
     y_rows, o_rows = int(n.sum()), int(T.sum())
     if y_rows > MAX_ROWS or o_rows > MAX_ROWS:

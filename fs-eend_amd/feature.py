@@ -6,13 +6,15 @@ subsample :133-138, extract_fbank :324-336) fused into three launches.
 The two librosa calls of the reference (librosa.stft, librosa.filters.mel; librosa is not installable here) are
 replaced by tables built below from librosa's published definitions: periodic Hann window of `frame_size`
 samples centred in an n_fft frame, centred framing with n_fft // 2 samples of padding (pad_mode "constant" as in
-librosa >= 0.10, or "reflect" as in older releases), Slaney mel scale and area normalisation.
+librosa >= 0.10, or "reflect" as in older releases), Slaney mel scale and area normalisation.  The frame count and the
+kernels' layout constants are `audio_plan`'s, shared with the streaming and the training-batch front-ends.
 """
 import math
 
 import torch
 
 from . import lib as _lib
+from .audio_plan import HOP, NMEL, WIN, stft_frames
 
 _F32 = torch.float32
 _TABLES = {}
@@ -73,32 +75,30 @@ def logmel(data, frame_size=200, frame_shift=80, input_transform="logmel23", pad
     """stft + transform of the reference for the log-mel-23 family: 1-D float32 GPU waveform -> (n_frames, 23)."""
     if not isinstance(data, torch.Tensor) or not data.is_cuda:
         raise _lib.EendHipError("feature.logmel: expected a GPU tensor (the HIP path has no CPU fallback)")
-    if frame_size != 200 or frame_shift != 80:
+    if frame_size != WIN or frame_shift != HOP:
         raise NotImplementedError("HIP feature front-end is specialised for frame_size=200, frame_shift=80 (all shipped configs)")
     if input_transform not in _MODES:
         raise ValueError("Unknown transform_type: %s" % input_transform)
     L = _lib.load()
     data = data.to(_F32).contiguous().view(-1)
     n = data.numel()
-    n_frames = 1 + n // frame_shift
-    if n % frame_shift == 0:
-        n_frames -= 1                     # feature.py:184-188: the excess last frame is dropped
+    n_frames = stft_frames(n)             # feature.py:184-188: the excess last frame is dropped
     dft, melT = _tables(data.device)
     if n_frames <= 0:
-        return torch.zeros(0, 23, dtype=_F32, device=data.device)
+        return torch.zeros(0, NMEL, dtype=_F32, device=data.device)
     first = -100                          # lpad - n_fft // 2
     if pad_mode == "reflect":
         data = torch.nn.functional.pad(data.view(1, 1, -1), (128, 128), mode="reflect").view(-1).contiguous()
         first = 28
     elif pad_mode != "constant":
         raise ValueError("pad_mode must be 'constant' or 'reflect'")
-    Y = torch.empty(n_frames, 23, dtype=_F32, device=data.device)
+    Y = torch.empty(n_frames, NMEL, dtype=_F32, device=data.device)
     _lib.check(L.eend_stft_logmel23_f32(data.data_ptr(), data.numel(), first, n_frames, dft.data_ptr(), melT.data_ptr(),
                                         Y.data_ptr(), _stream()), "eend_stft_logmel23_f32")
     mode = _MODES[input_transform]
     if mode:
         out = torch.empty_like(Y)
-        _lib.check(L.eend_feature_meannorm_f32(Y.data_ptr(), out.data_ptr(), n_frames, 23, mode, _stream()), "eend_feature_meannorm_f32")
+        _lib.check(L.eend_feature_meannorm_f32(Y.data_ptr(), out.data_ptr(), n_frames, NMEL, mode, _stream()), "eend_feature_meannorm_f32")
         Y = out
     return Y
 

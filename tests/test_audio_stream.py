@@ -160,6 +160,36 @@ def test_front_end_errors(hip_lib, dev):
     assert fe.feed({}) == {}
 
 
+@pytest.mark.parametrize("rate,encoding", [(8000, "f32"), (16000, "s16")])
+def test_cpu_chunks_of_odd_length_in_one_staging_block(hip_lib, dev, rate, encoding):
+    """Three slots fed together: per call 81 samples for slot 0 and 1 sample for slot 1 as CPU tensors (an odd-length chunk
+    followed by another CPU chunk, each placed on its own 8-byte boundary of the staging block) and 160 samples for slot 2
+    as a GPU tensor, until slot 0 has passed 900 samples.  Bit for bit the batch front-end of each whole waveform."""
+    from fs_eend_amd import feature
+    from fs_eend_amd.audio_stream import AudioFrontEnd
+    fe = AudioFrontEnd(3, "logmel23", 2, 4, device=dev, sample_rate=rate, encoding=encoding)
+    per_call, calls = [81, 1, 160], 900 // 81 + 1
+    whole = [wave(m * calls, 50 + s) for s, m in enumerate(per_call)]
+    if encoding == "s16":
+        whole = [(y * 16384).astype(np.int16) for y in whole]
+    whole = [torch.from_numpy(y) for y in whole]
+    for s in range(3):
+        fe.reset(s)
+    out = [[] for _ in whole]
+    for k in range(calls + 1):
+        cut = [y[m * k:m * (k + 1)] for y, m in zip(whole, per_call)]
+        got = fe.feed({0: cut[0], 1: cut[1], 2: cut[2].to(dev)}) if k < calls else fe.feed({}, end=[0, 1, 2])
+        for s in range(3):
+            out[s].append(got[s])
+    assert (fe.table if fe.ingest is None else fe.ingest.table).recv[0] == 81 * calls > 900
+    for s, y in enumerate(whole):
+        want = feature.extract_fbank_wave(y.to(dev), context_size=2, subsampling=4, input_transform="logmel23", sample_rate=rate,
+                                          encoding=encoding)
+        g = torch.cat(out[s])
+        assert g.shape == want.shape and want.shape[0] > 0, (s, g.shape, want.shape)
+        assert torch.equal(g, want), (s, float((g - want).abs().max()))
+
+
 # ---------------------------------------------------------------------------------------------- end to end
 def _fs_model(dev):
     from fs_eend_amd.fs_stream import StreamingTransformerEDADiarization, copy_params_from_masked_to_streaming

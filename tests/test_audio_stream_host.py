@@ -118,6 +118,33 @@ def test_errors():
             A.FrontEndTable(2, **bad)
 
 
+def test_feed_descriptor_and_tile_tables():
+    """The words of one feed, written out by hand from the rules of audio_stream's module text (ctx 2, sub 4: log-mel frame f
+    needs 80 f + 100 samples, model frame j needs log-mel frame 4 j + 2, the ring starts at frame max(0, min(T, 4 j - 2))).
+
+    Slots 1 and 2 each hold 500 samples from an earlier call: frames 0..5, model frame 0 emitted, ring = frames 2..5.
+    slot 0: 0 -> 5700 = 100 + 80 * 70 samples: frames 0..70 (two STFT tiles, 64 + 7), model frames 0..17 since 4 * 17 + 2 = 70
+            (two splice tiles, 16 + 2), ring afterwards from frame 4 * 18 - 2 = 70; its 71 rows of Y start at row 0.
+    slot 1: 500 -> 501 samples: frame 6 needs 580, so nothing new and no tile, but its 4 ring rows still take Y rows 71..74.
+    slot 2: ends at 500 samples: 1 + 500 // 80 = 7 frames in all, so frame 6 is new (one STFT tile), ceil(7 / 4) = 2 model
+            frames, so model frame 1 is new (one splice tile, output row 18), ring afterwards from frame 6; Y rows 75..79 hold
+            ring frames 2..5 and frame 6."""
+    t = A.FrontEndTable(3, 2, 4)
+    for s in range(3):
+        t.reset(s)
+    t.commit(t.plan({1: 500, 2: 500}))
+    assert (t.frames, t.mframes) == ([0, 6, 6], [0, 1, 1])
+    desc, stft, splice, rows, y_rows, o_rows = A.feed_words(t.plan({0: 5700, 1: 1}, end=[2]), [0x1000, 0x2000, 0])
+    #                chunk  recv0 recv1 f0 f1 rb0 rb1 ybase slot
+    assert desc == [[0x1000, 0, 5700, 0, 71, 0, 70, 0, 0],
+                    [0x2000, 500, 501, 6, 6, 2, 2, 71, 1],
+                    [0, 500, 500, 6, 7, 2, 6, 75, 2]]
+    assert stft == [[0, 0, 64], [0, 64, 7], [2, 6, 1]]                      # {descriptor, first frame, frames}
+    assert splice == [[0, 0, 16, 0], [0, 16, 2, 16], [2, 1, 1, 18]]         # {descriptor, first model frame, rows, output row}
+    assert (y_rows, o_rows) == (80, 19)
+    assert rows == {0: (0, 18), 1: (18, 0), 2: (18, 1)}
+
+
 def test_front_end_rejects_batch_only_options():
     for kw in [dict(input_transform="logmel23_mn"), dict(input_transform="logmel23", pad_mode="reflect"),
                dict(input_transform="mfcc")]:
