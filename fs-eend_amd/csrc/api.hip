@@ -503,6 +503,23 @@ int eend_collar_der_limits(int* tile, int* max_half_collar) {
     return EEND_OK;
 }
 
+int eend_collar_der_sweep_u64(const unsigned char* ref, const int* ref_off, int Cr, const float* pred, const int* pred_off, int Ch,
+                              const unsigned char* sad, int B, const float* thresholds, int n_thresholds, const int* medians,
+                              int n_medians, int subsampling, int half_collar, int skip_overlap, unsigned long long* counters,
+                              unsigned long long* cooc, int* mapping, unsigned long long* totals, void* stream) {
+    return eend_launch_collar_der_sweep(ref, ref_off, Cr, pred, pred_off, Ch, sad, B, thresholds, n_thresholds, medians, n_medians,
+                                        subsampling, half_collar, skip_overlap, counters, cooc, mapping, totals, (hipStream_t)stream);
+}
+
+int eend_der_sweep_limits(int* max_thresholds, int* max_medians, int* max_points, int* max_median) {
+    if (!max_thresholds || !max_medians || !max_points || !max_median) return EEND_EINVAL;
+    *max_thresholds = DER_SWEEP_NTHETA;
+    *max_medians = DER_SWEEP_NMED;
+    *max_points = DER_SWEEP_GMAX;
+    *max_median = DER_SWEEP_KMAX;
+    return EEND_OK;
+}
+
 int eend_stft_logmel23_f32(const float* y, long len, long first, int n_frames, const float* dft, const float* melT,
                            float* out, void* stream) {
     return eend_launch_stft_logmel(y, len, first, n_frames, dft, melT, out, (hipStream_t)stream);

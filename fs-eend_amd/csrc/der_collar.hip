@@ -19,57 +19,11 @@
 // value of the optimal assignment, so no second pass over the frames is needed.
 #include "common.h"
 #include "kernels.h"
+#include "der_tile.h"
 
 namespace {
 
-constexpr int CMAX = DER_CMAX;                    // speakers per side
-constexpr int TILE = DER_TILE;                    // reference frames per tile
-constexpr int HMAX = DER_HMAX;                    // largest half collar
-constexpr int NT = 256;                           // threads: thread (i, j) = (tid / 16, tid % 16) owns cooc[i][j]
-constexpr int EXT = TILE + 2 * HMAX;              // reference frames a tile reads
-constexpr int NWORDS = (EXT + 63) / 64;           // boundary-bit words
-constexpr int NGRP = TILE / 64;                   // 64-frame groups of a tile
-constexpr int STAGE_WORDS = NT * CMAX / 4 + 1;    // NT rows of CMAX bytes, entered at any byte of the first word
-static_assert(TILE % NT == 0 && NT == CMAX * CMAX && NWORDS <= NT, "der_collar tile layout");
-
-// mask[e] = speaker bits of frame f0 + e of a recording of `len` frames (row `row0 + f` of `rows`, C bytes each; non-zero:
-// active), 0 outside [0, len), for e in [0, n).  NT frames per round; `stage` is free for other use on return.
-DEV void load_masks(const unsigned char* __restrict__ rows, long row0, int len, int C, int f0, int n, unsigned short* mask,
-                    unsigned* stage) {
-    const int tid = threadIdx.x;
-    for (int c0 = 0; c0 < n; c0 += NT) {
-        int fa = f0 + c0, fb = f0 + (c0 + NT < n ? c0 + NT : n);
-        fa = fa < 0 ? 0 : fa;
-        fb = fb > len ? len : fb;
-        unsigned lead = 0;
-        if (fa < fb) {
-            const uintptr_t p = (uintptr_t)rows + (size_t)(row0 + fa) * C, pe = p + (size_t)(fb - fa) * C;
-            const uintptr_t a = p & ~(uintptr_t)3;
-            lead = (unsigned)(p - a);
-            const int nw = (int)((pe - a + 3) >> 2);
-            for (int k = tid; k < nw; k += NT) {
-                const uintptr_t q = a + 4 * (uintptr_t)k;
-                unsigned v = 0;
-                if (q >= p && q + 4 <= pe) v = *(const unsigned*)q;
-                else
-                    for (int b = 0; b < 4; ++b)
-                        if (q + b >= p && q + b < pe) v |= (unsigned)*(const unsigned char*)(q + b) << (8 * b);
-                stage[k] = v;
-            }
-        }
-        __syncthreads();
-        const int e = c0 + tid, f = f0 + e;
-        if (e < n) {
-            unsigned m = 0;
-            if (f >= fa && f < fb) {
-                const unsigned char* s = (const unsigned char*)stage + lead + (size_t)(f - fa) * C;
-                for (int c = 0; c < C; ++c) m |= (s[c] != 0 ? 1u : 0u) << c;
-            }
-            mask[e] = (unsigned short)m;
-        }
-        __syncthreads();
-    }
-}
+using namespace der;                              // the tile layout and load_masks, shared with der_sweep.hip
 
 // counters and co-occurrence counts start at 0.  A kernel, not hipMemsetAsync: memset nodes of a captured graph came back with
 // other values than 0 on replay (seen once with this entry in torch.cuda.graph; a launch replays as it was recorded).
@@ -173,26 +127,32 @@ void der_collar_pass_kernel(const unsigned char* __restrict__ ref, const int* __
     if (pair) atomicAdd(cooc + ((size_t)rec * CMAX + ci) * CMAX + cj, pair);
 }
 
-// One wave per recording.  rows = reference speakers, columns = hypothesis speakers, a[i][j] = -cooc[i][j]; the rows and columns
+// One wave per matrix m = g * B + b (the sweep of der_sweep.hip scores G points per recording b; here G = 1): the lengths are
+// those of recording b, the sums and the mapping those of m.  `medians` (the sweep's, nmed of them, point g uses g % nmed; may be
+// null): a point whose median is out of the sweep's range is marked like an out-of-scope recording.  `totals` (may be null):
+// u64 [G][8] running sums that every scored matrix's eight counters are added to.
+// rows = reference speakers, columns = hypothesis speakers, a[i][j] = -cooc[i][j]; the rows and columns
 // beyond Cr and Ch are 0 (cleared, never added to), which pads the matrix to a square of n = max(Cr, Ch).  The minimum-cost
 // perfect matching of the square, restricted to pairs with cooc > 0, is the mapping.  The wave stages the matrix in LDS with
 // coalesced loads, then lane 0 runs the solver on LDS arrays: the serial chain of its steps then waits for LDS, not for HBM
 // (read from global memory step by step it took 130-270 us, most of a call).
 __global__ __launch_bounds__(64)
-void der_collar_assign_kernel(const int* __restrict__ roff, const int* __restrict__ hoff, int Cr, int Ch, int sub,
-                              unsigned long long* __restrict__ counters, const unsigned long long* __restrict__ cooc,
-                              int* __restrict__ mapping) {
+void der_collar_assign_kernel(const int* __restrict__ roff, const int* __restrict__ hoff, int Cr, int Ch, int sub, int B,
+                              const int* __restrict__ medians, int nmed, unsigned long long* __restrict__ counters,
+                              const unsigned long long* __restrict__ cooc, int* __restrict__ mapping,
+                              unsigned long long* __restrict__ totals) {
     __shared__ long long a[CMAX * CMAX], u[CMAX + 1], v[CMAX + 1], minv[CMAX + 1];
     __shared__ int p[CMAX + 1], way[CMAX + 1];
     __shared__ bool used[CMAX + 1];
-    const int b = blockIdx.x, lane = threadIdx.x;
-    unsigned long long* cnt = counters + (size_t)b * 8;
-    int* map = mapping + (size_t)b * CMAX;
-    const unsigned long long* c = cooc + (size_t)b * CMAX * CMAX;
+    const int m = blockIdx.x, b = m % B, g = m / B, lane = threadIdx.x;
+    unsigned long long* cnt = counters + (size_t)m * 8;
+    int* map = mapping + (size_t)m * CMAX;
+    const unsigned long long* c = cooc + (size_t)m * CMAX * CMAX;
     const long Trl = (long)roff[b + 1] - roff[b], Thl = (long)hoff[b + 1] - hoff[b];
     const long Tl = Trl > Thl * sub ? Trl : Thl * sub;
     if (lane < CMAX) map[lane] = -1;
-    if (Trl < 0 || Thl < 0 || Tl > DER_MAX_FRAMES) {               // out of scope: every counter reads ~0
+    const bool point_ok = !medians || median_ok(medians[g % nmed]);
+    if (Trl < 0 || Thl < 0 || Tl > DER_MAX_FRAMES || !point_ok) {  // out of scope: every counter reads ~0
         if (lane < 8) cnt[lane] = ~0ull;
         return;
     }
@@ -240,6 +200,9 @@ void der_collar_assign_kernel(const int* __restrict__ roff, const int* __restric
     cnt[3] = cnt[7] - best;                                        // confusion = sum of min(nr, nh) - correct
     cnt[4] = best;
     cnt[6] = (unsigned long long)Tl - cnt[5];
+    if (totals)
+        for (int k = 0; k < 8; ++k)
+            if (cnt[k]) atomicAdd(totals + (size_t)g * 8 + k, cnt[k]);
 }
 
 }  // namespace
@@ -258,6 +221,13 @@ int eend_launch_collar_der(const unsigned char* ref, const int* roff, int Cr, co
     hipLaunchKernelGGL(der_collar_pass_kernel, dim3(groups, B), dim3(NT), 0, stream, ref, roff, Cr, hyp, hoff, Ch, sub, h,
                        skip ? 1 : 0, counters, cooc);
     if (hipGetLastError() != hipSuccess) return EEND_ELAUNCH;
-    hipLaunchKernelGGL(der_collar_assign_kernel, dim3(B), dim3(64), 0, stream, roff, hoff, Cr, Ch, sub, counters, cooc, mapping);
+    return eend_launch_collar_der_assign(roff, hoff, Cr, Ch, B, 1, sub, nullptr, 0, counters, cooc, mapping, nullptr, stream);
+}
+
+int eend_launch_collar_der_assign(const int* roff, const int* hoff, int Cr, int Ch, int B, int G, int sub, const int* medians, int nmed,
+                                  unsigned long long* counters, const unsigned long long* cooc, int* mapping,
+                                  unsigned long long* totals, hipStream_t stream) {
+    hipLaunchKernelGGL(der_collar_assign_kernel, dim3((unsigned)G * B), dim3(64), 0, stream, roff, hoff, Cr, Ch, sub, B, medians, nmed,
+                       counters, cooc, mapping, totals);
     return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
 }

@@ -116,6 +116,20 @@ int eend_launch_der_counters(const float* pred, int ldp, const float* label, int
 int eend_launch_collar_der(const unsigned char* ref, const int* roff, int Cr, const unsigned char* hyp, const int* hoff, int Ch, int B,
                            int sub, int h, int skip, unsigned long long* counters, unsigned long long* cooc, int* mapping,
                            hipStream_t stream);
+// the assignment launch of the collar DER on G * B matrices (matrix g * B + b has the lengths of recording b); medians, totals: may
+// be null (der_collar.hip at der_collar_assign_kernel)
+int eend_launch_collar_der_assign(const int* roff, const int* hoff, int Cr, int Ch, int B, int G, int sub, const int* medians, int nmed,
+                                  unsigned long long* counters, const unsigned long long* cooc, int* mapping,
+                                  unsigned long long* totals, hipStream_t stream);
+// collar DER over a threshold x median grid (der_sweep.hip): thresholds, medians, points per call, the largest median
+#define DER_SWEEP_NTHETA 16
+#define DER_SWEEP_NMED 4
+#define DER_SWEEP_GMAX 32
+#define DER_SWEEP_KMAX 127
+int eend_launch_collar_der_sweep(const unsigned char* ref, const int* roff, int Cr, const float* pred, const int* poff, int Ch,
+                                 const unsigned char* sad, int B, const float* thresholds, int nth, const int* medians, int nmed, int sub,
+                                 int h, int skip, unsigned long long* counters, unsigned long long* cooc, int* mapping,
+                                 unsigned long long* totals, hipStream_t stream);
 
 int eend_launch_stft_logmel(const float* y, long len, long first, int n_frames, const float* dft, const float* melT, float* out,
                             hipStream_t stream);

@@ -369,6 +369,47 @@ int eend_collar_der_u64(const unsigned char* ref, const int* ref_off, int Cr, co
 /* The reference frames per tile of eend_collar_der_u64's pass and the largest half_collar it takes (host arithmetic only). */
 int eend_collar_der_limits(int* tile, int* max_half_collar);
 
+/* Collar DER over a grid of operating points in one pass over the rows: what a development set is tuned with (the reference's
+ * scoring scripts take --thredshold and --median, LS-EEND/metrics.py and sad_post_process.py; additive to ABI version 5).  The
+ * grid is n_thresholds x n_medians, G = n_thresholds * n_medians points, point g = i_threshold * n_medians + i_median
+ * (threshold-major).  For every point g and recording b the results are exactly those of eend_collar_der_u64 over the activity
+ * that eend_sad_fuse_f32 (with sad) and eend_activity_median_u8 make of the posteriors at thresholds[i_threshold] and
+ * medians[i_median].
+ *   Inputs, all in device memory.  The reference as for eend_collar_der_u64: ref u8 [.][Cr], ref_off i32 [B + 1].  The hypothesis
+ * side as posteriors, packed the same way: pred f32 [.][Ch] (4-byte aligned; rows are dense, so a row start has no other
+ * alignment when Ch is odd), pred_off i32 [B + 1]; Cr and Ch independent, each in 1 .. 16; 1 <= B <= 65535.  sad u8 [.], one flag per
+ * posterior row under the same offsets (non-zero: speech), or NULL for no mask.  thresholds f32 [n_thresholds] and medians i32
+ * [n_medians] are read by the kernels, not by the host, so the call copies nothing and can be captured in a graph; thresholds
+ * may come in any order and may repeat (equal thresholds give equal results).
+ *   Per point.  1. The decision of a value p is p > threshold, strict: NaN is never active, +-inf are ordinary values (a NaN
+ * threshold makes nobody active).  2. With sad, a decision stands only in a speech row, and a speech row with no decision at
+ * this threshold gets its largest non-NaN value (the lowest column on ties; the winner does not depend on the threshold), as
+ * eend_sad_fuse_f32 states it; a speech row of NaN only stays 0.  3. The median of k (odd) along time is 1 iff at least k / 2 +
+ * 1 of the k decisions are 1; the window is centred and sees zeros beyond the recording's own first and last row (scipy's
+ * medfilt), never a neighbour's rows in the packed buffer.  It comes after the mask, so it may bridge a short non-speech gap;
+ * k = 1 is no filter.  4. The result is scored against the reference as eend_collar_der_u64 states it: T = max(Tr, Th *
+ * subsampling), a side is zero beyond its own end, half_collar, skip_overlap, the co-occurrence counts over the kept frames, the
+ * mapping and the counters.  total, frames kept and frames removed come from the reference alone and are equal for all g.
+ *   Outputs: counters u64 [G][B][8], cooc u64 [G][B][16][16], mapping i32 [G][B][16], slots and meaning as for eend_collar_der_u64;
+ * all three are written by the call.  totals u64 [G][8] (may be NULL) belongs to the caller and is not cleared: the eight
+ * counters of every scored (g, b) are added to row g with 64-bit integer atomics, so a development set larger than one batch
+ * accumulates on the device in any order.  Three launches (clear, one pass in which the reference work of a tile is done once and
+ * only the co-occurrence counts differ per point, the assignment of eend_collar_der_u64 on G * B matrices); integer atomics
+ * only, so every run gives the same bits; nothing is allocated and the host is not waited for.
+ *   EEND_EINVAL: a NULL pointer other than sad and totals, pred not 4-byte aligned, n_thresholds outside 1 .. 16, n_medians
+ * outside 1 .. 4, G > 32 (eend_der_sweep_limits reports these), and the domain of eend_collar_der_u64 for Cr, Ch, B, subsampling and
+ * half_collar.  A median must be odd and in 1 .. 127; the host cannot see the values, so a point whose median is not is not
+ * scored: its counters are all ~0 and its mapping is -1 for every recording, and it adds nothing to totals; the other points
+ * are unaffected.  A recording out of the scope of eend_collar_der_u64 is marked in the same way at every point. */
+int eend_collar_der_sweep_u64(const unsigned char* ref, const int* ref_off, int Cr, const float* pred, const int* pred_off, int Ch,
+                              const unsigned char* sad, int B, const float* thresholds, int n_thresholds, const int* medians,
+                              int n_medians, int subsampling, int half_collar, int skip_overlap, unsigned long long* counters,
+                              unsigned long long* cooc, int* mapping, unsigned long long* totals, void* stream);
+
+/* The grid limits of eend_collar_der_sweep_u64: thresholds, medians and points per call, and the largest median (host arithmetic
+ * only); the speaker, frame and collar limits are those of eend_collar_der_u64. */
+int eend_der_sweep_limits(int* max_thresholds, int* max_medians, int* max_points, int* max_median);
+
 /* ---- feature front-end ({LS,FS}-EEND/datasets/feature.py: stft :166-191, transform :43-131, splice :141-163,
  * subsample :133-138, extract_fbank :324-336); fp32 throughout.  ---- */
 
