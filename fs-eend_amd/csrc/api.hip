@@ -764,6 +764,23 @@ int eend_inproj_attn_causal_packed_f16(const void* X_f16, int ldx, const void* W
     return eend_launch_inproj_attn_stream(p, (hipStream_t)stream);
 }
 
+int eend_inproj_attn_slots_choice(int n_utt, int C, int workgroups) {
+    const int S = eend_attn_slots_choice(n_utt, C, workgroups);
+    return S > 0 ? S : EEND_EINVAL;
+}
+
+int eend_inproj_attn_causal_slots_f16(const void* X_f16, int ldx, const void* W_packed, const float* b_in, void* O_f16,
+                                      int nseq, int H, int Tp, int ldo, int mask_delay, int kv_len, int C, const float* slot_delta,
+                                      int slots_per_item, void* stream) {
+    if (!X_f16 || !W_packed || !b_in || !O_f16 || nseq > 16383) return EEND_EINVAL;
+    InprojAttnParams p;
+    memset(&p, 0, sizeof(p));
+    p.X = X_f16; p.ldx = ldx; p.W = W_packed; p.bias = b_in; p.O = O_f16;
+    p.nseq = nseq; p.H = H; p.Tp = Tp; p.ldo = ldo; p.mask_delay = mask_delay; p.kv_len = kv_len;
+    p.C = C; p.slot_delta = slot_delta; p.S = slots_per_item;
+    return eend_launch_inproj_attn_slots(p, (hipStream_t)stream);
+}
+
 int eend_inproj_attn_long_scratch_elems(int nseq, int Tp, int mask_delay, int kv_len, long long* part_f16_elems, long long* lse_f32_elems) {
     if (!part_f16_elems || !lse_f32_elems) return EEND_EINVAL;
     long a = 0, b = 0;

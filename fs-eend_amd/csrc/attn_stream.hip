@@ -12,6 +12,17 @@
 // (Round 3's form of the operator, attn_fused.hip -- weight slices in registers split by FEATURE across the waves, X streamed through
 //  an LDS tile every wave read completely, Q through an L2 scratch -- was LDS-read-bound, 19 us of a 32-us decoder item; removed in
 //  round 6 together with its A/B switch.)
+// Slot form (Tp = 512, eend_inproj_attn_causal_slots_f16): the sequences are the C speaker slots of nseq / C utterances and the rows of slot c
+// are those of slot 0 plus a constant pd[c] (the fan-out in front of the first fusion layer).  The in-projection is linear, so with
+// d_c = pd[c] - pd[0]:  K_c = K_0 + W_k d_c -- the same for every key of a query, it cancels in the softmax as the key bias does;
+// V_c = V_0 + W_v d_c, hence O_c = P_c V_0 + W_v d_c;  Q_c = Q_0 + W_q d_c.  An item is (utterance, head, S consecutive slots): it reads
+// the 512 rows of slot 0, projects K / V^T once and then Q, and runs the two flash passes of each of its slots against the resident tiles.
+// THE arithmetic of a slot, whatever S (the result does not depend on it, bit for bit; slot 0 equals the per-slot form on its rows):
+//   Q_c = bf16(acc_q + dq_c)       the f32 projection accumulators (bias included) kept through the slot loop, rounded once
+//   O_c = f16_sat(O^T / l + dv_c)  the add in f32 before the only f16 rounding
+// with (dq_c | dv_c) = row c of slot_delta f32 [C][512] = (W_q d_c pre-scaled like the packed q rows | W_v d_c), row 0 zero (never read).
+// The 64 accumulator registers fit beside the flash loop only with Q projected LAST (behind the K / V items they would sit beside the 128
+// X-fragment registers) and dv held one feature per lane: 247 VGPRs, no scratch.
 // Tp = 64 m <= 512 (eight waves x two query blocks of the 16 slots; round 6: shorter windows leave slots empty, see tokbase); longer chunk
 // lengths take eend_inproj_heads_bf16 + eend_attn_causal_bf16.
 #include "flash_tile.h"
@@ -72,11 +83,14 @@ __device__ unsigned long long g_as_trace[256 * 6 * 12];
 // MFMA orientation: a lane then owns 4 features of a token), the probabilities are dropped by the counter hash of eend_dropout (element
 // (a, b) = ((seq H + head) Tp + query, key); the row sums stay un-dropped) and the log2-domain log-sum-exp of every row is kept.
 // FULL: Tp = 512 known at compile time (the block map is (wave, 15 - wave) and no pass is skipped: the round-4 kernel, register for register)
-template <bool LONG, bool TRAIN = false, bool FULL = false>
+// SLOTS (Tp = 512 only): the slot form of the file header -- an item is (utterance, head, group of p.S consecutive speaker slots); its X rows
+// are those of the utterance's slot 0 (sequence utt * C), K / V^T are projected once, and the two flash passes run once per slot of the group
+template <bool LONG, bool TRAIN = false, bool FULL = false, bool SLOTS = false>
 __global__ __launch_bounds__(512)
 void inproj_attn_stream_kernel(const InprojAttnParams p) {
     static_assert(!(LONG && TRAIN), "the training form covers windows up to 512 frames");
     static_assert(!(LONG && FULL), "groups of a long window have their own lengths");
+    static_assert(!SLOTS || (FULL && !TRAIN), "the slot form exists for inference at 512 frames");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* Ks = smem + L_K;                           // [8][64 keys][128 B]
     char* Vs = smem + L_V;                           // [8][64 d][128 B]; before that: weight items 0..3
@@ -88,9 +102,10 @@ void inproj_attn_stream_kernel(const InprojAttnParams p) {
     int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     int frow = lane & 15, fkg = lane >> 4;
-    const int nsh = p.nseq * 4;
-    const int nitems = LONG ? nsh * p.npairs : nsh;
-    const bool xcd_map = (p.nseq & 7) == 0 && ((gridDim.x & 7) == 0 || (int)gridDim.x >= nitems);
+    const int nsq = SLOTS ? p.nutt : p.nseq;         // sequences whose rows are projected
+    const int nsh = nsq * 4;
+    const int nitems = LONG ? nsh * p.npairs : SLOTS ? nsh * p.ngrp : nsh;
+    const bool xcd_map = (nsq & 7) == 0 && ((gridDim.x & 7) == 0 || (int)gridDim.x >= nitems);
     auto item_of = [&](int L, int& seq_, int& h_) __attribute__((always_inline)) {
         if (xcd_map) {
             const int xcd = L & 7, slot = L >> 3;
@@ -109,6 +124,7 @@ void inproj_attn_stream_kernel(const InprojAttnParams p) {
     int b2 = FULL ? 15 - wave : (wave < (nblk >> 1) ? nblk - 1 - wave : b1 + 1);
     // item geometry (LONG: set per item): first row and row count of the query / key group, causal limit and valid keys in key-group terms
     int qoff = 0, koff = 0, Tq = p.Tp, Tk = p.Tp, dl = p.mask_delay, kvl = p.kv_len, pair = 0;
+    int c0 = 0, oseq = 0;                            // SLOTS: first slot of the item's group; sequence of the slot whose rows are being written
     bool offd = false;
     auto tokbase = [&](int jt) __attribute__((always_inline)) { return jt < 2 ? 32 * b1 + 16 * jt : 32 * b2 + 16 * (jt - 2); };
     char* Ow = Xs + wave * OSTG;
@@ -149,6 +165,11 @@ void inproj_attn_stream_kernel(const InprojAttnParams p) {
         nblk = Tq >> 5;
         b1 = wave < (nblk >> 1) ? wave : nblk + 2 * (wave - (nblk >> 1));
         b2 = wave < (nblk >> 1) ? nblk - 1 - wave : b1 + 1;
+    } else if constexpr (SLOTS) {
+        const int grp = item / nsh;
+        item_of(item - grp * nsh, seq, h);
+        c0 = grp * p.S;
+        seq *= p.C;                                  // slot 0 of the utterance: the rows every slot of it is projected from
     } else {
         item_of(item, seq, h);
     }
@@ -164,7 +185,22 @@ void inproj_attn_stream_kernel(const InprojAttnParams p) {
     AS_STAMP(0);
 
     // ================================================================== phase 1: K, V^T -> LDS, Q -> registers
-    u32x2 qpk[4][4];                                 // [feature fragment][token fragment]: bf16 q[tok][ff*16 + fkg*4 .. +3]
+    // SLOTS: the slot's rows of p.slot_delta -- dq[ff] for the lane's 4 features of fragment ff (projection layout); dv1 = dv of feature `lane`
+    // (one register: the 32 features a lane's output row needs are fetched from the other lanes when the row is staged, 32 registers
+    // through the flash loop were 16 too many).  Slot 0 and slots beyond the group read through an empty buffer: zeros, no access.
+    f32x4 dq[SLOTS ? 4 : 1];
+    float dv1 = 0.f;
+    auto slot_rsrc = [&](int c, int cend) __attribute__((always_inline)) {
+        return __builtin_amdgcn_make_buffer_rsrc((void*)(p.slot_delta + (size_t)c * 512), 0, c > 0 && c < cend ? 2048 : 0, 0x00020000);
+    };
+    auto load_dq = [&](int c, int cend, f32x4 (&d)[SLOTS ? 4 : 1]) __attribute__((always_inline)) {
+        const __amdgpu_buffer_rsrc_t rd = slot_rsrc(c, cend);
+#pragma unroll
+        for (int ff = 0; ff < (SLOTS ? 4 : 1); ++ff)
+            d[ff] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rd, (h * 64 + ff * 16 + fkg * 4) * 4, 0, 0));
+    };
+    u32x2 qpk[SLOTS ? 1 : 4][4];                     // [feature fragment][token fragment]: bf16 q[tok][ff*16 + fkg*4 .. +3]
+    f32x4 qacc[SLOTS ? 4 : 1][4];                    // SLOTS: the same elements before rounding (bias included), kept through the slot loop
     {
         const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)p.W + (size_t)h * NITEM * WITEM), 0,
                                                                             NITEM * WITEM, 0x00020000);
@@ -186,14 +222,16 @@ void inproj_attn_stream_kernel(const InprojAttnParams p) {
             }
         }
         // the head's six weight items: this wave moves pieces 2 wave, 2 wave + 1 of each
-#pragma unroll
-        for (int n = 0; n < NITEM; ++n) {
-            char* dst = n < 4 ? Vs + n * WITEM : Xs + (n - 4) * WITEM;
+        auto request_w = [&](int n, char* dst) __attribute__((always_inline)) {
 #pragma unroll
             for (int i = 0; i < 2; ++i)
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_char*)(dst + (wave * 2 + i) * 1024), 16, lane * 16,
                                                          n * WITEM + (wave * 2 + i) * 1024, 0, 0);
-        }
+        };
+        // (SLOTS: K, V, then Q -- the f32 query accumulators stay live to the end of the item, and behind the K / V items they would not
+        //  fit beside the X fragments.  The two Q items are requested later, into the V items' places once those are read: see below)
+#pragma unroll
+        for (int n = SLOTS ? 2 : 0; n < NITEM; ++n) request_w(n, n < 4 ? Vs + n * WITEM : Xs + (n - 4) * WITEM);
         // the X rows are turned into operand fragments x[jt][ks] = X[tok][ks*32 + fkg*8 .. +8] through a wave-private 8-KB tile in the
         // (still unused) K region: 16 rows x 32 chunks of 16 bytes, chunk index XORed with the row so that both the row-major
         // writes and the fragment reads are conflict-free.  No barrier: a wave only touches its own tile.
@@ -215,7 +253,8 @@ void inproj_attn_stream_kernel(const InprojAttnParams p) {
         };
         rows_to_fragments();
         sfor<NITEM>([&](auto N) __attribute__((always_inline)) {
-            constexpr int n = decltype(N)::value, kind = n >> 1, ffb = (n & 1) * 2;      // kind 0 q, 1 k, 2 v
+            constexpr int m = decltype(N)::value, n = SLOTS ? (m + 2) % NITEM : m;        // m: position in the item's order, n: weight item
+            constexpr int kind = n >> 1, ffb = (n & 1) * 2;                              // kind 0 q, 1 k, 2 v
             if constexpr (LONG && n == 2) {
                 // off-diagonal item: Q is done with the query rows; the key group's rows take their place (the K region is still this
                 // wave's to use: the first K rows are written behind the barrier below)
@@ -226,11 +265,15 @@ void inproj_attn_stream_kernel(const InprojAttnParams p) {
                 }
             }
             // this wave's pieces of item n have landed (its X rows are older): the younger requests are 2 (5 - n) pieces
-            wait_vm<2 * (NITEM - 1 - n)>();
+            // (SLOTS: K, K, V, V were requested together; each Q item is the only request in flight when it is waited for)
+            wait_vm<SLOTS ? (m < 3 ? 2 * (3 - m) : 0) : 2 * (NITEM - 1 - n)>();
             __builtin_amdgcn_s_barrier();
-            AS_STAMP(1 + n);
+            AS_STAMP(1 + m);
             relaunder();
-            const char* wi = smem + lane * 16 + (n < 4 ? L_V + n * WITEM : L_X + (n - 4) * WITEM);
+            // SLOTS: every wave has read the previous V item (m = 3: the first, m = 4: the second): its place takes a Q item, which lands
+            // under this item's MFMAs
+            if constexpr (SLOTS && (m == 3 || m == 4)) request_w(m - 3, Xs + (m - 3) * WITEM);
+            const char* wi = smem + lane * 16 + (SLOTS && n < 2 ? L_X + n * WITEM : n < 4 ? L_V + n * WITEM : L_X + (n - 4) * WITEM);
             f32x4 acc[2][4];
             f32x4 accv[TRAIN && kind == 2 ? 2 : 1][4];            // TRAIN: V a second time with the token as the lane's column (head rows for the backward)
 #pragma unroll
@@ -281,7 +324,8 @@ void inproj_attn_stream_kernel(const InprojAttnParams p) {
                         }
                     }
                     if constexpr (kind == 0) {
-                        qpk[ffb + hf][jt] = v;
+                        if constexpr (SLOTS) qacc[ffb + hf][jt] = acc[hf][jt];
+                        else qpk[ffb + hf][jt] = v;
                     } else if constexpr (kind == 1) {
                         const int key = (LONG && offd ? 64 * wave + 16 * jt : tokbase(jt)) + frow, d = (ffb + hf) * 16 + fkg * 4;
                         *(u32x2*)(Ks + (key >> 6) * TILE + swz128(key & 63, d >> 3) + (d & 7) * 2) = v;
@@ -291,6 +335,7 @@ void inproj_attn_stream_kernel(const InprojAttnParams p) {
                     }
                 }
         });
+        if constexpr (SLOTS) load_dq(c0, c0 + p.S, dq);       // (lands while the slower waves finish their rows)
         AS_STAMP(7);
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");    // K, V^T complete in LDS
         AS_STAMP(8);
@@ -298,8 +343,8 @@ void inproj_attn_stream_kernel(const InprojAttnParams p) {
 
     // ================================================================== phase 2: the flash loop (flash_tile.h, lazy softmax)
     relaunder();
-    const int lq = lane & 31, hi = lane >> 5;
-    const int krow = swap23(lq);
+    int lq = lane & 31, hi = lane >> 5;
+    int krow = swap23(lq);
 
     bf16x8 qf[4];
     f32x16 oT[2];
@@ -312,7 +357,19 @@ void inproj_attn_stream_kernel(const InprojAttnParams p) {
         qw0 = qb * 32;
         q = qw0 + lq;
         // Q of the pass's 32 queries: registers -> the wave's staging tile ([query][64 d] bf16 rows) -> operand layout
-        stage_packed(Ow, frow, fkg, qpk, jt0);
+        if constexpr (SLOTS) {
+            // Q_c = bf16(acc_q + dq_c): the only rounding of the slot's query
+            u32x2 qs[4][2];
+#pragma unroll
+            for (int ff = 0; ff < 4; ++ff)
+#pragma unroll
+                for (int jl = 0; jl < 2; ++jl) qs[ff][jl] = pack_bf16x4(qacc[ff][jt0 + jl] + dq[ff]);
+            // dq of the next pass (the slot's second, or the next slot's first) is requested a whole pass ahead of its use
+            load_dq(oseq - seq + (jt0 == 2 ? 0 : 1), c0 + p.S, dq);
+            stage_packed(Ow, frow, fkg, qs, 0);
+        } else {
+            stage_packed(Ow, frow, fkg, qpk, jt0);
+        }
         staged_operand(Ow, lq, hi, qf);
 #pragma unroll
         for (int i = 0; i < 16; ++i) { oT[0][i] = 0.f; oT[1][i] = 0.f; mneg[i] = 0.f; }
@@ -364,18 +421,42 @@ void inproj_attn_stream_kernel(const InprojAttnParams p) {
         if constexpr (TRAIN) {                         // log2-domain log-sum-exp of the row, for the backward
             if (hi == 0) p.lse[(size_t)(seq * 4 + h) * p.Tp + q] = __builtin_amdgcn_logf(l_tot) - mneg[0];
         }
-        stage_rows(Ow, lq, hi, [&](int db, int i) __attribute__((always_inline)) { return to_f16_sat(oT[db][i] * inv); });
-        _Float16* __restrict__ Og = (_Float16*)p.O + ((size_t)seq * p.Tp + qoff + qw0) * p.ldo + h * 64;
+        if constexpr (SLOTS) {
+            // O_c = f16_sat(O^T / l + dv_c), the add in f32 before the only f16 rounding
+            stage_rows(Ow, lq, hi, [&](int db, int i) __attribute__((always_inline)) { 
+                const int feat = db * 32 + (i >> 2) * 8 + hi * 4 + (i & 3);
+                return to_f16_sat(oT[db][i] * inv + __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(feat << 2, __builtin_bit_cast(int, dv1))));
+            });
+        } else {
+            stage_rows(Ow, lq, hi, [&](int db, int i) __attribute__((always_inline)) { return to_f16_sat(oT[db][i] * inv); });
+        }
+        _Float16* __restrict__ Og = (_Float16*)p.O + ((size_t)(SLOTS ? oseq : seq) * p.Tp + qoff + qw0) * p.ldo + h * 64;
         int ldo = p.ldo;
         if constexpr (LONG) {
             if (offd) { Og = (_Float16*)p.Opart + ((size_t)(p.pslot[pair] * p.nseq + seq) * TP + qw0) * 256 + h * 64; ldo = 256; }
         }
         store_staged_rows(Ow, lane, Og, ldo);
     };
+    if constexpr (SLOTS) {
+        // the group's slots against the resident K / V^T tiles: no workgroup barrier between slots, as there is none between passes
+        for (int c = c0; c < c0 + p.S; ++c) {
+            oseq = seq + c;
+            relaunder();                             // (per slot, as per item above: lane-derived addresses are recomputed, not carried)
+            lq = lane & 31; hi = lane >> 5; krow = swap23(lq);
+            // this slot's dv is first used behind a whole pass
+            const __amdgpu_buffer_rsrc_t rd = slot_rsrc(c, c0 + p.S);
+            dv1 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rd, (256 + h * 64 + lane) * 4, 0, 0));
+            run_pass(b2, std::integral_constant<int, 2>{});
+            AS_STAMP(9);
+            run_pass(b1, std::integral_constant<int, 0>{});
+            AS_STAMP(10);
+        }
+    } else {
     if (FULL || b2 < nblk) run_pass(b2, std::integral_constant<int, 2>{});      // (wave-uniform: a pass has no workgroup barrier)
     AS_STAMP(9);
     if (FULL || b1 < nblk) run_pass(b1, std::integral_constant<int, 0>{});
     AS_STAMP(10);
+    }
     AS_STAMP(11);
 #ifdef EEND_AS_TRACE
     if (tix < 6 && threadIdx.x == 0) {
@@ -459,6 +540,44 @@ int eend_launch_inproj_attn_stream(const InprojAttnParams& p, hipStream_t stream
     q.npairs = 0; q.Opart = nullptr; q.lse = nullptr;
     if (p.Tp == TP) hipLaunchKernelGGL((inproj_attn_stream_kernel<false, false, true>), dim3(nitems < n_cu ? nitems : n_cu), dim3(512), SMEM, stream, q);
     else hipLaunchKernelGGL((inproj_attn_stream_kernel<false, false, false>), dim3(nitems < n_cu ? nitems : n_cu), dim3(512), SMEM, stream, q);
+    return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
+}
+
+// Slots per item: among the divisors S of C the one with the least ceil(items / workgroups) * (t_fix + S t_slot), the smaller S on a tie
+// (more, shorter items).  t_fix : t_slot = 231 : 341, measured on the slot form (profiles/attn_slots/): the -DEEND_AS_TRACE stamps of wave 0
+// give 231 (cycles / 100) from the item's start to the K / V barrier at every S, and the launch times at 64 x 6 sequences over S = 1, 2, 3, 6
+// (177.7, 140.6, 128.6, 118.1 us = (6 / S) t_fix + 6 t_slot) give t_fix = 12.0 us and t_slot = 17.7 us, the wait for the SIMD's slower wave
+// included.  (The per-slot form's split in profiles/r06_trace_attn_stream.txt was 229 : 329.)
+int eend_attn_slots_choice(int nutt, int C, int workgroups) {
+    if (nutt < 1 || C < 1 || C > 12 || workgroups < 1) return 0;
+    constexpr long T_FIX = 231, T_SLOT = 341;
+    int best = 1;
+    long best_cost = -1;
+    for (int S = 1; S <= C; ++S) {
+        if (C % S) continue;
+        const long items = 4L * nutt * (C / S);
+        const long cost = ((items + workgroups - 1) / workgroups) * (T_FIX + S * T_SLOT);
+        if (best_cost < 0 || cost < best_cost) { best = S; best_cost = cost; }
+    }
+    return best;
+}
+
+// p.nseq = utterances * p.C sequences of 512 frames, p.slot_delta [C][512] (may be null for C = 1), p.S slots per item (0: choose)
+int eend_launch_inproj_attn_slots(const InprojAttnParams& p, hipStream_t stream) {
+    if (p.Tp != TP || (p.ldo & 7) || (p.ldx & 7) || p.H != 4 || p.nseq <= 0 || !p.X || !p.W || !p.bias || !p.O || p.kv_len < 1 || p.kv_len > p.Tp ||
+        p.C < 1 || p.C > 12 || p.nseq % p.C || (p.C > 1 && !p.slot_delta) || p.S < 0 || (p.S > 0 && p.C % p.S))
+        return EEND_EINVAL;
+    static EendOncePerDevice attr_once;
+    if (!eend_set_dynamic_lds(attr_once, (const void*)inproj_attn_stream_kernel<false, false, true, true>, SMEM)) return EEND_ELAUNCH;
+    int n_cu = eend_cu_count() & ~31;
+    if (n_cu <= 0) n_cu = 32;
+    InprojAttnParams q = p;
+    q.npairs = 0; q.Opart = nullptr; q.lse = nullptr;
+    q.nutt = p.nseq / p.C;
+    if (q.S == 0) q.S = eend_attn_slots_choice(q.nutt, p.C, n_cu);
+    q.ngrp = p.C / q.S;
+    const int nitems = q.nutt * 4 * q.ngrp;
+    hipLaunchKernelGGL((inproj_attn_stream_kernel<false, false, true, true>), dim3(nitems < n_cu ? nitems : n_cu), dim3(512), SMEM, stream, q);
     return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
 }
 

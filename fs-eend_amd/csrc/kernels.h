@@ -192,7 +192,14 @@ struct InprojAttnParams {
     // training forward (eend_launch_inproj_attn_train): bf16 head rows [seq][H][Tp][64] for the backward, lse [nseq][4][Tp], dropout of P
     void* Qh; void* Kh; void* Vh;
     DropSpec drop;
+    // slot form (eend_launch_inproj_attn_slots; the launcher fills nutt, ngrp and a chosen S): nseq = nutt * C sequences whose rows differ
+    // from those of slot 0 by a constant per slot; slot_delta f32 [C][512] = (dq pre-scaled like the packed q rows | dv), row 0 zero
+    int C, S, nutt, ngrp;
+    const float* slot_delta;
 };
+// S of the slot form for nutt utterances of C slots on `workgroups` persistent workgroups (a pure function of the three); 0 if C is out of range
+int eend_attn_slots_choice(int nutt, int C, int workgroups);
+int eend_launch_inproj_attn_slots(const InprojAttnParams& p, hipStream_t stream);
 int eend_launch_inproj_attn_train(const InprojAttnParams& p, hipStream_t stream);
 long eend_inproj_attn_packed_nelems();
 int eend_inproj_attn_long_scratch(int nseq, int Tp, int mask_delay, int kv_len, long* part_elems, long* lse_elems);

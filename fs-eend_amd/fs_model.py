@@ -214,6 +214,7 @@ class OnlineTransformerDADiarization(nn.Module):
         self._prep_key = None
         self._ws = WorkspaceCache()
         self._pc = {}
+        self._sd = {}
         self.register_load_state_dict_post_hook(lambda module, incompatible_keys: module.refresh_weights())
 
     def refresh_weights(self):
@@ -293,6 +294,7 @@ class OnlineTransformerDADiarization(nn.Module):
         P["dec.layers"] = dl
         self._prep, self._prep_key = P, key
         self._pc = {}
+        self._sd = {}
         return P
 
     def _convert_const(self, C):
@@ -310,6 +312,19 @@ class OnlineTransformerDADiarization(nn.Module):
                                                 torch.cuda.current_stream().cuda_stream), "eend_convert_const_f32")
             self._pc[C] = pc
         return self._pc[C]
+
+    def _slot_delta(self, C):
+        """slot_delta[c] = (W_q d_c | W_v d_c), d_c = pc[c] - pc[0]  (a (C, 512) f32 constant of the weights): what the slot constants of
+        the fan-out become behind the first fusion layer's time-axis in-projection.  W is the f16 operand copy the kernel multiplies
+        with (q rows pre-scaled), the products are summed in f32; cached like _convert_const, per parameter version and slot count."""
+        if C not in self._sd:
+            W = self._prep["dec.layers"][0]["in1_w"].to(torch.float32)
+            pc = self._convert_const(C)
+            d = pc - pc[:1]
+            sd = (d[:, None, :] * torch.cat([W[:256], W[512:]])[None]).sum(-1)
+            sd[0] = 0.0
+            self._sd[C] = sd.contiguous()
+        return self._sd[C]
 
     def _workspace(self, dev, B, Tp, C):
         key = (str(dev), B, Tp, C)
@@ -352,9 +367,14 @@ class OnlineTransformerDADiarization(nn.Module):
             ops.linear_res_ln(ws.xin16, P["enc.in.w"], P["enc.in.b"], None, P["enc.in.g"], P["enc.in.beta"], None, ws.h16, P["enc.in.eps"])
         o16 = ws.o16[:Me]
 
-        def time_attention(x16, Ly, wkey, bkey, nseq, delay, kv):
+        def time_attention(x16, Ly, wkey, bkey, nseq, delay, kv, slots=None):
             """in-projection + causal MHA over the frames of `nseq` sequences -> ws.o16 rows (merge_tfm_encoder.py:379-385)"""
             o = ws.o16[:nseq * Tp]
+            if slots is not None and Tp == 512:
+                # the sequences are the fan-out's speaker slots: K / V projected once per utterance, from the rows of slot 0 (slot form)
+                ops.inproj_attn_causal_packed(x16, Ly[wkey + "p"], Ly[bkey], o, nseq, H, Tp, delay, kv, slots=slots,
+                                              slot_delta=self._slot_delta(slots))
+                return o
             if Tp <= 512:            # token-owning waves, packed weights, Q in registers, K / V never leave the CU (attn_stream.hip)
                 ops.inproj_attn_causal_packed(x16, Ly[wkey + "p"], Ly[bkey], o, nseq, H, Tp, delay, kv)
                 return o
@@ -394,8 +414,9 @@ class OnlineTransformerDADiarization(nn.Module):
         # ---- attractor decoder (model :112-118, merge_tfm_encoder.py:356-376)
         ops.convert_fanout(ws.emb16, P["convert.w1"], self._convert_const(C), None, ws.a16, B, Tp, C)
         o16 = ws.o16[:Md]
-        for L in P["dec.layers"]:
-            time_attention(ws.a16, L, "in1_w", "in1_b", B * C, self.dec.mask_delay, T)
+        for li, L in enumerate(P["dec.layers"]):
+            # (the first layer reads the fan-out itself: its rows differ by pc[c] between the slots of an utterance)
+            time_attention(ws.a16, L, "in1_w", "in1_b", B * C, self.dec.mask_delay, T, slots=C if li == 0 and C <= 12 else None)
             # out-projection + norm11 + speaker-axis in-projection + C x C attention in one launch (spk_stream.hip; any slot count the
             # speaker-axis kernels take, C <= 12).  It takes no T_valid: the slab's padded frames [T, Tp) are computed too (finite
             # don't-care rows, masked as keys and dropped by the head) -- 2.4 % of the rows at T = 500 / Tp = 512; a per-tile T_valid test

@@ -304,12 +304,34 @@ def inproj_attn_pack(w_in):
     return out
 
 
-def inproj_attn_causal_packed(x16, w_packed, b_in, o16, nseq, H, Tp, mask_delay=0, kv_len=None):
-    """Packed in-projection + causal attention in one launch (attn_stream.hip; Tp = 64 m <= 512, H = 4): Q, K, V never reach HBM."""
+def inproj_attn_slots_choice(n_utt, C, workgroups):
+    """Slots per item the slot form of inproj_attn_causal_packed takes for n_utt utterances of C slots on `workgroups` workgroups."""
+    S = _lib.load().eend_inproj_attn_slots_choice(n_utt, C, workgroups)
+    if S < 1:
+        _lib.check(S, "eend_inproj_attn_slots_choice")
+    return S
+
+
+def inproj_attn_causal_packed(x16, w_packed, b_in, o16, nseq, H, Tp, mask_delay=0, kv_len=None, *, slots=None, slot_delta=None,
+                              slots_per_item=0):
+    """Packed in-projection + causal attention in one launch (attn_stream.hip; Tp = 64 m <= 512, H = 4): Q, K, V never reach HBM.
+    slots = C (Tp = 512 only): the nseq = B C sequences are the C speaker slots of B utterances whose rows differ from slot 0's by a
+    constant per slot; only slot 0's rows are read, K / V are projected once per utterance and head, and slot_delta f32 [C][512]
+    (dq | dv per slot, row 0 zero) carries the constants through the projection.  slots_per_item: slots an item covers (0: chosen)."""
     L = _lib.load()
     _chk(x16, F16, "x16"); _chk(w_packed, F16, "w_packed"); _chk(b_in, F32, "b_in"); _chk(o16, F16, "o16")
     if w_packed.numel() != L.eend_inproj_attn_packed_elems() or b_in.numel() != 768 or x16.shape[0] < nseq * Tp or o16.shape[0] < nseq * Tp:
         raise _lib.EendHipError("inproj_attn_causal_packed: shape mismatch")
+    if slots is not None:
+        if slot_delta is not None:
+            _chk(slot_delta, F32, "slot_delta")
+            if slot_delta.numel() < slots * 512:
+                raise _lib.EendHipError("inproj_attn_causal_packed: slot_delta must hold [slots][512]")
+        _lib.check(L.eend_inproj_attn_causal_slots_f16(_p(x16), x16.stride(0), _p(w_packed), _p(b_in), _p(o16), nseq, H, Tp,
+                                                       o16.stride(0), mask_delay, Tp if kv_len is None else kv_len, slots,
+                                                       _p(slot_delta), slots_per_item, _stream()),
+                   "eend_inproj_attn_causal_slots_f16")
+        return
     _lib.check(L.eend_inproj_attn_causal_packed_f16(_p(x16), x16.stride(0), _p(w_packed), _p(b_in), _p(o16), nseq, H, Tp,
                                                     o16.stride(0), mask_delay, Tp if kv_len is None else kv_len, _stream()),
                "eend_inproj_attn_causal_packed_f16")

@@ -804,6 +804,20 @@ int eend_inproj_attn_pack_f16(const void* W_in, void* packed_out, void* stream);
 int eend_inproj_attn_causal_packed_f16(const void* X_f16, int ldx, const void* W_packed, const float* b_in, void* O_f16,
                                        int nseq, int H, int Tp, int ldo, int mask_delay, int kv_len, void* stream);
 
+/* The same operator on the C speaker slots of n_utt = nseq / C utterances whose input rows differ by a constant per slot (the first
+ * fusion layer behind eend_convert_fanout_f16: row (b, c, t) = row (b, 0, t) + pd[c]), Tp = 512 only (EEND_EINVAL otherwise; the caller
+ * keeps the entry above there), 1 <= C <= 12, C | nseq.  Only the rows of slot 0 (sequences b C) are read: K and V^T are projected once
+ * per (utterance, head) and serve every slot -- a constant added to all keys cancels in the softmax, one added to all values passes
+ * through it -- and per slot Q_c = bf16(q_acc + dq_c) and O_c = f16(O / l + dv_c), both adds in f32 before the only rounding.
+ * slot_delta f32 [C][512]: row c = (W_q (pd[c] - pd[0]) with W_q pre-scaled like the packed q rows | W_v (pd[c] - pd[0])), row 0 zero
+ * (not read; NULL allowed for C = 1).  An item of the kernel covers slots_per_item consecutive slots (a divisor of C, EEND_EINVAL
+ * otherwise; 0: eend_inproj_attn_slots_choice for the device's workgroup count); the result does not depend on it, bit for bit, and
+ * slot 0 equals the entry above on the slot-0 sequences.  Rows of O go to sequence b C + c. */
+int eend_inproj_attn_slots_choice(int n_utt, int C, int workgroups);
+int eend_inproj_attn_causal_slots_f16(const void* X_f16, int ldx, const void* W_packed, const float* b_in, void* O_f16,
+                                      int nseq, int H, int Tp, int ldo, int mask_delay, int kv_len, int C, const float* slot_delta,
+                                      int slots_per_item, void* stream);
+
 /* The same operator for windows of more than 512 frames (round 6; Tp = 64 m, 1 <= kv_len <= Tp, mask_delay >= 0; whole recordings at
  * test time, FS model :147 on an un-chunked sequence): the frames are cut into groups of 512 and the launch runs one item of the kernel
  * above per (sequence, head, query group, key group the mask reaches).  The item of a group with itself writes its rows of O; an item
