@@ -553,6 +553,21 @@ int eend_audio_ingest(const long* desc, int n_desc, const long* tiles, int n_til
     return eend_launch_audio_ingest(desc, n_desc, tiles, n_tiles, hist, table, decode, L, M, H, P, encoding, out, (hipStream_t)stream);
 }
 
+int eend_sim_mix_f32(const void* utts, int utt_storage, const float* rirs, const void* noises, int noise_storage, const long* mix,
+                     int n_mix, const long* tracks, const long* places, const long* tiles, int n_tiles, float* Y, double* part,
+                     void* out, int out_storage, double* Ps, double* Pn, float* scale, int* clipped, void* stream) {
+    return eend_launch_sim_mix(utts, utt_storage, rirs, noises, noise_storage, mix, n_mix, tracks, places, tiles, n_tiles, Y, part, out,
+                               out_storage, Ps, Pn, scale, clipped, (hipStream_t)stream);
+}
+
+int eend_sim_limits(int* tile, int* slice, int* max_taps) {
+    if (!tile || !slice || !max_taps) return EEND_EINVAL;
+    *tile = SIM_TILE;
+    *slice = SIM_SLICE;
+    *max_taps = SIM_MAX_TAPS;
+    return EEND_OK;
+}
+
 int eend_pit_cost_f64(const float* y, const float* labels, int B, int T, int C, double* cost, void* stream) {
     return eend_launch_pit_cost(y, labels, B, T, C, cost, (hipStream_t)stream);
 }

@@ -148,6 +148,17 @@ int eend_launch_chunk_batch(const void* corpus, int storage, const int* segments
 int eend_launch_audio_ingest(const long* desc, int n_desc, const long* tiles, int n_tiles, float* hist, const float* table,
                              const float* decode, int L, int M, int H, int P, int encoding, float* out, hipStream_t stream);
 
+// simulated mixtures (simulate.hip): outputs per tile, m steps per tap slice, the most taps of a track, words per descriptor row
+#define SIM_TILE 2048
+#define SIM_SLICE 1024
+#define SIM_MAX_TAPS 8192
+#define SIM_MIX_WORDS 10
+#define SIM_TRACK_WORDS 5
+#define SIM_PLACE_WORDS 3
+int eend_launch_sim_mix(const void* utts, int utt_storage, const float* rirs, const void* noises, int noise_storage, const long* mix,
+                        int n_mix, const long* tracks, const long* places, const long* tiles, int n_tiles, float* Y, double* part,
+                        void* out, int out_storage, double* Ps, double* Pn, float* scale, int* clipped, hipStream_t stream);
+
 int eend_launch_pit_cost(const float* y, const float* lab, int B, int T, int C, double* cost, hipStream_t stream);
 int eend_launch_pit_assign(const double* cost, const int* nspk, int B, int C, int* perm, double* loss, hipStream_t stream);
 

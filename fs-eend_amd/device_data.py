@@ -111,6 +111,13 @@ class DeviceCorpus:
             raise TypeError(f"{rec}: an s16 corpus takes int16 samples, got {w.dtype}")
         if self.storage == "f32" and not w.is_floating_point():
             raise TypeError(f"{rec}: an f32 corpus takes float samples, got {w.dtype}")
+        spk, rows = self._segment_rows(rec, segments, utt2spk)
+        n = int(w.numel())
+        self._waves.append(w.detach().to(dtype))
+        self._enter(rec, n, spk, rows)
+
+    def _segment_rows(self, rec, segments, utt2spk):
+        """(the recording's speakers as np.unique orders them, its segment rows (start frame, end frame, speaker index))."""
         segments = list(segments)
         spk = np.unique([utt2spk[utt] for utt, _, _ in segments]).tolist()      # feature.py:290-292
         rows = []
@@ -122,8 +129,9 @@ class DeviceCorpus:
             rows.append((sf, ef, spk.index(utt2spk[utt])))
         if len(spk) > MAX_SPEAKERS:
             raise ValueError(f"{rec}: {len(spk)} speakers, at most {MAX_SPEAKERS} are supported")
-        n = int(w.numel())
-        self._waves.append(w.detach().to(dtype))
+        return spk, rows
+
+    def _enter(self, rec, n, spk, rows):
         self._len[rec], self._off[rec] = n, self._n_samples
         self._seg[rec] = (len(self._segrows), len(self._segrows) + len(rows))
         self._segrows += rows
@@ -145,12 +153,37 @@ class DeviceCorpus:
         for w in self._waves:
             self.samples[at:at + w.numel()].copy_(w, non_blocking=True)
             at += w.numel()
+        return self._finish()
+
+    def _finish(self, wait=True):
         seg = np.asarray(self._segrows if self._segrows else [(0, 0, 0)], dtype=np.int32).reshape(-1, 3)
         self.segments = torch.from_numpy(seg).to(self.dev)
-        torch.cuda.current_stream(self.dev).synchronize()       # the host copies may go once the upload is done
+        if wait:
+            torch.cuda.current_stream(self.dev).synchronize()   # the host copies may go once the upload is done
         self._waves = []
         self.dft, self.melT = feature._tables(self.dev)
         return self
+
+    @classmethod
+    def from_device(cls, samples, records, storage: str = "f32", device=None, **kw):
+        """A finalized corpus that adopts `samples`, a 1-D device tensor (float32 for storage "f32", int16 for "s16") holding
+        the recordings back to back, e.g. as simulate.simulate wrote them.  records: [(rec, samples, segments, utt2spk)] in that
+        order, segments and utt2spk as `add` takes them.  The tensor is kept, not copied."""
+        self = cls(samples.device if device is None else device, storage, **kw)
+        if not samples.is_cuda or self.dev.index not in (None, samples.device.index) or samples.dim() != 1 or samples.dtype != STORAGES[storage][1]:
+            raise TypeError(f"a {storage} corpus on {self.dev} adopts a 1-D {STORAGES[storage][1]} tensor there, got "
+                            f"{samples.dtype} {tuple(samples.shape)} on {samples.device}")
+        for rec, n, segments, utt2spk in records:
+            if rec in self._len:
+                raise ValueError(f"recording {rec!r} is already in the corpus")
+            if n < 0:
+                raise ValueError(f"{rec}: {n} samples")
+            spk, rows = self._segment_rows(rec, segments, utt2spk)
+            self._enter(rec, int(n), spk, rows)
+        if self._n_samples > samples.numel():
+            raise ValueError(f"the records name {self._n_samples} samples, the tensor holds {samples.numel()}")
+        self.samples = samples
+        return self._finish(wait=False)                         # no host copy of samples: whoever wrote them is not waited for
 
     # ---- one batch
     def plan(self, rows, context_size=7, subsampling=10, input_transform="logmel23_mn", n_speakers=None):

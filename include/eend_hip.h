@@ -490,6 +490,44 @@ int eend_chunk_batch_f32(const void* corpus, int storage, const int* segments, c
 int eend_audio_ingest(const long* desc, int n_desc, const long* tiles, int n_tiles, float* hist, const float* table,
                       const float* decode, int L, int M, int H, int P, int encoding, float* out, void* stream);
 
+/* Simulated training mixtures from resident dry sources: single-speaker utterances laid out with silences, convolved with a room
+ * impulse response per speaker, summed, with noise added at a chosen SNR (the `data_simu_*` sets both shipped configs train on;
+ * the reference takes them as files made elsewhere).  All audio is 8 kHz; all inputs are assumed finite.  Pools: utts and noises
+ * hold their waves back to back, storage 0 = f32, 1 = 16-bit PCM decoded as v / 32768; rirs f32.
+ *
+ * Arithmetic contract.  Mixture m has N samples and S <= 64 tracks.  Track s has a gain g (f32), an impulse response h[0 .. K),
+ * K <= 8192, or none, and placements (start >= 0, source, len), sorted by start and disjoint, len already clipped to N - start.
+ *   dry track   d_s[t] = the source sample where a placement covers t, 0 elsewhere and for t < 0;
+ *   taps        a_s[k] = f32(g h[k]), one f32 multiply; without a response a_s = {g}, K = 1;
+ *   wet mix     y[t] = sum_s sum_k a_s[k] d_s[t - k] for 0 <= t < N (the tail past N is dropped), in f32 with one accumulator per
+ *               output: acc = fmaf(a_s[k], d_s[t - k], acc) from +0, tracks ascending, taps ascending.  Zero products are added
+ *               or left out freely (before and after the taps, and whole spans that meet no placement): they leave acc as it
+ *               is, so an output's value depends on its own taps and samples only, not on its tile, on the other mixtures of
+ *               the call or on the silences skipped (only the sign of a zero that arose from a product underflowing to -0 can
+ *               differ);
+ *   noise       Ps = sum_t y[t]^2 and Pn = sum_t n[(o + t) mod L]^2 over t < N in float64, both in one fixed order (per tile of
+ *               2048 samples 256 running sums of stride 256, then a binary tree; per mixture the same over its tiles);
+ *               scale = f32(sqrt(c Ps / Pn)) in float64 with c = 10^(-snr_db / 10) from the host, 0 when there is no noise
+ *               (L = 0) or Pn = 0 or Ps = 0;  out[t] = fmaf(scale, n[(o + t) mod L], y[t]), and y[t] itself when scale = 0;
+ *   storage     out_storage 0 stores out as f32; 1 stores rint(out 32768), half to even, clamped to [-32768, 32767], and
+ *               clipped[m] counts the clamped samples.
+ * Tables, i64, trusted (fs-eend_amd/simulate.py `plan` builds and checks them): mix [n_mix][10] = {N, index of its first sample in
+ * Y and out, first track row, tracks, index in noises of its noise, L (0 = none), o >= 0, the bits of the double c, first tile
+ * row, tiles}; tracks [.][5] = {index in rirs of h or -1, K, the bits of the f32 g, first placement row, placements}; places
+ * [.][3] = {start, index in utts of the utterance's first sample, len}; tiles [n_tiles][2] = {mixture, first output}, the tiles
+ * of a mixture consecutive and 2048 outputs apart.  Y f32 scratch [sum N]: the wet mix; part f64 scratch [n_tiles][2]; out f32
+ * or s16 [sum N]; Ps, Pn f64 [n_mix], scale f32 [n_mix], clipped i32 [n_mix].  Four launches whatever the call holds: the FIR
+ * on v_mfma_f32_16x16x4_f32 (a Toeplitz product, csrc/simulate.hip), the tile sums, the scales, the store.  Stateless,
+ * stream-ordered, nothing allocated, the host not waited for.  EEND_EINVAL: a NULL pointer (pass any valid address for an empty
+ * pool), a storage outside 0 .. 1, n_mix above 65535, fewer tiles than mixtures. */
+int eend_sim_mix_f32(const void* utts, int utt_storage, const float* rirs, const void* noises, int noise_storage, const long* mix,
+                     int n_mix, const long* tracks, const long* places, const long* tiles, int n_tiles, float* Y, double* part,
+                     void* out, int out_storage, double* Ps, double* Pn, float* scale, int* clipped, void* stream);
+
+/* The layout constants of eend_sim_mix_f32: outputs per tile, FIR steps per tap slice, the most taps of a track (host arithmetic
+ * only). */
+int eend_sim_limits(int* tile, int* slice, int* max_taps);
+
 /* ---- permutation-invariant label assignment (FS-EEND/train/utils/loss.py:257-327 batch_pit_n_speaker_loss;
  * LS-EEND/train/utils/loss.py:350-379 pit_loss_multispk) ---- */
 
