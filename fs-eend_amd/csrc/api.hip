@@ -568,6 +568,19 @@ int eend_sim_limits(int* tile, int* slice, int* max_taps) {
     return EEND_OK;
 }
 
+int eend_room_rir_f32(const long* rooms, int n_rows, const long* tiles, int n_tiles, float* out, void* stream) {
+    return eend_launch_room_rir(rooms, n_rows, tiles, n_tiles, out, (hipStream_t)stream);
+}
+
+int eend_room_limits(int* tile, int* window, int* max_rows, int* max_axis) {
+    if (!tile || !window || !max_rows || !max_axis) return EEND_EINVAL;
+    *tile = ROOM_TILE;
+    *window = ROOM_WINDOW;
+    *max_rows = ROOM_MAX_ROWS;
+    *max_axis = ROOM_MAX_AXIS;
+    return EEND_OK;
+}
+
 int eend_pit_cost_f64(const float* y, const float* labels, int B, int T, int C, double* cost, void* stream) {
     return eend_launch_pit_cost(y, labels, B, T, C, cost, (hipStream_t)stream);
 }

@@ -159,6 +159,15 @@ int eend_launch_sim_mix(const void* utts, int utt_storage, const float* rirs, co
                         int n_mix, const long* tracks, const long* places, const long* tiles, int n_tiles, float* Y, double* part,
                         void* out, int out_storage, double* Ps, double* Pn, float* scale, int* clipped, hipStream_t stream);
 
+// room impulse responses (room.hip): taps per tile, the interpolator's width in taps, the most rows of a call, the most table
+// entries of an axis (2 (2 N + 1) for image indices |n| <= N), words per row
+#define ROOM_TILE 64
+#define ROOM_WINDOW 64
+#define ROOM_MAX_ROWS 65535
+#define ROOM_MAX_AXIS 1022
+#define ROOM_WORDS 20
+int eend_launch_room_rir(const long* rooms, int n_rows, const long* tiles, int n_tiles, float* out, hipStream_t stream);
+
 int eend_launch_pit_cost(const float* y, const float* lab, int B, int T, int C, double* cost, hipStream_t stream);
 int eend_launch_pit_assign(const double* cost, const int* nspk, int B, int C, int* perm, double* loss, hipStream_t stream);
 

@@ -88,6 +88,8 @@ PROTOTYPES = {
     "eend_audio_ingest": [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp],
     "eend_sim_mix_f32": [_vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp],
     "eend_sim_limits": [_vp, _vp, _vp],
+    "eend_room_rir_f32": [_vp, _i, _vp, _i, _vp, _vp],
+    "eend_room_limits": [_vp, _vp, _vp, _vp],
     "eend_pit_cost_f64": [_vp, _vp, _i, _i, _i, _vp, _vp],
     "eend_pit_assign_i32": [_vp, _vp, _i, _i, _vp, _vp, _vp],
     "eend_retention_proj_f16": [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],

@@ -7,6 +7,7 @@ and one call turns a list of recipes into a finalized `device_data.DeviceCorpus`
 
     utts, rirs, noises = SourcePool("cuda:0", "s16"), SourcePool("cuda:0"), SourcePool("cuda:0", "s16")
     utts.add(name, wave) ...; utts.finalize()            # likewise rirs (always "f32") and noises
+    rirs = rooms.room_responses(rows, taps)              # or: responses of drawn rooms made on the device (rooms.py), none loaded
     recipes = draw_recipes(seed, spk2utt, utts, rirs=rirs, noises=noises, n_mixtures=64)
     corpus, stats = simulate(utts, rirs, noises, recipes, storage="f32")
     feats, labels, recs = corpus.batch(rows)             # as with a corpus built by add / finalize
@@ -16,6 +17,10 @@ name, start sample)]}], "noise" (name or None), "noise_offset", "snr_db" (or Non
 wet mix, noise scale, storage) is written down at eend_sim_mix_f32 in include/eend_hip.h and in DESIGN 10d; tests/simulate_ref.py
 restates it in float64.  `plan` does everything the host decides, with every refusal, in numpy and without a device; the tables
 travel in one pinned block with one asynchronous copy, and the device runs four launches whatever the call holds.
+
+Impulse responses no longer have to be loaded: `rooms.room_responses` generates them on the device by the image method and
+returns the pool `simulate` takes as `rirs` (`SourcePool.from_device` adopts any device tensor), and `draw_recipes(...,
+rir_groups=groups)` keeps the speakers of a mixture in one room.
 
 Out of scope: reading audio or Kaldi files, rates other than 8 kHz (convert with `audio_ingest.convert` first), FFT or
 overlap-save convolution, sharding across ranks, equality with any particular external mixing script.
@@ -73,6 +78,26 @@ class SourcePool:
             at += w.numel()
         torch.cuda.current_stream(self.dev).synchronize()       # the host copies may go once the upload is done
         self._waves = []
+        return self
+
+    @classmethod
+    def from_device(cls, samples, table, storage: str = "f32"):
+        """A finalized pool that adopts `samples`, a 1-D device tensor (float32 for storage "f32", int16 for "s16") holding the
+        waves named by `table` {name: (first sample, samples)}, e.g. as rooms.room_responses wrote them: the counterpart of
+        DeviceCorpus.from_device.  The tensor is kept, not copied, and whoever wrote it is not waited for."""
+        if storage not in STORAGES:
+            raise ValueError(f"storage must be one of {sorted(STORAGES)}, got {storage!r}")
+        if not isinstance(samples, torch.Tensor) or samples.dtype != STORAGES[storage][1] or samples.dim() != 1:
+            raise TypeError(f"a {storage} pool adopts a 1-D {STORAGES[storage][1]} tensor, got "
+                            f"{getattr(samples, 'dtype', type(samples))} {tuple(getattr(samples, 'shape', ()))}")
+        table = {name: (int(first), int(n)) for name, (first, n) in dict(table).items()}
+        for name, (first, n) in table.items():
+            if first < 0 or n < 0 or first + n > samples.numel():
+                raise ValueError(f"{name!r}: samples {first} .. {first + n} lie outside the tensor's {samples.numel()}")
+        if not samples.is_cuda:
+            raise _lib.EendHipError("SourcePool lives on the GPU (no CPU fallback)")
+        self = cls(samples.device, storage)
+        self.table, self._n, self.samples = table, int(samples.numel()), samples
         return self
 
 
@@ -225,16 +250,30 @@ def _length(utts, name):
 
 
 def draw_recipes(seed, spk2utt, utts, rirs=None, noises=None, n_mixtures=1, n_speakers=(1, 4), n_utts=(2, 5), beta=2.0,
-                 gain_db=(-3.0, 3.0), snr_db=(10.0, 15.0, 20.0), prefix="mix"):
+                 gain_db=(-3.0, 3.0), snr_db=(10.0, 15.0, 20.0), prefix="mix", rir_groups=None):
     """The usual generator of simulated mixtures (host only, deterministic in the seed).  spk2utt: {speaker: [utterance name]};
     utts, rirs, noises: a SourcePool or its table (rirs / noises None or empty: dry / clean mixtures).  Per mixture: a number of
     speakers in n_speakers (inclusive, drawn without replacement); per speaker a number of utterances in n_utts (inclusive),
     each preceded by a silence drawn from an exponential with mean `beta` seconds, one impulse response and one gain (uniform
     in dB over gain_db); per mixture one noise, an offset into it and an SNR from snr_db.  The mixture's length is the end of
-    its longest track.  Every draw comes from numpy.random.Generator(PCG64(seed)) in a fixed order."""
+    its longest track.  Every draw comes from numpy.random.Generator(PCG64(seed)) in a fixed order.
+
+    rir_groups {room: [response names]} (rooms.draw_rooms makes one) puts a mixture in one room: after its speakers the mixture
+    draws a room, then one response per speaker from that room without replacement, so all its speakers share a room and a
+    microphone; the per-speaker response draw is left out.  A room with fewer responses than the mixture has speakers is
+    refused.  With None every draw and the result are what they are without the argument."""
     rng = np.random.Generator(np.random.PCG64(seed))
     speakers = sorted(spk2utt)
     rir_names, noise_names = sorted(_table(rirs)), sorted(_table(noises))
+    rooms = None
+    if rir_groups is not None:
+        rooms = sorted(rir_groups)
+        if not rooms:
+            raise ValueError("rir_groups names no room")
+        for room in rooms:
+            for h in rir_groups[room]:
+                if h not in _table(rirs):
+                    raise KeyError(f"room {room!r}: unknown impulse response {h!r}")
     lo, hi = n_speakers
     if not 1 <= lo <= hi <= min(len(speakers), MAX_TRACKS):
         raise ValueError(f"n_speakers {n_speakers} must lie in 1 .. {min(len(speakers), MAX_TRACKS)}")
@@ -242,6 +281,12 @@ def draw_recipes(seed, spk2utt, utts, rirs=None, noises=None, n_mixtures=1, n_sp
     for i in range(n_mixtures):
         chosen = rng.choice(len(speakers), size=int(rng.integers(lo, hi + 1)), replace=False)
         tracks, length = [], 1
+        shared = None
+        if rooms is not None:
+            room = rooms[int(rng.integers(len(rooms)))]
+            if len(rir_groups[room]) < len(chosen):
+                raise ValueError(f"room {room!r} has {len(rir_groups[room])} responses, the mixture {len(chosen)} speakers")
+            shared = [rir_groups[room][j] for j in rng.choice(len(rir_groups[room]), size=len(chosen), replace=False).tolist()]
         for si in chosen.tolist():
             spk, pos, placements = speakers[si], 0, []
             for _ in range(int(rng.integers(n_utts[0], n_utts[1] + 1))):
@@ -249,7 +294,10 @@ def draw_recipes(seed, spk2utt, utts, rirs=None, noises=None, n_mixtures=1, n_sp
                 pos += int(np.rint(rng.exponential(beta) * RATE))
                 placements.append((utt, pos))
                 pos += _length(utts, utt)
-            rir = rir_names[int(rng.integers(len(rir_names)))] if rir_names else None
+            if shared is not None:
+                rir = shared[len(tracks)]
+            else:
+                rir = rir_names[int(rng.integers(len(rir_names)))] if rir_names else None
             gain = float(10.0 ** (rng.uniform(*gain_db) / 20.0))
             tracks.append({"speaker": spk, "rir": rir, "gain": gain, "placements": placements})
             length = max(length, pos)

@@ -528,6 +528,40 @@ int eend_sim_mix_f32(const void* utts, int utt_storage, const float* rirs, const
  * only). */
 int eend_sim_limits(int* tile, int* slice, int* max_taps);
 
+/* Room impulse responses of shoebox rooms by the image method: the `rirs` pool of eend_sim_mix_f32 made on the device.  8 kHz
+ * throughout; all inputs are finite doubles from the host.  One row is one response of K taps, 1 <= K <= 8192.
+ *
+ * Arithmetic contract.  A row has a room L = (Lx, Ly, Lz), a source s and a receiver r strictly inside it, six wall reflection
+ * coefficients in [0, 1] (x0 the wall at x = 0, x1 the wall at x = Lx, then y0, y1, z0, z1), q = 8000 / c samples per metre, a
+ * scale g.  Image (n, l, m, u, v, w), n, l, m integer, u, v, w in {0, 1}:
+ *   offset      p = (((1 - 2u) sx + 2n Lx) - rx, ((1 - 2v) sy + 2l Ly) - ry, ((1 - 2w) sz + 2m Lz) - rz)
+ *   distance    d = sqrt(px px + (py py + pz pz)),  delay  tau = q d  samples,  tau = kc + f with kc = rint(tau), |f| <= 1/2
+ *   amplitude   A = g x0^|n-u| x1^|n| y0^|l-v| y1^|l| z0^|m-w| z1^|m| / d,  0^0 = 1
+ *               all of this in IEEE float64, the offset, distance and delay operation by operation as written, without fused
+ *               multiply-adds: kc and f are then the same bits on any machine;
+ *   interpolator  w(x) = sinc(x) (1 + cos(2 pi x / W)) / 2 for |x| < W / 2, else 0; W = 64 samples; sinc(0) = 1.  At tap k the
+ *               image stands at x = j - f, j = k - kc, and is evaluated in the split form, which keeps f where x would lose it:
+ *                 sin(pi x) = -(-1)^j sin(pi f),    (1 + cos(2 pi x / W)) / 2 = sin^2(pi y / W),  y = W / 2 - |x| = (W / 2 - |j|) +- f,
+ *               live exactly when y > 0: |j| < 32, or j = 32 with f > 0, or j = -32 with f < 0;
+ *   response    h[k] = sum A_i w(k - tau_i), k = 0 .. K - 1, over every image whose window meets [0, K): the image set is defined
+ *               by time, not by a reflection order; what falls at k < 0 or k >= K is dropped; images with A = 0 are skipped.
+ *               Output f32.  Against the float64 sum every tap satisfies |h[k] - ref[k]| <= (n_k + 16) 2^-24 S_k, n_k the number
+ *               of images with a non-zero term at k and S_k the sum of the terms' magnitudes: an f32 sum of n_k terms in any
+ *               order plus 16 units for one term (tests/room_ref.py is the float64 restatement).
+ *   bits        a response's bits depend on its own row only: not on the other rows, their order or the run.  No atomics.
+ * rooms i64 [n_rows][20], trusted (fs-eend_amd/rooms.py `plan_rooms` builds and checks them): words 0 .. 16 the bits of the doubles
+ * Lx, Ly, Lz, sx, sy, sz, rx, ry, rz, x0, x1, y0, y1, z0, z1, q, g; 17 = K; 18 = index in out of the row's first tap; 19 = the
+ * row's tiles.  tiles i64 [n_tiles][2] = {row, first tap}, a multiple of 64, in any order (the host puts the tiles with the most
+ * images first).  out f32: every tap k < K of every tile is written once.  One launch, one workgroup per tile (csrc/room.hip);
+ * stateless, stream-ordered, nothing allocated, the host not waited for.  A row must keep 2 (2 N + 1) <= 1022 on every axis,
+ * N = floor((K + 31) / (2 q L)) + 1 (eend_room_limits); the kernel clamps N there and would lose images beyond it.
+ * EEND_EINVAL: a NULL pointer, n_rows above 65535, fewer tiles than rows. */
+int eend_room_rir_f32(const long* rooms, int n_rows, const long* tiles, int n_tiles, float* out, void* stream);
+
+/* The layout constants of eend_room_rir_f32: taps per tile, W, the most rows of a call, the most table entries of an axis (host
+ * arithmetic only). */
+int eend_room_limits(int* tile, int* window, int* max_rows, int* max_axis);
+
 /* ---- permutation-invariant label assignment (FS-EEND/train/utils/loss.py:257-327 batch_pit_n_speaker_loss;
  * LS-EEND/train/utils/loss.py:350-379 pit_loss_multispk) ---- */
 
