@@ -3,9 +3,13 @@
 // contract is stated in include/eend_hip.h at eend_collar_der_sweep_u64; point g = i_theta * n_medians + i_median gives exactly
 // eend_collar_der_u64 over eend_sad_fuse_f32 (with flags) + eend_activity_median_u8 of the posteriors at that point.
 //
-// der_sweep_pass_kernel, grid (tile groups, recordings), 256 threads, follows der_collar_pass_kernel: a workgroup walks tiles of
-// DER_TILE reference frames of one recording.  Per tile
-//   1. once, the reference side as in der_collar.hip: speaker masks with the collar halo, boundary bits and their prefix
+// der_sweep_pass_kernel, grid (tile groups, recordings), 256 threads, is der_collar_pass_kernel at G points: a workgroup walks
+// tiles of DER_TILE reference frames of one recording.  From der_tile.h it takes load_masks, the launcher's parts and the scalar
+// rules of decision.h.  Its recording header, tile extents and steps 1 and 4 below are rec_header, tile_extents, ref_side and
+// score_point of der_tile.h in this kernel's own text, so a change to one of them is made in both places: written with the
+// functions the kernel compiled to other code (147 or 165 VGPRs for 164; with the header and extents alone the same
+// instructions but one) that measured 0.1 to 1.8 % slower on the 5 x 2 and 16 x 2 grids.  Per tile
+//   1. once, the reference side: speaker masks with the collar halo, boundary bits and their prefix
 //      population count, keep; total and frames kept; the bit planes R_i & keep; per thread, keep and nr of its 4 frames and the
 //      hypothesis frame under each (one byte and one index per frame, in registers);
 //   2. once, the float32 posterior rows of the hypothesis frames under the tile plus max(median) / 2 frames on each side (zeros
@@ -17,13 +21,13 @@
 //   3. per threshold, a ballot per speaker turns the masks into bit planes over the staged frames, and a prefix population count
 //      over their 64-bit words follows;
 //   4. per median k of that threshold, the filtered mask of a hypothesis frame is 16 window counts, each the difference of two
-//      prefix counts (k = 1 copies the decision); then per reference frame nh, min(nr, nh) and a ballot per speaker into the
-//      planes H_j, and thread (i, j) adds popcount(R_i & keep & H_j) over the tile's 64-frame groups.
+//      prefix counts (k = 1 copies the decision); then per reference frame nh, min(nr, nh) and a ballot per speaker
+//      into the planes H_j, and thread (i, j) adds popcount(R_i & keep & H_j) over the tile's 64-frame groups.
 // The sums of nh over kept frames fall out of the ballots (popcount(H_j & keep)), the sums of min(nr, nh) are taken by ballots
 // over its 7 bits, both per wave in scalar registers; miss = total - sum of min, false alarm = sum of nh - sum of min.  The 32
 // co-occurrence accumulators of a thread are named registers: the point loop is not unrolled, the add selects the register by
 // an unrolled compare, so nothing is indexed dynamically and nothing spills.  All sums are 64-bit; one integer atomic per sum
-// and workgroup at the end, after der_sweep_clear_kernel, so every run gives the same bits.  The assignment is
+// and workgroup at the end, after der_clear_kernel, so every run gives the same bits.  The assignment is
 // der_collar_assign_kernel on G * B matrices, which also marks the points with a median out of range and adds to the totals.
 //
 // LDS per workgroup: 21 488 bytes static (16 416 of them one block that holds, in turn, the reference masks, the float rows
@@ -43,21 +47,13 @@ using namespace der;
 
 constexpr int NTH = DER_SWEEP_NTHETA, NMED = DER_SWEEP_NMED, GMAX = DER_SWEEP_GMAX;
 constexpr int HKMAX = DER_SWEEP_KMAX / 2;                       // largest median halo, hypothesis frames
-constexpr int ROUNDS = TILE / NT;                               // reference frames per thread and tile
 constexpr int FSTAGE = NT * CMAX + 8;                           // floats: NT rows of CMAX, entered at any float of the first 16 bytes
 constexpr int PW = (TILE + 2 * HKMAX + NT - 1) / NT * (NT / 64) + 1;   // plane words per speaker, and one prefix count beyond
 constexpr int P_BYTES = CMAX * PW * 8, PH_BYTES = NGRP * CMAX * 8, CUM_BYTES = CMAX * PW * 2, HM_BYTES = TILE * 2;
 constexpr int REF_BYTES = EXT * 2 + STAGE_WORDS * 4, POINT_BYTES = P_BYTES + PH_BYTES + CUM_BYTES + HM_BYTES;
 constexpr int SCRATCH = FSTAGE * 4;
 static_assert(SCRATCH >= REF_BYTES && SCRATCH >= POINT_BYTES && SCRATCH % 16 == 0 && (EXT * 2) % 4 == 0, "der_sweep scratch block");
-static_assert(ROUNDS == 4 && GMAX == NTH * 2 && NT / 64 == 4, "der_sweep layout");
-
-__global__ __launch_bounds__(NT)
-void der_sweep_clear_kernel(unsigned long long* __restrict__ counters, unsigned long long* __restrict__ cooc, long n) {
-    const size_t i = (size_t)blockIdx.x * NT + threadIdx.x;
-    if (i < (size_t)n * 8) counters[i] = 0;
-    if (i < (size_t)n * CMAX * CMAX) cooc[i] = 0;
-}
+static_assert(GMAX == NTH * 2 && NT / 64 == 4, "der_sweep layout");
 
 __global__ __launch_bounds__(NT)
 void der_sweep_pass_kernel(const unsigned char* __restrict__ ref, const int* __restrict__ roff, int Cr,
@@ -113,7 +109,7 @@ void der_sweep_pass_kernel(const unsigned char* __restrict__ ref, const int* __r
         const int k0 = t0 / sub, nk = (t0 + tl - 1) / sub - k0 + 1;
         const int ng = ((tl + NT - 1) / NT) * (NT / 64);
 
-        // ---- 1. the reference side, as der_collar_pass_kernel
+        // ---- 1. the reference side, as ref_side of der_tile.h
         load_masks(ref, r0, Tr, Cr, t0 - h, n, rmask, stage);
         for (int e0 = 0; e0 <= n - 1; e0 += NT) {
             const int e = e0 + tid;
@@ -205,10 +201,7 @@ void der_sweep_pass_kernel(const unsigned char* __restrict__ ref, const int* __r
                         const float v = row[cc];
 #pragma unroll
                         for (int i = 0; i < NTH; ++i) d[i] |= (v > th[i] ? 1u : 0u) << cc;
-                        if (v == v && (best < 0 || v > top || (v == top && cc < best))) {   // never NaN; lowest index on ties
-                            best = cc;
-                            top = v;
-                        }
+                        winner_update(best, top, v, cc);
                         cc = cc + 1 == Ch ? 0 : cc + 1;
                     }
                     if (sad) {
@@ -263,13 +256,14 @@ void der_sweep_pass_kernel(const unsigned char* __restrict__ ref, const int* __r
                             const int o = s * PW;
                             const unsigned clo = cum[o + (lo >> 6)] + __popcll(P[o + (lo >> 6)] & mlo);
                             const unsigned chi = cum[o + (hi >> 6)] + __popcll(P[o + (hi >> 6)] & mhi);
-                            m |= (chi - clo >= (unsigned)hk + 1 ? 1u : 0u) << s;
+                            m |= (median_of(chi - clo, k) ? 1u : 0u) << s;
                         }
                     }
                     hm[e] = (unsigned short)m;
                 }
                 __syncthreads();
-                unsigned bt = 0, nhw = 0;                         // this thread's sum of min(nr, nh); this wave's sum of nh, kept
+                // as score_point of der_tile.h: this thread's sum of min(nr, nh); this wave's sum of nh over kept frames
+                unsigned bt = 0, nhw = 0;
 #pragma unroll
                 for (int r = 0; r < ROUNDS; ++r)
                     if (r * NT < tl) {
@@ -339,19 +333,14 @@ int eend_launch_collar_der_sweep(const unsigned char* ref, const int* roff, int 
                                  int h, int skip, unsigned long long* counters, unsigned long long* cooc, int* mapping,
                                  unsigned long long* totals, hipStream_t stream) {
     if (!ref || !roff || !pred || !poff || !thresholds || !medians || !counters || !cooc || !mapping) return EEND_EINVAL;
-    if (Cr < 1 || Cr > CMAX || Ch < 1 || Ch > CMAX || B < 1 || B > 65535 || sub < 1 || h < 0 || h > HMAX) return EEND_EINVAL;
+    if (!der_args_ok(Cr, Ch, B, sub, h)) return EEND_EINVAL;
     if (nth < 1 || nth > NTH || nmed < 1 || nmed > NMED || nth * nmed > GMAX) return EEND_EINVAL;
     if (((uintptr_t)pred & 3) != 0) return EEND_EINVAL;
     const int G = nth * nmed;
-    const long n = (long)G * B;
-    hipLaunchKernelGGL(der_sweep_clear_kernel, dim3((unsigned)n), dim3(NT), 0, stream, counters, cooc, n);
-    if (hipGetLastError() != hipSuccess) return EEND_ELAUNCH;
-    // tile groups as eend_launch_collar_der sizes them: the lengths live on the device
-    int groups = 4096 / B;
-    groups = groups < 1 ? 1 : (groups > DER_MAX_GROUPS ? DER_MAX_GROUPS : groups);
+    if (!der_clear(counters, cooc, (long)G * B, stream)) return EEND_ELAUNCH;
     const int hcap = sweep_staged_frames(sub);
-    hipLaunchKernelGGL(der_sweep_pass_kernel, dim3(groups, B), dim3(NT), (size_t)nth * hcap * 2, stream, ref, roff, Cr, pred, poff, Ch, sad,
-                       thresholds, nth, medians, nmed, sub, h, skip ? 1 : 0, hcap, B, counters, cooc);
+    hipLaunchKernelGGL(der_sweep_pass_kernel, dim3(der_tile_groups(B), B), dim3(NT), (size_t)nth * hcap * 2, stream, ref, roff, Cr,
+                       pred, poff, Ch, sad, thresholds, nth, medians, nmed, sub, h, skip ? 1 : 0, hcap, B, counters, cooc);
     if (hipGetLastError() != hipSuccess) return EEND_ELAUNCH;
     return eend_launch_collar_der_assign(roff, poff, Cr, Ch, B, G, sub, medians, nmed, counters, cooc, mapping, totals, stream);
 }

@@ -5,10 +5,11 @@
 //     cost[i][j] = sum_t BCEwithLogits(y[t,i], label[t,j]) = sum_t softplus(y[t,i]) - sum_t y[t,i] label[t,j]
 // over the -1-padded batch length, and an assignment on its leading n x n block (the other slots keep their
 // place).  pit_cost_kernel: one block per utterance, thread (i,j), frames staged through LDS, fp64 sums.
-// pit_assign_kernel: one thread per utterance runs the O(n^3) shortest-augmenting-path (Jonker-Volgenant /
-// Hungarian) solver in fp64 -- n <= 16, so this is latency, not throughput, work; no host round trip.
+// pit_assign_kernel: one thread per utterance runs the shortest-augmenting-path solver of assign.h (shared with
+// der_collar.hip) in fp64 on per-thread arrays; no host round trip.
 #include "common.h"
 #include "kernels.h"
+#include "assign.h"
 
 namespace {
 
@@ -60,33 +61,7 @@ void pit_assign_kernel(const double* __restrict__ cost, const int* __restrict__ 
     double u[CMAX + 1], v[CMAX + 1], minv[CMAX + 1];
     int p[CMAX + 1], way[CMAX + 1];
     bool used[CMAX + 1];
-    for (int k = 0; k <= n; ++k) { u[k] = 0.0; v[k] = 0.0; p[k] = 0; way[k] = 0; }
-    for (int i = 1; i <= n; ++i) {
-        p[0] = i;
-        int j0 = 0;
-        for (int k = 0; k <= n; ++k) { minv[k] = 1e300; used[k] = false; }
-        do {
-            used[j0] = true;
-            const int i0 = p[j0];
-            double delta = 1e300;
-            int j1 = 0;
-            for (int j = 1; j <= n; ++j)
-                if (!used[j]) {
-                    const double cur = a[(i0 - 1) * C + (j - 1)] - u[i0] - v[j];
-                    if (cur < minv[j]) { minv[j] = cur; way[j] = j0; }
-                    if (minv[j] < delta) { delta = minv[j]; j1 = j; }
-                }
-            for (int j = 0; j <= n; ++j)
-                if (used[j]) { u[p[j]] += delta; v[j] -= delta; }
-                else minv[j] -= delta;
-            j0 = j1;
-        } while (p[j0] != 0);
-        do {
-            const int j1 = way[j0];
-            p[j0] = p[j1];
-            j0 = j1;
-        } while (j0);
-    }
+    assign_rows<double>(a, C, n, 1e300, u, v, minv, p, way, used);
     double tot = 0.0;
     for (int j = 1; j <= n; ++j) {
         perm[(size_t)b * C + (p[j] - 1)] = j - 1;

@@ -6,11 +6,11 @@
 // All results are bit exact against the reference (tests/golden/post_*.npz).
 #include "common.h"
 #include "kernels.h"
+#include "decision.h"                                // winner_update, median_of
 
 namespace {
 
-// pred (T, S) probabilities -> 0/1 after `> thr` and a zero-padded median of k (odd) along time: the median of k
-// binary values is 1 exactly when at least k/2 + 1 of them are 1.
+// pred (T, S) probabilities -> 0/1 after `> thr` and a zero-padded median of k (odd) along time (der::median_of).
 __global__ __launch_bounds__(256)
 void activity_median_kernel(const float* __restrict__ pred, int ld, int T, int S, float thr, int k, unsigned char* __restrict__ out) {
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
@@ -22,12 +22,12 @@ void activity_median_kernel(const float* __restrict__ pred, int ld, int T, int S
         const int u = t + d;
         if (u >= 0 && u < T) cnt += pred[(long)u * ld + s] > thr ? 1 : 0;
     }
-    out[idx] = cnt >= h + 1 ? 1 : 0;
+    out[idx] = der::median_of(cnt, k) ? 1 : 0;
 }
 
 // External speech-activity mask (LS-EEND/sad_post_process.py:23-33): row t keeps its decisions pred > thr only where the mask
-// calls it speech, and a speech row in which nobody passed the threshold gets its largest posterior (lowest index on ties, as
-// torch.argmax; NaN is never active and never wins).  One thread per row; out f32 (T, S) of 0 / 1, which
+// calls it speech, and a speech row in which nobody passed the threshold gets its largest posterior (der::winner_update: lowest
+// index on ties, as torch.argmax; NaN is never active and never wins).  One thread per row; out f32 (T, S) of 0 / 1, which
 // activity_median_kernel reads with threshold 0.5.
 __global__ __launch_bounds__(256)
 void sad_fuse_kernel(const float* __restrict__ pred, int ld, int T, int S, float thr, const unsigned char* __restrict__ sad,
@@ -45,10 +45,7 @@ void sad_fuse_kernel(const float* __restrict__ pred, int ld, int T, int S, float
         const bool d = g && v > thr;
         any |= d;
         o[s] = d ? 1.0f : 0.0f;
-        if (v == v && (best < 0 || v > top)) {
-            best = s;
-            top = v;
-        }
+        der::winner_update(best, top, v, s);
     }
     if (g && !any && best >= 0) o[best] = 1.0f;
 }

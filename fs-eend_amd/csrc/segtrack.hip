@@ -93,7 +93,8 @@ void segtrack_kernel(const long* __restrict__ desc, const int* __restrict__ coun
 #pragma unroll
                         for (int m = 1; m < 64; m <<= 1) top = fmaxf(top, __shfl_xor(top, m, 64));
                         const unsigned long long w = __builtin_amdgcn_ballot_w64(cand && v == top);
-                        d = w != 0ull && lane == __builtin_ctzll(w);                   // ties: the lowest track, as torch.argmax
+                        d = w != 0ull && lane == __builtin_ctzll(w);                   // ties: the lowest track (decision.h
+                                                                                       // winner_update is the scalar statement)
                     }
                 }
                 dec |= (unsigned)d << i;

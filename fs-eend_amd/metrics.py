@@ -21,6 +21,9 @@ ties between equally good mappings are broken.
 One quirk of the reference's script is not reproduced: `reference[Segment(s, e)] = str(spkid)` lets a second speaker with an
 identical run (s, e) overwrite the first; here both speakers count.
 """
+import ctypes
+import math
+
 import torch
 
 from . import lib as _lib
@@ -35,7 +38,6 @@ _U8, _I32, _I64 = torch.uint8, torch.int32, torch.int64
 
 def limits():
     """(reference frames per tile of the kernel, largest half collar it takes)"""
-    import ctypes
     tile, hmax = ctypes.c_int(), ctypes.c_int()
     _lib.check(_lib.load().eend_collar_der_limits(ctypes.byref(tile), ctypes.byref(hmax)), "eend_collar_der_limits")
     return tile.value, hmax.value
@@ -79,23 +81,28 @@ def _as_list(x):
     return [x if isinstance(x, torch.Tensor) else torch.as_tensor(x)]
 
 
-def _pack_side(ts, device):
-    """Tensors (T_b, C_b) of any dtype -> (uint8 (max(sum T_b, 1), C) of 0 / 1 with C = max(C_b, 1), int32 (B + 1,) offsets), on
-    the device.  Narrower recordings get silent speakers, which change no counter."""
+def _pack_rows(ts, dtype, fill, device, convert):
+    """Tensors (T_b, C_b) -> (rows (max(sum T_b, 1), C) of `dtype` with C = max(C_b, 1): recording b's rows, `convert`ed, from
+    row off[b], `fill` in the columns a narrower recording lacks; int32 (B + 1,) offsets; off as a list), on the device."""
     C = max(1, max(t.shape[1] for t in ts))
-    lens = [t.shape[0] for t in ts]
     off = [0]
-    for n in lens:
-        off.append(off[-1] + n)
-    parts = [(t.to(device) != 0).to(_U8) for t in ts]
+    for t in ts:
+        off.append(off[-1] + t.shape[0])
+    parts = [convert(t.to(device)) for t in ts]
     if all(p.shape[1] == C for p in parts) and off[-1] > 0:
         rows = torch.cat(parts, 0).contiguous()
     else:
-        rows = torch.zeros(max(off[-1], 1), C, dtype=_U8, device=device)
+        rows = torch.full((max(off[-1], 1), C), fill, dtype=dtype, device=device)
         for p, o in zip(parts, off):
             if p.numel():
                 rows[o:o + p.shape[0], :p.shape[1]] = p
-    return rows, torch.tensor(off, dtype=_I32).to(device)
+    return rows, torch.tensor(off, dtype=_I32).to(device), off
+
+
+def _pack_side(ts, device):
+    """Tensors (T_b, C_b) of any dtype -> (uint8 rows of 0 / 1, int32 offsets).  Narrower recordings get silent speakers, which
+    change no counter."""
+    return _pack_rows(ts, _U8, 0, device, lambda t: (t != 0).to(_U8))[:2]
 
 
 def pack(refs, hyps, subsampling=10):
@@ -109,24 +116,41 @@ def pack(refs, hyps, subsampling=10):
     return _pack_side(refs, dev) + _pack_side(hyps, dev)
 
 
+def _check_packed(ref, roff, rows, off, dtype, *, side, what):
+    """The reference half and the `side` ("hyp" / "pred", rows of `dtype`) half of a packed batch -> B, or EendHipError: `what`
+    if they are not a batch."""
+    for t, dt, name in ((ref, _U8, "ref rows"), (rows, dtype, side + " rows"), (roff, _I32, "ref offsets"), (off, _I32, side + " offsets")):
+        if not t.is_cuda or t.dtype != dt or not t.is_contiguous():
+            raise _lib.EendHipError(f"{name}: expected a contiguous {dt} GPU tensor")
+    B = roff.numel() - 1
+    if B < 1 or off.numel() != B + 1 or ref.dim() != 2 or rows.dim() != 2 or not ref.numel() or not rows.numel():
+        raise _lib.EendHipError(what)
+    return B
+
+
+_OUT = (((8,), _I64), ((CMAX, CMAX), _I64), ((CMAX,), _I32))   # counters, cooc, mapping behind the leading dimensions
+
+
+def _check_out(out, lead, name, device):
+    """`out` = (counters int64 (*lead, 8), cooc int64 (*lead, 16, 16), mapping int32 (*lead, 16)) on the GPU, lead = (B,) or
+    (G, B); made here if None."""
+    if out is None:
+        return tuple(torch.empty(lead + s, dtype=dt, device=device) for s, dt in _OUT)
+    counters, cooc, mapping = out
+    for t, (s, dt) in zip(out, _OUT):
+        if t.shape != lead + s or t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+            d = "G, B" if len(lead) == 2 else "B"
+            raise _lib.EendHipError(f"{name}: out = (int64 ({d}, 8), int64 ({d}, 16, 16), int32 ({d}, 16)) on the GPU")
+    return out
+
+
 def collar_der_packed(batch, collar=50, subsampling=10, skip_overlap=False, out=None):
     """Score a packed batch (see `pack`): three launches on the current stream, no host sync, so the call can be
     captured in a graph.  `out` = (counters int64 (B, 8), cooc int64 (B, 16, 16), mapping int32 (B, 16)) to write into."""
     _check_numbers(collar, subsampling)
     ref, roff, hyp, hoff = batch
-    for t, dt, name in ((ref, _U8, "ref rows"), (hyp, _U8, "hyp rows"), (roff, _I32, "ref offsets"), (hoff, _I32, "hyp offsets")):
-        if not t.is_cuda or t.dtype != dt or not t.is_contiguous():
-            raise _lib.EendHipError(f"{name}: expected a contiguous {dt} GPU tensor")
-    B = roff.numel() - 1
-    if B < 1 or hoff.numel() != B + 1 or ref.dim() != 2 or hyp.dim() != 2 or not ref.numel() or not hyp.numel():
-        raise _lib.EendHipError("collar_der_packed: not a batch made by pack()")
-    if out is None:
-        out = (torch.empty(B, 8, dtype=_I64, device=ref.device), torch.empty(B, CMAX, CMAX, dtype=_I64, device=ref.device),
-               torch.empty(B, CMAX, dtype=_I32, device=ref.device))
-    counters, cooc, mapping = out
-    if (counters.shape != (B, 8) or cooc.shape != (B, CMAX, CMAX) or mapping.shape != (B, CMAX) or counters.dtype != _I64
-            or cooc.dtype != _I64 or mapping.dtype != _I32 or not all(t.is_cuda and t.is_contiguous() for t in out)):
-        raise _lib.EendHipError("collar_der_packed: out = (int64 (B, 8), int64 (B, 16, 16), int32 (B, 16)) on the GPU")
+    B = _check_packed(ref, roff, hyp, hoff, _U8, side="hyp", what="collar_der_packed: not a batch made by pack()")
+    out = counters, cooc, mapping = _check_out(out, (B,), "collar_der_packed", ref.device)
     _lib.check(_lib.load().eend_collar_der_u64(ref.data_ptr(), roff.data_ptr(), ref.shape[1], hyp.data_ptr(), hoff.data_ptr(),
                                                hyp.shape[1], B, int(subsampling), int(collar) // 2, int(bool(skip_overlap)),
                                                counters.data_ptr(), cooc.data_ptr(), mapping.data_ptr(), _post._stream()),
@@ -149,11 +173,15 @@ def rate(total, errors):
     return errors / total if total else (0.0 if errors == 0 else 1.0)
 
 
-def _detail(c, mapping):
-    total, miss, fa, conf, correct, kept, removed = c[:7]
+def _components(c):
+    """The eight counters of a recording, or their sums -> pyannote's components."""
+    total, miss, fa, conf, correct = c[:5]
     return {"total": total, "correct": correct, "confusion": conf, "false alarm": fa, "missed detection": miss,
-            "diarization error rate": rate(total, miss + fa + conf),
-            "mapping": {j: i for j, i in enumerate(mapping) if i >= 0}, "frames kept": kept, "frames removed": removed}
+            "diarization error rate": rate(total, miss + fa + conf)}
+
+
+def _detail(c, mapping):
+    return {**_components(c), "mapping": {j: i for j, i in enumerate(mapping) if i >= 0}, "frames kept": c[5], "frames removed": c[6]}
 
 
 def _details(refs, hyps, collar, subsampling, skip_overlap):
@@ -223,24 +251,18 @@ _F32 = torch.float32
 
 def sweep_limits():
     """(thresholds, medians and points per call, largest median) of the sweep kernel"""
-    import ctypes
     v = [ctypes.c_int() for _ in range(4)]
     _lib.check(_lib.load().eend_der_sweep_limits(*(ctypes.byref(x) for x in v)), "eend_der_sweep_limits")
     return tuple(x.value for x in v)
-
-
-def _on_device(t):
-    return isinstance(t, torch.Tensor) and t.is_cuda
 
 
 def _check_grid(thresholds, medians):
     """The grid as the kernel will see it -> (thresholds rounded to float32, medians) as lists, or None in place of a list for
     a device tensor, whose values the host does not read (its length is still checked).  ValueError for an empty grid, more
     than 16 thresholds, 4 medians or 32 points, a non-finite threshold, and a median that is not an odd integer in 1 .. 127."""
-    import math
     out = []
     for name, x, dt in (("thresholds", thresholds, _F32), ("medians", medians, _I32)):
-        if _on_device(x):
+        if isinstance(x, torch.Tensor) and x.is_cuda:
             if x.dim() != 1 or x.dtype != dt or not x.is_contiguous():
                 raise ValueError(f"{name}: a device tensor must be contiguous, one-dimensional and {dt}, got {x.dtype} {tuple(x.shape)}")
             out.append((None, x.numel()))
@@ -298,24 +320,14 @@ def pack_predictions(preds, sads=None):
     sads = _check_sads(preds, sads)
     preds = [_post._to_device(t, "pred") for t in preds]
     dev = preds[0].device
-    C = max(1, max(t.shape[1] for t in preds))
-    off = [0]
-    for t in preds:
-        off.append(off[-1] + t.shape[0])
-    if all(t.shape[1] == C for t in preds) and off[-1] > 0:
-        rows = torch.cat([t.to(_F32) for t in preds], 0).contiguous()
-    else:
-        rows = torch.full((max(off[-1], 1), C), float("nan"), dtype=_F32, device=dev)
-        for t, o in zip(preds, off):
-            if t.numel():
-                rows[o:o + t.shape[0], :t.shape[1]] = t
+    rows, offsets, off = _pack_rows(preds, _F32, float("nan"), dev, lambda t: t.to(_F32))
     flags = None
     if sads is not None:
         flags = torch.zeros(max(off[-1], 1), dtype=_U8, device=dev)
         for s, t, o in zip(sads, preds, off):
             if t.shape[0]:
                 flags[o:o + t.shape[0]] = _post._sad_u8(s, t.shape[0], dev)
-    return rows, torch.tensor(off, dtype=_I32).to(dev), flags
+    return rows, offsets, flags
 
 
 def collar_der_sweep_packed(ref_batch, pred_batch, thresholds, medians, collar=50, subsampling=10, skip_overlap=False, out=None,
@@ -330,12 +342,8 @@ def collar_der_sweep_packed(ref_batch, pred_batch, thresholds, medians, collar=5
     th, med = _check_grid(thresholds, medians)
     ref, roff = ref_batch[:2]
     rows, poff, flags = pred_batch
-    for t, dt, name in ((ref, _U8, "ref rows"), (rows, _F32, "pred rows"), (roff, _I32, "ref offsets"), (poff, _I32, "pred offsets")):
-        if not t.is_cuda or t.dtype != dt or not t.is_contiguous():
-            raise _lib.EendHipError(f"{name}: expected a contiguous {dt} GPU tensor")
-    B = roff.numel() - 1
-    if B < 1 or poff.numel() != B + 1 or ref.dim() != 2 or rows.dim() != 2 or not ref.numel() or not rows.numel():
-        raise _lib.EendHipError("collar_der_sweep_packed: not batches made by pack_references() and pack_predictions()")
+    B = _check_packed(ref, roff, rows, poff, _F32, side="pred",
+                      what="collar_der_sweep_packed: not batches made by pack_references() and pack_predictions()")
     if flags is not None and (not flags.is_cuda or flags.dtype != _U8 or not flags.is_contiguous() or flags.numel() < rows.shape[0]):
         raise _lib.EendHipError("collar_der_sweep_packed: flags = one contiguous uint8 per posterior row on the GPU")
     dev = ref.device
@@ -343,13 +351,7 @@ def collar_der_sweep_packed(ref_batch, pred_batch, thresholds, medians, collar=5
     medians = medians if med is None else torch.tensor(med, dtype=_I32).to(dev)
     nth, nmed = thresholds.numel(), medians.numel()
     G = nth * nmed
-    if out is None:
-        out = (torch.empty(G, B, 8, dtype=_I64, device=dev), torch.empty(G, B, CMAX, CMAX, dtype=_I64, device=dev),
-               torch.empty(G, B, CMAX, dtype=_I32, device=dev))
-    counters, cooc, mapping = out
-    if (counters.shape != (G, B, 8) or cooc.shape != (G, B, CMAX, CMAX) or mapping.shape != (G, B, CMAX) or counters.dtype != _I64
-            or cooc.dtype != _I64 or mapping.dtype != _I32 or not all(t.is_cuda and t.is_contiguous() for t in out)):
-        raise _lib.EendHipError("collar_der_sweep_packed: out = (int64 (G, B, 8), int64 (G, B, 16, 16), int32 (G, B, 16)) on the GPU")
+    out = counters, cooc, mapping = _check_out(out, (G, B), "collar_der_sweep_packed", dev)
     if totals is not None and (totals.shape != (G, 8) or totals.dtype != _I64 or not totals.is_cuda or not totals.is_contiguous()):
         raise _lib.EendHipError("collar_der_sweep_packed: totals = int64 (G, 8) on the GPU")
     _lib.check(_lib.load().eend_collar_der_sweep_u64(
@@ -385,12 +387,8 @@ class SweepResult:
 
     def __init__(self, thresholds, medians, sums, details=None, recordings=0):
         self.thresholds, self.medians, self.details, self.recordings = list(thresholds), list(medians), details, recordings
-        self.table = []
-        for g, c in enumerate(sums):
-            total, miss, fa, conf, correct = c[:5]
-            self.table.append({"threshold": self.thresholds[g // len(self.medians)], "median": self.medians[g % len(self.medians)],
-                               "total": total, "correct": correct, "confusion": conf, "false alarm": fa, "missed detection": miss,
-                               "diarization error rate": rate(total, miss + fa + conf)})
+        self.table = [{"threshold": self.thresholds[g // len(self.medians)], "median": self.medians[g % len(self.medians)],
+                       **_components(c)} for g, c in enumerate(sums)]
         g = min(range(len(self.table)), key=lambda i: (self.table[i]["diarization error rate"], i))
         self.best = (self.table[g]["threshold"], self.table[g]["median"], self.table[g]["diarization error rate"])
 
