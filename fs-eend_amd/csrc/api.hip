@@ -581,6 +581,22 @@ int eend_room_limits(int* tile, int* window, int* max_rows, int* max_axis) {
     return EEND_OK;
 }
 
+int eend_lstm_ok(int B, int T, int hidden) { return eend_lstm_shape_ok(B, T, hidden); }
+
+int eend_lstm_f32(const float* G, int g_rows, const int* order, const float* bias, const float* W_hh, const float* h0, const float* c0,
+                  float* hT, float* cT, float* h_all, int B, int T, int hidden, void* stream) {
+    return eend_launch_lstm(G, g_rows, order, bias, W_hh, h0, c0, hT, cT, h_all, B, T, hidden, (hipStream_t)stream);
+}
+
+int eend_eda_count_f32(const float* attractors, const float* w, const float* bias, float th, float* probs, int* count, int B, int C,
+                       void* stream) {
+    return eend_launch_eda_count(attractors, w, bias, th, probs, count, B, C, (hipStream_t)stream);
+}
+
+int eend_eda_head_f32(const float* emb, int emb_rows, const float* attractors, float* logits, int B, int T, int C, void* stream) {
+    return eend_launch_eda_head(emb, emb_rows, attractors, logits, B, T, C, (hipStream_t)stream);
+}
+
 int eend_pit_cost_f64(const float* y, const float* labels, int B, int T, int C, double* cost, void* stream) {
     return eend_launch_pit_cost(y, labels, B, T, C, cost, (hipStream_t)stream);
 }

@@ -168,6 +168,16 @@ int eend_launch_sim_mix(const void* utts, int utt_storage, const float* rirs, co
 #define ROOM_WORDS 20
 int eend_launch_room_rir(const long* rooms, int n_rows, const long* tiles, int n_tiles, float* out, hipStream_t stream);
 
+// EEND-EDA attractor path (lstm.hip): the hidden size the recurrence is built for, the most attractors of the counter and the head
+#define LSTM_HIDDEN 256
+#define EDA_MAX_ATTRACTORS 16
+int eend_lstm_shape_ok(int B, int T, int hidden);
+int eend_launch_lstm(const float* G, int g_rows, const int* order, const float* bias, const float* Whh, const float* h0, const float* c0,
+                     float* hT, float* cT, float* h_all, int B, int T, int hidden, hipStream_t stream);
+int eend_launch_eda_count(const float* attr, const float* w, const float* bias, float th, float* probs, int* count, int B, int C,
+                          hipStream_t stream);
+int eend_launch_eda_head(const float* emb, int emb_rows, const float* attr, float* logits, int B, int T, int C, hipStream_t stream);
+
 int eend_launch_pit_cost(const float* y, const float* lab, int B, int T, int C, double* cost, hipStream_t stream);
 int eend_launch_pit_assign(const double* cost, const int* nspk, int B, int C, int* perm, double* loss, hipStream_t stream);
 

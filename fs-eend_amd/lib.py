@@ -90,6 +90,10 @@ PROTOTYPES = {
     "eend_sim_limits": [_vp, _vp, _vp],
     "eend_room_rir_f32": [_vp, _i, _vp, _i, _vp, _vp],
     "eend_room_limits": [_vp, _vp, _vp, _vp],
+    "eend_lstm_ok": [_i, _i, _i],
+    "eend_lstm_f32": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "eend_eda_count_f32": [_vp, _vp, _vp, _f, _vp, _vp, _i, _i, _vp],
+    "eend_eda_head_f32": [_vp, _i, _vp, _vp, _i, _i, _i, _vp],
     "eend_pit_cost_f64": [_vp, _vp, _i, _i, _i, _vp, _vp],
     "eend_pit_assign_i32": [_vp, _vp, _i, _i, _vp, _vp, _vp],
     "eend_retention_proj_f16": [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],

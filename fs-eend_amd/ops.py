@@ -532,6 +532,61 @@ def head_l2dot(emb32, attr, attr_out, logits, B, T, Tp, C, D):
                "eend_head_l2dot_f32")
 
 
+def lstm_ok(B, T, hidden):
+    """Whether lstm() takes the shape (hidden 256, T >= 1, B >= 1)."""
+    return bool(_lib.load().eend_lstm_ok(int(B), int(T), int(hidden)))
+
+
+def lstm(G, order, bias, w_hh, h0, c0, hT, cT, h_all, B, T):
+    """Single-layer LSTM recurrence (lstm.hip).  G f32 (B, g_rows, 1024) input pre-activations, read at row order[t] in step t, or None
+    = zero input (pre-activation = bias f32 (1024,) = b_ih + b_hh); order i32 (T,) or None = identity; w_hh f32 (1024, 256); h0 / c0
+    f32 (B, 256), both or neither; hT / cT f32 (B, 256); h_all f32 (B, T, 256) or None."""
+    L = _lib.load()
+    for n, t in (("G", G), ("bias", bias), ("w_hh", w_hh), ("h0", h0), ("c0", c0), ("hT", hT), ("cT", cT), ("h_all", h_all)):
+        _chk(t, F32, n)
+    _chk(order, torch.int32, "order")
+    hidden = w_hh.shape[1] if w_hh.dim() == 2 else -1
+    if w_hh.dim() != 2 or w_hh.shape[0] != 4 * hidden:
+        raise _lib.EendHipError("lstm: w_hh must be (4 * hidden, hidden)")
+    g_rows = 0
+    if G is not None:
+        if G.dim() != 3 or G.shape[0] != B or G.shape[2] != 4 * hidden:
+            raise _lib.EendHipError("lstm: G must be (B, g_rows, 4 * hidden)")
+        g_rows = G.shape[1]
+    elif bias is None or bias.numel() != 4 * hidden:
+        raise _lib.EendHipError("lstm: zero input needs the bias sum (4 * hidden,)")
+    if order is not None and order.numel() != T:
+        raise _lib.EendHipError("lstm: order must have T entries")
+    for n, t, want in (("h0", h0, B * hidden), ("c0", c0, B * hidden), ("hT", hT, B * hidden), ("cT", cT, B * hidden),
+                       ("h_all", h_all, B * T * hidden)):
+        if t is not None and t.numel() != want:
+            raise _lib.EendHipError(f"lstm: {n} has {t.numel()} elements, expected {want}")
+    _lib.check(L.eend_lstm_f32(_p(G), g_rows, _p(order), _p(bias), _p(w_hh), _p(h0), _p(c0), _p(hT), _p(cT), _p(h_all), B, T, hidden,
+                               _stream()), "eend_lstm_f32")
+
+
+def eda_count(attractors, w, bias, th, probs, count):
+    """probs (B, C) = sigmoid(attractors (B, C, 256) . w (256,) + bias (1,)); count i32 (B,) or None = first c with probs < th, else C."""
+    L = _lib.load()
+    _chk(attractors, F32, "attractors"); _chk(w, F32, "w"); _chk(bias, F32, "bias"); _chk(probs, F32, "probs")
+    _chk(count, torch.int32, "count")
+    B, C, D = attractors.shape
+    if D != 256 or w.numel() != 256 or bias.numel() != 1 or probs.numel() != B * C or (count is not None and count.numel() != B):
+        raise _lib.EendHipError("eda_count: attractors (B, C, 256), w (256,), bias (1,), probs (B, C), count (B,)")
+    _lib.check(L.eend_eda_count_f32(_p(attractors), _p(w), _p(bias), float(th), _p(probs), _p(count), B, C, _stream()),
+               "eend_eda_count_f32")
+
+
+def eda_head(emb32, attractors, logits, T):
+    """logits (B, T, C) = emb32 (B, emb_rows >= T, 256) . attractors (B, C, 256)^T."""
+    L = _lib.load()
+    _chk(emb32, F32, "emb32"); _chk(attractors, F32, "attractors"); _chk(logits, F32, "logits")
+    B, C, D = attractors.shape
+    if emb32.dim() != 3 or emb32.shape[0] != B or emb32.shape[2] != 256 or D != 256 or logits.numel() != B * T * C:
+        raise _lib.EendHipError("eda_head: emb (B, rows, 256), attractors (B, C, 256), logits (B, T, C)")
+    _lib.check(L.eend_eda_head_f32(_p(emb32), emb32.shape[1], _p(attractors), _p(logits), B, T, C, _stream()), "eend_eda_head_f32")
+
+
 def retention_step(qkvg16, kv_state, scale_in, scale_out, out16, N, H, gn_eps=1e-6):
     L = _lib.load()
     _chk(qkvg16, F16, "qkvg16"); _chk(kv_state, F32, "kv_state"); _chk(scale_in, F32, "scale_in")

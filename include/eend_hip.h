@@ -562,6 +562,41 @@ int eend_room_rir_f32(const long* rooms, int n_rows, const long* tiles, int n_ti
  * arithmetic only). */
 int eend_room_limits(int* tile, int* window, int* max_rows, int* max_axis);
 
+/* ---- offline EEND-EDA attractor path (FS-EEND/nnet/model/offl_tfm_enc_lstm_enc_dec.py, inference only) ---- */
+
+/* Whether eend_lstm_f32 takes the shape: hidden == 256, T >= 1, B >= 1 (host arithmetic only). */
+int eend_lstm_ok(int B, int T, int hidden);
+
+/* Single-layer, unidirectional LSTM recurrence of B independent sequences over T steps, PyTorch gate order (i, f, g, o), hidden
+ * size 256: the nn.LSTM calls of EncoderDecoderAttractor.eda_forward (offl_tfm_enc_lstm_enc_dec.py:82-83, :88, :91) without their
+ * input GEMM.
+ *   G      f32 [B][g_rows][1024], g_rows >= T: the input pre-activations x W_ih^T + b_ih + b_hh, computed beforehand (any f32 linear
+ *          entry, e.g. eend_linear_step_f32).  Step t reads row order[t] of its sequence: the shuffle of model :62-65 is an index,
+ *          nothing is gathered or copied.  NULL = zero input (the decoder's zeros of :104): the pre-activation is `bias` alone.
+ *   order  i32 [T], a permutation of 0 .. T-1 shared by the batch; NULL = identity.  Validated by the host; the kernel clamps an
+ *          entry into [0, T) so that it never reads outside G.
+ *   bias   f32 [1024] = b_ih + b_hh, read only when G is NULL.
+ *   W_hh   f32 [1024][256] as nn.LSTM stores weight_hh_l0.
+ *   h0, c0 f32 [B][256], both or neither; NULL = zeros.
+ *   hT, cT f32 [B][256]: the state after step T-1.  h_all (optional) f32 [B][T][256]: h after every step, in step order.
+ *   step   z = G[order[t]] + W_hh h;  c = sigmoid(z_f) c + sigmoid(z_i) tanh(z_g);  h = sigmoid(z_o) tanh(c).
+ * h, c and every sum are f32; the gate functions are finite for every finite pre-activation.  A sequence's bits depend on its own
+ * inputs only (not on its batch mates or the run).  One workgroup per sequence from the first step to the last, no workgroup waits
+ * on another; W_hh is re-read from L2 every step (csrc/lstm.hip).  Stateless, stream-ordered, nothing allocated, the host not waited
+ * for.  EEND_EINVAL: hidden != 256, T < 1, B < 1, g_rows < T, a NULL W_hh / hT / cT, G and bias both NULL, one of h0 / c0 alone. */
+int eend_lstm_f32(const float* G, int g_rows, const int* order, const float* bias, const float* W_hh, const float* h0, const float* c0,
+                  float* hT, float* cT, float* h_all, int B, int T, int hidden, void* stream);
+
+/* probs[b][c] = sigmoid(attractors[b][c] . w + bias[0]) (model :106, `counter` is Linear(256, 1)) and, where count is given,
+ * count[b] = the first c with probs[b][c] < th, C if there is none: the speaker count of model :72-73 per sequence.
+ * attractors f32 [B][C][256], w f32 [256], bias f32 [1], probs f32 [B][C], count i32 [B] or NULL; 1 <= C <= 16. */
+int eend_eda_count_f32(const float* attractors, const float* w, const float* bias, float th, float* probs, int* count, int B, int C,
+                       void* stream);
+
+/* logits[b][t][c] = emb[b][t] . attractors[b][c] (the torch.bmm of model :66) over all C columns.  emb f32 [B][emb_rows][256] with
+ * emb_rows >= T (a slab: rows t >= T are never read), attractors f32 [B][C][256], logits f32 [B][T][C]; 1 <= C <= 16, B <= 65535. */
+int eend_eda_head_f32(const float* emb, int emb_rows, const float* attractors, float* logits, int B, int T, int C, void* stream);
+
 /* ---- permutation-invariant label assignment (FS-EEND/train/utils/loss.py:257-327 batch_pit_n_speaker_loss;
  * LS-EEND/train/utils/loss.py:350-379 pit_loss_multispk) ---- */
 
