@@ -74,7 +74,7 @@ int eend_linear_res_ln_train_f16(const void* A, int lda, const void* W, int ldw,
 
 int eend_linear_relu_train_f16(const void* A, int lda, const void* W, int ldw, const float* bias, void* out_f16, int ldo,
                                int M, int N, int K, const eend_dropout* drop, void* stream) {
-    if (!A || !W || !out_f16 || (ldo & 3)) return EEND_EINVAL;
+    if (!A || !W || !out_f16 || (ldo & 7)) return EEND_EINVAL;      // (the 128 x 128 tile writes 16-byte pieces of the output rows)
     GemmParams p = gemm_base(A, lda, W, ldw, bias, M, N, K);
     p.out16 = out_f16; p.ldo = ldo; p.drop = drop_spec(drop);
     return eend_launch_gemm(p, EPI_PLAIN_RELU_F16, (hipStream_t)stream);

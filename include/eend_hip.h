@@ -1032,7 +1032,8 @@ int eend_linear_res_ln_train_f16(const void* A, int lda, const void* W, int ldw,
                                  void* out_f16, void* xhat_f16, float* rstd, int M, int K, const eend_dropout* drop,
                                  void* stream);
 /* relu(A W^T + bias) with dropout after the activation (the FFN's inner `self.dropout`, merge_tfm_encoder.py:398,613);
- * the stored activation is the dropped one, so its zeros are the ReLU-and-dropout mask of the backward. */
+ * the stored activation is the dropped one, so its zeros are the ReLU-and-dropout mask of the backward.
+ * N % 128 == 0, K % 64 == 0, lda / ldw / ldo % 8 == 0 (the tile writes 16-byte pieces of the output rows); EEND_EINVAL otherwise. */
 int eend_linear_relu_train_f16(const void* A, int lda, const void* W, int ldw, const float* bias, void* out_f16, int ldo,
                                int M, int N, int K, const eend_dropout* drop, void* stream);
 /* The two entries above as ONE launch for a post-norm ReLU block (round 5; FS nn.TransformerEncoderLayer._ff_block + norm2,
