@@ -7,7 +7,7 @@ with ``load_state_dict`` and default initialisation under a given ``torch.manual
 
 The torch.nn modules are parameter containers only; all arithmetic runs in libeend_hip.so:
 
-  encoder      the FS-EEND encoder path without BatchNorm and without a mask (fs_model._run): pad_sequence(-1), Linear, LayerNorm,
+  encoder      the FS-EEND encoder path without BatchNorm and without a mask (fs_model.encoder_layer): pad_sequence(-1), Linear, LayerNorm,
                then the post-norm layers on the packed stream kernels with unmasked attention over the T rows of the padded batch.
                The reference has no key-padding mask, so in a ragged batch a shorter sequence sees its -1 padding, here as there.
                The last layer also writes its rows in f32: the embeddings are not L2-normalised in this model, and both the LSTM
@@ -29,8 +29,9 @@ import torch.nn as nn
 from torch import Tensor
 
 from . import ops
-from .fs_model import TransformerEncoder, WorkspaceCache, _f16, _f32, _qscaled
+from .fs_model import TransformerEncoder, WorkspaceCache, encoder_layer
 from .lib import EendHipError
+from .weights import PreparedOperands, _f32, encoder_layer_operands, input_operands, need_gpu_params
 
 _D_SUPPORTED = 256
 _H_SUPPORTED = 4
@@ -87,7 +88,7 @@ class _EdaWorkspace:
         self.q = self.k = self.vt = None
 
 
-class EncoderDecoderAttractor(nn.Module):
+class EncoderDecoderAttractor(PreparedOperands, nn.Module):
     """LSTM encoder-decoder attractor calculation (reference model :79-107), inference only."""
 
     def __init__(self, n_units, encoder_dropout=0.1, decoder_dropout=0.1):
@@ -100,31 +101,18 @@ class EncoderDecoderAttractor(nn.Module):
         self.decoder = nn.LSTM(n_units, n_units, 1, batch_first=True)
         self.counter = nn.Linear(n_units, 1)
         self.n_units = n_units
-        self._prep = None
-        self._prep_key = None
-        self.register_load_state_dict_post_hook(lambda module, incompatible_keys: module.refresh_weights())
 
-    def refresh_weights(self):
-        """Drop the cached f32 operand copies (as fs_model: needed after a write through `.data`)."""
-        self._prep = None
+    def _fingerprint_tensors(self):
+        return list(self.parameters())
 
-    def _apply(self, fn, *a, **kw):
-        out = super()._apply(fn, *a, **kw)
-        self._prep = None
-        return out
-
-    def _prepare(self):
-        key = tuple((p.data_ptr(), p._version) for p in self.parameters())
-        if self._prep is not None and key == self._prep_key:
-            return self._prep
-        if self.counter.weight.device.type != "cuda":
-            raise EendHipError("model parameters must live on the GPU: the HIP path has no CPU fallback")
+    def _build_operands(self):
+        """f32 operand copies of the two LSTMs and the counter."""
+        need_gpu_params(self.counter.weight)
         e, d = self.encoder, self.decoder
         P = dict(enc_wih=_f32(e.weight_ih_l0), enc_whh=_f32(e.weight_hh_l0),
                  enc_b=(_f32(e.bias_ih_l0) + _f32(e.bias_hh_l0)).contiguous(),
                  dec_whh=_f32(d.weight_hh_l0), dec_b=(_f32(d.bias_ih_l0) + _f32(d.bias_hh_l0)).contiguous(),
                  cnt_w=_f32(self.counter.weight).view(-1), cnt_b=_f32(self.counter.bias).view(-1))
-        self._prep, self._prep_key = P, key
         return P
 
     def _attractors(self, rows32: Tensor, T: int, order: Optional[Tensor], max_n_speakers: int, th: Optional[float]):
@@ -160,7 +148,7 @@ class EncoderDecoderAttractor(nn.Module):
         return attractors, probs
 
 
-class TransformerEDADiarization(nn.Module):
+class TransformerEDADiarization(PreparedOperands, nn.Module):
     """Offline EEND-EDA on MI355X (reference model :10-76), inference only."""
 
     def __init__(self, n_speakers, in_size, n_units, n_heads, n_layers, dropout, attractor_loss_ratio=1.0,
@@ -173,51 +161,26 @@ class TransformerEDADiarization(nn.Module):
         self.eda = EncoderDecoderAttractor(n_units, encoder_dropout=attractor_encoder_dropout,
                                            decoder_dropout=attractor_decoder_dropout)
         self.attractor_loss_ratio = attractor_loss_ratio
-        self._prep = None
-        self._prep_key = None
         self._ws = WorkspaceCache()
-        self.register_load_state_dict_post_hook(lambda module, incompatible_keys: module.refresh_weights())
 
     def refresh_weights(self):
-        self._prep = None
+        super().refresh_weights()
         self.eda.refresh_weights()
 
-    def _apply(self, fn, *a, **kw):
-        out = super()._apply(fn, *a, **kw)
-        self._prep = None
-        return out
+    def _fingerprint_tensors(self):
+        return list(self.enc.parameters())
 
-    def _prepare(self):
+    def _build_operands(self):
         """f16 MFMA-operand copies of the encoder weights in the layouts of the packed stream kernels."""
-        key = tuple((p.data_ptr(), p._version) for p in self.enc.parameters())
-        if self._prep is not None and key == self._prep_key:
-            return self._prep
         enc = self.enc
-        dev = enc.encoder.weight.device
-        if dev.type != "cuda":
-            raise EendHipError("model parameters must live on the GPU: the HIP path has no CPU fallback")
+        need_gpu_params(enc.encoder.weight)
         P = {}
-        Fin = enc.in_size
-        Fin_pad = (Fin + 63) // 64 * 64
-        w = torch.zeros(enc.n_units, Fin_pad, dtype=torch.float16, device=dev)
-        w[:, :Fin] = enc.encoder.weight.detach().to(torch.float16)
-        P["in.w"], P["in.b"] = w, _f32(enc.encoder.bias)
-        P["in.g"], P["in.beta"], P["in.eps"] = _f32(enc.encoder_norm.weight), _f32(enc.encoder_norm.bias), enc.encoder_norm.eps
-        P["Fin_pad"] = Fin_pad
-        layers = []
+        P["in.w"], P["in.b"], P["in.g"], P["in.beta"], P["in.eps"], P["Fin_pad"] = input_operands(enc.encoder, enc.encoder_norm,
+                                                                                                  enc.in_size)
         for l in enc.transformer_encoder.layers:
             if not ops.stream_ok(l.linear1.weight.shape[0]):
                 raise EendHipError("EEND-EDA encoder: the packed stream kernels take hidden widths that are multiples of 64 up to 2048")
-            L = dict(in_b=_f32(_qscaled(l.self_attn.in_proj_bias)), out_b=_f32(l.self_attn.out_proj.bias),
-                     b1=_f32(l.linear1.bias), b2=_f32(l.linear2.bias),
-                     g1=_f32(l.norm1.weight), be1=_f32(l.norm1.bias), eps1=l.norm1.eps,
-                     g2=_f32(l.norm2.weight), be2=_f32(l.norm2.bias), eps2=l.norm2.eps)
-            L["in_w"] = _f16(_qscaled(l.self_attn.in_proj_weight))
-            L["in_wp"] = ops.inproj_attn_pack(L["in_w"])
-            L["ws"] = ops.ffn_stream_pack(_f16(l.self_attn.out_proj.weight), _f16(l.linear1.weight), _f16(l.linear2.weight))
-            layers.append(L)
-        P["layers"] = layers
-        self._prep, self._prep_key = P, key
+        P["layers"] = [encoder_layer_operands(l, keep_unpacked=False) for l in enc.transformer_encoder.layers]
         return P
 
     def _encode(self, src: Sequence[Tensor]):
@@ -243,33 +206,10 @@ class TransformerEDADiarization(nn.Module):
         ops.linear_res_ln(ws.xin16, P["in.w"], P["in.b"], None, P["in.g"], P["in.beta"], emb32 if n_layers == 0 else None, ws.h16,
                           P["in.eps"])
         for li, L in enumerate(P["layers"]):
-            self._attention(ws, L, B, H, Tp, T)
-            # out-projection + norm1 + FFN + norm2 on the packed weight stream; the last layer's rows also in f32
-            ops.attnout_ffn_stream(ws.o16, L["ws"], L["out_b"], None, ws.h16, L["g1"], L["be1"], L["eps1"], L["b1"], L["b2"], L["g2"],
-                                   L["be2"], L["eps2"], emb32 if li == n_layers - 1 else None, ws.h16)
+            # unmasked MHA over the T rows of the padded batch (delay >= Tp switches the causal mask off, kv_len = T keeps the slab's
+            # own padding out); the last layer's rows also in f32
+            encoder_layer(ws, L, B, H, Tp, Tp, T, out32=emb32 if li == n_layers - 1 else None)
         return emb32.view(B, Tp, D), T
-
-    @staticmethod
-    def _attention(ws, L, B, H, Tp, T):
-        """Unmasked MHA over the T rows of the padded batch (delay >= Tp switches the causal mask off, kv_len = T keeps the slab's own
-        padding out): the three forms of fs_model._run's time_attention, chosen by Tp alone."""
-        o = ws.o16
-        if Tp <= 512:
-            ops.inproj_attn_causal_packed(ws.h16, L["in_wp"], L["in_b"], o, B, H, Tp, Tp, T)
-            return
-        need = ops.inproj_attn_long_scratch(B, Tp, Tp, T) if Tp <= 3072 else None
-        if need is not None:
-            if ws.attn_part.numel() < need[0]:
-                ws.attn_part = torch.empty(need[0], dtype=torch.float16, device=o.device)
-            if ws.attn_lse.numel() < need[1]:
-                ws.attn_lse = torch.empty(need[1], dtype=torch.float32, device=o.device)
-            ops.inproj_attn_causal_long(ws.h16, L["in_wp"], L["in_b"], o, ws.attn_part, ws.attn_lse, B, H, Tp, Tp, T)
-            return
-        n = o.numel()
-        if ws.q is None:
-            ws.q, ws.k, ws.vt = (torch.empty(n, dtype=torch.bfloat16, device=o.device) for _ in range(3))
-        ops.inproj_heads(ws.h16, L["in_w"], L["in_b"], ws.q, ws.k, ws.vt, B, Tp, H)
-        ops.attn_causal(ws.q, ws.k, ws.vt, o, B, H, Tp, Tp, T, scale=ops.LN2)
 
     @torch.no_grad()
     def test(self, src, ilens, n_spk=None, th=None, order=None):

@@ -21,7 +21,8 @@ import torch.nn as nn
 from torch import Tensor
 
 from . import ops
-from .lib import EendHipError
+from .weights import (PreparedOperands, _f16, _f32, _qscaled, convert_const, encoder_layer_operands, input_operands,
+                      need_gpu_params)
 
 _D_SUPPORTED = 256
 _H_SUPPORTED = 4
@@ -120,23 +121,6 @@ class MaskedTransformerDecoderModel(nn.Module):
         self.attractor_decoder = TransformerEncoder(decoder_layers, n_layers)
 
 
-def _f16(t: Tensor) -> Tensor:
-    return t.detach().to(torch.float16).contiguous()
-
-
-def _f32(t: Tensor) -> Tensor:
-    return t.detach().to(torch.float32).contiguous()
-
-
-def _qscaled(t: Tensor) -> Tensor:
-    """Packed in-projection (3D x D weight or 3D bias) with the q rows pre-multiplied by
-    1/sqrt(dh) * log2(e) in fp32 (ops.QSCALE_LOG2): the attention kernel then needs no per-score scale."""
-    from . import ops
-    t = t.detach().to(torch.float32).clone()
-    t[: t.shape[0] // 3] *= ops.QSCALE_LOG2
-    return t
-
-
 class _Workspace:
     """Device buffers for one (B, Tp, C) problem shape (allocated once, reused)."""
 
@@ -149,7 +133,6 @@ class _Workspace:
         self.h16 = e(Me, D, dt=f16)
         # windows of more than 512 frames: partial rows + softmax denominators of the grouped form (attn_stream.hip), or -- where that form
         # does not cover the shape -- bf16 Q / K / V^T of the un-packed path; both allocated at first use (grow-only)
-        self.Mx, self.D = Mx, D
         self.q = self.k = self.vt = None
         self.attn_part, self.attn_lse = e(0, dt=f16), e(0, dt=f32)
         self.o16 = e(Mx, D, dt=f16)
@@ -193,7 +176,49 @@ class WorkspaceCache:
         return len(self._d)
 
 
-class OnlineTransformerDADiarization(nn.Module):
+def time_attention(ws, x16, Ly, nseq, H, Tp, delay, kv, key="in", slots=None, slot_delta=None):
+    """in-projection + causal MHA over the frames of `nseq` sequences of the rows x16 -> ws.o16 rows (merge_tfm_encoder.py:379-385).
+    Ly[key + "_w" / "_wp" / "_b"] are the layer's q-scaled in-projection operands; delay >= Tp switches the causal mask off, kv is
+    the number of real frames.  The form is chosen by Tp (and `slots`) alone."""
+    o = ws.o16[:nseq * Tp]
+    wp, b = Ly[key + "_wp"], Ly[key + "_b"]
+    if slots is not None and Tp == 512:
+        # the sequences are the fan-out's speaker slots: K / V projected once per utterance, from the rows of slot 0 (slot form)
+        ops.inproj_attn_causal_packed(x16, wp, b, o, nseq, H, Tp, delay, kv, slots=slots, slot_delta=slot_delta)
+        return o
+    if Tp <= 512:            # token-owning waves, packed weights, Q in registers, K / V never leave the CU (attn_stream.hip)
+        ops.inproj_attn_causal_packed(x16, wp, b, o, nseq, H, Tp, delay, kv)
+        return o
+    # (same-box A/B, 163840 frames: Tp 1024 326 vs 454 us, 2048 586 vs 664 us, 4096 1098 vs 1090 us -- an item re-projects its key
+    #  group's K / V, so the grouped form stops paying at about six groups)
+    need = ops.inproj_attn_long_scratch(nseq, Tp, delay, kv) if Tp <= 3072 else None
+    if need is not None:     # the same kernel on (query group, key group) items of 512 frames + a combine pass over the partial rows
+        if ws.attn_part.numel() < need[0]:
+            ws.attn_part = torch.empty(need[0], dtype=torch.float16, device=o.device)
+        if ws.attn_lse.numel() < need[1]:
+            ws.attn_lse = torch.empty(need[1], dtype=torch.float32, device=o.device)
+        ops.inproj_attn_causal_long(x16, wp, b, o, ws.attn_part, ws.attn_lse, nseq, H, Tp, delay, kv)
+    else:                    # bf16 Q / K / V^T through HBM, tiled attention kernel; the scratch, made at first use, covers every o16 row
+        n = nseq * Tp * o.shape[1]
+        if ws.q is None:
+            ws.q, ws.k, ws.vt = (torch.empty(ws.o16.numel(), dtype=torch.bfloat16, device=o.device) for _ in range(3))
+        ops.inproj_heads(x16, Ly[key + "_w"], b, ws.q[:n], ws.k[:n], ws.vt[:n], nseq, Tp, H)
+        ops.attn_causal(ws.q[:n], ws.k[:n], ws.vt[:n], o, nseq, H, Tp, delay, kv, scale=ops.LN2)
+    return o
+
+
+def encoder_layer(ws, L, nseq, H, Tp, delay, kv, out32=None):
+    """One post-norm encoder layer (operands: weights.encoder_layer_operands) on the rows ws.h16, in place; out32: the rows in f32 too."""
+    o16 = time_attention(ws, ws.h16, L, nseq, H, Tp, delay, kv)
+    if "ws" in L:            # out-projection + norm1 + FFN + norm2 in one launch on the packed weight stream (ffn_stream.hip)
+        ops.attnout_ffn_stream(o16, L["ws"], L["out_b"], None, ws.h16, L["g1"], L["be1"], L["eps1"], L["b1"], L["b2"], L["g2"],
+                               L["be2"], L["eps2"], out32, ws.h16)
+    else:                    # hidden sizes the packed stream does not take (ffn.hip)
+        ops.attnout_ffn_fused_res16(o16, L["out_w"], L["out_b"], ws.h16, L["g1"], L["be1"], L["eps1"], L["w1"], L["b1"],
+                                    L["w2"], L["b2"], L["g2"], L["be2"], L["eps2"], out32, ws.h16)
+
+
+class OnlineTransformerDADiarization(PreparedOperands, nn.Module):
     """FS-EEND batch model on MI355X (reference model :10-84)."""
 
     def __init__(self, n_speakers, in_size, n_units, n_heads, enc_n_layers, dec_n_layers, dropout, has_mask,
@@ -210,61 +235,18 @@ class OnlineTransformerDADiarization(nn.Module):
                                                  has_mask=has_mask, max_seqlen=max_seqlen, mask_delay=mask_delay)
         # NB padding is hard-coded 9 in the reference (model :30), whatever conv_delay is
         self.cnn = nn.Conv1d(n_units, n_units, kernel_size=2 * conv_delay + 1, padding=9)
-        self._prep = None
-        self._prep_key = None
         self._ws = WorkspaceCache()
-        self._pc = {}
-        self._sd = {}
-        self.register_load_state_dict_post_hook(lambda module, incompatible_keys: module.refresh_weights())
 
-    def refresh_weights(self):
-        """Drop the cached f16 operand copies.  They are keyed on (data_ptr, _version) of every parameter, which sees
-        optimiser steps, load_state_dict and .to(); writes through `.data` (p.data.copy_) do NOT bump _version --
-        call this after such a write."""
-        self._prep = None
-
-    def _apply(self, fn, *a, **kw):
-        out = super()._apply(fn, *a, **kw)
-        self._prep = None
-        return out
-
-    # ------------------------------------------------------------------ weight preparation
-    def _fingerprint(self):
-        return tuple((p.data_ptr(), p._version) for p in list(self.parameters()) + list(self.buffers()))
-
-    def _prepare(self):
-        """f16 MFMA-operand copies of the weights in kernel layouts (rebuilt when parameters change)."""
-        key = self._fingerprint()
-        if self._prep is not None and key == self._prep_key:
-            return self._prep
-        dev = self.cnn.weight.device
-        if dev.type != "cuda":
-            raise EendHipError("model parameters must live on the GPU: the HIP path has no CPU fallback")
+    # ------------------------------------------------------------------ weight preparation (the cache: weights.PreparedOperands)
+    def _build_operands(self):
+        """f16 MFMA-operand copies of the weights in kernel layouts."""
+        need_gpu_params(self.cnn.weight)
         P = {}
         enc = self.enc
-        Fin = enc.in_size
-        Fin_pad = (Fin + 63) // 64 * 64
-        w = torch.zeros(enc.n_units, Fin_pad, dtype=torch.float16, device=dev)
-        w[:, :Fin] = enc.encoder.weight.detach().to(torch.float16)
-        P["enc.in.w"], P["enc.in.b"] = w, _f32(enc.encoder.bias)
-        P["enc.in.g"], P["enc.in.beta"] = _f32(enc.encoder_norm.weight), _f32(enc.encoder_norm.bias)
-        P["enc.in.eps"] = enc.encoder_norm.eps
-        P["bn"] = tuple(_f32(t) for t in (enc.bn.weight, enc.bn.bias, enc.bn.running_mean, enc.bn.running_var))
+        (P["enc.in.w"], P["enc.in.b"], P["enc.in.g"], P["enc.in.beta"], P["enc.in.eps"], P["Fin_pad"],
+         P["bn"]) = input_operands(enc.encoder, enc.encoder_norm, enc.in_size, enc.bn)
         P["bn.eps"] = enc.bn.eps
-        P["Fin_pad"] = Fin_pad
-        layers = []
-        for l in enc.transformer_encoder.layers:
-            layers.append(dict(
-                in_w=_f16(_qscaled(l.self_attn.in_proj_weight)), in_b=_f32(_qscaled(l.self_attn.in_proj_bias)),
-                out_w=_f16(l.self_attn.out_proj.weight), out_b=_f32(l.self_attn.out_proj.bias),
-                w1=_f16(l.linear1.weight), b1=_f32(l.linear1.bias), w2=_f16(l.linear2.weight), b2=_f32(l.linear2.bias),
-                g1=_f32(l.norm1.weight), be1=_f32(l.norm1.bias), eps1=l.norm1.eps,
-                g2=_f32(l.norm2.weight), be2=_f32(l.norm2.bias), eps2=l.norm2.eps))
-        for L in layers:
-            if ops.stream_ok(L["w1"].shape[0]):
-                L["ws"] = ops.ffn_stream_pack(L["out_w"], L["w1"], L["w2"])
-            L["in_wp"] = ops.inproj_attn_pack(L["in_w"])
-        P["enc.layers"] = layers
+        P["enc.layers"] = [encoder_layer_operands(l, keep_unpacked=True) for l in enc.transformer_encoder.layers]
         cw = self.cnn.weight.detach()                       # (Dout, Din, k)
         P["cnn.w"] = cw.permute(0, 2, 1).reshape(cw.shape[0], -1).to(torch.float16).contiguous()
         P["cnn.b"] = _f32(self.cnn.bias)
@@ -292,39 +274,26 @@ class OnlineTransformerDADiarization(nn.Module):
                 L["wsd"] = ops.dec_stream_pack(L["out1_w"], L["in2_w"], L["out2_w"], L["w1"], L["w2"])
             L["in1_wp"] = ops.inproj_attn_pack(L["in1_w"])
         P["dec.layers"] = dl
-        self._prep, self._prep_key = P, key
-        self._pc = {}
-        self._sd = {}
         return P
-
-    def _convert_const(self, C):
-        """pc[c] = convert.weight[:, D:] pe[c] + convert.bias  (a (C, D) constant of the weights): eend_convert_const_f32."""
-        if C not in self._pc:
-            from . import lib as _lib
-            D = self.enc.n_units if hasattr(self.enc, "n_units") else self.n_units
-            dev = self.dec.convert.weight.device
-            W = self.dec.convert.weight.detach().to(torch.float32).contiguous()
-            b = self.dec.convert.bias.detach().to(torch.float32).contiguous()
-            pe = self.dec.pos_enc.pe[0, :C].to(device=dev, dtype=torch.float32).contiguous()
-            pc = torch.empty(C, D, dtype=torch.float32, device=dev)
-            L = _lib.load()
-            _lib.check(L.eend_convert_const_f32(0, W.data_ptr(), b.data_ptr(), pe.data_ptr(), pc.data_ptr(), None, None, None, C,
-                                                torch.cuda.current_stream().cuda_stream), "eend_convert_const_f32")
-            self._pc[C] = pc
-        return self._pc[C]
 
     def _slot_delta(self, C):
         """slot_delta[c] = (W_q d_c | W_v d_c), d_c = pc[c] - pc[0]  (a (C, 512) f32 constant of the weights): what the slot constants of
         the fan-out become behind the first fusion layer's time-axis in-projection.  W is the f16 operand copy the kernel multiplies
-        with (q rows pre-scaled), the products are summed in f32; cached like _convert_const, per parameter version and slot count."""
-        if C not in self._sd:
+        with (q rows pre-scaled), the products are summed in f32; cached like convert_const, per parameter version and slot count."""
+        def build():
             W = self._prep["dec.layers"][0]["in1_w"].to(torch.float32)
-            pc = self._convert_const(C)
+            pc = convert_const(self, C)
             d = pc - pc[:1]
             sd = (d[:, None, :] * torch.cat([W[:256], W[512:]])[None]).sum(-1)
             sd[0] = 0.0
-            self._sd[C] = sd.contiguous()
-        return self._sd[C]
+            return sd.contiguous()
+
+        return self._derived(("sd", C), build)
+
+    @property
+    def _sd(self):
+        """{C: slot delta} of the present operand set: a read-only view of the derived cache."""
+        return {k[1]: v for k, v in self._consts.items() if k[0] == "sd"}
 
     def _workspace(self, dev, B, Tp, C):
         key = (str(dev), B, Tp, C)
@@ -365,44 +334,8 @@ class OnlineTransformerDADiarization(nn.Module):
         else:
             ops.gather_bn_cast_pad(srcs, P["bn"], ws.xin16, T, Tp, -1.0, True, P["bn.eps"])
             ops.linear_res_ln(ws.xin16, P["enc.in.w"], P["enc.in.b"], None, P["enc.in.g"], P["enc.in.beta"], None, ws.h16, P["enc.in.eps"])
-        o16 = ws.o16[:Me]
-
-        def time_attention(x16, Ly, wkey, bkey, nseq, delay, kv, slots=None):
-            """in-projection + causal MHA over the frames of `nseq` sequences -> ws.o16 rows (merge_tfm_encoder.py:379-385)"""
-            o = ws.o16[:nseq * Tp]
-            if slots is not None and Tp == 512:
-                # the sequences are the fan-out's speaker slots: K / V projected once per utterance, from the rows of slot 0 (slot form)
-                ops.inproj_attn_causal_packed(x16, Ly[wkey + "p"], Ly[bkey], o, nseq, H, Tp, delay, kv, slots=slots,
-                                              slot_delta=self._slot_delta(slots))
-                return o
-            if Tp <= 512:            # token-owning waves, packed weights, Q in registers, K / V never leave the CU (attn_stream.hip)
-                ops.inproj_attn_causal_packed(x16, Ly[wkey + "p"], Ly[bkey], o, nseq, H, Tp, delay, kv)
-                return o
-            # (same-box A/B, 163840 frames: Tp 1024 326 vs 454 us, 2048 586 vs 664 us, 4096 1098 vs 1090 us -- an item re-projects its key
-            #  group's K / V, so the grouped form stops paying at about six groups)
-            need = ops.inproj_attn_long_scratch(nseq, Tp, delay, kv) if Tp <= 3072 else None
-            if need is not None:     # the same kernel on (query group, key group) items of 512 frames + a combine pass over the partial rows
-                if ws.attn_part.numel() < need[0]:
-                    ws.attn_part = torch.empty(need[0], dtype=torch.float16, device=o.device)
-                if ws.attn_lse.numel() < need[1]:
-                    ws.attn_lse = torch.empty(need[1], dtype=torch.float32, device=o.device)
-                ops.inproj_attn_causal_long(x16, Ly[wkey + "p"], Ly[bkey], o, ws.attn_part, ws.attn_lse, nseq, H, Tp, delay, kv)
-            else:                    # bf16 Q / K / V^T through HBM, tiled attention kernel
-                n = nseq * Tp * D
-                if ws.q is None:
-                    ws.q, ws.k, ws.vt = (torch.empty(ws.Mx * ws.D, dtype=torch.bfloat16, device=o.device) for _ in range(3))
-                ops.inproj_heads(x16, Ly[wkey], Ly[bkey], ws.q[:n], ws.k[:n], ws.vt[:n], nseq, Tp, H)
-                ops.attn_causal(ws.q[:n], ws.k[:n], ws.vt[:n], o, nseq, H, Tp, delay, kv, scale=ops.LN2)
-            return o
-
         for L in P["enc.layers"]:
-            time_attention(ws.h16, L, "in_w", "in_b", B, delay_e, kv_e)
-            if "ws" in L:            # out-projection + norm1 + FFN + norm2 in one launch on the packed weight stream (ffn_stream.hip)
-                ops.attnout_ffn_stream(o16, L["ws"], L["out_b"], None, ws.h16, L["g1"], L["be1"], L["eps1"], L["b1"], L["b2"], L["g2"],
-                                       L["be2"], L["eps2"], None, ws.h16)
-            else:                    # hidden sizes the packed stream does not take (ffn.hip)
-                ops.attnout_ffn_fused_res16(o16, L["out_w"], L["out_b"], ws.h16, L["g1"], L["be1"], L["eps1"], L["w1"], L["b1"],
-                                            L["w2"], L["b2"], L["g2"], L["be2"], L["eps2"], None, ws.h16)
+            encoder_layer(ws, L, B, H, Tp, delay_e, kv_e)
 
         # ---- truncate to ilen / zero re-pad, look-ahead conv, L2 norm (model :38-41)
         emb32 = torch.empty(Me, D, dtype=torch.float32, device=dev)       # returned to the caller (views, no copies)
@@ -412,11 +345,13 @@ class OnlineTransformerDADiarization(nn.Module):
             ops.conv1d_l2norm(ws.h16, P["cnn.w"], P["cnn.b"], il, emb32, ws.emb16, B, Tp, D, P["cnn.k"], P["cnn.pad"])
 
         # ---- attractor decoder (model :112-118, merge_tfm_encoder.py:356-376)
-        ops.convert_fanout(ws.emb16, P["convert.w1"], self._convert_const(C), None, ws.a16, B, Tp, C)
+        ops.convert_fanout(ws.emb16, P["convert.w1"], convert_const(self, C), None, ws.a16, B, Tp, C)
         o16 = ws.o16[:Md]
         for li, L in enumerate(P["dec.layers"]):
             # (the first layer reads the fan-out itself: its rows differ by pc[c] between the slots of an utterance)
-            time_attention(ws.a16, L, "in1_w", "in1_b", B * C, self.dec.mask_delay, T, slots=C if li == 0 and C <= 12 else None)
+            slots = C if li == 0 and C <= 12 and Tp == 512 else None
+            time_attention(ws, ws.a16, L, B * C, H, Tp, self.dec.mask_delay, T, key="in1", slots=slots,
+                           slot_delta=None if slots is None else self._slot_delta(C))
             # out-projection + norm11 + speaker-axis in-projection + C x C attention in one launch (spk_stream.hip; any slot count the
             # speaker-axis kernels take, C <= 12).  It takes no T_valid: the slab's padded frames [T, Tp) are computed too (finite
             # don't-care rows, masked as keys and dropped by the head) -- 2.4 % of the rows at T = 500 / Tp = 512; a per-tile T_valid test

@@ -18,6 +18,7 @@ import torch
 from . import ops
 from .fs_stream import dec_layers, enc_layers, front_end
 from .lib import EendHipError
+from .weights import convert_const
 # the slot model lives in multistream.py; its names stay importable from here for existing callers
 from .multistream import DONE, FLUSHING, FREE, OPEN, MultiStreamSession, SlotError, SlotTable  # noqa: F401
 
@@ -173,7 +174,7 @@ class FsMultiStreamSession(MultiStreamSession):
             ops.window_chunk(self.win16, r.h32, r.cols, r.ctl[1], r.ctl[2], r.ctl[3], n)
         self._conv_l2(r.cols, r.conv32, r.e32, r.e16)
         # decoder, (B = S, C, Tp = n) slabs
-        ops.convert_fanout(r.e16, P["convert.w1"], self.m._convert_const(C), r.a32, r.a16, S, n, C)
+        ops.convert_fanout(r.e16, P["convert.w1"], convert_const(self.m, C), r.a32, r.a16, S, n, C)
         dec_layers(P, r.a32, r.a16, r.qkv, r.o16, r.ff,
                    lambda i, qkv, o16: self._attn(r, qkv, *self.dec_kv[i], o16, S * C, C, self.len_dec, dec_c), S, C, n, self.H)
         advance(self.len_dec, dec_c)
@@ -208,7 +209,7 @@ class FsMultiStreamSession(MultiStreamSession):
         self._conv_l2(cols, r.conv32[:ne], e32, e16)
         R = C * ne
         a32, a16 = r.a32[:R], r.a16[:R]
-        ops.convert_fanout(e16, P["convert.w1"], self.m._convert_const(C), a32, a16, 1, ne, C)
+        ops.convert_fanout(e16, P["convert.w1"], convert_const(self.m, C), a32, a16, 1, ne, C)
         dec_layers(P, a32, a16, r.qkv[:R], r.o16[:R], r.ff,
                    lambda i, qkv, o16: ops.attn_prefill(qkv, *self.dec_kv[i], o16, s * C, C, self.H, t_dec, ne), 1, C, ne, self.H)
         logits = r.logits[:ne * C].view(1, ne, C)

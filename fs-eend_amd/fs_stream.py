@@ -16,9 +16,9 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from .fs_model import PositionalEncoding, _f16, _f32
-from .lib import EendHipError
-from .ls_stream import StreamingConv1d as _LsStreamingConv1d
+from .fs_model import PositionalEncoding
+from .weights import PreparedOperands, _f16, _f32, convert_const, input_operands, need_gpu_params
+from .ls_stream import StagedStreamSession, StreamingConv1d as _LsStreamingConv1d
 
 
 class StreamingConv1d(_LsStreamingConv1d):
@@ -150,7 +150,7 @@ def dec_layers(P, x32, x16, qkv, o16, ff, attn, B, C, n, H):
         ops.linear_res_ln(f, L["w2"], L["b2"], x32, L["n3"][0], L["n3"][1], x32, x16, L["n3"][2])
 
 
-class StreamingTransformerEDADiarization(nn.Module):
+class StreamingTransformerEDADiarization(PreparedOperands, nn.Module):
     """reference FS-EEND/nnet/model/streaming_tfm_enc_...l2norm.py:9-60."""
 
     def __init__(self, in_size, n_units, n_heads, enc_n_layers, dec_n_layers, dropout, has_mask, max_seqlen,
@@ -167,40 +167,17 @@ class StreamingTransformerEDADiarization(nn.Module):
         self.cnn = StreamingConv1d(n_units, n_units, kernel_size=2 * conv_delay + 1)
         self.dec = StreamingAttractorDecoder(n_units, n_heads, dec_n_layers, dim_feedforward=dec_dim_feedforward,
                                              dropout=dropout)
-        self._prep = self._prep_key = None
-        self._pc, self._sc = {}, None
+        self._sc = None
         self._enc_kv, self._dec_kv = None, None
-        self.register_load_state_dict_post_hook(lambda module, incompatible_keys: module.refresh_weights())
 
-    def refresh_weights(self):
-        """Drop the cached operand copies (needed after writes through `.data`, which do not bump _version)."""
-        self._prep = None
-
-    def _apply(self, fn, *a, **kw):
-        out = super()._apply(fn, *a, **kw)
-        self._prep = None
-        return out
-
-    # ------------------------------------------------------------------ weights
-    def _fingerprint(self):
-        return tuple((p.data_ptr(), p._version) for p in list(self.parameters()) + list(self.buffers()))
-
-    def _prepare(self):
-        key = self._fingerprint()
-        if self._prep is not None and key == self._prep_key:
-            return self._prep
-        dev = self.cnn.conv.weight.device
-        if dev.type != "cuda":
-            raise EendHipError("model parameters must live on the GPU: the HIP path has no CPU fallback")
+    # ------------------------------------------------------------------ weights (the cache: weights.PreparedOperands)
+    def _build_operands(self):
+        need_gpu_params(self.cnn.conv.weight)
         D, e = self.n_units, self.enc
         P = {}
-        Fin_pad = (self._in_size + 63) // 64 * 64
-        w = torch.zeros(D, Fin_pad, dtype=F16, device=dev)
-        w[:, :self._in_size] = e.proj.weight.detach().to(F16)
-        P["in.w"], P["in.b"] = w, _f32(e.proj.bias)
-        P["in.g"], P["in.beta"], P["in.eps"] = _f32(e.proj_norm.weight), _f32(e.proj_norm.bias), e.proj_norm.eps
-        P["bn"] = tuple(_f32(t) for t in (e.bn.weight, e.bn.bias, e.bn.running_mean, e.bn.running_var))
-        P["bn.eps"], P["Fin_pad"] = e.bn.eps, Fin_pad
+        (P["in.w"], P["in.b"], P["in.g"], P["in.beta"], P["in.eps"], P["Fin_pad"],
+         P["bn"]) = input_operands(e.proj, e.proj_norm, self._in_size, e.bn)
+        P["bn.eps"] = e.bn.eps
 
         def mha(m):
             return _f16(m.in_proj_weight), _f32(m.in_proj_bias), _f16(m.out_proj.weight), _f32(m.out_proj.bias)
@@ -216,24 +193,7 @@ class StreamingTransformerEDADiarization(nn.Module):
                          b1=_f32(l.linear1.bias), w2=_f16(l.linear2.weight), b2=_f32(l.linear2.bias),
                          n1=ln(l.norm1), n2=ln(l.norm2), n3=ln(l.norm3)) for l in self.dec.layers]
         P["Fmax"] = max([l["w1"].shape[0] for l in P["enc"] + P["dec"]] + [1])     # the widest FFN: sizes the ff scratch
-        self._prep, self._prep_key, self._pc = P, key, {}
         return P
-
-    def _convert_const(self, C):
-        """pc[c] = convert.weight[:, D:] pe[c] + convert.bias (a (C, D) constant of the weights): eend_convert_const_f32."""
-        if C not in self._pc:
-            from . import lib as _lib
-            D = self.n_units
-            dev = self.dec.convert.weight.device
-            W = self.dec.convert.weight.detach().to(F32).contiguous()
-            b = self.dec.convert.bias.detach().to(F32).contiguous()
-            pe = self.dec.pos_enc.pe[0, :C].to(device=dev, dtype=F32).contiguous()
-            pc = torch.empty(C, D, dtype=F32, device=dev)
-            L = _lib.load()
-            _lib.check(L.eend_convert_const_f32(0, W.data_ptr(), b.data_ptr(), pe.data_ptr(), pc.data_ptr(), None, None, None, C,
-                                                torch.cuda.current_stream().cuda_stream), "eend_convert_const_f32")
-            self._pc[C] = pc
-        return self._pc[C]
 
     def reset_streaming_state(self):
         """Forget the K/V history and the conv ring buffer (start of a new stream)."""
@@ -280,7 +240,7 @@ class StreamingTransformerEDADiarization(nn.Module):
         if self._dec_kv is None or self._dec_kv[0].N != C:
             self._dec_kv = [_KvCache(C, H, dev) for _ in P["dec"]]
         a32, a16 = sc["a32"][:C], sc["a16"][:C]
-        ops.convert_fanout(e32.to(F16), P["convert.w1"], self._convert_const(C), a32, a16, 1, 1, C)
+        ops.convert_fanout(e32.to(F16), P["convert.w1"], convert_const(self, C), a32, a16, 1, 1, C)
         dec_layers(P, a32, a16, sc["qkv"][:C], sc["o16"][:C], sc["ff"], lambda i, qkv, o16: self._dec_kv[i].decode(qkv, o16), 1, C, 1, H)
         attr = torch.empty(1, 1, C, D, dtype=F32, device=dev)
         y = torch.empty(1, 1, C, dtype=F32, device=dev)
@@ -288,7 +248,7 @@ class StreamingTransformerEDADiarization(nn.Module):
         return y
 
 
-class FsStreamSession:
+class FsStreamSession(StagedStreamSession):
     """Frame-by-frame FS-EEND with all streaming state in fixed HBM buffers and the per-frame work replayed from three
     captured hipGraphs (FS-EEND/streaming_infer_dia.py's per-frame loop is the procedure reproduced):
 
@@ -383,40 +343,16 @@ class FsStreamSession:
         """Decoder stage, on the first C rows of the encoder's buffers: `_decode` on the decoder caches at t_dec."""
         P, C = self.m._prepare(), self.C
         a32, a16 = self.h32[:C], self.h16[:C]
-        ops.convert_fanout(self.e16, P["convert.w1"], self.m._convert_const(C), a32, a16, 1, 1, C)
+        ops.convert_fanout(self.e16, P["convert.w1"], convert_const(self.m, C), a32, a16, 1, 1, C)
         dec_layers(P, a32, a16, self.qkv[:C], self.o16[:C], self.ff,
                    lambda i, qkv, o16: self._decode(qkv, *self.dec_kv[i], o16, C, self.t_dec), 1, C, 1, self.H)
         ops.counter_add(self.t_dec, 1)
         ops.head_l2dot(self.e32, a32, self.attr, self.logits, 1, 1, 1, C, self.D)
 
-    def _capture(self):
-        keep = [t_.clone() for t_ in (self.t_enc, self.t_dec, self.win16, self.enc_out, self.x_in)]
-        snap = [[c.clone() for c in kv] for kv in self.enc_kv + self.dec_kv] if (self.n_enc or self.n_dec) else None
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):                                        # warm-up: workspaces, operand caches
-            self._enc(); self._conv(); self._dec()
-        torch.cuda.current_stream().wait_stream(s)
-        gs = []
-        for fn in (self._enc, self._conv, self._dec):
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                fn()
-            gs.append(g)
-        self._graphs = gs
-        for dst, src in zip((self.t_enc, self.t_dec, self.win16, self.enc_out, self.x_in), keep):    # undo the warm-up's effects
-            dst.copy_(src)
-        if snap is not None:
-            for kv, sv in zip(self.enc_kv + self.dec_kv, snap):
-                for a, b in zip(kv, sv):
-                    a.copy_(b)
-
-    def _run(self, i):
-        if not self.use_graph:
-            return (self._enc, self._conv, self._dec)[i]()
-        if self._graphs is None:
-            self._capture()
-        self._graphs[i].replay()
+    def _state(self):
+        """The K/V caches only once there is history: before that nothing reads what a warm-up run appends."""
+        kv = [c for kv in self.enc_kv + self.dec_kv for c in kv] if (self.n_enc or self.n_dec) else []
+        return [self.t_enc, self.t_dec, self.win16, self.enc_out, self.x_in] + kv
 
     def seek(self, t: int):
         """Benchmarking aid: continue as if `t` frames had already been pushed -- the K/V caches keep whatever they hold
@@ -431,50 +367,6 @@ class FsStreamSession:
     def _room(self):
         if max(self.n_enc, self.n_dec) + 1 >= self.cap:                   # next capacity bucket: bigger caches, new graphs
             self._alloc_caches(2 * self.cap, keep=True)
-
-    def _check_weights(self):
-        """The captured graphs hold raw pointers into the model's operand copies (model._prepare()): if the weights were
-        refreshed since the capture (load_state_dict, .to(), an optimiser step) those copies are stale or freed -- capture
-        again on the new ones instead of replaying over dead memory."""
-        P = self.m._prep
-        if P is None or (self.t & 255) == 0:
-            P = self.m._prepare()
-        if P is not getattr(self, "_P_captured", None):
-            self._P_captured = P
-            self._graphs = None
-
-    @torch.no_grad()
-    def push(self, x_t):
-        """x_t: features of the next frame ((1,1,in) / (1,in) / (in,)) -> logits (1,1,C) of frame t - conv_delay, or None
-        during the first conv_delay frames."""
-        self._check_weights()
-        self._room()
-        self.x_in.copy_(x_t.reshape(1, 1, -1))
-        self._run(0)
-        self.n_enc += 1
-        return self._emit()
-
-    def _emit(self):
-        self._run(1)
-        self.t += 1
-        if self.t < self.center + 1:
-            return None
-        self._run(2)
-        self.n_dec += 1
-        return self.logits.clone()
-
-    @torch.no_grad()
-    def flush(self):
-        """the last conv_delay frames: zero embeddings through the look-ahead window (the reference driver's
-        `dummy_conv_input=True` calls)"""
-        out = []
-        for _ in range(self.center):
-            self._room()
-            self.enc_out.zero_()
-            y = self._emit()
-            if y is not None:
-                out.append(y)
-        return out
 
 
 # ---------------------------------------------------------------------------------------------

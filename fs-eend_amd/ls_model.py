@@ -19,7 +19,8 @@ import torch.nn as nn
 from torch import Tensor
 
 from . import ops
-from .fs_model import PositionalEncoding, WorkspaceCache, _f16, _f32
+from .fs_model import PositionalEncoding, WorkspaceCache
+from .weights import PreparedOperands, _f16, _f32, convert_const, input_operands, need_gpu_params
 
 # One fast form + one general fallback per operator, selected by SHAPE (round 6: the A/B environment switches of rounds 2 - 5 are gone;
 # their questions are answered in profiles/OPTIMISATION_LOG.md):
@@ -29,7 +30,6 @@ from .fs_model import PositionalEncoding, WorkspaceCache, _f16, _f32
 #   Conformer half-step FFNs  ffn.hip (the packed-stream form measured slower on this model's f32 residual stream: round 4)
 #   decoder input             convert_f32.hip (f32 MFMA; the batch forward hands over f32 embeddings) | f16 form (chunked long-form path)
 #   look-ahead conv           conv_stream.hip (256 channels)              | implicit-GEMM epilogue (gemm.hip)
-from .lib import EendHipError
 from . import ls_stream
 from .ls_stream import StreamingConv1d  # noqa: F401  (re-exported: the reference defines it next to the model)
 
@@ -259,7 +259,7 @@ class _Workspace:
         self.cscale, self.sexp = e(nseq * H * nc, dt=f32), e(nseq * H * nc, dt=f32)
 
 
-class OnlineConformerRetentionDADiarization(nn.Module):
+class OnlineConformerRetentionDADiarization(PreparedOperands, nn.Module):
     """LS-EEND on MI355X (reference LS model :14-147)."""
 
     def __init__(self, n_speakers, in_size, n_units, n_heads, enc_n_layers, dec_n_layers, dropout, max_seqlen,
@@ -283,33 +283,14 @@ class OnlineConformerRetentionDADiarization(nn.Module):
                                                  max_seqlen=max_seqlen, mask_delay=mask_delay)
         self.cnn = nn.Conv1d(n_units, n_units, kernel_size=2 * conv_delay + 1, padding=conv_delay)
         self._in_size, self._n_heads = in_size, n_heads
-        self._prep = self._prep_key = None
-        self._ws, self._pc, self._step_scratch = WorkspaceCache(), {}, {}
-        self.register_load_state_dict_post_hook(lambda module, incompatible_keys: module.refresh_weights())
+        self._ws, self._step_scratch = WorkspaceCache(), {}
         # back-references for the one-step API (bypass nn.Module registration: no module cycle)
         object.__setattr__(self.enc, "_owner", weakref.ref(self))
         object.__setattr__(self.dec, "_owner", weakref.ref(self))
 
-    # ------------------------------------------------------------------ weight preparation
-    def refresh_weights(self):
-        """Drop the cached operand copies (needed after writes through `.data`, which do not bump _version)."""
-        self._prep = None
-
-    def _apply(self, fn, *a, **kw):
-        out = super()._apply(fn, *a, **kw)
-        self._prep = None
-        return out
-
-    def _fingerprint(self):
-        return tuple((p.data_ptr(), p._version) for p in list(self.parameters()) + list(self.buffers()))
-
-    def _prepare(self):
-        key = self._fingerprint()
-        if self._prep is not None and key == self._prep_key:
-            return self._prep
-        dev = self.cnn.weight.device
-        if dev.type != "cuda":
-            raise EendHipError("model parameters must live on the GPU: the HIP path has no CPU fallback")
+    # ------------------------------------------------------------------ weight preparation (the cache: weights.PreparedOperands)
+    def _build_operands(self):
+        dev = need_gpu_params(self.cnn.weight)
         for name, buf in self.named_buffers():
             # the retention kernels hard-code decay == 1 (log-decay 0) and no rotary shift, as the reference ships
             # (modules/retention.py:20, :209-213); a checkpoint with another decay must fail loudly, not silently
@@ -318,16 +299,11 @@ class OnlineConformerRetentionDADiarization(nn.Module):
         D = self.n_units
         P = {}
         e = self.enc.encoder
-        Fin = self._in_size
-        Fin_pad = (Fin + 63) // 64 * 64
-        w = torch.zeros(D, Fin_pad, dtype=torch.float16, device=dev)
-        w[:, :Fin] = e.input_projection.linear.weight.detach().to(torch.float16)
-        P["in.w"], P["in.b"] = w, _f32(e.input_projection.linear.bias)
+        P["in.w"], P["in.b"], P["in.g"], P["in.beta"], P["in.eps"], Fin_pad = input_operands(e.input_projection.linear, e.layer_norm,
+                                                                                            self._in_size)
         w32 = torch.zeros(D, Fin_pad, dtype=torch.float32, device=dev)            # f32 frame step (ls_stream.enc_step)
-        w32[:, :Fin] = e.input_projection.linear.weight.detach()
-        P["in.w32"] = w32
-        P["in.g"], P["in.beta"], P["in.eps"] = _f32(e.layer_norm.weight), _f32(e.layer_norm.bias), e.layer_norm.eps
-        P["Fin_pad"] = Fin_pad
+        w32[:, :self._in_size] = e.input_projection.linear.weight.detach()
+        P["in.w32"], P["Fin_pad"] = w32, Fin_pad
         blocks = []
         for blk in e.layers:
             s = blk.sequential
@@ -391,24 +367,7 @@ class OnlineConformerRetentionDADiarization(nn.Module):
             Fd = Ld["w1"].shape[0]      # layer tail on the packed stream (LO form) where its shape allows, else the un-packed ffn.hip launch
             Ld["ws2"] = ops.ffn_stream_pack_lo(Ld["out2_w"], Ld["out2_wlo"], Ld["w1"], Ld["w2"]) if (Fd % 64 == 0 and 64 <= Fd <= 2048) else None
         P["dec.layers"] = dl
-        self._prep, self._prep_key, self._pc = P, key, {}
         return P
-
-    def _convert_const(self, C):
-        """pc[c] = convert.weight[:, D:] pe[c] + convert.bias  (a (C, D) constant of the weights): eend_convert_const_f32."""
-        if C not in self._pc:
-            from . import lib as _lib
-            D = self.enc.n_units if hasattr(self.enc, "n_units") else self.n_units
-            dev = self.dec.convert.weight.device
-            W = self.dec.convert.weight.detach().to(torch.float32).contiguous()
-            b = self.dec.convert.bias.detach().to(torch.float32).contiguous()
-            pe = self.dec.pos_enc.pe[0, :C].to(device=dev, dtype=torch.float32).contiguous()
-            pc = torch.empty(C, D, dtype=torch.float32, device=dev)
-            L = _lib.load()
-            _lib.check(L.eend_convert_const_f32(0, W.data_ptr(), b.data_ptr(), pe.data_ptr(), pc.data_ptr(), None, None, None, C,
-                                                torch.cuda.current_stream().cuda_stream), "eend_convert_const_f32")
-            self._pc[C] = pc
-        return self._pc[C]
 
     def _workspace(self, dev, B, Tp, C, nc):
         key = (str(dev), B, Tp, C, nc)
@@ -535,7 +494,7 @@ class OnlineConformerRetentionDADiarization(nn.Module):
             ops.conv1d_l2norm_stream(ws.h16, P["cnn.ws"], P["cnn.b"], ws.il, emb32, ws.emb16, B, Tp, P["cnn.k"], P["cnn.pad"])
         else:
             ops.conv1d_l2norm(ws.h16, P["cnn.w"], P["cnn.b"], ws.il, emb32, ws.emb16, B, Tp, D, P["cnn.k"], P["cnn.pad"])
-        self._decode_span(P, ws, ws.emb16, self._convert_const(C), B, Tpad, Tp, C, emb32=emb32)
+        self._decode_span(P, ws, ws.emb16, convert_const(self, C), B, Tpad, Tp, C, emb32=emb32)
         attr = torch.empty(B, T, C, D, dtype=torch.float32, device=dev)
         logits = torch.empty(B, T, C, dtype=torch.float32, device=dev)
         ops.head_l2dot(emb32, ws.a32, attr, logits, B, T, Tp, C, D)
@@ -597,7 +556,7 @@ class OnlineConformerRetentionDADiarization(nn.Module):
         logits = torch.empty(B, T, C, dtype=f32, device=dev)
         attr = torch.empty(B, T, C, D, dtype=f32, device=dev) if return_attractors else None
         dec_state = [torch.zeros(B * C, H, 64, 64, dtype=f32, device=dev) for _ in range(nd)]
-        pc = self._convert_const(C)
+        pc = convert_const(self, C)
         for s0, s1 in spans:
             Tc = s1 - s0
             Tv = min(s1, T) - s0                                   # real frames of this super-chunk

@@ -20,6 +20,7 @@ from . import ops
 from .lib import EendHipError
 from .ls_stream import f32_blocks, f32_dec_layers, f32_input
 from .multistream import OPEN, MultiStreamSession, SlotError
+from .weights import convert_const
 
 F16, F32, I32 = torch.float16, torch.float32, torch.int32
 
@@ -158,9 +159,9 @@ class LsMultiStreamSession(MultiStreamSession):
         ops.l2norm_rows_f32(r.y32, r.e32)
         # decoder, S*C*n rows in (B = S, C, Tp = n) slabs
         if n == 1:
-            ops.convert_fanout_step_f32(r.e32, P["convert.w32"], self.m._convert_const(C), r.a32, r.a16, S, C)
+            ops.convert_fanout_step_f32(r.e32, P["convert.w32"], convert_const(self.m, C), r.a32, r.a16, S, C)
         else:
-            ops.convert_fanout_f32(r.e32, P["convert.w32"], self.m._convert_const(C), r.a32, r.a16, S, n, C)
+            ops.convert_fanout_f32(r.e32, P["convert.w32"], convert_const(self.m, C), r.a32, r.a16, S, n, C)
         ret = lambda i, Ld, q32, **out: self._ret(r, q32, self.dec_kv[i], self.len_dec, dec_c, C, S * C, Ld["gn_eps"], **out)
         f32_dec_layers(P, r.a32, r.q32, r.o32, r.qkv32, r.ff32, ret, S, C, n)
         advance(self.len_dec, dec_c)
@@ -210,7 +211,7 @@ class LsMultiStreamSession(MultiStreamSession):
         ops.l2norm_rows_f32(r.y32[:ne], e32)
         R = C * ne
         a32 = r.a32[:R]
-        ops.convert_fanout_f32(e32, P["convert.w32"], self.m._convert_const(C), a32, r.a16[:R], 1, ne, C)
+        ops.convert_fanout_f32(e32, P["convert.w32"], convert_const(self.m, C), a32, r.a16[:R], 1, ne, C)
         ret = lambda i, Ld, q32, **out: ops.retention_prefill(q32, self.dec_kv[i], r.ws, s * C, C, H, t_dec, ne, Ld["gn_eps"], **out)
         f32_dec_layers(P, a32, r.q32[:R], r.o32[:R], r.qkv32[:R], r.ff32, ret, 1, C, ne)
         logits = r.logits[:R].view(1, ne, C)

@@ -19,6 +19,8 @@ import torch.nn as nn
 
 from . import ops
 from .lib import EendHipError
+from .multistream import capture_graphs
+from .weights import convert_const
 
 F16, F32 = torch.float16, torch.float32
 
@@ -207,9 +209,9 @@ def dec_step(owner, emb_t, t, max_nspks, ret_states):
     e32 = emb_t.to(device=dev, dtype=F32).reshape(B, D).contiguous()
     a32, a16 = sc["h32"][:N], sc["h16"][:N]
     if F32_PROJ:
-        ops.convert_fanout_step_f32(e32, P["convert.w32"], owner._convert_const(C), a32, a16, B, C)
+        ops.convert_fanout_step_f32(e32, P["convert.w32"], convert_const(owner, C), a32, a16, B, C)
     else:
-        ops.convert_fanout(e32.to(F16), P["convert.w1"], owner._convert_const(C), a32, a16, B, 1, C)
+        ops.convert_fanout(e32.to(F16), P["convert.w1"], convert_const(owner, C), a32, a16, B, 1, C)
     if F32_PROJ and DEC_F32 and N <= ops.STEP_F32_MAX_ROWS:               # the all-f32 layers on the driver's states
         f32_dec_layers(P, a32, sc["qkvg32"][:N], sc["o32"][:N], sc["qkv32"][:N], sc["ff32"], _ret_f32(ret_states, N, H, sc["o16"][:N]),
                        B, C, 1)
@@ -277,7 +279,83 @@ class StreamingConv1d(nn.Module):
         return out.unsqueeze(-1) if self.t >= self.center + 1 else None
 
 
-class LsStreamSession:
+class StagedStreamSession:
+    """The single-stream protocol of `LsStreamSession` and `fs_stream.FsStreamSession`: a frame goes through three stages, each an
+    eager body that is captured once into a graph and replayed (`use_graph`), or run as it is.
+
+    The subclass sets m (the model), use_graph, center (the conv delay), x_in (the input frame; its shape is what `push` takes),
+    enc_out (the encoder's row, zeroed by `flush`) and logits, gives the stage bodies _enc / _conv / _dec and _state(): the
+    tensors a warm-up run may disturb and a recapture must keep.  _room() is called before every frame (caches that grow).
+
+    One recapture rule: the graphs hold raw pointers into the model's operand copies (model._prepare()) and into the session's
+    buffers.  `_check_weights` drops them when the operands were rebuilt since the capture (load_state_dict, .to(), an
+    optimiser step), a subclass when it replaces a buffer; the next stage that runs captures again, on the state as it is then:
+    `_capture` snapshots _state(), warms up, records, restores, and notes the operand set it recorded (so a refresh between
+    construction and the first push re-captures like any later one).  The host counters t / n_enc / n_dec are never touched."""
+
+    _graphs = None
+    _P_captured = None
+
+    def _room(self):
+        pass
+
+    def _capture(self):
+        self._P_captured = self.m._prepare()
+        state = self._state()
+        keep = [t_.clone() for t_ in state]
+        self._graphs = capture_graphs(self._enc, self._conv, self._dec)
+        for dst, src in zip(state, keep):                                         # undo the warm-up's effects
+            dst.copy_(src)
+
+    def _run(self, i):
+        if not self.use_graph:
+            return (self._enc, self._conv, self._dec)[i]()
+        if self._graphs is None:
+            self._capture()
+        self._graphs[i].replay()
+
+    def _check_weights(self):
+        P = self.m._prep
+        if P is None or (self.t & 255) == 0:
+            P = self.m._prepare()
+        if P is not self._P_captured:
+            self._graphs = None
+
+    @torch.no_grad()
+    def push(self, x_t):
+        """x_t: features of the next frame (any shape with x_in's elements) -> logits of frame t - conv_delay, or None during the
+        first conv_delay frames."""
+        self._check_weights()
+        self._room()
+        self.x_in.copy_(x_t.reshape(self.x_in.shape))
+        self._run(0)
+        self.n_enc += 1
+        return self._emit()
+
+    def _emit(self):
+        self._run(1)
+        self.t += 1
+        if self.t < self.center + 1:
+            return None
+        self._run(2)
+        self.n_dec += 1
+        return self.logits.clone()
+
+    @torch.no_grad()
+    def flush(self):
+        """the last conv_delay frames: zero embeddings through the look-ahead window (the reference drivers'
+        `dummy_conv_input=True` calls, LS-EEND/streaming_infer_dia.py:91-95)"""
+        out = []
+        for _ in range(self.center):
+            self._room()
+            self.enc_out.zero_()
+            y = self._emit()
+            if y is not None:
+                out.append(y)
+        return out
+
+
+class LsStreamSession(StagedStreamSession):
     """Frame-by-frame LS-EEND with every piece of state resident in fixed HBM buffers and the per-frame work replayed
     from three captured hipGraphs (LS-EEND/streaming_infer_dia.py:52-97 is the procedure reproduced):
 
@@ -292,7 +370,7 @@ class LsStreamSession:
     """
 
     def __init__(self, model, max_nspks: int, batch: int = 1, use_graph: bool = True):
-        self.m, self.C, self.B = model, max_nspks, batch
+        self.m, self.C, self.B, self.use_graph = model, max_nspks, batch, use_graph
         P = model._prepare()
         dev = model.cnn.weight.device
         self.dev = dev
@@ -324,15 +402,17 @@ class LsStreamSession:
         self.klen = torch.full((batch,), self.k, dtype=torch.int32, device=dev)
         self.attr = torch.zeros(batch, 1, max_nspks, D, dtype=F32, device=dev)
         self.logits = torch.zeros(batch, 1, max_nspks, dtype=F32, device=dev)
-        self.t = 0
-        self._graphs = None
+        self.t = self.n_enc = self.n_dec = 0                                      # frames through the window / encoder / decoder
         self._stateful = ([s["prev_key_value"] for s in self.enc_states + self.dec_states] +
                           [s[k_] for s in self.enc_states + self.dec_states for k_ in ("scale", "_scale_next")] + self.caches +
                           [self.win16, self.win32, self.enc_out])
         if use_graph:
             self._capture()
 
-    # ---- the three stages (eager bodies; captured once)
+    def _state(self):
+        return self._stateful
+
+    # ---- the three stages (eager bodies; captured once per operand set)
     def _enc(self):
         self.enc_out.copy_(enc_step(self.m, self.x_in, self.t, self.enc_states, self.caches))
 
@@ -360,74 +440,7 @@ class LsStreamSession:
                        self.C, self.D)
 
     def reset(self):
+        """Start of a new stream."""
         for t_ in self._stateful:
             t_.zero_()
-        self.t = 0
-
-    def _capture(self):
-        self._P_captured = self.m._prepare()             # the operand set the recorded graphs point into
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):                                                # warm-up: workspaces, operand caches
-            self._enc(); self._conv(); self._dec()
-        torch.cuda.current_stream().wait_stream(s)
-        gs = []
-        for fn in (self._enc, self._conv, self._dec):
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                fn()
-            gs.append(g)
-        self._graphs = gs
-        self.reset()
-
-    def _run(self, i):
-        if self._graphs is not None:
-            self._graphs[i].replay()
-        else:
-            (self._enc, self._conv, self._dec)[i]()
-
-    def _check_weights(self):
-        """The captured graphs hold raw pointers into the model's operand copies: re-capture (keeping the streaming state)
-        when the weights were refreshed since -- load_state_dict, .to(), an optimiser step."""
-        P = self.m._prep
-        if P is None or (self.t & 255) == 0:
-            P = self.m._prepare()
-        if P is not getattr(self, "_P_captured", None):
-            # (_P_captured is set by _capture() itself, at the time the graphs are recorded: a refresh between construction and
-            # the first push re-captures like any later one -- ADVICE r03)
-            if self._graphs is None:
-                self._P_captured = P
-            else:
-                keep = [t_.clone() for t_ in self._stateful]
-                t = self.t
-                self._capture()
-                for dst, src in zip(self._stateful, keep):
-                    dst.copy_(src)
-                self.t = t
-
-    @torch.no_grad()
-    def push(self, x_t):
-        """x_t (B, 1, in_size) or (B, in_size) features of the next frame -> logits (B, 1, C) of frame t - delay, or None."""
-        self._check_weights()
-        self.x_in.copy_(x_t.reshape(self.B, 1, -1))
-        self._run(0)
-        return self._emit()
-
-    def _emit(self):
-        self._run(1)
-        self.t += 1
-        if self.t < self.center + 1:
-            return None
-        self._run(2)
-        return self.logits.clone()
-
-    @torch.no_grad()
-    def flush(self):
-        """the last conv_delay frames: zero embeddings through the look-ahead window (reference driver :91-95)"""
-        out = []
-        for _ in range(self.center):
-            self.enc_out.zero_()
-            y = self._emit()
-            if y is not None:
-                out.append(y)
-        return out
+        self.t = self.n_enc = self.n_dec = 0

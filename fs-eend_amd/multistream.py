@@ -20,6 +20,24 @@ F32, I32 = torch.float32, torch.int32
 FREE, OPEN, FLUSHING, DONE = "free", "open", "flushing", "done"
 
 
+def capture_graphs(*fns):
+    """Run every fn once on a side stream (warm-up: workspaces, operand caches, lazy allocations), then record each into a graph
+    of its own -> the graphs, in order.  The caller keeps whatever state the warm-up run may disturb."""
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        for fn in fns:
+            fn()
+    torch.cuda.current_stream().wait_stream(s)
+    graphs = []
+    for fn in fns:
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            fn()
+        graphs.append(g)
+    return graphs
+
+
 class SlotError(ValueError):
     pass
 
@@ -361,15 +379,7 @@ class MultiStreamSession:
 
     def _capture(self, r):
         r.ctl.zero_()                           # warm-up and capture with every mask / count off: no slot state changes
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):                                    # warm-up: workspaces, operand caches
-            self._body(r)
-        torch.cuda.current_stream().wait_stream(s)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            self._body(r)
-        return g
+        return capture_graphs(lambda: self._body(r))[0]
 
     # ---- public API
     def open(self) -> int:

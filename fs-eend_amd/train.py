@@ -508,7 +508,7 @@ class TrainStepBase:
         _call("eend_adam_step_f32", fl.params, fl.grads, fl.m, fl.v, fl.numel, self.hp, self.gsumsq, self.b1, self.b2, self.eps)
         self.last_lr = lr
         self.prep_weights()
-        self.model._prep = None            # the inference-path operand cache is stale now
+        self.model.refresh_weights()       # the inference-path operand cache is stale now
         return lr
 
     def step(self, src, labels, ilens, pit: bool = False):

@@ -123,7 +123,7 @@ class SpeakerDiarization:
             for k, v in sd.items():
                 if k in own:
                     own[k].copy_(v)                    # in place: parameters may be views of the flat buffer
-        self.model._prep = None
+        self.model.refresh_weights()
         if self._step is not None:
             self._step.prep_weights()
 

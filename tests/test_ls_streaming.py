@@ -140,7 +140,8 @@ def test_ls_stream_session(hip_lib, dev, use_graph):
 def test_stream_sessions_survive_a_weight_refresh(hip_lib, dev):
     """the captured graphs point into the model's operand copies; after load_state_dict (which rebuilds them)
     the sessions must capture again instead of replaying over freed memory -- same weights reloaded mid-stream must not
-    change a single output bit, for both flavours."""
+    change a single output bit, for both flavours.  ADVICE r03: a refresh between construction and the first push re-captures like
+    any later one.  The FS run crosses a cache doubling (cap = 64, 70 frames) with history in the caches after a re-capture."""
     import gc
     from fs_eend_amd.fs_stream import FsStreamSession, StreamingTransformerEDADiarization, copy_params_from_masked_to_streaming
     from fs_eend_amd.ls_stream import LsStreamSession
@@ -153,7 +154,7 @@ def test_stream_sessions_survive_a_weight_refresh(hip_lib, dev):
         s = LsStreamSession(m, meta["C"])
         out = []
         for t in range(60):
-            if refresh and t == 30:
+            if refresh and t in (0, 30):
                 m.load_state_dict({k: v.clone() for k, v in m.state_dict().items()})
                 gc.collect()
                 torch.cuda.empty_cache()
@@ -169,13 +170,13 @@ def test_stream_sessions_survive_a_weight_refresh(hip_lib, dev):
     fm = build_fs_mirror(fmeta).to(dev)
     sm = StreamingTransformerEDADiarization(in_size=fmeta["in_size"], **fmeta["cfg"]).eval().to(dev)
     copy_params_from_masked_to_streaming(fm, sm)
-    fsrc = FX.make_src([fmeta["T"]], fmeta["in_size"], fmeta["xseed"])[0].to(dev)
+    fsrc = FX.make_src([70], fmeta["in_size"], fmeta["xseed"])[0].to(dev)
 
     def run_fs(refresh):
         s = FsStreamSession(sm, fmeta["C"], cap=64)
         out = []
-        for t in range(50):
-            if refresh and t == 25:
+        for t in range(70):
+            if refresh and t in (0, 25):
                 sm.load_state_dict({k: v.clone() for k, v in sm.state_dict().items()})
                 gc.collect()
                 torch.cuda.empty_cache()
