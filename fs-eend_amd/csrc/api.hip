@@ -585,7 +585,13 @@ int eend_lstm_ok(int B, int T, int hidden) { return eend_lstm_shape_ok(B, T, hid
 
 int eend_lstm_f32(const float* G, int g_rows, const int* order, const float* bias, const float* W_hh, const float* h0, const float* c0,
                   float* hT, float* cT, float* h_all, int B, int T, int hidden, void* stream) {
-    return eend_launch_lstm(G, g_rows, order, bias, W_hh, h0, c0, hT, cT, h_all, B, T, hidden, (hipStream_t)stream);
+    return eend_launch_lstm(G, g_rows, order, bias, W_hh, h0, c0, hT, cT, h_all, B, T, hidden, 0, (hipStream_t)stream);
+}
+
+int eend_lstm_orders_f32(const float* G, int g_rows, const int* order, const float* W_hh, const float* h0, const float* c0, float* hT,
+                         float* cT, float* h_all, int B, int T, int hidden, void* stream) {
+    if (!G || !order) return EEND_EINVAL;
+    return eend_launch_lstm(G, g_rows, order, nullptr, W_hh, h0, c0, hT, cT, h_all, B, T, hidden, T, (hipStream_t)stream);
 }
 
 int eend_eda_count_f32(const float* attractors, const float* w, const float* bias, float th, float* probs, int* count, int B, int C,
@@ -595,6 +601,15 @@ int eend_eda_count_f32(const float* attractors, const float* w, const float* bia
 
 int eend_eda_head_f32(const float* emb, int emb_rows, const float* attractors, float* logits, int B, int T, int C, void* stream) {
     return eend_launch_eda_head(emb, emb_rows, attractors, logits, B, T, C, (hipStream_t)stream);
+}
+
+int eend_stb_center_f32(const long* desc, float* out, int B, int T, int F, int buf_size, int blk_size, void* stream) {
+    return eend_launch_stb_center(desc, out, B, T, F, buf_size, blk_size, (hipStream_t)stream);
+}
+
+int eend_stb_track_f32(const float* logits, const int* count, const float* xc, const long* desc, int* perm_out, int* sel_out, int B,
+                       int T, int F, int buf_size, int blk_size, int policy, void* stream) {
+    return eend_launch_stb_track(logits, count, xc, desc, perm_out, sel_out, B, T, F, buf_size, blk_size, policy, (hipStream_t)stream);
 }
 
 int eend_pit_cost_f64(const float* y, const float* labels, int B, int T, int C, double* cost, void* stream) {

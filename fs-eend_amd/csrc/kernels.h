@@ -173,10 +173,22 @@ int eend_launch_room_rir(const long* rooms, int n_rows, const long* tiles, int n
 #define EDA_MAX_ATTRACTORS 16
 int eend_lstm_shape_ok(int B, int T, int hidden);
 int eend_launch_lstm(const float* G, int g_rows, const int* order, const float* bias, const float* Whh, const float* h0, const float* c0,
-                     float* hT, float* cT, float* h_all, int B, int T, int hidden, hipStream_t stream);
+                     float* hT, float* cT, float* h_all, int B, int T, int hidden, int order_stride, hipStream_t stream);
 int eend_launch_eda_count(const float* attr, const float* w, const float* bias, float th, float* probs, int* count, int B, int C,
                           hipStream_t stream);
 int eend_launch_eda_head(const float* emb, int emb_rows, const float* attr, float* logits, int B, int T, int C, hipStream_t stream);
+
+// speaker-tracing buffer of block-online EEND-EDA (stb.hip): tracked columns, the most rows of buffer + block, the widest feature
+// row, the 64-bit words of a sequence's descriptor and the buffer policies
+#define STB_MAX_SPEAKERS 15
+#define STB_MAX_ROWS 4096
+#define STB_MAX_FEATURES 512
+#define STB_DESC_WORDS 12
+#define STB_POLICY_KLD 0
+#define STB_POLICY_FIFO 1
+int eend_launch_stb_center(const long* desc, float* out, int B, int T, int F, int buf_size, int blk_size, hipStream_t stream);
+int eend_launch_stb_track(const float* logits, const int* count, const float* xc, const long* desc, int* perm_out, int* sel_out, int B,
+                          int T, int F, int buf_size, int blk_size, int policy, hipStream_t stream);
 
 int eend_launch_pit_cost(const float* y, const float* lab, int B, int T, int C, double* cost, hipStream_t stream);
 int eend_launch_pit_assign(const double* cost, const int* nspk, int B, int C, int* perm, double* loss, hipStream_t stream);

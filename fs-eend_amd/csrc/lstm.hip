@@ -1,5 +1,5 @@
 // The attractor path of the offline EEND-EDA baseline (FS-EEND/nnet/model/offl_tfm_enc_lstm_enc_dec.py:79-107): a single-layer
-// LSTM recurrence (eend_lstm_f32), the attractor-existence counter with the speaker count taken from it (eend_eda_count_f32) and the
+// LSTM recurrence (eend_lstm_f32, eend_lstm_orders_f32), the attractor-existence counter with the speaker count taken from it (eend_eda_count_f32) and the
 // embedding . attractor head (eend_eda_head_f32).  The contracts are in include/eend_hip.h; DESIGN 12 has the reasoning and the times.
 //
 // eend_lstm_f32.  One workgroup of 16 waves owns one sequence from its first step to its last; workgroups never talk to each other
@@ -34,9 +34,11 @@ DEV float lstm_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
 __global__ __launch_bounds__(LNT) void lstm_seq_kernel(const float* __restrict__ G, int g_rows, const int* __restrict__ order,
                                                        const float* __restrict__ bias, const float* __restrict__ Whh,
                                                        const float* __restrict__ h0, const float* __restrict__ c0,
-                                                       float* __restrict__ hT, float* __restrict__ cT, float* __restrict__ h_all, int T) {
+                                                       float* __restrict__ hT, float* __restrict__ cT, float* __restrict__ h_all, int T,
+                                                       int order_stride) {
     __shared__ __attribute__((aligned(16))) float hbuf[2][LH];
     const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (order) order += (size_t)b * order_stride;                 // 0: one order for the batch, T: one per sequence
     const int unit = wave * 16 + (lane & 15);
     const int my_row = (lane >> 4) * LH + unit;                  // the gate row this lane holds after the butterfly
     if (threadIdx.x < LH) hbuf[0][threadIdx.x] = h0 ? h0[(size_t)b * LH + threadIdx.x] : 0.f;
@@ -172,11 +174,13 @@ __global__ __launch_bounds__(256) void eda_head_kernel(const float* __restrict__
 int eend_lstm_shape_ok(int B, int T, int hidden) { return hidden == LSTM_HIDDEN && T >= 1 && B >= 1; }
 
 int eend_launch_lstm(const float* G, int g_rows, const int* order, const float* bias, const float* Whh, const float* h0, const float* c0,
-                     float* hT, float* cT, float* h_all, int B, int T, int hidden, hipStream_t stream) {
+                     float* hT, float* cT, float* h_all, int B, int T, int hidden, int order_stride, hipStream_t stream) {
     if (!eend_lstm_shape_ok(B, T, hidden) || !Whh || !hT || !cT) return EEND_EINVAL;
+    if (order_stride != 0 && (order_stride < T || !order || !G)) return EEND_EINVAL;
     if (G ? g_rows < T : !bias) return EEND_EINVAL;               // rows of G per sequence; zero input needs the bias sum
     if ((h0 == nullptr) != (c0 == nullptr)) return EEND_EINVAL;
-    hipLaunchKernelGGL(lstm_seq_kernel, dim3(B), dim3(LNT), 0, stream, G, g_rows, order, bias, Whh, h0, c0, hT, cT, h_all, T);
+    hipLaunchKernelGGL(lstm_seq_kernel, dim3(B), dim3(LNT), 0, stream, G, g_rows, order, bias, Whh, h0, c0, hT, cT, h_all, T,
+                       order_stride);
     return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
 }
 

@@ -19,7 +19,9 @@ The torch.nn modules are parameter containers only; all arithmetic runs in libee
 Two quirks of the reference's ``test`` are deliberately not reproduced: with B > 1 it applies the first item's
 count to every later item (here every sequence keeps the columns before its own first p < th), and it raises on a recording where
 no probability is below ``th`` (here all 15 columns are kept).  ``forward``, the attractor loss and the LSTM backward are out of
-scope, as are the STB baseline and the Lightning module train/offl_tfm_lstm.py.
+scope, as is the Lightning module train/offl_tfm_lstm.py.  The block-online use of this model with a speaker-tracing buffer
+(train/tfm_STB.py) is ``fs_eend_amd.stb.StbSession``: it runs ``_encode`` and ``eda._attractors`` on many streams at once, every
+stream with its own frame order (a (B, T) ``order``).
 """
 from typing import Optional, Sequence
 
@@ -117,7 +119,7 @@ class EncoderDecoderAttractor(PreparedOperands, nn.Module):
 
     def _attractors(self, rows32: Tensor, T: int, order: Optional[Tensor], max_n_speakers: int, th: Optional[float]):
         """rows32 f32 (B, rows >= T, D) -> attractors (B, C, D), probs (B, C), count i32 (B,) or None.  Step t of the encoder LSTM
-        reads row order[t]."""
+        reads row order[t]; order i32 (T,) for the batch or (B, T), one per sequence."""
         P = self._prepare()
         B, rows, D = rows32.shape
         dev = rows32.device

@@ -92,6 +92,9 @@ PROTOTYPES = {
     "eend_room_limits": [_vp, _vp, _vp, _vp],
     "eend_lstm_ok": [_i, _i, _i],
     "eend_lstm_f32": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "eend_lstm_orders_f32": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "eend_stb_center_f32": [_vp, _vp, _i, _i, _i, _i, _i, _vp],
+    "eend_stb_track_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
     "eend_eda_count_f32": [_vp, _vp, _vp, _f, _vp, _vp, _i, _i, _vp],
     "eend_eda_head_f32": [_vp, _i, _vp, _vp, _i, _i, _i, _vp],
     "eend_pit_cost_f64": [_vp, _vp, _i, _i, _i, _vp, _vp],

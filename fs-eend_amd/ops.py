@@ -539,7 +539,8 @@ def lstm_ok(B, T, hidden):
 
 def lstm(G, order, bias, w_hh, h0, c0, hT, cT, h_all, B, T):
     """Single-layer LSTM recurrence (lstm.hip).  G f32 (B, g_rows, 1024) input pre-activations, read at row order[t] in step t, or None
-    = zero input (pre-activation = bias f32 (1024,) = b_ih + b_hh); order i32 (T,) or None = identity; w_hh f32 (1024, 256); h0 / c0
+    = zero input (pre-activation = bias f32 (1024,) = b_ih + b_hh); order i32 (T,) shared by the batch, (B, T) one per sequence
+    (eend_lstm_orders_f32, the same kernel), or None = identity; w_hh f32 (1024, 256); h0 / c0
     f32 (B, 256), both or neither; hT / cT f32 (B, 256); h_all f32 (B, T, 256) or None."""
     L = _lib.load()
     for n, t in (("G", G), ("bias", bias), ("w_hh", w_hh), ("h0", h0), ("c0", c0), ("hT", hT), ("cT", cT), ("h_all", h_all)):
@@ -555,12 +556,19 @@ def lstm(G, order, bias, w_hh, h0, c0, hT, cT, h_all, B, T):
         g_rows = G.shape[1]
     elif bias is None or bias.numel() != 4 * hidden:
         raise _lib.EendHipError("lstm: zero input needs the bias sum (4 * hidden,)")
-    if order is not None and order.numel() != T:
-        raise _lib.EendHipError("lstm: order must have T entries")
+    per_seq = order is not None and order.dim() == 2
+    if order is not None and (tuple(order.shape) != (B, T) if per_seq else order.numel() != T):
+        raise _lib.EendHipError("lstm: order must have T entries, or be (B, T)")
+    if per_seq and G is None:
+        raise _lib.EendHipError("lstm: an order per sequence needs G")
     for n, t, want in (("h0", h0, B * hidden), ("c0", c0, B * hidden), ("hT", hT, B * hidden), ("cT", cT, B * hidden),
                        ("h_all", h_all, B * T * hidden)):
         if t is not None and t.numel() != want:
             raise _lib.EendHipError(f"lstm: {n} has {t.numel()} elements, expected {want}")
+    if per_seq:
+        _lib.check(L.eend_lstm_orders_f32(_p(G), g_rows, _p(order), _p(w_hh), _p(h0), _p(c0), _p(hT), _p(cT), _p(h_all), B, T, hidden,
+                                          _stream()), "eend_lstm_orders_f32")
+        return
     _lib.check(L.eend_lstm_f32(_p(G), g_rows, _p(order), _p(bias), _p(w_hh), _p(h0), _p(c0), _p(hT), _p(cT), _p(h_all), B, T, hidden,
                                _stream()), "eend_lstm_f32")
 
@@ -585,6 +593,40 @@ def eda_head(emb32, attractors, logits, T):
     if emb32.dim() != 3 or emb32.shape[0] != B or emb32.shape[2] != 256 or D != 256 or logits.numel() != B * T * C:
         raise _lib.EendHipError("eda_head: emb (B, rows, 256), attractors (B, C, 256), logits (B, T, C)")
     _lib.check(L.eend_eda_head_f32(_p(emb32), emb32.shape[1], _p(attractors), _p(logits), B, T, C, _stream()), "eend_eda_head_f32")
+
+
+STB_DESC_WORDS, STB_MAX_ROWS, STB_MAX_FEATURES = 12, 4096, 512
+STB_POLICIES = {"kld": 0, "fifo": 1}
+
+
+def _stb_args(desc, B, T, F):
+    _chk(desc, torch.int64, "desc")
+    if tuple(desc.shape) != (B, STB_DESC_WORDS):
+        raise _lib.EendHipError(f"stb: desc must be i64 (B, {STB_DESC_WORDS})")
+
+
+def stb_center(desc, out, buf_size, blk_size):
+    """out f32 (B, T, F) = the rows [x_buf; x_i] of each descriptor minus their column mean (stb.hip, eend_stb_center_f32)."""
+    L = _lib.load()
+    _chk(out, F32, "out")
+    B, T, F = out.shape
+    _stb_args(desc, B, T, F)
+    _lib.check(L.eend_stb_center_f32(_p(desc), _p(out), B, T, F, int(buf_size), int(blk_size), _stream()), "eend_stb_center_f32")
+
+
+def stb_track(logits, count, xc, desc, perm_out, sel_out, buf_size, blk_size, policy):
+    """Everything of an STB block after the head (stb.hip, eend_stb_track_f32): logits f32 (B, T, 15), count i32 (B,), xc f32 (B, T, F),
+    desc i64 (B, 12); perm_out i32 (B, 15) / sel_out i32 (B, buf_size) or None; policy 0 = kld, 1 = fifo."""
+    L = _lib.load()
+    _chk(logits, F32, "logits"); _chk(count, torch.int32, "count"); _chk(xc, F32, "xc")
+    _chk(perm_out, torch.int32, "perm_out"); _chk(sel_out, torch.int32, "sel_out")
+    B, T, F = xc.shape
+    _stb_args(desc, B, T, F)
+    if tuple(logits.shape) != (B, T, 15) or count.numel() != B or (perm_out is not None and perm_out.numel() != B * 15) or \
+            (sel_out is not None and sel_out.numel() != B * int(buf_size)):
+        raise _lib.EendHipError("stb_track: logits (B, T, 15), count (B,), perm_out (B, 15), sel_out (B, buf_size)")
+    _lib.check(L.eend_stb_track_f32(_p(logits), _p(count), _p(xc), _p(desc), _p(perm_out), _p(sel_out), B, T, F, int(buf_size),
+                                    int(blk_size), int(policy), _stream()), "eend_stb_track_f32")
 
 
 def retention_step(qkvg16, kv_state, scale_in, scale_out, out16, N, H, gn_eps=1e-6):

@@ -587,6 +587,13 @@ int eend_lstm_ok(int B, int T, int hidden);
 int eend_lstm_f32(const float* G, int g_rows, const int* order, const float* bias, const float* W_hh, const float* h0, const float* c0,
                   float* hT, float* cT, float* h_all, int B, int T, int hidden, void* stream);
 
+/* eend_lstm_f32 with one frame order per sequence: order i32 [B][T], row b a permutation of 0 .. T-1 read by sequence b alone, so
+ * that sequences of different streams share a launch and none depends on its batch mates.  The same kernel as eend_lstm_f32 (which
+ * passes an order stride of 0); with B equal rows the two entries give the same bits.  G must be given (an order over a zero input
+ * means nothing).  EEND_EINVAL: as eend_lstm_f32, and a NULL G or order. */
+int eend_lstm_orders_f32(const float* G, int g_rows, const int* order, const float* W_hh, const float* h0, const float* c0, float* hT,
+                         float* cT, float* h_all, int B, int T, int hidden, void* stream);
+
 /* probs[b][c] = sigmoid(attractors[b][c] . w + bias[0]) (model :106, `counter` is Linear(256, 1)) and, where count is given,
  * count[b] = the first c with probs[b][c] < th, C if there is none: the speaker count of model :72-73 per sequence.
  * attractors f32 [B][C][256], w f32 [256], bias f32 [1], probs f32 [B][C], count i32 [B] or NULL; 1 <= C <= 16. */
@@ -596,6 +603,51 @@ int eend_eda_count_f32(const float* attractors, const float* w, const float* bia
 /* logits[b][t][c] = emb[b][t] . attractors[b][c] (the torch.bmm of model :66) over all C columns.  emb f32 [B][emb_rows][256] with
  * emb_rows >= T (a slab: rows t >= T are never read), attractors f32 [B][C][256], logits f32 [B][T][C]; 1 <= C <= 16, B <= 65535. */
 int eend_eda_head_f32(const float* emb, int emb_rows, const float* attractors, float* logits, int B, int T, int C, void* stream);
+
+/* ---- block-online EEND-EDA with a speaker-tracing buffer, STB (FS-EEND/train/tfm_STB.py:147-204; find_best_perm, cal_cor, upd_buf,
+ * upd_buf_FIFO of train/utils/utils.py) ----
+ *
+ * Both entries read one descriptor of 12 64-bit words per sequence, desc i64 [B][12] in device memory:
+ *   0 x_buf   f32 [L][F]   the stream's buffered feature rows (the current half of its ping-pong buffer); unread when L = 0
+ *   1 L       buffered rows, 0 for a stream's first block
+ *   2 x_i     f32 [n][F]   the new block's raw rows
+ *   3 n       rows of the block; L + n = T, the T of the call
+ *   4 y_buf   f32 [L][15]  the tracked posteriors of the buffered rows, zero beyond the tracked width
+ *   5 x_buf'  f32 [min(T, buf_size)][F]   the OTHER half of the buffer, written; never the half of word 0
+ *   6 y_buf'  f32 [min(T, buf_size)][15]  likewise
+ *   7 width   i32 [1]      the tracked width S: read (ignored when L = 0), then overwritten with the new width
+ *   8 y_i     f32 [n][15]  the emitted block, written
+ *   9 k       the block index and 10 seed, the stream's 32-bit seed: the counters of the draw;  11 unused
+ * A kernel forces L into [max(0, T - blk_size), min(buf_size, T - 1)] and takes n = T - L, so that a wrong descriptor cannot make
+ * it leave buffers of the stated sizes.  Stateless, stream-ordered, nothing allocated, the host not waited for.
+ * EEND_EINVAL (before any launch): a NULL pointer, B < 1, T < 1, F < 1 or F > 512, blk_size < 1, blk_size > buf_size,
+ * buf_size + blk_size > 4096, T > buf_size + blk_size, an unknown policy. */
+
+/* out f32 [B][T][F]: rows [x_buf; x_i] of sequence b minus their column mean (tfm_STB.py:168, :177-178).  The column sums are
+ * float64: thread r of 16 adds rows r, r + 16, .. in ascending order and the 16 partial sums are added in the order r = 0 .. 15;
+ * out = (float)((double)x - sum / T).  A sequence's bits depend on its own rows only. */
+int eend_stb_center_f32(const long* desc, float* out, int B, int T, int F, int buf_size, int blk_size, void* stream);
+
+/* Everything of a block after the head, one workgroup per sequence.  logits f32 [B][T][15] (eend_eda_head_f32 on the centred rows),
+ * count i32 [B] (eend_eda_count_f32, forced into 0 .. 15), xc f32 [B][T][F] the centred rows (eend_stb_center_f32; read for L = 0 only).
+ *   p       = (float) sigmoid in float64 of logits[:, :c];  S' = max(S, c);  columns beyond c or S are zero
+ *   L = 0   y_i = p, the buffer takes the centred rows and p, the width becomes c (tfm_STB.py:165-172)
+ *   L > 0   corr[r][q] = cov / (sqrt(var_r) sqrt(var_q) + 1e-6) of tracked column r and predicted column q over the L buffer rows, two
+ *           passes, float64 sums in ascending row order (cal_cor);  perm = the assignment of largest total correlation
+ *           (csrc/assign.h): only its pairs of a tracked row r < S with a predicted column q < c are kept, the other rows take the
+ *           columns left over in ascending order (padding rows and columns have correlation 0 with everything, so this is an
+ *           optimum and the choice among equal ones is fixed);  y_i[:, r] = p[L:, perm[r]]
+ *   buffer  T <= buf_size: all T rows of [x_buf; x_i] (raw) and [y_buf; y_i].  Otherwise buf_size of them in ascending time order:
+ *           policy 1 (fifo) the last ones (upd_buf_FIFO); policy 0 (kld, upd_buf) p_t = y_t / sum_c y_t (0 where the sum is 0), zeros
+ *           set to 1e-6, w_t = sum_c p log(p S') over the S' columns, negative set to 0, then 0 set to 1e-6 (w = 1 when S' = 0); the
+ *           rows of the buf_size largest keys  key_t = w_t / -ln(u_t),  u_t = (h + 0.5) 2^-32,  h = mix(mix(mix(seed ^ 0x9E3779B9) + k) + t)
+ *           in 32-bit arithmetic,  mix(x): x ^= x >> 16, x *= 0x85EBCA6B, x ^= x >> 13, x *= 0xC2B2AE35, x ^= x >> 16  (the
+ *           exponential race: a draw of buf_size rows without replacement with probability proportional to w); on equal keys the
+ *           lower t wins.  w and the keys are float64 from the f32 posteriors.
+ * perm_out i32 [B][15] or NULL: perm (identity where nothing was assigned).  sel_out i32 [B][buf_size] or NULL: the kept rows' indices
+ * into [x_buf; x_i], the first min(T, buf_size) entries of a row written. */
+int eend_stb_track_f32(const float* logits, const int* count, const float* xc, const long* desc, int* perm_out, int* sel_out, int B,
+                       int T, int F, int buf_size, int blk_size, int policy, void* stream);
 
 /* ---- permutation-invariant label assignment (FS-EEND/train/utils/loss.py:257-327 batch_pit_n_speaker_loss;
  * LS-EEND/train/utils/loss.py:350-379 pit_loss_multispk) ---- */
