@@ -603,6 +603,41 @@ int eend_eda_head_f32(const float* emb, int emb_rows, const float* attractors, f
     return eend_launch_eda_head(emb, emb_rows, attractors, logits, B, T, C, (hipStream_t)stream);
 }
 
+int eend_lstm_train_f32(const float* G, int g_rows, const int* order, int order_stride, const float* bias, const float* W_hh,
+                        const float* h0, const float* c0, float* hT, float* cT, float* h_all, float* gates, float* c_all, float* h_prev,
+                        int hp_rows, int B, int T, int hidden, void* stream) {
+    return eend_launch_lstm_train(G, g_rows, order, bias, W_hh, h0, c0, hT, cT, h_all, gates, c_all, h_prev, hp_rows, B, T, hidden, order_stride,
+                                  (hipStream_t)stream);
+}
+
+int eend_lstm_bwd_f32(const float* gates, const float* c_all, const float* c0, const float* W_hh, const float* dh_all, const float* dhT,
+                      const float* dcT, const int* order, int order_stride, float* dG, int g_rows, float* dh0, float* dc0, int B, int T,
+                      int hidden, void* stream) {
+    return eend_launch_lstm_bwd(gates, c_all, c0, W_hh, dh_all, dhT, dcT, order, order_stride, dG, g_rows, dh0, dc0, B, T, hidden,
+                                (hipStream_t)stream);
+}
+
+long eend_wgrad_f32_workspace_bytes(int N, int K, int with_bias) { return eend_wgrad_f32_ws_floats(N, K, with_bias) * (long)sizeof(float); }
+
+int eend_wgrad_f32(const float* dY, int ldy, const float* X, int ldx, long M, int N, int K, float* ws, long ws_bytes, float* dW, float* db,
+                   void* stream) {
+    return eend_launch_wgrad_f32(dY, ldy, X, ldx, M, N, K, ws, ws_bytes, dW, db, (hipStream_t)stream);
+}
+
+int eend_eda_count_loss_f32(const float* attractors, const float* w, const float* bias, const int* n_spk, float* loss, float* dattractors,
+                            float* dw, float* dbias, float* ws, long ws_bytes, int B, int C, void* stream) {
+    return eend_launch_eda_count_loss(attractors, w, bias, n_spk, loss, dattractors, dw, dbias, ws, ws_bytes, B, C, (hipStream_t)stream);
+}
+
+long eend_eda_count_loss_workspace_bytes(int B) { return eend_eda_count_loss_ws_floats(B) * (long)sizeof(float); }
+
+long eend_eda_head_bwd_workspace_bytes(int B, int T, int C) { return eend_eda_head_bwd_ws_floats(B, T, C) * (long)sizeof(float); }
+
+int eend_eda_head_bwd_f32(const float* dlogits, const float* emb, int emb_rows, const float* attractors, float* dattractors, float* demb,
+                          float* ws, long ws_bytes, int B, int T, int C, void* stream) {
+    return eend_launch_eda_head_bwd(dlogits, emb, emb_rows, attractors, dattractors, demb, ws, ws_bytes, B, T, C, (hipStream_t)stream);
+}
+
 int eend_stb_center_f32(const long* desc, float* out, int B, int T, int F, int buf_size, int blk_size, void* stream) {
     return eend_launch_stb_center(desc, out, B, T, F, buf_size, blk_size, (hipStream_t)stream);
 }

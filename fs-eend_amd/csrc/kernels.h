@@ -177,6 +177,26 @@ int eend_launch_lstm(const float* G, int g_rows, const int* order, const float* 
 int eend_launch_eda_count(const float* attr, const float* w, const float* bias, float th, float* probs, int* count, int B, int C,
                           hipStream_t stream);
 int eend_launch_eda_head(const float* emb, int emb_rows, const float* attr, float* logits, int B, int T, int C, hipStream_t stream);
+// the differentiable attractor path (lstm.hip, wgrad_f32.hip): floats per sequence of the counter loss's workspace, frames per
+// partial of the head backward, row slices of the exact-f32 weight gradient (fixed: the bits do not depend on the device)
+#define EDA_COUNT_LOSS_WS 258
+#define EDA_HEAD_BWD_TILE 64
+#define WGRAD_F32_SLICES 16
+int eend_launch_lstm_train(const float* G, int g_rows, const int* order, const float* bias, const float* Whh, const float* h0,
+                           const float* c0, float* hT, float* cT, float* h_all, float* gates, float* c_all, float* h_prev, int hp_rows,
+                           int B, int T, int hidden, int order_stride, hipStream_t stream);
+int eend_launch_lstm_bwd(const float* gates, const float* c_all, const float* c0, const float* Whh, const float* dh_all, const float* dhT,
+                         const float* dcT, const int* order, int order_stride, float* dG, int g_rows, float* dh0, float* dc0, int B, int T,
+                         int hidden, hipStream_t stream);
+int eend_launch_eda_count_loss(const float* attr, const float* w, const float* bias, const int* n_spk, float* loss, float* dattr,
+                               float* dw, float* dbias, float* ws, long ws_bytes, int B, int C, hipStream_t stream);
+long eend_eda_count_loss_ws_floats(int B);
+long eend_eda_head_bwd_ws_floats(int B, int T, int C);
+int eend_launch_eda_head_bwd(const float* dlogits, const float* emb, int emb_rows, const float* attr, float* dattr, float* demb, float* ws,
+                             long ws_bytes, int B, int T, int C, hipStream_t stream);
+long eend_wgrad_f32_ws_floats(int N, int K, int with_bias);
+int eend_launch_wgrad_f32(const float* dY, int ldy, const float* X, int ldx, long M, int N, int K, float* ws, long ws_bytes, float* dW,
+                          float* db, hipStream_t stream);
 
 // speaker-tracing buffer of block-online EEND-EDA (stb.hip): tracked columns, the most rows of buffer + block, the widest feature
 // row, the 64-bit words of a sequence's descriptor and the buffer policies

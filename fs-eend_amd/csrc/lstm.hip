@@ -1,6 +1,9 @@
 // The attractor path of the offline EEND-EDA baseline (FS-EEND/nnet/model/offl_tfm_enc_lstm_enc_dec.py:79-107): a single-layer
 // LSTM recurrence (eend_lstm_f32, eend_lstm_orders_f32), the attractor-existence counter with the speaker count taken from it (eend_eda_count_f32) and the
-// embedding . attractor head (eend_eda_head_f32).  The contracts are in include/eend_hip.h; DESIGN 12 has the reasoning and the times.
+// embedding . attractor head (eend_eda_head_f32); and what makes that path differentiable (model :109-127): the recurrence that keeps
+// its gates and states (eend_lstm_train_f32), its backward (eend_lstm_bwd_f32), the attractor-existence loss with its gradients
+// (eend_eda_count_loss_f32) and the head's backward (eend_eda_head_bwd_f32); the weight gradients are wgrad_f32.hip.  The contracts
+// are in include/eend_hip.h; DESIGN 12 has the reasoning and the times.
 //
 // eend_lstm_f32.  One workgroup of 16 waves owns one sequence from its first step to its last; workgroups never talk to each other
 // (no flags, no spins, no cooperative launch) and every loop is bounded by T.  W_hh stays f32 in global memory and is re-read from L2
@@ -31,11 +34,16 @@ typedef __attribute__((address_space(1))) f32x4 gf32x4;
 // finite for every finite x: exp overflows to +inf only where 1 / (1 + inf) = 0 is the limit
 DEV float lstm_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
 
+// TRAIN: the same steps, and what the backward needs of every step (eend_lstm_train_f32): the four gates after their functions and the
+// cell state in step order, the hidden state that ENTERS step t at the row of G the step read (hp_rows rows per sequence), which is
+// the row the step's pre-activation gradient goes to, so that dW_hh = dG^T h_prev needs no gather.
+template <bool TRAIN>
 __global__ __launch_bounds__(LNT) void lstm_seq_kernel(const float* __restrict__ G, int g_rows, const int* __restrict__ order,
                                                        const float* __restrict__ bias, const float* __restrict__ Whh,
                                                        const float* __restrict__ h0, const float* __restrict__ c0,
                                                        float* __restrict__ hT, float* __restrict__ cT, float* __restrict__ h_all, int T,
-                                                       int order_stride) {
+                                                       int order_stride, float* __restrict__ gates, float* __restrict__ c_all,
+                                                       float* __restrict__ h_prev, int hp_rows) {
     __shared__ __attribute__((aligned(16))) float hbuf[2][LH];
     const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (order) order += (size_t)b * order_stride;                 // 0: one order for the batch, T: one per sequence
@@ -58,10 +66,12 @@ __global__ __launch_bounds__(LNT) void lstm_seq_kernel(const float* __restrict__
     for (int t = 0; t < T; ++t) {
         const int cur = t & 1;
         float pre = bias_r;
+        int row = t;
         if (Gb) {                                                 // issued first: lands behind the weight stream
             int o = order ? order[t] : t;
             o = o < 0 ? 0 : (o >= T ? T - 1 : o);                 // the host validates the permutation; never read outside G
             pre = Gb[(size_t)o * LG];
+            row = o;
         }
         const f32x4 hv = *(const f32x4*)&hbuf[cur][lane * 4];
         // rows r and r + 32 together, so that the butterfly's first exchange retires them at once: 32 partials stay live, not 64.
@@ -105,8 +115,20 @@ __global__ __launch_bounds__(LNT) void lstm_seq_kernel(const float* __restrict__
         const float gg = __shfl(pre, (lane & 15) + 32, 64);
         const float go = __shfl(pre, (lane & 15) + 48, 64);
         if (lane < 16) {
-            c = lstm_sigmoid(gf) * c + lstm_sigmoid(pre) * tanhf(gg);
-            h = lstm_sigmoid(go) * tanhf(c);
+            if constexpr (TRAIN) {
+                const float si = lstm_sigmoid(pre), sf = lstm_sigmoid(gf), tg = tanhf(gg), so = lstm_sigmoid(go);
+                if (h_prev) h_prev[((size_t)b * hp_rows + row) * LH + unit] = h;
+                c = sf * c + si * tg;
+                h = so * tanhf(c);
+                if (gates) {
+                    float* gt = gates + ((size_t)b * T + t) * LG + unit;
+                    gt[0] = si; gt[LH] = sf; gt[2 * LH] = tg; gt[3 * LH] = so;
+                }
+                if (c_all) c_all[((size_t)b * T + t) * LH + unit] = c;
+            } else {
+                c = lstm_sigmoid(gf) * c + lstm_sigmoid(pre) * tanhf(gg);
+                h = lstm_sigmoid(go) * tanhf(c);
+            }
             hbuf[cur ^ 1][unit] = h;
             if (h_all) h_all[((size_t)b * T + t) * LH + unit] = h;
         }
@@ -115,6 +137,105 @@ __global__ __launch_bounds__(LNT) void lstm_seq_kernel(const float* __restrict__
     if (lane < 16) {
         hT[(size_t)b * LH + unit] = h;
         cT[(size_t)b * LH + unit] = c;
+    }
+}
+
+// eend_lstm_bwd_f32: backpropagation through time of the recurrence above, again one workgroup of 16 waves per sequence, from step
+// T - 1 down to 0, everything f32.  A step has two halves and two barriers:
+//   units  threads 0 .. 255 own one hidden unit each and keep its dc in a register: dh = dh_all[t] + the recurrent part (the 16 wave
+//          partials of the step before, summed in wave order), the four pre-activation gradients into LDS and into dG at the row of G
+//          the forward step read;
+//   W^T    wave w owns gate rows 64 w .. 64 w + 63: lane l loads its float4 of each row (the forward's coalesced 1-KiB row requests,
+//          1 MiB of W_hh from L2 per step) and accumulates four column partials of W_hh^T dpre against the broadcast dpre[r], r
+//          ascending; the 16 x 256 partials go to LDS.
+// No cross-lane reduction is needed (the forward's butterfly sums over the columns a lane holds; here a lane's columns are the outputs).
+// The order of every sum is fixed by (row, wave), so a sequence's bits do not depend on its batch mates or on the run.  The units'
+// operands of step t - 1 are requested before the weight stream of step t, so their latency hides behind it.
+constexpr int BWD_LOADS_IN_FLIGHT = 16;  // rows per load batch: 16 float4 loads = 64 registers
+
+__global__ __launch_bounds__(LNT) void lstm_bwd_kernel(const float* __restrict__ gates, const float* __restrict__ c_all,
+                                                       const float* __restrict__ c0, const float* __restrict__ Whh,
+                                                       const float* __restrict__ dh_all, const float* __restrict__ dhT,
+                                                       const float* __restrict__ dcT, const int* __restrict__ order, int order_stride,
+                                                       float* __restrict__ dG, int g_rows, float* __restrict__ dh0,
+                                                       float* __restrict__ dc0, int T) {
+    __shared__ __attribute__((aligned(16))) float dpre[LG];
+    __shared__ __attribute__((aligned(16))) float part[16][LH];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (order) order += (size_t)b * order_stride;
+    const bool owner = tid < LH;                                  // waves 0 .. 3: wave-uniform
+    const int u = tid & (LH - 1);
+    for (int i = tid; i < 16 * LH; i += LNT) part[i / LH][i % LH] = (i < LH && dhT) ? dhT[(size_t)b * LH + i] : 0.f;
+    float dc = (owner && dcT) ? dcT[(size_t)b * LH + u] : 0.f;
+    const gfloat* wwave = (const gfloat*)Whh + (size_t)__builtin_amdgcn_readfirstlane(wave) * 64 * LH;
+    const unsigned loff = lane * 4;
+    // the operands of the unit half, one step ahead
+    float gi = 0.f, gf = 0.f, gg = 0.f, go = 0.f, ct = 0.f, cp = 0.f, du = 0.f;
+    auto fetch = [&](int t) {
+        const float* gt = gates + ((size_t)b * T + t) * LG + u;
+        gi = gt[0]; gf = gt[LH]; gg = gt[2 * LH]; go = gt[3 * LH];
+        ct = c_all[((size_t)b * T + t) * LH + u];
+        cp = t > 0 ? c_all[((size_t)b * T + t - 1) * LH + u] : (c0 ? c0[(size_t)b * LH + u] : 0.f);
+        du = dh_all ? dh_all[((size_t)b * T + t) * LH + u] : 0.f;
+    };
+    if (owner) fetch(T - 1);
+    __syncthreads();
+
+    for (int t = T - 1; t >= 0; --t) {
+        if (owner) {
+            float rec = part[0][u];
+#pragma unroll
+            for (int w = 1; w < 16; ++w) rec += part[w][u];
+            const float dh = du + rec;
+            const float tc = tanhf(ct);
+            dc += dh * go * (1.0f - tc * tc);
+            const float d_i = dc * gg * (gi * (1.0f - gi));
+            const float d_f = dc * cp * (gf * (1.0f - gf));
+            const float d_g = dc * gi * (1.0f - gg * gg);
+            const float d_o = dh * tc * (go * (1.0f - go));
+            dc *= gf;
+            dpre[u] = d_i; dpre[LH + u] = d_f; dpre[2 * LH + u] = d_g; dpre[3 * LH + u] = d_o;
+            int o = order ? order[t] : t;
+            o = o < 0 ? 0 : (o >= T ? T - 1 : o);                 // as the forward: never outside the T rows
+            float* dg = dG + ((size_t)b * g_rows + o) * LG + u;
+            dg[0] = d_i; dg[LH] = d_f; dg[2 * LH] = d_g; dg[3 * LH] = d_o;
+            if (t > 0) fetch(t - 1);                              // lands behind the weight stream below
+        }
+        __syncthreads();
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        const gfloat* wt = wwave;
+        asm volatile("" : "+s"(wt));      // opaque per step: the row addresses are scalar adds here, not hoisted register pairs
+        const float* dw = &dpre[wave * 64];
+#pragma unroll
+        for (int r0 = 0; r0 < 64; r0 += BWD_LOADS_IN_FLIGHT) {
+            f32x4 wv[BWD_LOADS_IN_FLIGHT];
+#pragma unroll
+            for (int j = 0; j < BWD_LOADS_IN_FLIGHT; ++j) wv[j] = *(const gf32x4*)(wt + (r0 + j) * LH + loff);
+#pragma unroll
+            for (int j = 0; j < BWD_LOADS_IN_FLIGHT; j += 4) {
+                const f32x4 d = *(const f32x4*)&dw[r0 + j];       // one address for the wave: a broadcast read
+                const float ds[4] = {d.x, d.y, d.z, d.w};
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    acc.x = fmaf(ds[q], wv[j + q].x, acc.x);
+                    acc.y = fmaf(ds[q], wv[j + q].y, acc.y);
+                    acc.z = fmaf(ds[q], wv[j + q].z, acc.z);
+                    acc.w = fmaf(ds[q], wv[j + q].w, acc.w);
+                }
+            }
+            // the next batch's loads stay below this batch's sums: all 64 rows at once are 256 registers, which spill
+            asm volatile("" : "+v"(acc.x), "+v"(acc.y), "+v"(acc.z), "+v"(acc.w) : : "memory");
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        *(f32x4*)&part[wave][lane * 4] = acc;
+        __syncthreads();
+    }
+    if (owner) {
+        float rec = part[0][u];
+#pragma unroll
+        for (int w = 1; w < 16; ++w) rec += part[w][u];
+        dh0[(size_t)b * LH + u] = rec;
+        dc0[(size_t)b * LH + u] = dc;
     }
 }
 
@@ -169,6 +290,125 @@ __global__ __launch_bounds__(256) void eda_head_kernel(const float* __restrict__
     }
 }
 
+// eend_eda_count_loss_f32, first pass: one workgroup per sequence.  A wave per attractor forms the counter's logit, its BCE term and
+// d loss / d logit (already divided by the element count of the whole batch); then thread j writes column j of d attractors and
+// of the sequence's part of dw (c ascending).  ws [B][EDA_COUNT_LOSS_WS]: dw part (256), loss part, dbias part.
+DEV int eda_clamp_n(int n, int C) { return n < 0 ? 0 : (n > C - 1 ? C - 1 : n); }
+
+__global__ __launch_bounds__(256) void eda_count_loss_kernel(const float* __restrict__ attr, const float* __restrict__ w,
+                                                             const float* __restrict__ bias, const int* __restrict__ n_spk,
+                                                             float* __restrict__ dattr, float* __restrict__ ws, int B, int C) {
+    __shared__ float dz[EDA_MAX_ATTRACTORS], le[EDA_MAX_ATTRACTORS];
+    __shared__ int ntot;
+    const int b = blockIdx.x, j = threadIdx.x, lane = j & 63, wave = j >> 6;
+    if (j == 0) {
+        int n = 0;
+        for (int i = 0; i < B; ++i) n += eda_clamp_n(n_spk[i], C) + 1;
+        ntot = n;
+    }
+    const int nb = eda_clamp_n(n_spk[b], C);
+    const f32x4 wv = *(const f32x4*)(w + lane * 4);
+    __syncthreads();
+    const float inv = 1.0f / (float)ntot;
+    for (int cidx = wave; cidx < C; cidx += 4) {
+        float l = 0.f, g = 0.f;
+        if (cidx <= nb) {                                         // wave-uniform: labels [1] * n_b + [0], nothing beyond
+            const f32x4 a = *(const f32x4*)(attr + ((size_t)b * C + cidx) * LH + lane * 4);
+            const float z = wave_sum(fmaf(a.w, wv.w, fmaf(a.z, wv.z, fmaf(a.y, wv.y, a.x * wv.x)))) + bias[0];
+            const float y = cidx < nb ? 1.f : 0.f;
+            l = fmaxf(z, 0.f) - z * y + log1pf(expf(-fabsf(z)));   // BCE with logits, finite for every finite z
+            g = (lstm_sigmoid(z) - y) * inv;
+        }
+        if (lane == 0) { dz[cidx] = g; le[cidx] = l; }
+    }
+    __syncthreads();
+    if (dattr) {                                                  // NULL: the loss alone
+        const float wj = w[j];
+        float dwp = 0.f;
+        for (int cidx = 0; cidx < C; ++cidx) {
+            const float g = dz[cidx];
+            const size_t at = ((size_t)b * C + cidx) * LH + j;
+            dattr[at] = g * wj;
+            dwp = fmaf(g, attr[at], dwp);
+        }
+        ws[(size_t)b * EDA_COUNT_LOSS_WS + j] = dwp;
+    }
+    if (j == 0) {
+        float ls = 0.f, db = 0.f;
+        for (int cidx = 0; cidx < C; ++cidx) { ls += le[cidx]; db += dz[cidx]; }
+        ws[(size_t)b * EDA_COUNT_LOSS_WS + LH] = ls;
+        ws[(size_t)b * EDA_COUNT_LOSS_WS + LH + 1] = db;
+    }
+}
+
+// second pass, one workgroup: the sequences' parts summed in batch order
+__global__ __launch_bounds__(256) void eda_count_loss_reduce_kernel(const float* __restrict__ ws, const int* __restrict__ n_spk,
+                                                                    float* __restrict__ loss, float* __restrict__ dw,
+                                                                    float* __restrict__ dbias, int B, int C) {
+    const int j = threadIdx.x;
+    if (dw) {
+        float s = 0.f;
+        for (int b = 0; b < B; ++b) s += ws[(size_t)b * EDA_COUNT_LOSS_WS + j];
+        dw[j] = s;
+    }
+    if (j == 0) {
+        int n = 0;
+        float ls = 0.f, db = 0.f;
+        for (int b = 0; b < B; ++b) {
+            n += eda_clamp_n(n_spk[b], C) + 1;
+            ls += ws[(size_t)b * EDA_COUNT_LOSS_WS + LH];
+            db += ws[(size_t)b * EDA_COUNT_LOSS_WS + LH + 1];
+        }
+        loss[0] = ls / (float)n;
+        if (dbias) dbias[0] = db;
+    }
+}
+
+// eend_eda_head_bwd_f32: EDA_HEAD_BWD_TILE frames of one sequence per workgroup, thread j owns column j of emb and of the attractors.
+// d emb of a frame is complete here; d attractors is the tile's part (frames ascending), summed over the tiles in order afterwards.
+__global__ __launch_bounds__(256) void eda_head_bwd_kernel(const float* __restrict__ dlogits, const float* __restrict__ emb, int emb_rows,
+                                                           const float* __restrict__ attr, float* __restrict__ part,
+                                                           float* __restrict__ demb, int T, int C) {
+    __shared__ float dl[EDA_HEAD_BWD_TILE][EDA_MAX_ATTRACTORS];
+    const int b = blockIdx.y, t0 = blockIdx.x * EDA_HEAD_BWD_TILE, j = threadIdx.x;
+    const int nt = T - t0 < EDA_HEAD_BWD_TILE ? T - t0 : EDA_HEAD_BWD_TILE;
+    for (int i = j; i < EDA_HEAD_BWD_TILE * EDA_MAX_ATTRACTORS; i += 256) {
+        const int r = i / EDA_MAX_ATTRACTORS, cidx = i % EDA_MAX_ATTRACTORS;
+        dl[r][cidx] = (r < nt && cidx < C) ? dlogits[((size_t)b * T + t0 + r) * C + cidx] : 0.f;   // zeros leave a sum as it is
+    }
+    float a[EDA_MAX_ATTRACTORS], acc[EDA_MAX_ATTRACTORS];
+#pragma unroll
+    for (int cidx = 0; cidx < EDA_MAX_ATTRACTORS; ++cidx) {
+        a[cidx] = cidx < C ? attr[((size_t)b * C + cidx) * LH + j] : 0.f;
+        acc[cidx] = 0.f;
+    }
+    __syncthreads();
+    for (int r = 0; r < nt; ++r) {
+        const float e = emb[((size_t)b * emb_rows + t0 + r) * LH + j];
+        float de = 0.f;
+#pragma unroll
+        for (int cidx = 0; cidx < EDA_MAX_ATTRACTORS; ++cidx) {
+            const float d = dl[r][cidx];                          // one address for the workgroup: a broadcast read
+            acc[cidx] = fmaf(d, e, acc[cidx]);
+            de = fmaf(d, a[cidx], de);
+        }
+        if (demb) demb[((size_t)b * T + t0 + r) * LH + j] = de;
+    }
+    if (part) {
+#pragma unroll
+        for (int cidx = 0; cidx < EDA_MAX_ATTRACTORS; ++cidx)
+            if (cidx < C) part[(((size_t)b * gridDim.x + blockIdx.x) * C + cidx) * LH + j] = acc[cidx];
+    }
+}
+
+__global__ __launch_bounds__(256) void eda_head_bwd_reduce_kernel(const float* __restrict__ part, float* __restrict__ dattr, int ntiles,
+                                                                  int C) {
+    const int b = blockIdx.x / C, cidx = blockIdx.x % C, j = threadIdx.x;
+    float s = 0.f;
+    for (int i = 0; i < ntiles; ++i) s += part[(((size_t)b * ntiles + i) * C + cidx) * LH + j];
+    dattr[(size_t)blockIdx.x * LH + j] = s;
+}
+
 }  // namespace
 
 int eend_lstm_shape_ok(int B, int T, int hidden) { return hidden == LSTM_HIDDEN && T >= 1 && B >= 1; }
@@ -179,8 +419,63 @@ int eend_launch_lstm(const float* G, int g_rows, const int* order, const float* 
     if (order_stride != 0 && (order_stride < T || !order || !G)) return EEND_EINVAL;
     if (G ? g_rows < T : !bias) return EEND_EINVAL;               // rows of G per sequence; zero input needs the bias sum
     if ((h0 == nullptr) != (c0 == nullptr)) return EEND_EINVAL;
-    hipLaunchKernelGGL(lstm_seq_kernel, dim3(B), dim3(LNT), 0, stream, G, g_rows, order, bias, Whh, h0, c0, hT, cT, h_all, T,
-                       order_stride);
+    hipLaunchKernelGGL(lstm_seq_kernel<false>, dim3(B), dim3(LNT), 0, stream, G, g_rows, order, bias, Whh, h0, c0, hT, cT, h_all, T,
+                       order_stride, (float*)nullptr, (float*)nullptr, (float*)nullptr, 0);
+    return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
+}
+
+// the argument rules of eend_launch_lstm; h_prev has hp_rows >= T rows per sequence, its own count: the backward's operands need
+// not be as tall as a padded slab of G
+int eend_launch_lstm_train(const float* G, int g_rows, const int* order, const float* bias, const float* Whh, const float* h0,
+                           const float* c0, float* hT, float* cT, float* h_all, float* gates, float* c_all, float* h_prev, int hp_rows,
+                           int B, int T, int hidden, int order_stride, hipStream_t stream) {
+    if (!eend_lstm_shape_ok(B, T, hidden) || !Whh || !hT || !cT) return EEND_EINVAL;
+    if (order_stride != 0 && (order_stride < T || !order || !G)) return EEND_EINVAL;
+    if (G ? g_rows < T : !bias) return EEND_EINVAL;
+    if (!G && order) return EEND_EINVAL;                          // an order over a zero input means nothing
+    if ((h0 == nullptr) != (c0 == nullptr) || (h_prev && hp_rows < T)) return EEND_EINVAL;
+    hipLaunchKernelGGL(lstm_seq_kernel<true>, dim3(B), dim3(LNT), 0, stream, G, g_rows, order, bias, Whh, h0, c0, hT, cT, h_all, T,
+                       order_stride, gates, c_all, h_prev, hp_rows);
+    return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
+}
+
+int eend_launch_lstm_bwd(const float* gates, const float* c_all, const float* c0, const float* Whh, const float* dh_all, const float* dhT,
+                         const float* dcT, const int* order, int order_stride, float* dG, int g_rows, float* dh0, float* dc0, int B, int T,
+                         int hidden, hipStream_t stream) {
+    if (!eend_lstm_shape_ok(B, T, hidden) || !gates || !c_all || !Whh || !dG || !dh0 || !dc0 || g_rows < T) return EEND_EINVAL;
+    if (!dh_all && !dhT && !dcT) return EEND_EINVAL;              // no upstream gradient at all
+    if (order_stride != 0 && (order_stride < T || !order)) return EEND_EINVAL;
+    hipLaunchKernelGGL(lstm_bwd_kernel, dim3(B), dim3(LNT), 0, stream, gates, c_all, c0, Whh, dh_all, dhT, dcT, order, order_stride, dG,
+                       g_rows, dh0, dc0, T);
+    return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
+}
+
+int eend_launch_eda_count_loss(const float* attr, const float* w, const float* bias, const int* n_spk, float* loss, float* dattr,
+                               float* dw, float* dbias, float* ws, long ws_bytes, int B, int C, hipStream_t stream) {
+    if (B < 1 || C < 1 || C > EDA_MAX_ATTRACTORS || !attr || !w || !bias || !n_spk || !loss || !ws) return EEND_EINVAL;
+    if ((!dattr || !dw || !dbias) && (dattr || dw || dbias)) return EEND_EINVAL;      // the three gradients together, or none
+    if (ws_bytes < eend_eda_count_loss_ws_floats(B) * (long)sizeof(float)) return EEND_EINVAL;
+    hipLaunchKernelGGL(eda_count_loss_kernel, dim3(B), dim3(256), 0, stream, attr, w, bias, n_spk, dattr, ws, B, C);
+    hipLaunchKernelGGL(eda_count_loss_reduce_kernel, dim3(1), dim3(256), 0, stream, ws, n_spk, loss, dw, dbias, B, C);
+    return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
+}
+
+long eend_eda_count_loss_ws_floats(int B) { return B < 1 ? 0 : (long)B * EDA_COUNT_LOSS_WS; }
+
+long eend_eda_head_bwd_ws_floats(int B, int T, int C) {
+    if (B < 1 || T < 1 || C < 1 || C > EDA_MAX_ATTRACTORS) return 0;
+    return (long)B * ((T + EDA_HEAD_BWD_TILE - 1) / EDA_HEAD_BWD_TILE) * C * LSTM_HIDDEN;
+}
+
+int eend_launch_eda_head_bwd(const float* dlogits, const float* emb, int emb_rows, const float* attr, float* dattr, float* demb, float* ws,
+                             long ws_bytes, int B, int T, int C, hipStream_t stream) {
+    if (B < 1 || B > 65535 || T < 1 || emb_rows < T || C < 1 || C > EDA_MAX_ATTRACTORS || !dlogits || !emb || !attr) return EEND_EINVAL;
+    if (!dattr && !demb) return EEND_EINVAL;
+    if (dattr && (!ws || ws_bytes < eend_eda_head_bwd_ws_floats(B, T, C) * (long)sizeof(float))) return EEND_EINVAL;
+    const int ntiles = (T + EDA_HEAD_BWD_TILE - 1) / EDA_HEAD_BWD_TILE;
+    hipLaunchKernelGGL(eda_head_bwd_kernel, dim3(ntiles, B), dim3(256), 0, stream, dlogits, emb, emb_rows, attr, dattr ? ws : nullptr, demb,
+                       T, C);
+    if (dattr) hipLaunchKernelGGL(eda_head_bwd_reduce_kernel, dim3(B * C), dim3(256), 0, stream, ws, dattr, ntiles, C);
     return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
 }
 

@@ -1,4 +1,4 @@
-"""Host-side mirror of the reference's offline EEND-EDA baseline, inference only.
+"""Host-side mirror of the reference's offline EEND-EDA baseline: inference, and a differentiable attractor path.
 
 Public face of ``nnet.model.offl_tfm_enc_lstm_enc_dec`` (reference FS-EEND/nnet/model/offl_tfm_enc_lstm_enc_dec.py): the same class
 names, constructor arguments, attribute tree and ``state_dict`` keys (``enc.encoder.*``, ``enc.encoder_norm.*``,
@@ -18,8 +18,17 @@ The torch.nn modules are parameter containers only; all arithmetic runs in libee
 
 Two quirks of the reference's ``test`` are deliberately not reproduced: with B > 1 it applies the first item's
 count to every later item (here every sequence keeps the columns before its own first p < th), and it raises on a recording where
-no probability is below ``th`` (here all 15 columns are kept).  ``forward``, the attractor loss and the LSTM backward are out of
-scope, as is the Lightning module train/offl_tfm_lstm.py.  The block-online use of this model with a speaker-tracing buffer
+no probability is below ``th`` (here all 15 columns are kept).
+
+Training.  The attractor path is differentiable end to end: ``EncoderDecoderAttractor.forward(xs, n_speakers, order=None)`` is the
+reference's (model :109-127) as a ``torch.autograd.Function`` over eend_lstm_train_f32 (the inference recurrence that also keeps
+gates, cell states and the entering hidden states), eend_eda_count_loss_f32 (the attractor-existence loss and its gradients),
+eend_lstm_bwd_f32 (the recurrence backwards, decoder then encoder) and eend_wgrad_f32 (exact-f32 weight and bias gradients);
+gradients reach ``xs`` and every ``eda.*`` parameter.  ``TransformerEDADiarization.forward(src, tgt, ilens)`` (model :39-52) runs
+it for a FROZEN encoder -- embeddings from the inference kernels, so without dropout, and without a gradient -- with the logits
+behind a second Function (eend_eda_head_f32 / eend_eda_head_bwd_f32).  Not built: the encoder backward of this model (``forward``
+raises NotImplementedError while any ``enc.*`` parameter requires grad), the Lightning module train/offl_tfm_lstm.py, and STB
+training.  The block-online use of this model with a speaker-tracing buffer
 (train/tfm_STB.py) is ``fs_eend_amd.stb.StbSession``: it runs ``_encode`` and ``eda._attractors`` on many streams at once, every
 stream with its own frame order (a (B, T) ``order``).
 """
@@ -29,6 +38,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 from torch import Tensor
+from torch.autograd.function import once_differentiable
 
 from . import ops
 from .fs_model import TransformerEncoder, WorkspaceCache, encoder_layer
@@ -90,8 +100,122 @@ class _EdaWorkspace:
         self.q = self.k = self.vt = None
 
 
+def check_n_speakers(n_speakers, B: int) -> list:
+    """The speaker counts of a batch as a list of B ints in 0 .. MAX_N_SPEAKERS, or ValueError."""
+    try:
+        n = [int(v) for v in n_speakers]
+    except TypeError as e:
+        raise ValueError("n_speakers must be a sequence of integers") from e
+    if len(n) != B or any(v != w for v, w in zip(n, n_speakers)):
+        raise ValueError(f"n_speakers must hold one integer per sequence ({B}), got {list(n_speakers)}")
+    if min(n) < 0 or max(n) > MAX_N_SPEAKERS:
+        raise ValueError(f"n_speakers must lie in 0 .. {MAX_N_SPEAKERS}, got {n}")
+    return n
+
+
+_EDA_PARAMS = ("encoder.weight_ih_l0", "encoder.weight_hh_l0", "encoder.bias_ih_l0", "encoder.bias_hh_l0", "decoder.weight_ih_l0",
+               "decoder.weight_hh_l0", "decoder.bias_ih_l0", "decoder.bias_hh_l0", "counter.weight", "counter.bias")
+
+
+class _AttractorLoss(torch.autograd.Function):
+    """rows32 (B, rows >= T, D) -> (attractor loss, attractors (B, C, D)) on the kernels of csrc/lstm.hip; the backward fills the
+    gradients of rows32 and of the ten `eda.*` tensors (_EDA_PARAMS order; the two biases of an LSTM receive the same gradient, the
+    decoder's weight_ih, whose input is zero, receives zeros)."""
+
+    @staticmethod
+    def forward(ctx, holder, rows32, *params):
+        eda, T, order, n_spk = holder["eda"], holder["T"], holder["order"], holder["n_speakers"]
+        P = eda._prepare()
+        B, rows, D = rows32.shape
+        C = max(n_spk) + 1
+        dev = rows32.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        # grad mode is always off in here and needs_input_grad ignores it: the caller read it (holder["save"])
+        save = holder["save"] and any(ctx.needs_input_grad)
+        G = torch.empty(B, rows, 4 * D, **f32)                   # over all slab rows, as in inference: the same bits as test()
+        ops.linear_step_f32(rows32.view(B * rows, D), P["enc_wih"], P["enc_b"], G.view(B * rows, 4 * D))
+        hT, cT, hD, cD = (torch.empty(B, D, **f32) for _ in range(4))
+        # what the backward reads is T rows tall whatever the slab: its GEMMs never meet a padding row
+        ge, ce, pe = (torch.empty(B, T, 4 * D, **f32), torch.empty(B, T, D, **f32), torch.empty(B, T, D, **f32)) if save else (None,) * 3
+        gd, cd, pd = (torch.empty(B, C, 4 * D, **f32), torch.empty(B, C, D, **f32), torch.empty(B, C, D, **f32)) if save else (None,) * 3
+        ops.lstm_train(G, order, None, P["enc_whh"], None, None, hT, cT, None, ge, ce, pe, B, T)
+        attractors = torch.empty(B, C, D, **f32)
+        ops.lstm_train(None, None, P["dec_b"], P["dec_whh"], hT, cT, hD, cD, attractors, gd, cd, pd, B, C)   # zero input: no GEMM
+        loss = torch.empty(1, **f32)
+        dattr, dw, db = (torch.empty(B, C, D, **f32), torch.empty(D, **f32), torch.empty(1, **f32)) if save else (None,) * 3
+        ops.eda_count_loss(attractors, P["cnt_w"], P["cnt_b"], torch.tensor(n_spk, dtype=torch.int32, device=dev), loss, dattr, dw, db)
+        if save:
+            xs = rows32 if rows == T else rows32[:, :T].contiguous()
+            # through save_for_backward, so that an in-place write to xs or a parameter before the backward raises (the operand
+            # copies share the parameters' version counters where they alias them)
+            ctx.save_for_backward(xs, order, ge, ce, pe, gd, cd, pd, cT, dattr, dw, db, P["enc_whh"], P["dec_whh"], P["enc_wih_t"])
+            ctx.rows = rows
+        return loss.view(()), attractors
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dloss, dattractors):
+        xs, order, ge, ce, pe, gd, cd, pd, cT, dattr, dw, db, enc_whh, dec_whh, enc_wih_t = ctx.saved_tensors
+        B, T, D = xs.shape
+        C = gd.shape[1]
+        f32 = dict(dtype=torch.float32, device=xs.device)
+        scale = torch.zeros((), **f32) if dloss is None else dloss.to(torch.float32)
+        dA = dattr * scale
+        if dattractors is not None:
+            dA = dA + dattractors
+        # decoder: every step's h is an attractor
+        dGd, dh0, dc0 = torch.empty(B, C, 4 * D, **f32), torch.empty(B, D, **f32), torch.empty(B, D, **f32)
+        ops.lstm_bwd(gd, cd, cT, dec_whh, dA.contiguous(), None, None, None, dGd, dh0, dc0, B, C)
+        ws = torch.empty(ops.wgrad_f32_workspace_bytes(4 * D, D, True) // 4, **f32)
+        dWd, dbd = torch.empty(4 * D, D, **f32), torch.empty(4 * D, **f32)
+        ops.wgrad_f32(dGd.view(B * C, 4 * D), pd.view(B * C, D), ws, dWd, dbd)
+        # encoder: fed by the decoder's initial-state gradients
+        dGe, dhe, dce = torch.empty(B, T, 4 * D, **f32), torch.empty(B, D, **f32), torch.empty(B, D, **f32)
+        ops.lstm_bwd(ge, ce, None, enc_whh, None, dh0, dc0, order, dGe, dhe, dce, B, T)
+        dWhh, dWih, dbe = torch.empty(4 * D, D, **f32), torch.empty(4 * D, D, **f32), torch.empty(4 * D, **f32)
+        ops.wgrad_f32(dGe.view(B * T, 4 * D), pe.view(B * T, D), ws, dWhh, dbe)
+        ops.wgrad_f32(dGe.view(B * T, 4 * D), xs.view(B * T, D), ws, dWih, None)
+        dxs = None
+        if ctx.needs_input_grad[1]:
+            dxs = torch.empty(B, T, D, **f32)
+            ops.linear_step_f32(dGe.view(B * T, 4 * D), enc_wih_t, None, dxs.view(B * T, D))
+            if ctx.rows > T:                                      # slab rows no step read
+                dxs = torch.cat([dxs, dxs.new_zeros(B, ctx.rows - T, D)], dim=1)
+        grads = (dWih, dWhh, dbe, dbe.clone(), torch.zeros(4 * D, D, **f32), dWd, dbd, dbd.clone(), (dw * scale).view(1, D),
+                 (db * scale).view(1))
+        return (None, dxs) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[2:]))
+
+
+class _HeadLogits(torch.autograd.Function):
+    """logits (B, T, C) = emb (B, rows >= T, D) attractors (B, C, D)^T (eend_eda_head_f32) with eend_eda_head_bwd_f32 behind it."""
+
+    @staticmethod
+    def forward(ctx, emb32, attractors, T):
+        B, C, _ = attractors.shape
+        logits = torch.empty(B, T, C, dtype=torch.float32, device=emb32.device)
+        ops.eda_head(emb32, attractors, logits, T)
+        ctx.save_for_backward(emb32, attractors)
+        ctx.T = T
+        return logits
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dlogits):
+        emb32, attractors = ctx.saved_tensors
+        B, rows, D = emb32.shape
+        T = ctx.T
+        need_emb, need_attr = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        dattr = torch.empty_like(attractors) if need_attr else None
+        demb = torch.empty(B, T, D, dtype=torch.float32, device=emb32.device) if need_emb else None
+        ops.eda_head_bwd(dlogits.contiguous(), emb32, attractors, dattr, demb, T)
+        if need_emb and rows > T:
+            demb = torch.cat([demb, demb.new_zeros(B, rows - T, D)], dim=1)
+        return demb, dattr, None
+
+
 class EncoderDecoderAttractor(PreparedOperands, nn.Module):
-    """LSTM encoder-decoder attractor calculation (reference model :79-107), inference only."""
+    """LSTM encoder-decoder attractor calculation (reference model :79-127): `estimate` for inference, `forward` with the attractor
+    loss under autograd (the LSTM backward of csrc/lstm.hip)."""
 
     def __init__(self, n_units, encoder_dropout=0.1, decoder_dropout=0.1):
         super().__init__()
@@ -115,6 +239,7 @@ class EncoderDecoderAttractor(PreparedOperands, nn.Module):
                  enc_b=(_f32(e.bias_ih_l0) + _f32(e.bias_hh_l0)).contiguous(),
                  dec_whh=_f32(d.weight_hh_l0), dec_b=(_f32(d.bias_ih_l0) + _f32(d.bias_hh_l0)).contiguous(),
                  cnt_w=_f32(self.counter.weight).view(-1), cnt_b=_f32(self.counter.bias).view(-1))
+        P["enc_wih_t"] = P["enc_wih"].t().contiguous()            # the backward's d xs = dG W_ih as a linear layer over W_ih^T
         return P
 
     def _attractors(self, rows32: Tensor, T: int, order: Optional[Tensor], max_n_speakers: int, th: Optional[float]):
@@ -149,9 +274,33 @@ class EncoderDecoderAttractor(PreparedOperands, nn.Module):
         attractors, probs, _ = self._attractors(xs, xs.shape[1], None, max_n_speakers, None)
         return attractors, probs
 
+    def _loss_and_attractors(self, rows32: Tensor, T: int, n_speakers: list, order: Optional[Tensor]):
+        """rows32 f32 (B, rows >= T, D), contiguous -> (loss, attractors (B, max(n_speakers) + 1, D)) under autograd."""
+        B, _, D = rows32.shape
+        if not ops.lstm_ok(B, T, D):
+            raise EendHipError(f"EDA attractors: unsupported shape B={B}, T={T}, D={D}")
+        params = [self.get_parameter(n) for n in _EDA_PARAMS]
+        holder = dict(eda=self, T=T, order=order, n_speakers=n_speakers, save=torch.is_grad_enabled())
+        return _AttractorLoss.apply(holder, rows32, *params)
+
+    def forward(self, xs: Tensor, n_speakers, order=None):
+        """Attractors from embedding sequences with the number of speakers given, and the attractor-existence loss (reference model
+        :109-127): xs (B, T, E), n_speakers a list of B counts -> (loss, attractors (B, max(n_speakers) + 1, E)).  `loss.backward()`
+        reaches xs (if it requires grad) and every parameter of this module; without grad mode nothing is kept for it.
+        `order` (ours): None reads the frames as they lie, as the reference's forward does; a permutation of 0 .. T-1 reads frame
+        order[t] at step t, as `test` does."""
+        if not isinstance(xs, Tensor) or xs.dim() != 3:
+            raise EendHipError("forward: xs must be a (B, T, E) tensor")
+        n = check_n_speakers(n_speakers, xs.shape[0])
+        o = None if order is None else check_order(order, xs.shape[1])
+        _need_gpu(xs, "xs")
+        if xs.dtype != torch.float32 or not xs.is_contiguous():
+            xs = xs.to(torch.float32).contiguous()
+        return self._loss_and_attractors(xs, xs.shape[1], n, None if o is None else torch.from_numpy(o).to(xs.device))
+
 
 class TransformerEDADiarization(PreparedOperands, nn.Module):
-    """Offline EEND-EDA on MI355X (reference model :10-76), inference only."""
+    """Offline EEND-EDA on MI355X (reference model :10-76): `test` for inference, `forward` for training with a frozen encoder."""
 
     def __init__(self, n_speakers, in_size, n_units, n_heads, n_layers, dropout, attractor_loss_ratio=1.0,
                  attractor_encoder_dropout=0.1, attractor_decoder_dropout=0.1):
@@ -242,4 +391,19 @@ class TransformerEDADiarization(PreparedOperands, nn.Module):
         return output_active, emb_slab[:, :T], attractors[:, :-1, :]
 
     def forward(self, src, tgt, ilens):
-        raise NotImplementedError("EEND-EDA training (forward, the attractor loss, the LSTM backward) is out of scope: inference only")
+        """reference model :39-52 for a FROZEN encoder -> ([logits (ilen_i, n_i)], attractor_loss_ratio * attractor loss, emb (B, T, E),
+        attractors[:, :-1, :]) with n_i = tgt[i].shape[1].  The embeddings come from the inference kernels (no dropout, no gradient);
+        the attractor loss and the logits carry gradients to every `eda.*` parameter.  The caller's PIT / BCE loss on the slices is
+        ordinary torch."""
+        if any(p.requires_grad for p in self.enc.parameters()):
+            raise NotImplementedError("the encoder backward of EEND-EDA is not built: freeze the encoder "
+                                      "(model.enc.requires_grad_(False)) to train the attractor path")
+        if tgt is None or len(src) == 0 or len(src) != len(tgt) or len(src) != len(ilens):
+            raise ValueError("src, tgt and ilens must be non-empty lists of one length")
+        n_speakers = check_n_speakers([t.shape[1] for t in tgt], len(src))
+        with torch.no_grad():
+            emb_slab, T = self._encode(src)
+        loss, attractors = self.eda._loss_and_attractors(emb_slab, T, n_speakers, None)
+        logits = _HeadLogits.apply(emb_slab, attractors, T)
+        output = [logits[b, :int(l), :n] for b, (l, n) in enumerate(zip(ilens, n_speakers))]
+        return output, self.attractor_loss_ratio * loss, emb_slab[:, :T], attractors[:, :-1, :]

@@ -97,6 +97,11 @@ PROTOTYPES = {
     "eend_stb_track_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
     "eend_eda_count_f32": [_vp, _vp, _vp, _f, _vp, _vp, _i, _i, _vp],
     "eend_eda_head_f32": [_vp, _i, _vp, _vp, _i, _i, _i, _vp],
+    "eend_lstm_train_f32": [_vp, _i, _vp, _i] + [_vp] * 10 + [_i, _i, _i, _i, _vp],
+    "eend_lstm_bwd_f32": [_vp] * 8 + [_i, _vp, _i, _vp, _vp, _i, _i, _i, _vp],
+    "eend_wgrad_f32": [_vp, _i, _vp, _i, _l, _i, _i, _vp, _l, _vp, _vp, _vp],
+    "eend_eda_count_loss_f32": [_vp] * 9 + [_l, _i, _i, _vp],
+    "eend_eda_head_bwd_f32": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _l, _i, _i, _i, _vp],
     "eend_pit_cost_f64": [_vp, _vp, _i, _i, _i, _vp, _vp],
     "eend_pit_assign_i32": [_vp, _vp, _i, _i, _vp, _vp, _vp],
     "eend_retention_proj_f16": [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
@@ -208,6 +213,9 @@ PROTOTYPES = {
 # entries that return a long rather than an int status
 LONG_PROTOTYPES = {
     "eend_copy_blocks_tile_bytes": [],
+    "eend_wgrad_f32_workspace_bytes": [_i, _i, _i],
+    "eend_eda_head_bwd_workspace_bytes": [_i, _i, _i],
+    "eend_eda_count_loss_workspace_bytes": [_i],
 }
 
 

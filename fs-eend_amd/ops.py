@@ -595,6 +595,134 @@ def eda_head(emb32, attractors, logits, T):
     _lib.check(L.eend_eda_head_f32(_p(emb32), emb32.shape[1], _p(attractors), _p(logits), B, T, C, _stream()), "eend_eda_head_f32")
 
 
+def _order_stride(order, B, T, what):
+    if order is None:
+        return 0
+    _chk(order, torch.int32, "order")
+    if order.dim() == 2:
+        if tuple(order.shape) != (B, T):
+            raise _lib.EendHipError(f"{what}: an order per sequence must be (B, T)")
+        return T
+    if order.numel() != T:
+        raise _lib.EendHipError(f"{what}: order must have T entries, or be (B, T)")
+    return 0
+
+
+def lstm_train(G, order, bias, w_hh, h0, c0, hT, cT, h_all, gates, c_all, h_prev, B, T):
+    """lstm() that also keeps what lstm_bwd() reads (eend_lstm_train_f32; hT, cT, h_all have lstm()'s bits): gates f32 (B, T, 1024)
+    after their functions, c_all f32 (B, T, 256), h_prev f32 (B, rows >= T, 256) = the hidden state entering step t at row order[t]
+    (row t without an order; its row count is its own, not G's); each of the three may be None."""
+    L = _lib.load()
+    for n, t in (("G", G), ("bias", bias), ("w_hh", w_hh), ("h0", h0), ("c0", c0), ("hT", hT), ("cT", cT), ("h_all", h_all),
+                 ("gates", gates), ("c_all", c_all), ("h_prev", h_prev)):
+        _chk(t, F32, n)
+    if w_hh.dim() != 2 or w_hh.shape[0] != 4 * w_hh.shape[1]:
+        raise _lib.EendHipError("lstm_train: w_hh must be (4 * hidden, hidden)")
+    hidden = w_hh.shape[1]
+    g_rows = 0
+    if G is not None:
+        if G.dim() != 3 or G.shape[0] != B or G.shape[2] != 4 * hidden:
+            raise _lib.EendHipError("lstm_train: G must be (B, g_rows, 4 * hidden)")
+        g_rows = G.shape[1]
+    elif bias is None or bias.numel() != 4 * hidden or order is not None:
+        raise _lib.EendHipError("lstm_train: zero input needs the bias sum (4 * hidden,) and takes no order")
+    stride = _order_stride(order, B, T, "lstm_train")
+    hp_rows = 0
+    if h_prev is not None:
+        if h_prev.dim() != 3 or h_prev.shape[0] != B or h_prev.shape[1] < T or h_prev.shape[2] != hidden:
+            raise _lib.EendHipError("lstm_train: h_prev must be (B, rows >= T, hidden)")
+        hp_rows = h_prev.shape[1]
+    for n, t, want in (("h0", h0, B * hidden), ("c0", c0, B * hidden), ("hT", hT, B * hidden), ("cT", cT, B * hidden),
+                       ("h_all", h_all, B * T * hidden), ("gates", gates, B * T * 4 * hidden), ("c_all", c_all, B * T * hidden)):
+        if t is not None and t.numel() != want:
+            raise _lib.EendHipError(f"lstm_train: {n} has {t.numel()} elements, expected {want}")
+    _lib.check(L.eend_lstm_train_f32(_p(G), g_rows, _p(order), stride, _p(bias), _p(w_hh), _p(h0), _p(c0), _p(hT), _p(cT), _p(h_all),
+                                     _p(gates), _p(c_all), _p(h_prev), hp_rows, B, T, hidden, _stream()), "eend_lstm_train_f32")
+
+
+def lstm_bwd(gates, c_all, c0, w_hh, dh_all, dhT, dcT, order, dG, dh0, dc0, B, T):
+    """Backward of lstm_train (eend_lstm_bwd_f32): upstream dh_all f32 (B, T, 256) and / or dhT, dcT f32 (B, 256) -> dG f32
+    (B, g_rows >= T, 1024) with step t's pre-activation gradients at row order[t] (other rows are left as they are), dh0, dc0 (B, 256)."""
+    L = _lib.load()
+    for n, t in (("gates", gates), ("c_all", c_all), ("c0", c0), ("w_hh", w_hh), ("dh_all", dh_all), ("dhT", dhT), ("dcT", dcT),
+                 ("dG", dG), ("dh0", dh0), ("dc0", dc0)):
+        _chk(t, F32, n)
+    if w_hh.dim() != 2 or w_hh.shape[0] != 4 * w_hh.shape[1]:
+        raise _lib.EendHipError("lstm_bwd: w_hh must be (4 * hidden, hidden)")
+    hidden = w_hh.shape[1]
+    if dG is None or dG.dim() != 3 or dG.shape[0] != B or dG.shape[2] != 4 * hidden:
+        raise _lib.EendHipError("lstm_bwd: dG must be (B, g_rows, 4 * hidden)")
+    stride = _order_stride(order, B, T, "lstm_bwd")
+    for n, t, want in (("gates", gates, B * T * 4 * hidden), ("c_all", c_all, B * T * hidden), ("c0", c0, B * hidden),
+                       ("dh_all", dh_all, B * T * hidden), ("dhT", dhT, B * hidden), ("dcT", dcT, B * hidden), ("dh0", dh0, B * hidden),
+                       ("dc0", dc0, B * hidden)):
+        if t is not None and t.numel() != want:
+            raise _lib.EendHipError(f"lstm_bwd: {n} has {t.numel()} elements, expected {want}")
+    _lib.check(L.eend_lstm_bwd_f32(_p(gates), _p(c_all), _p(c0), _p(w_hh), _p(dh_all), _p(dhT), _p(dcT), _p(order), stride, _p(dG),
+                                   dG.shape[1], _p(dh0), _p(dc0), B, T, hidden, _stream()), "eend_lstm_bwd_f32")
+
+
+def wgrad_f32_workspace_bytes(N, K, with_bias=False):
+    """Bytes of workspace wgrad_f32 needs; 0 where it refuses the sizes (N, K multiples of 64)."""
+    return int(_lib.load().eend_wgrad_f32_workspace_bytes(int(N), int(K), 1 if with_bias else 0))
+
+
+def wgrad_f32(dy, x, ws, dw, db=None):
+    """dw (N, K) = dy (M, N)^T x (M, K), db (N,) = column sums of dy; all f32, exact-f32 MFMA, fixed row slices summed in order
+    (wgrad_f32.hip).  ws: f32 workspace of wgrad_f32_workspace_bytes(N, K, db is not None) bytes."""
+    L = _lib.load()
+    for n, t in (("dy", dy), ("x", x), ("ws", ws), ("dw", dw), ("db", db)):
+        _chk(t, F32, n)
+    if dy.dim() != 2 or x.dim() != 2 or dy.shape[0] != x.shape[0]:
+        raise _lib.EendHipError("wgrad_f32: dy (M, N) and x (M, K)")
+    M, N = dy.shape
+    K = x.shape[1]
+    if tuple(dw.shape) != (N, K) or (db is not None and db.numel() != N):
+        raise _lib.EendHipError("wgrad_f32: dw (N, K), db (N,)")
+    _lib.check(L.eend_wgrad_f32(_p(dy), dy.stride(0), _p(x), x.stride(0), M, N, K, _p(ws), ws.numel() * 4, _p(dw), _p(db), _stream()),
+               "eend_wgrad_f32")
+
+
+def eda_count_loss(attractors, w, bias, n_spk, loss, dattractors, dw, dbias):
+    """The attractor-existence loss (eend_eda_count_loss_f32): mean BCE-with-logits of attractors[b, :n_b + 1] . w + bias against
+    [1] * n_b + [0], and for a unit loss gradient dattractors (B, C, 256), dw (256,), dbias (1,): all three, or all three None for the
+    loss alone.  n_spk i32 (B,), 0 <= n_b < C."""
+    L = _lib.load()
+    for n, t in (("attractors", attractors), ("w", w), ("bias", bias), ("loss", loss), ("dattractors", dattractors), ("dw", dw),
+                 ("dbias", dbias)):
+        _chk(t, F32, n)
+    _chk(n_spk, torch.int32, "n_spk")
+    B, C, D = attractors.shape
+    grads = (dattractors, dw, dbias)
+    if any(g is None for g in grads) != all(g is None for g in grads):
+        raise _lib.EendHipError("eda_count_loss: dattractors, dw and dbias together, or none of them")
+    if D != 256 or w.numel() != 256 or bias.numel() != 1 or n_spk.numel() != B or loss.numel() != 1 or (dw is not None and (
+            dattractors.numel() != B * C * D or dw.numel() != 256 or dbias.numel() != 1)):
+        raise _lib.EendHipError("eda_count_loss: attractors (B, C, 256), w (256,), bias (1,), n_spk (B,), loss (1,), dattractors "
+                                "(B, C, 256), dw (256,), dbias (1,)")
+    nbytes = int(L.eend_eda_count_loss_workspace_bytes(B))
+    ws = torch.empty(nbytes // 4, dtype=F32, device=attractors.device)
+    _lib.check(L.eend_eda_count_loss_f32(_p(attractors), _p(w), _p(bias), _p(n_spk), _p(loss), _p(dattractors), _p(dw), _p(dbias),
+                                         _p(ws), nbytes, B, C, _stream()), "eend_eda_count_loss_f32")
+
+
+def eda_head_bwd(dlogits, emb32, attractors, dattractors, demb, T):
+    """Backward of eda_head (eend_eda_head_bwd_f32): dlogits (B, T, C) -> dattractors (B, C, 256) and / or demb (B, T, 256)."""
+    L = _lib.load()
+    for n, t in (("dlogits", dlogits), ("emb32", emb32), ("attractors", attractors), ("dattractors", dattractors), ("demb", demb)):
+        _chk(t, F32, n)
+    B, C, D = attractors.shape
+    if emb32.dim() != 3 or emb32.shape[0] != B or emb32.shape[2] != 256 or D != 256 or dlogits.numel() != B * T * C or \
+            (dattractors is not None and dattractors.numel() != B * C * D) or (demb is not None and demb.numel() != B * T * D):
+        raise _lib.EendHipError("eda_head_bwd: dlogits (B, T, C), emb (B, rows, 256), attractors (B, C, 256), demb (B, T, 256)")
+    ws, nbytes = None, 0
+    if dattractors is not None:
+        nbytes = int(L.eend_eda_head_bwd_workspace_bytes(B, T, C))
+        ws = torch.empty(max(nbytes // 4, 1), dtype=F32, device=attractors.device)
+    _lib.check(L.eend_eda_head_bwd_f32(_p(dlogits), _p(emb32), emb32.shape[1], _p(attractors), _p(dattractors), _p(demb), _p(ws), nbytes,
+                                       B, T, C, _stream()), "eend_eda_head_bwd_f32")
+
+
 STB_DESC_WORDS, STB_MAX_ROWS, STB_MAX_FEATURES = 12, 4096, 512
 STB_POLICIES = {"kld": 0, "fifo": 1}
 

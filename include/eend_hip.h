@@ -562,7 +562,7 @@ int eend_room_rir_f32(const long* rooms, int n_rows, const long* tiles, int n_ti
  * arithmetic only). */
 int eend_room_limits(int* tile, int* window, int* max_rows, int* max_axis);
 
-/* ---- offline EEND-EDA attractor path (FS-EEND/nnet/model/offl_tfm_enc_lstm_enc_dec.py, inference only) ---- */
+/* ---- offline EEND-EDA attractor path (FS-EEND/nnet/model/offl_tfm_enc_lstm_enc_dec.py): inference ---- */
 
 /* Whether eend_lstm_f32 takes the shape: hidden == 256, T >= 1, B >= 1 (host arithmetic only). */
 int eend_lstm_ok(int B, int T, int hidden);
@@ -603,6 +603,62 @@ int eend_eda_count_f32(const float* attractors, const float* w, const float* bia
 /* logits[b][t][c] = emb[b][t] . attractors[b][c] (the torch.bmm of model :66) over all C columns.  emb f32 [B][emb_rows][256] with
  * emb_rows >= T (a slab: rows t >= T are never read), attractors f32 [B][C][256], logits f32 [B][T][C]; 1 <= C <= 16, B <= 65535. */
 int eend_eda_head_f32(const float* emb, int emb_rows, const float* attractors, float* logits, int B, int T, int C, void* stream);
+
+/* ---- the differentiable attractor path: EncoderDecoderAttractor.forward (model :109-127) and its backward.  The encoder backward
+ * and the Lightning module are not built. ---- */
+
+/* eend_lstm_f32 / eend_lstm_orders_f32 (the same kernel body; hT, cT and h_all have the same bits) which also keeps what the backward
+ * reads.  order_stride: 0 = order i32 [T] for the batch, T = order i32 [B][T], one per sequence.  Each of the three may be NULL:
+ *   gates   f32 [B][T][1024]  sigmoid(z_i), sigmoid(z_f), tanh(z_g), sigmoid(z_o) of every step, in step order
+ *   c_all   f32 [B][T][256]   the cell state after every step, in step order
+ *   h_prev  f32 [B][hp_rows][256], hp_rows >= T: the hidden state that enters step t, written at row order[t] (row t without an
+ *           order): the row of dG the step's gradient goes to.  hp_rows is its own count, so that the backward's operands can be
+ *           T rows tall where G is a taller slab.  Rows no step reads are not written.
+ * EEND_EINVAL: as eend_lstm_f32; an order with a NULL G; 0 < order_stride < T; h_prev with hp_rows < T. */
+int eend_lstm_train_f32(const float* G, int g_rows, const int* order, int order_stride, const float* bias, const float* W_hh,
+                        const float* h0, const float* c0, float* hT, float* cT, float* h_all, float* gates, float* c_all, float* h_prev,
+                        int hp_rows, int B, int T, int hidden, void* stream);
+
+/* Backpropagation through time of eend_lstm_train_f32, step T-1 down to 0, all f32, one workgroup per sequence.
+ *   gates, c_all, order, order_stride as the forward wrote / read them; c0 f32 [B][256] the forward's c0 (NULL = zeros); W_hh.
+ *   dh_all  f32 [B][T][256] or NULL: d loss / d h of every step (the decoder: every h is an attractor)
+ *   dhT, dcT f32 [B][256] or NULL: d loss / d of the final state (the encoder, fed by the decoder's dh0 / dc0).  One of the three at least.
+ *   dG      f32 [B][g_rows][1024]: step t's pre-activation gradients at row order[t] (row t without an order); other rows are not written
+ *   dh0, dc0 f32 [B][256]: d loss / d of the initial state.
+ *   step    dh = dh_all[t] + W_hh^T dz(t+1);  dc += dh o (1 - tanh^2 c_t);  dz_o = dh tanh(c_t) o (1 - o);  dz_i = dc g i (1 - i);
+ *           dz_g = dc i (1 - g^2);  dz_f = dc c_{t-1} f (1 - f);  dc <- dc f.
+ * The order of every sum is fixed by (gate row, wave): a sequence's bits depend neither on its batch mates nor on the run.
+ * EEND_EINVAL: hidden != 256, T < 1, B < 1, g_rows < T, a NULL gates / c_all / W_hh / dG / dh0 / dc0, no upstream gradient,
+ * order_stride != 0 with a NULL order or below T. */
+int eend_lstm_bwd_f32(const float* gates, const float* c_all, const float* c0, const float* W_hh, const float* dh_all, const float* dhT,
+                      const float* dcT, const int* order, int order_stride, float* dG, int g_rows, float* dh0, float* dc0, int B, int T,
+                      int hidden, void* stream);
+
+/* Bytes of workspace eend_wgrad_f32 needs for these sizes (with_bias: db is asked for); 0 where it refuses them. */
+long eend_wgrad_f32_workspace_bytes(int N, int K, int with_bias);
+/* dW[n][k] = sum_m dY[m][n] X[m][k] and, where db is given, db[n] = sum_m dY[m][n]; dY f32 [M][ldy], X f32 [M][ldx], dW f32 [N][K],
+ * everything f32 on the exact-f32 MFMA (an m-ordered fmaf chain).  The rows are cut into a fixed number of slices (16, whatever the
+ * device), whose partials go to ws and are summed in slice order: the bits are the same in every run.  Overwrites dW and db.
+ * EEND_EINVAL: N or K not a multiple of 64, M < 1, ldy < N, ldx < K, a NULL dY / X / ws / dW, ws_bytes below the query. */
+int eend_wgrad_f32(const float* dY, int ldy, const float* X, int ldx, long M, int N, int K, float* ws, long ws_bytes, float* dW, float* db,
+                   void* stream);
+
+/* The attractor-existence loss of model :121-123 and its gradients for d loss = 1.  With n_b = n_spk[b] (i32 [B], 0 <= n_b < C; the
+ * kernel clamps into that range): z[b][c] = attractors[b][c] . w + bias for c <= n_b, labels [1] * n_b + [0],
+ * loss[0] = mean over the sum_b (n_b + 1) elements of BCE-with-logits.  dattractors f32 [B][C][256] (zero rows for c > n_b), dw f32
+ * [256], dbias f32 [1]: all three, or all three NULL for the loss alone.  ws: eend_eda_count_loss_workspace_bytes(B) bytes.  Sums
+ * run in the order (c, then b).  1 <= C <= 16.  EEND_EINVAL: sizes, a NULL input / loss / ws, a short ws, some gradients only. */
+long eend_eda_count_loss_workspace_bytes(int B);
+int eend_eda_count_loss_f32(const float* attractors, const float* w, const float* bias, const int* n_spk, float* loss, float* dattractors,
+                            float* dw, float* dbias, float* ws, long ws_bytes, int B, int C, void* stream);
+
+/* Bytes of workspace eend_eda_head_bwd_f32 needs when dattractors is asked for; 0 for sizes it refuses. */
+long eend_eda_head_bwd_workspace_bytes(int B, int T, int C);
+/* Backward of eend_eda_head_f32: dattractors[b][c] = sum_t dlogits[b][t][c] emb[b][t] (partials of 64 frames, frames ascending,
+ * summed in tile order) and demb[b][t] = sum_c dlogits[b][t][c] attractors[b][c].  dlogits f32 [B][T][C], emb f32 [B][emb_rows][256],
+ * dattractors f32 [B][C][256] or NULL, demb f32 [B][T][256] or NULL (one of the two at least).  Sizes as eend_eda_head_f32. */
+int eend_eda_head_bwd_f32(const float* dlogits, const float* emb, int emb_rows, const float* attractors, float* dattractors, float* demb,
+                          float* ws, long ws_bytes, int B, int T, int C, void* stream);
 
 /* ---- block-online EEND-EDA with a speaker-tracing buffer, STB (FS-EEND/train/tfm_STB.py:147-204; find_best_perm, cal_cor, upd_buf,
  * upd_buf_FIFO of train/utils/utils.py) ----
