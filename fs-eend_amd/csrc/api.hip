@@ -585,13 +585,16 @@ int eend_lstm_ok(int B, int T, int hidden) { return eend_lstm_shape_ok(B, T, hid
 
 int eend_lstm_f32(const float* G, int g_rows, const int* order, const float* bias, const float* W_hh, const float* h0, const float* c0,
                   float* hT, float* cT, float* h_all, int B, int T, int hidden, void* stream) {
-    return eend_launch_lstm(G, g_rows, order, bias, W_hh, h0, c0, hT, cT, h_all, B, T, hidden, 0, (hipStream_t)stream);
+    // a shared order over a zero input is accepted and ignored here; eend_lstm_train_f32 refuses it
+    return eend_launch_lstm(G, g_rows, G ? order : nullptr, bias, W_hh, h0, c0, hT, cT, h_all, nullptr, nullptr, nullptr, 0, B, T, hidden, 0,
+                            (hipStream_t)stream);
 }
 
 int eend_lstm_orders_f32(const float* G, int g_rows, const int* order, const float* W_hh, const float* h0, const float* c0, float* hT,
                          float* cT, float* h_all, int B, int T, int hidden, void* stream) {
     if (!G || !order) return EEND_EINVAL;
-    return eend_launch_lstm(G, g_rows, order, nullptr, W_hh, h0, c0, hT, cT, h_all, B, T, hidden, T, (hipStream_t)stream);
+    return eend_launch_lstm(G, g_rows, order, nullptr, W_hh, h0, c0, hT, cT, h_all, nullptr, nullptr, nullptr, 0, B, T, hidden, T,
+                            (hipStream_t)stream);
 }
 
 int eend_eda_count_f32(const float* attractors, const float* w, const float* bias, float th, float* probs, int* count, int B, int C,
@@ -606,8 +609,8 @@ int eend_eda_head_f32(const float* emb, int emb_rows, const float* attractors, f
 int eend_lstm_train_f32(const float* G, int g_rows, const int* order, int order_stride, const float* bias, const float* W_hh,
                         const float* h0, const float* c0, float* hT, float* cT, float* h_all, float* gates, float* c_all, float* h_prev,
                         int hp_rows, int B, int T, int hidden, void* stream) {
-    return eend_launch_lstm_train(G, g_rows, order, bias, W_hh, h0, c0, hT, cT, h_all, gates, c_all, h_prev, hp_rows, B, T, hidden, order_stride,
-                                  (hipStream_t)stream);
+    return eend_launch_lstm(G, g_rows, order, bias, W_hh, h0, c0, hT, cT, h_all, gates, c_all, h_prev, hp_rows, B, T, hidden, order_stride,
+                            (hipStream_t)stream);
 }
 
 int eend_lstm_bwd_f32(const float* gates, const float* c_all, const float* c0, const float* W_hh, const float* dh_all, const float* dhT,

@@ -172,8 +172,10 @@ int eend_launch_room_rir(const long* rooms, int n_rows, const long* tiles, int n
 #define LSTM_HIDDEN 256
 #define EDA_MAX_ATTRACTORS 16
 int eend_lstm_shape_ok(int B, int T, int hidden);
+// gates / c_all / h_prev (hp_rows rows per sequence): what the backward reads, each or all NULL
 int eend_launch_lstm(const float* G, int g_rows, const int* order, const float* bias, const float* Whh, const float* h0, const float* c0,
-                     float* hT, float* cT, float* h_all, int B, int T, int hidden, int order_stride, hipStream_t stream);
+                     float* hT, float* cT, float* h_all, float* gates, float* c_all, float* h_prev, int hp_rows, int B, int T, int hidden,
+                     int order_stride, hipStream_t stream);
 int eend_launch_eda_count(const float* attr, const float* w, const float* bias, float th, float* probs, int* count, int B, int C,
                           hipStream_t stream);
 int eend_launch_eda_head(const float* emb, int emb_rows, const float* attr, float* logits, int B, int T, int C, hipStream_t stream);
@@ -182,9 +184,6 @@ int eend_launch_eda_head(const float* emb, int emb_rows, const float* attr, floa
 #define EDA_COUNT_LOSS_WS 258
 #define EDA_HEAD_BWD_TILE 64
 #define WGRAD_F32_SLICES 16
-int eend_launch_lstm_train(const float* G, int g_rows, const int* order, const float* bias, const float* Whh, const float* h0,
-                           const float* c0, float* hT, float* cT, float* h_all, float* gates, float* c_all, float* h_prev, int hp_rows,
-                           int B, int T, int hidden, int order_stride, hipStream_t stream);
 int eend_launch_lstm_bwd(const float* gates, const float* c_all, const float* c0, const float* Whh, const float* dh_all, const float* dhT,
                          const float* dcT, const int* order, int order_stride, float* dG, int g_rows, float* dh0, float* dc0, int B, int T,
                          int hidden, hipStream_t stream);

@@ -2,8 +2,10 @@
 // LSTM recurrence (eend_lstm_f32, eend_lstm_orders_f32), the attractor-existence counter with the speaker count taken from it (eend_eda_count_f32) and the
 // embedding . attractor head (eend_eda_head_f32); and what makes that path differentiable (model :109-127): the recurrence that keeps
 // its gates and states (eend_lstm_train_f32), its backward (eend_lstm_bwd_f32), the attractor-existence loss with its gradients
-// (eend_eda_count_loss_f32) and the head's backward (eend_eda_head_bwd_f32); the weight gradients are wgrad_f32.hip.  The contracts
-// are in include/eend_hip.h; DESIGN 12 has the reasoning and the times.
+// (eend_eda_count_loss_f32) and the head's backward (eend_eda_head_bwd_f32); the weight gradients are wgrad_f32.hip.  The three
+// recurrence entries reach lstm_seq_kernel<TRAIN> through one launcher, eend_launch_lstm, with one block of argument rules: TRAIN only
+// where something is kept.  The counter, its loss and the head share one 256-wide dot (dot256).  The contracts are in
+// include/eend_hip.h; DESIGN 12 has the reasoning and the times.
 //
 // eend_lstm_f32.  One workgroup of 16 waves owns one sequence from its first step to its last; workgroups never talk to each other
 // (no flags, no spins, no cooperative launch) and every loop is bounded by T.  W_hh stays f32 in global memory and is re-read from L2
@@ -239,11 +241,16 @@ __global__ __launch_bounds__(LNT) void lstm_bwd_kernel(const float* __restrict__
     }
 }
 
-DEV float wave_sum(float v) {
+// NOT train_common.h's wave_sum: that one adds the halves 1 -> 32, this one 32 -> 1.  The two orders give different bits, so neither
+// may stand in for the other (the counter's probabilities and the logits are pinned bit for bit).
+DEV float wave_sum_32to1(float v) {
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
     return v;
 }
+
+// the 256-wide dot of the counter and the head: lane l's four columns as one fmaf chain from x up, then the sum above
+DEV float dot256(f32x4 a, f32x4 b) { return wave_sum_32to1(fmaf(a.w, b.w, fmaf(a.z, b.z, fmaf(a.y, b.y, a.x * b.x)))); }
 
 // one workgroup per sequence: a wave per attractor, then one lane scans the C probabilities
 __global__ __launch_bounds__(256) void eda_count_kernel(const float* __restrict__ attr, const float* __restrict__ w,
@@ -254,7 +261,7 @@ __global__ __launch_bounds__(256) void eda_count_kernel(const float* __restrict_
     const f32x4 wv = *(const f32x4*)(w + lane * 4);
     for (int cidx = wave; cidx < C; cidx += 4) {
         const f32x4 a = *(const f32x4*)(attr + ((size_t)b * C + cidx) * LH + lane * 4);
-        const float s = wave_sum(fmaf(a.w, wv.w, fmaf(a.z, wv.z, fmaf(a.y, wv.y, a.x * wv.x)))) + bias[0];
+        const float s = dot256(a, wv) + bias[0];
         if (lane == 0) {
             const float pr = lstm_sigmoid(s);
             ps[cidx] = pr;
@@ -284,7 +291,7 @@ __global__ __launch_bounds__(256) void eda_head_kernel(const float* __restrict__
         const f32x4 e = *(const f32x4*)(emb + ((size_t)b * emb_rows + t) * LH + lane * 4);
         for (int cidx = 0; cidx < C; ++cidx) {
             const f32x4 a = *(const f32x4*)&as[cidx * LH + lane * 4];
-            const float s = wave_sum(fmaf(a.w, e.w, fmaf(a.z, e.z, fmaf(a.y, e.y, a.x * e.x))));
+            const float s = dot256(a, e);
             if (lane == 0) logits[((size_t)b * T + t) * C + cidx] = s;
         }
     }
@@ -314,7 +321,7 @@ __global__ __launch_bounds__(256) void eda_count_loss_kernel(const float* __rest
         float l = 0.f, g = 0.f;
         if (cidx <= nb) {                                         // wave-uniform: labels [1] * n_b + [0], nothing beyond
             const f32x4 a = *(const f32x4*)(attr + ((size_t)b * C + cidx) * LH + lane * 4);
-            const float z = wave_sum(fmaf(a.w, wv.w, fmaf(a.z, wv.z, fmaf(a.y, wv.y, a.x * wv.x)))) + bias[0];
+            const float z = dot256(a, wv) + bias[0];
             const float y = cidx < nb ? 1.f : 0.f;
             l = fmaxf(z, 0.f) - z * y + log1pf(expf(-fabsf(z)));   // BCE with logits, finite for every finite z
             g = (lstm_sigmoid(z) - y) * inv;
@@ -413,29 +420,19 @@ __global__ __launch_bounds__(256) void eda_head_bwd_reduce_kernel(const float* _
 
 int eend_lstm_shape_ok(int B, int T, int hidden) { return hidden == LSTM_HIDDEN && T >= 1 && B >= 1; }
 
+// One launcher for eend_lstm_f32, eend_lstm_orders_f32 and eend_lstm_train_f32.  With nothing to keep it runs the inference instance,
+// whose hT, cT and h_all have the training instance's bits.  h_prev has hp_rows >= T rows per sequence, its own count: the
+// backward's operands need not be as tall as a padded slab of G.
 int eend_launch_lstm(const float* G, int g_rows, const int* order, const float* bias, const float* Whh, const float* h0, const float* c0,
-                     float* hT, float* cT, float* h_all, int B, int T, int hidden, int order_stride, hipStream_t stream) {
+                     float* hT, float* cT, float* h_all, float* gates, float* c_all, float* h_prev, int hp_rows, int B, int T, int hidden,
+                     int order_stride, hipStream_t stream) {
     if (!eend_lstm_shape_ok(B, T, hidden) || !Whh || !hT || !cT) return EEND_EINVAL;
-    if (order_stride != 0 && (order_stride < T || !order || !G)) return EEND_EINVAL;
-    if (G ? g_rows < T : !bias) return EEND_EINVAL;               // rows of G per sequence; zero input needs the bias sum
-    if ((h0 == nullptr) != (c0 == nullptr)) return EEND_EINVAL;
-    hipLaunchKernelGGL(lstm_seq_kernel<false>, dim3(B), dim3(LNT), 0, stream, G, g_rows, order, bias, Whh, h0, c0, hT, cT, h_all, T,
-                       order_stride, (float*)nullptr, (float*)nullptr, (float*)nullptr, 0);
-    return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
-}
-
-// the argument rules of eend_launch_lstm; h_prev has hp_rows >= T rows per sequence, its own count: the backward's operands need
-// not be as tall as a padded slab of G
-int eend_launch_lstm_train(const float* G, int g_rows, const int* order, const float* bias, const float* Whh, const float* h0,
-                           const float* c0, float* hT, float* cT, float* h_all, float* gates, float* c_all, float* h_prev, int hp_rows,
-                           int B, int T, int hidden, int order_stride, hipStream_t stream) {
-    if (!eend_lstm_shape_ok(B, T, hidden) || !Whh || !hT || !cT) return EEND_EINVAL;
-    if (order_stride != 0 && (order_stride < T || !order || !G)) return EEND_EINVAL;
-    if (G ? g_rows < T : !bias) return EEND_EINVAL;
-    if (!G && order) return EEND_EINVAL;                          // an order over a zero input means nothing
+    if (order_stride != 0 && (order_stride < T || !order)) return EEND_EINVAL;
+    if (G ? g_rows < T : (!bias || order)) return EEND_EINVAL;    // rows of G per sequence; zero input needs the bias sum, takes no order
     if ((h0 == nullptr) != (c0 == nullptr) || (h_prev && hp_rows < T)) return EEND_EINVAL;
-    hipLaunchKernelGGL(lstm_seq_kernel<true>, dim3(B), dim3(LNT), 0, stream, G, g_rows, order, bias, Whh, h0, c0, hT, cT, h_all, T,
-                       order_stride, gates, c_all, h_prev, hp_rows);
+    const auto kernel = !gates && !c_all && !h_prev ? lstm_seq_kernel<false> : lstm_seq_kernel<true>;
+    hipLaunchKernelGGL(kernel, dim3(B), dim3(LNT), 0, stream, G, g_rows, order, bias, Whh, h0, c0, hT, cT, h_all, T, order_stride, gates,
+                       c_all, h_prev, hp_rows);
     return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
 }
 

@@ -12,9 +12,11 @@ The torch.nn modules are parameter containers only; all arithmetic runs in libee
                The reference has no key-padding mask, so in a ragged batch a shorter sequence sees its -1 padding, here as there.
                The last layer also writes its rows in f32: the embeddings are not L2-normalised in this model, and both the LSTM
                and the head read them.
-  attractors   the input projection of the encoder LSTM (eend_linear_step_f32), the two recurrences (eend_lstm_f32: the shuffle of
-               model :62-65 is an index into the projected rows, the decoder's zero input needs no GEMM), the counter with the
-               speaker count (eend_eda_count_f32) and the head (eend_eda_head_f32).
+  attractors   one pass for inference and training (``_attractor_pass``): the input projection of the encoder LSTM
+               (eend_linear_step_f32) and the two recurrences (eend_lstm_train_f32, which keeps nothing and runs the inference
+               kernel unless the backward's buffers are given: the shuffle of model :62-65 is an index into the projected rows, the
+               decoder's zero input needs no GEMM); then the counter with the speaker count (eend_eda_count_f32) and the head
+               (eend_eda_head_f32).
 
 Two quirks of the reference's ``test`` are deliberately not reproduced: with B > 1 it applies the first item's
 count to every later item (here every sequence keeps the columns before its own first p < th), and it raises on a recording where
@@ -117,6 +119,20 @@ _EDA_PARAMS = ("encoder.weight_ih_l0", "encoder.weight_hh_l0", "encoder.bias_ih_
                "decoder.weight_hh_l0", "decoder.bias_ih_l0", "decoder.bias_hh_l0", "counter.weight", "counter.bias")
 
 
+def _slab_logits(emb32: Tensor, attractors: Tensor, T: int) -> Tensor:
+    """logits (B, T, C) f32 = emb32 (B, rows >= T, D) attractors (B, C, D)^T (eend_eda_head_f32)."""
+    B, C, _ = attractors.shape
+    logits = torch.empty(B, T, C, dtype=torch.float32, device=emb32.device)
+    ops.eda_head(emb32, attractors, logits, T)
+    return logits
+
+
+def _pad_rows(grad: Tensor, rows: int) -> Tensor:
+    """A gradient over the T rows the steps read, back to the slab's `rows` rows: zeros for the rows no step read."""
+    B, T, D = grad.shape
+    return grad if rows <= T else torch.cat([grad, grad.new_zeros(B, rows - T, D)], dim=1)
+
+
 class _AttractorLoss(torch.autograd.Function):
     """rows32 (B, rows >= T, D) -> (attractor loss, attractors (B, C, D)) on the kernels of csrc/lstm.hip; the backward fills the
     gradients of rows32 and of the ten `eda.*` tensors (_EDA_PARAMS order; the two biases of an LSTM receive the same gradient, the
@@ -132,17 +148,12 @@ class _AttractorLoss(torch.autograd.Function):
         f32 = dict(dtype=torch.float32, device=dev)
         # grad mode is always off in here and needs_input_grad ignores it: the caller read it (holder["save"])
         save = holder["save"] and any(ctx.needs_input_grad)
-        G = torch.empty(B, rows, 4 * D, **f32)                   # over all slab rows, as in inference: the same bits as test()
-        ops.linear_step_f32(rows32.view(B * rows, D), P["enc_wih"], P["enc_b"], G.view(B * rows, 4 * D))
-        hT, cT, hD, cD = (torch.empty(B, D, **f32) for _ in range(4))
         # what the backward reads is T rows tall whatever the slab: its GEMMs never meet a padding row
         ge, ce, pe = (torch.empty(B, T, 4 * D, **f32), torch.empty(B, T, D, **f32), torch.empty(B, T, D, **f32)) if save else (None,) * 3
         gd, cd, pd = (torch.empty(B, C, 4 * D, **f32), torch.empty(B, C, D, **f32), torch.empty(B, C, D, **f32)) if save else (None,) * 3
-        ops.lstm_train(G, order, None, P["enc_whh"], None, None, hT, cT, None, ge, ce, pe, B, T)
-        attractors = torch.empty(B, C, D, **f32)
-        ops.lstm_train(None, None, P["dec_b"], P["dec_whh"], hT, cT, hD, cD, attractors, gd, cd, pd, B, C)   # zero input: no GEMM
-        loss = torch.empty(1, **f32)
         dattr, dw, db = (torch.empty(B, C, D, **f32), torch.empty(D, **f32), torch.empty(1, **f32)) if save else (None,) * 3
+        attractors, cT = eda._attractor_pass(P, rows32, T, order, C, (ge, ce, pe), (gd, cd, pd))
+        loss = torch.empty(1, **f32)
         ops.eda_count_loss(attractors, P["cnt_w"], P["cnt_b"], torch.tensor(n_spk, dtype=torch.int32, device=dev), loss, dattr, dw, db)
         if save:
             xs = rows32 if rows == T else rows32[:, :T].contiguous()
@@ -179,8 +190,7 @@ class _AttractorLoss(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             dxs = torch.empty(B, T, D, **f32)
             ops.linear_step_f32(dGe.view(B * T, 4 * D), enc_wih_t, None, dxs.view(B * T, D))
-            if ctx.rows > T:                                      # slab rows no step read
-                dxs = torch.cat([dxs, dxs.new_zeros(B, ctx.rows - T, D)], dim=1)
+            dxs = _pad_rows(dxs, ctx.rows)
         grads = (dWih, dWhh, dbe, dbe.clone(), torch.zeros(4 * D, D, **f32), dWd, dbd, dbd.clone(), (dw * scale).view(1, D),
                  (db * scale).view(1))
         return (None, dxs) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[2:]))
@@ -191,12 +201,9 @@ class _HeadLogits(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, emb32, attractors, T):
-        B, C, _ = attractors.shape
-        logits = torch.empty(B, T, C, dtype=torch.float32, device=emb32.device)
-        ops.eda_head(emb32, attractors, logits, T)
         ctx.save_for_backward(emb32, attractors)
         ctx.T = T
-        return logits
+        return _slab_logits(emb32, attractors, T)
 
     @staticmethod
     @once_differentiable
@@ -208,9 +215,7 @@ class _HeadLogits(torch.autograd.Function):
         dattr = torch.empty_like(attractors) if need_attr else None
         demb = torch.empty(B, T, D, dtype=torch.float32, device=emb32.device) if need_emb else None
         ops.eda_head_bwd(dlogits.contiguous(), emb32, attractors, dattr, demb, T)
-        if need_emb and rows > T:
-            demb = torch.cat([demb, demb.new_zeros(B, rows - T, D)], dim=1)
-        return demb, dattr, None
+        return _pad_rows(demb, rows) if need_emb else None, dattr, None
 
 
 class EncoderDecoderAttractor(PreparedOperands, nn.Module):
@@ -242,24 +247,34 @@ class EncoderDecoderAttractor(PreparedOperands, nn.Module):
         P["enc_wih_t"] = P["enc_wih"].t().contiguous()            # the backward's d xs = dG W_ih as a linear layer over W_ih^T
         return P
 
-    def _attractors(self, rows32: Tensor, T: int, order: Optional[Tensor], max_n_speakers: int, th: Optional[float]):
-        """rows32 f32 (B, rows >= T, D) -> attractors (B, C, D), probs (B, C), count i32 (B,) or None.  Step t of the encoder LSTM
-        reads row order[t]; order i32 (T,) for the batch or (B, T), one per sequence."""
-        P = self._prepare()
+    @staticmethod
+    def _attractor_pass(P, rows32: Tensor, T: int, order: Optional[Tensor], C: int, enc_keep=(None,) * 3, dec_keep=(None,) * 3):
+        """The one encoder-LSTM-then-decoder-LSTM pass: rows32 f32 (B, rows >= T, D) -> attractors (B, C, D) and the encoder's final
+        cell state.  The input projection runs over all slab rows; step t of the encoder LSTM reads row order[t] (order i32 (T,) for
+        the batch, (B, T) one per sequence, or None); the decoder reads C zero vectors from the encoder's (hT, cT).  enc_keep /
+        dec_keep: (gates, c_all, h_prev) for the backward; with None everywhere the recurrence runs its inference instance.  P: the
+        operands of _prepare()."""
         B, rows, D = rows32.shape
-        dev = rows32.device
-        C = int(max_n_speakers)
-        if not ops.lstm_ok(B, T, D) or not 1 <= C <= 16:
-            raise EendHipError(f"EDA attractors: unsupported shape B={B}, T={T}, D={D}, C={C}")
-        f32 = dict(dtype=torch.float32, device=dev)
+        f32 = dict(dtype=torch.float32, device=rows32.device)
         G = torch.empty(B, rows, 4 * D, **f32)
         ops.linear_step_f32(rows32.view(B * rows, D), P["enc_wih"], P["enc_b"], G.view(B * rows, 4 * D))
         hT, cT, hD, cD = (torch.empty(B, D, **f32) for _ in range(4))
-        ops.lstm(G, order, None, P["enc_whh"], None, None, hT, cT, None, B, T)
+        ops.lstm_train(G, order, None, P["enc_whh"], None, None, hT, cT, None, *enc_keep, B, T)
         attractors = torch.empty(B, C, D, **f32)
-        ops.lstm(None, None, P["dec_b"], P["dec_whh"], hT, cT, hD, cD, attractors, B, C)       # zero input: no GEMM
-        probs = torch.empty(B, C, **f32)
-        count = torch.empty(B, dtype=torch.int32, device=dev) if th is not None else None
+        ops.lstm_train(None, None, P["dec_b"], P["dec_whh"], hT, cT, hD, cD, attractors, *dec_keep, B, C)    # zero input: no GEMM
+        return attractors, cT
+
+    def _attractors(self, rows32: Tensor, T: int, order: Optional[Tensor], max_n_speakers: int, th: Optional[float]):
+        """rows32 f32 (B, rows >= T, D) -> attractors (B, C, D), probs (B, C), count i32 (B,) or None (_attractor_pass, then the
+        counter)."""
+        P = self._prepare()
+        B, _, D = rows32.shape
+        C = int(max_n_speakers)
+        if not ops.lstm_ok(B, T, D) or not 1 <= C <= 16:
+            raise EendHipError(f"EDA attractors: unsupported shape B={B}, T={T}, D={D}, C={C}")
+        attractors, _ = self._attractor_pass(P, rows32, T, order, C)
+        probs = torch.empty(B, C, dtype=torch.float32, device=rows32.device)
+        count = torch.empty(B, dtype=torch.int32, device=rows32.device) if th is not None else None
         ops.eda_count(attractors, P["cnt_w"], P["cnt_b"], 0.0 if th is None else th, probs, count)
         return attractors, probs, count
 
@@ -379,13 +394,10 @@ class TransformerEDADiarization(PreparedOperands, nn.Module):
             np.random.shuffle(order)
         order = check_order(order, T)
         emb_slab, T = self._encode(src)
-        dev = emb_slab.device
-        B = emb_slab.shape[0]
-        order_dev = torch.from_numpy(order).to(dev)
+        order_dev = torch.from_numpy(order).to(emb_slab.device)
         attractors, probs, count = self.eda._attractors(emb_slab, T, order_dev, MAX_N_SPEAKERS, None if n_spk is not None else float(th))
-        logits = torch.empty(B, T, MAX_N_SPEAKERS, dtype=torch.float32, device=dev)
-        ops.eda_head(emb_slab, attractors, logits, T)
-        counts = [int(n_spk)] * B if n_spk is not None else count.tolist()
+        logits = _slab_logits(emb_slab, attractors, T)
+        counts = [int(n_spk)] * len(src) if n_spk is not None else count.tolist()
         self.last_probs, self.last_counts, self.last_logits = probs, counts, logits
         output_active = [logits[b, :int(l), :counts[b]] for b, l in enumerate(ilens)]
         return output_active, emb_slab[:, :T], attractors[:, :-1, :]

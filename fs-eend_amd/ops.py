@@ -537,35 +537,51 @@ def lstm_ok(B, T, hidden):
     return bool(_lib.load().eend_lstm_ok(int(B), int(T), int(hidden)))
 
 
+def _order_stride(order, B, T, what):
+    if order is None:
+        return 0
+    _chk(order, torch.int32, "order")
+    if order.dim() == 2:
+        if tuple(order.shape) != (B, T):
+            raise _lib.EendHipError(f"{what}: an order per sequence must be (B, T)")
+        return T
+    if order.numel() != T:
+        raise _lib.EendHipError(f"{what}: order must have T entries, or be (B, T)")
+    return 0
+
+
+def _lstm_args(what, w_hh, g_name, G, bias, order, B, T, sized):
+    """What lstm, lstm_train and lstm_bwd check alike -> (hidden, g_rows, order_stride).  w_hh f32 (4 * hidden, hidden); G (the
+    backward's dG) f32 (B, g_rows, 4 * hidden), or None = zero input, which needs the bias sum (4 * hidden,); the order by
+    _order_stride; sized = (name, tensor or None, elements per sequence in units of hidden)."""
+    for n, t in ((g_name, G), ("bias", bias), ("w_hh", w_hh)) + tuple(s[:2] for s in sized):
+        _chk(t, F32, n)
+    if w_hh.dim() != 2 or w_hh.shape[0] != 4 * w_hh.shape[1]:
+        raise _lib.EendHipError(f"{what}: w_hh must be (4 * hidden, hidden)")
+    hidden = w_hh.shape[1]
+    if G is None:
+        if bias is None or bias.numel() != 4 * hidden:            # lstm_bwd has no bias: its dG is not optional
+            raise _lib.EendHipError(f"{what}: needs {g_name} (B, g_rows, 4 * hidden), or for a zero input the bias sum (4 * hidden,)")
+    elif G.dim() != 3 or G.shape[0] != B or G.shape[2] != 4 * hidden:
+        raise _lib.EendHipError(f"{what}: {g_name} must be (B, g_rows, 4 * hidden)")
+    stride = _order_stride(order, B, T, what)
+    for n, t, per_seq in sized:
+        if t is not None and t.numel() != B * per_seq * hidden:
+            raise _lib.EendHipError(f"{what}: {n} has {t.numel()} elements, expected {B * per_seq * hidden}")
+    return hidden, 0 if G is None else G.shape[1], stride
+
+
 def lstm(G, order, bias, w_hh, h0, c0, hT, cT, h_all, B, T):
     """Single-layer LSTM recurrence (lstm.hip).  G f32 (B, g_rows, 1024) input pre-activations, read at row order[t] in step t, or None
     = zero input (pre-activation = bias f32 (1024,) = b_ih + b_hh); order i32 (T,) shared by the batch, (B, T) one per sequence
     (eend_lstm_orders_f32, the same kernel), or None = identity; w_hh f32 (1024, 256); h0 / c0
     f32 (B, 256), both or neither; hT / cT f32 (B, 256); h_all f32 (B, T, 256) or None."""
     L = _lib.load()
-    for n, t in (("G", G), ("bias", bias), ("w_hh", w_hh), ("h0", h0), ("c0", c0), ("hT", hT), ("cT", cT), ("h_all", h_all)):
-        _chk(t, F32, n)
-    _chk(order, torch.int32, "order")
-    hidden = w_hh.shape[1] if w_hh.dim() == 2 else -1
-    if w_hh.dim() != 2 or w_hh.shape[0] != 4 * hidden:
-        raise _lib.EendHipError("lstm: w_hh must be (4 * hidden, hidden)")
-    g_rows = 0
-    if G is not None:
-        if G.dim() != 3 or G.shape[0] != B or G.shape[2] != 4 * hidden:
-            raise _lib.EendHipError("lstm: G must be (B, g_rows, 4 * hidden)")
-        g_rows = G.shape[1]
-    elif bias is None or bias.numel() != 4 * hidden:
-        raise _lib.EendHipError("lstm: zero input needs the bias sum (4 * hidden,)")
-    per_seq = order is not None and order.dim() == 2
-    if order is not None and (tuple(order.shape) != (B, T) if per_seq else order.numel() != T):
-        raise _lib.EendHipError("lstm: order must have T entries, or be (B, T)")
-    if per_seq and G is None:
-        raise _lib.EendHipError("lstm: an order per sequence needs G")
-    for n, t, want in (("h0", h0, B * hidden), ("c0", c0, B * hidden), ("hT", hT, B * hidden), ("cT", cT, B * hidden),
-                       ("h_all", h_all, B * T * hidden)):
-        if t is not None and t.numel() != want:
-            raise _lib.EendHipError(f"lstm: {n} has {t.numel()} elements, expected {want}")
-    if per_seq:
+    hidden, g_rows, stride = _lstm_args("lstm", w_hh, "G", G, bias, order, B, T,
+                                        (("h0", h0, 1), ("c0", c0, 1), ("hT", hT, 1), ("cT", cT, 1), ("h_all", h_all, T)))
+    if stride:
+        if G is None:
+            raise _lib.EendHipError("lstm: an order per sequence needs G")
         _lib.check(L.eend_lstm_orders_f32(_p(G), g_rows, _p(order), _p(w_hh), _p(h0), _p(c0), _p(hT), _p(cT), _p(h_all), B, T, hidden,
                                           _stream()), "eend_lstm_orders_f32")
         return
@@ -595,47 +611,22 @@ def eda_head(emb32, attractors, logits, T):
     _lib.check(L.eend_eda_head_f32(_p(emb32), emb32.shape[1], _p(attractors), _p(logits), B, T, C, _stream()), "eend_eda_head_f32")
 
 
-def _order_stride(order, B, T, what):
-    if order is None:
-        return 0
-    _chk(order, torch.int32, "order")
-    if order.dim() == 2:
-        if tuple(order.shape) != (B, T):
-            raise _lib.EendHipError(f"{what}: an order per sequence must be (B, T)")
-        return T
-    if order.numel() != T:
-        raise _lib.EendHipError(f"{what}: order must have T entries, or be (B, T)")
-    return 0
-
-
 def lstm_train(G, order, bias, w_hh, h0, c0, hT, cT, h_all, gates, c_all, h_prev, B, T):
     """lstm() that also keeps what lstm_bwd() reads (eend_lstm_train_f32; hT, cT, h_all have lstm()'s bits): gates f32 (B, T, 1024)
     after their functions, c_all f32 (B, T, 256), h_prev f32 (B, rows >= T, 256) = the hidden state entering step t at row order[t]
     (row t without an order; its row count is its own, not G's); each of the three may be None."""
     L = _lib.load()
-    for n, t in (("G", G), ("bias", bias), ("w_hh", w_hh), ("h0", h0), ("c0", c0), ("hT", hT), ("cT", cT), ("h_all", h_all),
-                 ("gates", gates), ("c_all", c_all), ("h_prev", h_prev)):
-        _chk(t, F32, n)
-    if w_hh.dim() != 2 or w_hh.shape[0] != 4 * w_hh.shape[1]:
-        raise _lib.EendHipError("lstm_train: w_hh must be (4 * hidden, hidden)")
-    hidden = w_hh.shape[1]
-    g_rows = 0
-    if G is not None:
-        if G.dim() != 3 or G.shape[0] != B or G.shape[2] != 4 * hidden:
-            raise _lib.EendHipError("lstm_train: G must be (B, g_rows, 4 * hidden)")
-        g_rows = G.shape[1]
-    elif bias is None or bias.numel() != 4 * hidden or order is not None:
-        raise _lib.EendHipError("lstm_train: zero input needs the bias sum (4 * hidden,) and takes no order")
-    stride = _order_stride(order, B, T, "lstm_train")
+    _chk(h_prev, F32, "h_prev")
+    hidden, g_rows, stride = _lstm_args("lstm_train", w_hh, "G", G, bias, order, B, T,
+                                        (("h0", h0, 1), ("c0", c0, 1), ("hT", hT, 1), ("cT", cT, 1), ("h_all", h_all, T),
+                                         ("gates", gates, 4 * T), ("c_all", c_all, T)))
+    if G is None and order is not None:
+        raise _lib.EendHipError("lstm_train: a zero input takes no order")
     hp_rows = 0
     if h_prev is not None:
         if h_prev.dim() != 3 or h_prev.shape[0] != B or h_prev.shape[1] < T or h_prev.shape[2] != hidden:
             raise _lib.EendHipError("lstm_train: h_prev must be (B, rows >= T, hidden)")
         hp_rows = h_prev.shape[1]
-    for n, t, want in (("h0", h0, B * hidden), ("c0", c0, B * hidden), ("hT", hT, B * hidden), ("cT", cT, B * hidden),
-                       ("h_all", h_all, B * T * hidden), ("gates", gates, B * T * 4 * hidden), ("c_all", c_all, B * T * hidden)):
-        if t is not None and t.numel() != want:
-            raise _lib.EendHipError(f"lstm_train: {n} has {t.numel()} elements, expected {want}")
     _lib.check(L.eend_lstm_train_f32(_p(G), g_rows, _p(order), stride, _p(bias), _p(w_hh), _p(h0), _p(c0), _p(hT), _p(cT), _p(h_all),
                                      _p(gates), _p(c_all), _p(h_prev), hp_rows, B, T, hidden, _stream()), "eend_lstm_train_f32")
 
@@ -644,22 +635,11 @@ def lstm_bwd(gates, c_all, c0, w_hh, dh_all, dhT, dcT, order, dG, dh0, dc0, B, T
     """Backward of lstm_train (eend_lstm_bwd_f32): upstream dh_all f32 (B, T, 256) and / or dhT, dcT f32 (B, 256) -> dG f32
     (B, g_rows >= T, 1024) with step t's pre-activation gradients at row order[t] (other rows are left as they are), dh0, dc0 (B, 256)."""
     L = _lib.load()
-    for n, t in (("gates", gates), ("c_all", c_all), ("c0", c0), ("w_hh", w_hh), ("dh_all", dh_all), ("dhT", dhT), ("dcT", dcT),
-                 ("dG", dG), ("dh0", dh0), ("dc0", dc0)):
-        _chk(t, F32, n)
-    if w_hh.dim() != 2 or w_hh.shape[0] != 4 * w_hh.shape[1]:
-        raise _lib.EendHipError("lstm_bwd: w_hh must be (4 * hidden, hidden)")
-    hidden = w_hh.shape[1]
-    if dG is None or dG.dim() != 3 or dG.shape[0] != B or dG.shape[2] != 4 * hidden:
-        raise _lib.EendHipError("lstm_bwd: dG must be (B, g_rows, 4 * hidden)")
-    stride = _order_stride(order, B, T, "lstm_bwd")
-    for n, t, want in (("gates", gates, B * T * 4 * hidden), ("c_all", c_all, B * T * hidden), ("c0", c0, B * hidden),
-                       ("dh_all", dh_all, B * T * hidden), ("dhT", dhT, B * hidden), ("dcT", dcT, B * hidden), ("dh0", dh0, B * hidden),
-                       ("dc0", dc0, B * hidden)):
-        if t is not None and t.numel() != want:
-            raise _lib.EendHipError(f"lstm_bwd: {n} has {t.numel()} elements, expected {want}")
+    hidden, g_rows, stride = _lstm_args("lstm_bwd", w_hh, "dG", dG, None, order, B, T,
+                                        (("gates", gates, 4 * T), ("c_all", c_all, T), ("c0", c0, 1), ("dh_all", dh_all, T),
+                                         ("dhT", dhT, 1), ("dcT", dcT, 1), ("dh0", dh0, 1), ("dc0", dc0, 1)))
     _lib.check(L.eend_lstm_bwd_f32(_p(gates), _p(c_all), _p(c0), _p(w_hh), _p(dh_all), _p(dhT), _p(dcT), _p(order), stride, _p(dG),
-                                   dG.shape[1], _p(dh0), _p(dc0), B, T, hidden, _stream()), "eend_lstm_bwd_f32")
+                                   g_rows, _p(dh0), _p(dc0), B, T, hidden, _stream()), "eend_lstm_bwd_f32")
 
 
 def wgrad_f32_workspace_bytes(N, K, with_bias=False):

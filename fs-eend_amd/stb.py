@@ -28,7 +28,7 @@ import torch
 from torch import Tensor
 
 from . import ops
-from .eda_model import MAX_N_SPEAKERS, TransformerEDADiarization, check_order
+from .eda_model import MAX_N_SPEAKERS, TransformerEDADiarization, _slab_logits, check_order
 from .lib import EendHipError
 from .multistream import DONE, FREE, OPEN, SlotError
 
@@ -207,8 +207,7 @@ class StbSession:
         model = self.model
         emb, _ = model._encode([xc[b] for b in range(B)])
         attractors, probs, count = model.eda._attractors(emb, T, order, MAX_N_SPEAKERS, self.th)
-        logits = torch.empty(B, T, MAX_N_SPEAKERS, dtype=F32, device=dev)
-        ops.eda_head(emb, attractors, logits, T)
+        logits = _slab_logits(emb, attractors, T)
         perm = torch.empty(B, MAX_N_SPEAKERS, dtype=I32, device=dev) if self.debug else None
         sel = torch.full((B, self.buf_size), -1, dtype=I32, device=dev) if self.debug else None
         ops.stb_track(logits, count, xc, desc, perm, sel, self.buf_size, self.blk_size, ops.STB_POLICIES[self.policy])

@@ -14,52 +14,23 @@ of eend_lstm_f32.  Everything is computed in float64 from a state dict with the 
 import numpy as np
 import torch
 
+from tests.eda_train_ref import _sigmoid, lstm_forward, mirror_of
+
 MAX_N_SPEAKERS = 15
 
 
 def build_mirror(meta):
-    """The golden case's parameters in the product's own class, as tools/gen_golden_eda.py built them in the reference's: default
-    initialisation under the seed, oracle.fixtures.perturb_, the counter gain; verified against the stored checksums."""
+    """The golden case's parameters in the product's own class, as tools/gen_golden_eda.py built them in the reference's
+    (eda_train_ref.mirror_of)."""
     from fs_eend_amd.eda_model import TransformerEDADiarization
-    from oracle import fixtures as FX
-    torch.manual_seed(meta["seed"])
-    m = TransformerEDADiarization(n_speakers=None, in_size=meta["in_size"], **meta["cfg"]).eval()
-    FX.perturb_(m, meta["pseed"])
-    with torch.no_grad():
-        m.eda.counter.weight.mul_(meta["counter_gain"])
-    FX.check_params(m.state_dict(), meta["checksums"])
-    return m
-
-
-def _sigmoid(x):
-    return 1.0 / (1.0 + np.exp(-x))
+    return mirror_of(meta, lambda: TransformerEDADiarization(n_speakers=None, in_size=meta["in_size"], **meta["cfg"]).eval(),
+                     lambda m: m.eda.counter)
 
 
 def lstm(W_hh, G=None, order=None, h0=None, c0=None, bias=None, T=None):
-    """The recurrence alone, as eend_lstm_f32 states it.  G (B, rows, 4H) input pre-activations read at row order[t] (None: the
-    bias (4H,) alone, for T steps); -> hT (B, H), cT (B, H), h_all (B, T, H), all float64."""
-    W = np.asarray(W_hh, dtype=np.float64)
-    H = W.shape[1]
-    if G is not None:
-        G = np.asarray(G, dtype=np.float64)
-        B = G.shape[0]
-        T = G.shape[1] if T is None else T
-    else:
-        B = 1 if h0 is None else np.asarray(h0).shape[0]
-    h = np.zeros((B, H)) if h0 is None else np.asarray(h0, dtype=np.float64).copy()
-    c = np.zeros((B, H)) if c0 is None else np.asarray(c0, dtype=np.float64).copy()
-    out = np.zeros((B, T, H))
-    for t in range(T):
-        z = h @ W.T
-        if G is not None:
-            z = z + G[:, t if order is None else int(order[t])]
-        else:
-            z = z + np.asarray(bias, dtype=np.float64)[None]
-        i, f, g, o = z[:, :H], z[:, H:2 * H], z[:, 2 * H:3 * H], z[:, 3 * H:]
-        c = _sigmoid(f) * c + _sigmoid(i) * np.tanh(g)
-        h = _sigmoid(o) * np.tanh(c)
-        out[:, t] = h
-    return h, c, out
+    """The recurrence alone, as eend_lstm_f32 states it (eda_train_ref.lstm_forward) -> hT (B, H), cT (B, H), h_all (B, T, H)."""
+    f = lstm_forward(W_hh, G, order, h0, c0, bias, T)
+    return f["hT"], f["cT"], f["h_all"]
 
 
 def _ln(x, w, b, eps=1e-5):

@@ -16,19 +16,25 @@ EDA_PARAMS = ("encoder.weight_ih_l0", "encoder.weight_hh_l0", "encoder.bias_ih_l
               "decoder.weight_hh_l0", "decoder.bias_ih_l0", "decoder.bias_hh_l0", "counter.weight", "counter.bias")
 
 
-def build_mirror(meta):
-    """A training golden's parameters in the product's own EncoderDecoderAttractor, as tools/gen_golden_eda_train.py built them in the
-    reference's: default initialisation under the seed, oracle.fixtures.perturb_, the counter gain; verified against the checksums."""
+def mirror_of(meta, make, counter):
+    """make() under the golden's seed (default initialisation), oracle.fixtures.perturb_, the counter gain on counter(module).weight;
+    verified against the stored checksums.  The common part of this module's build_mirror and tests/eda_ref.py's."""
     import torch
-    from fs_eend_amd.eda_model import EncoderDecoderAttractor
     from oracle import fixtures as FX
     torch.manual_seed(meta["seed"])
-    eda = EncoderDecoderAttractor(256)
-    FX.perturb_(eda, meta["pseed"])
+    m = make()
+    FX.perturb_(m, meta["pseed"])
     with torch.no_grad():
-        eda.counter.weight.mul_(meta["counter_gain"])
-    FX.check_params(eda.state_dict(), meta["checksums"])
-    return eda
+        counter(m).weight.mul_(meta["counter_gain"])
+    FX.check_params(m.state_dict(), meta["checksums"])
+    return m
+
+
+def build_mirror(meta):
+    """A training golden's parameters in the product's own EncoderDecoderAttractor, as tools/gen_golden_eda_train.py built them in the
+    reference's (mirror_of)."""
+    from fs_eend_amd.eda_model import EncoderDecoderAttractor
+    return mirror_of(meta, lambda: EncoderDecoderAttractor(256), lambda m: m.counter)
 
 
 def golden_inputs(meta):
@@ -53,7 +59,9 @@ def _f64(x):
 
 
 def lstm_forward(W_hh, G=None, order=None, h0=None, c0=None, bias=None, T=None):
-    """-> dict(hT, cT, h_all, c_all (B, T, H), gates (B, T, 4H) after their functions, h_prev (B, T, H) in step order, c0)."""
+    """The one float64 recurrence of the tests (tests/eda_ref.lstm is a view of it).  G (B, rows, 4H) input pre-activations read at
+    row order[t] (None: the bias (4H,) alone, for T steps) -> dict(hT, cT, h_all, c_all (B, T, H), gates (B, T, 4H) after their
+    functions, h_prev (B, T, H) in step order, c0)."""
     W = _f64(W_hh)
     H = W.shape[1]
     if G is not None:

@@ -19,10 +19,12 @@ import numpy as np
 import pytest
 import torch
 
+from tests import lstm_cases as LC
+from tests.lstm_cases import H
+
 pytestmark = pytest.mark.gpu
 
 K = 8.0
-H = 256
 SHAPES = [(1, 1), (1, 2), (3, 65), (2, 130), (17, 5)]
 MARGINS = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "eda_train_margins.json")
 _worst = {}
@@ -50,11 +52,7 @@ def _write_margins():
 @pytest.fixture(scope="module")
 def net():
     """The seeded nn.LSTM of test_lstm_gpu.py and its widened twins (1024 identity input columns) in fp32 and float64."""
-    torch.manual_seed(1234)
-    lstm = torch.nn.LSTM(H, H, 1, batch_first=True)
-    with torch.no_grad():
-        for p in lstm.parameters():
-            p.mul_(1.5)
+    lstm = LC.seeded_lstm()
     wide = {}
     for dt in (torch.float32, torch.float64):
         w = torch.nn.LSTM(H + 4 * H, H, 1, batch_first=True).to(dt)
@@ -68,10 +66,7 @@ def net():
 
 
 def _dev_params(net, dev):
-    lstm, _ = net
-    w_ih = lstm.weight_ih_l0.detach().to(dev).contiguous()
-    return dict(w_ih=w_ih, w_ih_t=w_ih.t().contiguous(), w_hh=lstm.weight_hh_l0.detach().to(dev).contiguous(),
-                b=(lstm.bias_ih_l0 + lstm.bias_hh_l0).detach().to(dev).contiguous())
+    return LC.dev_params(net[0], dev)
 
 
 def _orders(order, B, T):
@@ -112,12 +107,8 @@ def _kernel(dev, P, x, order, h0, c0, R):
     f32 = dict(dtype=torch.float32, device=dev)
     zero_input = x is None
     B, T = (R[0].shape[0], R[0].shape[1])
-    G = None
-    if not zero_input:
-        G = torch.empty(B, T, 4 * H, **f32)
-        xd = x.to(dev).reshape(B * T, H).contiguous()
-        ops.linear_step_f32(xd, P["w_ih"], P["b"], G.view(B * T, 4 * H))
-    o = None if order is None else torch.as_tensor(np.asarray(order), dtype=torch.int32, device=dev)
+    G, xd = (None, None) if zero_input else LC.device_G(P, x, dev)
+    o = LC.dev_order(order, dev)
     h0d, c0d = (None if t is None else t.to(dev) for t in (h0, c0))
     hT, cT = torch.empty(B, H, **f32), torch.empty(B, H, **f32)
     h_all, c_all, h_prev = (torch.full((B, T, H), float("nan"), **f32) for _ in range(3))
@@ -144,17 +135,26 @@ def _kernel(dev, P, x, order, h0, c0, R):
 def _check(name, got, ref, t32):
     failed = []
     for what in ref:
-        g = got[what].double().numpy()
-        gap32 = float(np.abs(t32[what] - ref[what]).max())
-        bar = K * max(gap32, 2.0 ** -24 * float(np.abs(ref[what]).max()))
-        err = float(np.abs(g - ref[what]).max())
-        ratio = err / bar if bar > 0 else (0.0 if err == 0 else float("inf"))
-        print(f"{name} {what}: err {err:.2e} gap32 {gap32:.2e} err/bar {ratio:.3f}")
+        err, bar, ratio = LC.err_and_bar(name, what, got[what], ref[what], t32[what], K, 2.0 ** -24)
         _record(what, ratio)
-        assert np.isfinite(g).all(), f"{name} {what}"
         if err > bar:
             failed.append(f"{what}: {err:.2e} > {bar:.2e}")
     assert not failed, f"{name}: " + "; ".join(failed)
+
+
+def _forward(dev, P, G, o, h0, c0, B, T, keep):
+    """hT, cT, h_all of ops.lstm (keep None), or of ops.lstm_train without (False) / with (True) the backward's three buffers."""
+    from fs_eend_amd import ops
+    f32 = dict(dtype=torch.float32, device=dev)
+    hT, cT, h_all = torch.empty(B, H, **f32), torch.empty(B, H, **f32), torch.full((B, T, H), float("nan"), **f32)
+    args = (G, o, None if G is not None else P["b"], P["w_hh"], None if h0 is None else h0.to(dev), None if c0 is None else c0.to(dev))
+    if keep is None:
+        ops.lstm(*args, hT, cT, h_all, B, T)
+    else:
+        kept = (torch.empty(B, T, 4 * H, **f32), torch.empty(B, T, H, **f32), torch.empty(B, T, H, **f32)) if keep else (None,) * 3
+        ops.lstm_train(*args, hT, cT, h_all, *kept, B, T)
+    torch.cuda.synchronize()
+    return hT.cpu(), cT.cpu(), h_all.cpu()
 
 
 def _inputs(B, T, state, seed):
@@ -170,7 +170,6 @@ def _inputs(B, T, state, seed):
 @pytest.mark.parametrize("order_kind", ["identity", "permuted", "per_sequence"])
 @pytest.mark.parametrize("state", [False, True])
 def test_backward_vs_float64_autograd(hip_lib, dev, net, B, T, order_kind, state):
-    from fs_eend_amd import ops
     _, wide = net
     x, h0, c0, R = _inputs(B, T, state, 100 * B + T)
     order = None
@@ -184,12 +183,8 @@ def test_backward_vs_float64_autograd(hip_lib, dev, net, B, T, order_kind, state
     got, fwd = _kernel(dev, P, x, order, h0, c0, R)
     _check(f"B{B} T{T} {order_kind} state{int(state)}", got, ref, t32)
     # the training forward has the inference entry's bits
-    f32 = dict(dtype=torch.float32, device=dev)
-    hT, cT, h_all = torch.empty(B, H, **f32), torch.empty(B, H, **f32), torch.empty(B, T, H, **f32)
-    o = None if order is None else torch.as_tensor(np.asarray(order), dtype=torch.int32, device=dev)
-    ops.lstm(fwd["G"], o, None, P["w_hh"], None if h0 is None else h0.to(dev), None if c0 is None else c0.to(dev), hT, cT, h_all, B, T)
-    torch.cuda.synchronize()
-    assert torch.equal(hT.cpu(), fwd["hT"]) and torch.equal(cT.cpu(), fwd["cT"]) and torch.equal(h_all.cpu(), fwd["h_all"])
+    hT, cT, h_all = _forward(dev, P, fwd["G"], LC.dev_order(order, dev), h0, c0, B, T, None)
+    assert torch.equal(hT, fwd["hT"]) and torch.equal(cT, fwd["cT"]) and torch.equal(h_all, fwd["h_all"])
     # h_prev: row order[t] holds the hidden state that entered step t
     ob = _orders(order, B, T)
     first = torch.zeros(B, H) if h0 is None else h0
@@ -274,6 +269,33 @@ def test_saturating_preactivations_give_finite_gradients(hip_lib, dev, net):
     torch.cuda.synchronize()
     for t in (gates, c_all, h_prev, dG, dh0, dc0, dW, db):
         assert torch.isfinite(t).all()
+
+
+@pytest.mark.parametrize("B,T", [(1, 1), (3, 65), (2, 130)])
+def test_one_launcher_gives_one_set_of_bits(hip_lib, dev, net, B, T):
+    """eend_lstm_orders_f32, eend_lstm_train_f32 with nothing to keep (the inference instance) and with all three buffers (the
+    training instance): the same hT, cT and h_all, with an order per sequence and a given initial state."""
+    x, h0, c0, _ = _inputs(B, T, True, 300 * B + T)
+    P = _dev_params(net, dev)
+    G, _ = LC.device_G(P, x, dev)
+    o = LC.dev_order(np.stack([np.random.RandomState(2000 + 7 * b + T).permutation(T) for b in range(B)]), dev)
+    runs = [_forward(dev, P, G, o, h0, c0, B, T, keep) for keep in (None, False, True)]
+    assert all(torch.isfinite(t).all() for t in runs[0])
+    for other in runs[1:]:
+        assert all(torch.equal(u, v) for u, v in zip(runs[0], other))
+
+
+def test_zero_input_with_a_shared_order(hip_lib, dev, net):
+    """The one argument rule on which the entries differ: over a zero input lstm() ignores a shared order, lstm_train() refuses it."""
+    from fs_eend_amd.lib import EendHipError
+    B, T = 2, 3
+    _, h0, c0, _ = _inputs(B, T, True, 11)
+    P = _dev_params(net, dev)
+    order = LC.dev_order(np.array([2, 0, 1]), dev)
+    plain, ordered = (_forward(dev, P, None, o, h0, c0, B, T, None) for o in (None, order))
+    assert all(torch.isfinite(t).all() for t in plain) and all(torch.equal(u, v) for u, v in zip(plain, ordered))
+    with pytest.raises(EendHipError):
+        _forward(dev, P, None, order, h0, c0, B, T, False)
 
 
 ROUND = 64          # 16 slices x the MFMA's 4 rows

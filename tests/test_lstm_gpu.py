@@ -10,30 +10,24 @@ import pytest
 import torch
 
 from tests import eda_ref as ER
+from tests import lstm_cases as LC
+from tests.lstm_cases import H
 
 pytestmark = pytest.mark.gpu
 
 K = 8.0
-H = 256
 SHAPES = [(1, 1), (1, 2), (3, 65), (2, 130), (17, 5)]
 
 
 @pytest.fixture(scope="module")
 def net():
-    """One seeded nn.LSTM (CPU fp32: the gap32 side) and its parameters in float64 and on the device."""
-    torch.manual_seed(1234)
-    lstm = torch.nn.LSTM(H, H, 1, batch_first=True)
-    with torch.no_grad():
-        for p in lstm.parameters():
-            p.mul_(1.5)                   # a livelier recurrence than the default 1/16 range
-    p64 = {k: v.detach().double().numpy() for k, v in lstm.named_parameters()}
-    return lstm, p64
+    """The seeded nn.LSTM (CPU fp32: the gap32 side) and its parameters in float64."""
+    lstm = LC.seeded_lstm()
+    return lstm, {k: v.detach().double().numpy() for k, v in lstm.named_parameters()}
 
 
 def _dev_params(net, dev):
-    lstm, _ = net
-    return dict(w_ih=lstm.weight_ih_l0.detach().to(dev).contiguous(), w_hh=lstm.weight_hh_l0.detach().to(dev).contiguous(),
-                b=(lstm.bias_ih_l0 + lstm.bias_hh_l0).detach().to(dev).contiguous())
+    return LC.dev_params(net[0], dev)
 
 
 def _run(dev, P, x=None, order=None, h0=None, c0=None, T=None, with_all=True, G=None):
@@ -41,16 +35,13 @@ def _run(dev, P, x=None, order=None, h0=None, c0=None, T=None, with_all=True, G=
     from fs_eend_amd import ops
     f32 = dict(dtype=torch.float32, device=dev)
     if x is not None:
-        B, T, _ = x.shape
-        G = torch.empty(B, T, 4 * H, **f32)
-        ops.linear_step_f32(x.to(dev).reshape(B * T, H).contiguous(), P["w_ih"], P["b"], G.view(B * T, 4 * H))
+        G, _ = LC.device_G(P, x, dev)
     B = G.shape[0] if G is not None else h0.shape[0]
     T = G.shape[1] if G is not None else T
     hT, cT = torch.empty(B, H, **f32), torch.empty(B, H, **f32)
     h_all = torch.full((B, T, H), float("nan"), **f32) if with_all else None
-    o = None if order is None else torch.as_tensor(np.asarray(order), dtype=torch.int32, device=dev)
-    ops.lstm(G, o, None if G is not None else P["b"], P["w_hh"], None if h0 is None else h0.to(dev), None if c0 is None else c0.to(dev),
-             hT, cT, h_all, B, T)
+    ops.lstm(G, LC.dev_order(order, dev), None if G is not None else P["b"], P["w_hh"], None if h0 is None else h0.to(dev),
+             None if c0 is None else c0.to(dev), hT, cT, h_all, B, T)
     torch.cuda.synchronize()
     return hT.cpu(), cT.cpu(), None if h_all is None else h_all.cpu()
 
@@ -58,11 +49,8 @@ def _run(dev, P, x=None, order=None, h0=None, c0=None, T=None, with_all=True, G=
 def _check(name, got, ref, t32):
     """got / ref / t32: (hT, cT, h_all) of the kernel, the float64 restatement, torch's fp32 LSTM."""
     for what, g, r, t in zip(("hT", "cT", "h_all"), got, ref, t32):
-        gap32 = float(np.abs(t.double().numpy() - r).max())
-        err = float(np.abs(g.double().numpy() - r).max())
-        print(f"{name} {what}: err {err:.2e} gap32 {gap32:.2e} err/bar {err / (K * gap32):.2f}")
-        assert torch.isfinite(g).all()
-        assert err <= K * gap32, f"{name} {what}: {err:.2e} > {K} x {gap32:.2e}"
+        err, bar, _ = LC.err_and_bar(name, what, g, r, t.double().numpy(), K)       # bar = K x gap32
+        assert err <= bar, f"{name} {what}: {err:.2e} > {bar:.2e}"
 
 
 @pytest.mark.parametrize("B,T", SHAPES)

@@ -68,34 +68,42 @@ def gpu_step(name):
     print("RESULT " + json.dumps(res), flush=True)
 
 
-def cpu_lstm(B, T, reps=3):
+def cpu_lstm(B, T, reps=3, backward=False):
+    """torch's CPU nn.LSTM on the same shape: the forward without grad mode, or (tools/eda_train_bench.py) forward + backward."""
     import torch
     torch.manual_seed(0)
     lstm = torch.nn.LSTM(H, H, 1, batch_first=True)
-    x = torch.randn(B, T, H)
-    with torch.no_grad():
-        lstm(x)
-        out = []
-        for _ in range(reps):
-            t0 = time.perf_counter()
-            lstm(x)
+    x = torch.randn(B, T, H, requires_grad=backward)
+    R = torch.randn(B, T, H) if backward else None
+    out = []
+    for i in range(reps + 1):
+        lstm.zero_grad()
+        x.grad = None
+        t0 = time.perf_counter()
+        if backward:
+            (lstm(x)[0] * R).sum().backward()
+        else:
+            with torch.no_grad():
+                lstm(x)
+        if i:                                      # the first call warms up
             out.append(1e3 * (time.perf_counter() - t0))
-    import torch as _t
-    return dict(step=f"cpu_nn_lstm_B{B}_T{T}", B=B, T=T, ms=statistics.median(out), us_per_step=1e3 * statistics.median(out) / T,
-                threads=_t.get_num_threads())
+    med = statistics.median(out)
+    res = dict(step=f"cpu_nn_lstm_fwd_bwd_B{B}_T{T}", fwd_bwd_ms=med) if backward else dict(step=f"cpu_nn_lstm_B{B}_T{T}", ms=med)
+    return dict(res, B=B, T=T, us_per_step=1e3 * med / T, threads=torch.get_num_threads())
 
 
-def main():
+def main(script=__file__, steps=STEPS, gpu_step=gpu_step, cpu=cpu_lstm, out="eda_bench.json"):
+    """--step NAME: that GPU step in this process; otherwise every step of `script` as a child process, then the CPU lines."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--step")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "eda_bench.json"))
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", out))
     a = ap.parse_args()
     if a.step:
         gpu_step(a.step)
         return
     results = []
-    for name, limit in STEPS:
-        r = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", name],
+    for name, limit in steps:
+        r = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(script), "--step", name],
                            capture_output=True, text=True)
         lines = [l for l in r.stdout.splitlines() if l.startswith("RESULT ")]
         if r.returncode != 0 or not lines:
@@ -105,7 +113,7 @@ def main():
         results.append(json.loads(lines[-1][7:]))
         print(lines[-1], flush=True)
     for B, T in SHAPES.values():
-        results.append(cpu_lstm(B, T))
+        results.append(cpu(B, T))
         print("RESULT " + json.dumps(results[-1]), flush=True)
     with open(a.out, "w") as f:
         json.dump(results, f, indent=1)

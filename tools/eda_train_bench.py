@@ -8,36 +8,18 @@ Shapes: B = 1, T = 5000 and B = 64, T = 500, as tools/eda_bench.py.  The parent 
 process of its own under `timeout`, run one after the other, and the first one that fails ends the run.  Device times are medians of
 7 repeats between two events on the stream, after warm-up calls.
 """
-import argparse
 import json
 import os
-import statistics
-import subprocess
 import sys
-import time
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
 
+from tools.eda_bench import _median_ms, cpu_lstm, main  # noqa: E402
+
 SHAPES = {"b1": (1, 5000), "b64": (64, 500)}
 STEPS = [("train_b1", 240), ("train_b64", 240)]
 H, N_SPK, REPS = 256, 4, 7
-
-
-def _median_ms(fn, warmup, reps):
-    import torch
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        out.append(a.elapsed_time(b))
-    return statistics.median(out), min(out), max(out)
 
 
 def gpu_step(name):
@@ -88,53 +70,5 @@ def gpu_step(name):
     print("RESULT " + json.dumps(res), flush=True)
 
 
-def cpu_lstm(B, T, reps=3):
-    import torch
-    torch.manual_seed(0)
-    lstm = torch.nn.LSTM(H, H, 1, batch_first=True)
-    x = torch.randn(B, T, H, requires_grad=True)
-    R = torch.randn(B, T, H)
-    out = []
-    for i in range(reps + 1):
-        lstm.zero_grad()
-        x.grad = None
-        t0 = time.perf_counter()
-        y, _ = lstm(x)
-        (y * R).sum().backward()
-        if i:                                      # the first call warms up
-            out.append(1e3 * (time.perf_counter() - t0))
-    med = statistics.median(out)
-    return dict(step=f"cpu_nn_lstm_fwd_bwd_B{B}_T{T}", B=B, T=T, fwd_bwd_ms=med, us_per_step=1e3 * med / T, threads=torch.get_num_threads())
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--step")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "eda_train_bench.json"))
-    a = ap.parse_args()
-    if a.step:
-        gpu_step(a.step)
-        return
-    results = []
-    for name, limit in STEPS:
-        r = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", name],
-                           capture_output=True, text=True)
-        lines = [l for l in r.stdout.splitlines() if l.startswith("RESULT ")]
-        if r.returncode != 0 or not lines:
-            print(f"{name}: exit {r.returncode}\n{r.stdout[-2000:]}\n{r.stderr[-2000:]}", flush=True)
-            results.append(dict(step=name, failed=r.returncode))
-            break                                  # nothing more is started on the GPU after a failed step
-        results.append(json.loads(lines[-1][7:]))
-        print(lines[-1], flush=True)
-    for B, T in SHAPES.values():
-        results.append(cpu_lstm(B, T))
-        print("RESULT " + json.dumps(results[-1]), flush=True)
-    with open(a.out, "w") as f:
-        json.dump(results, f, indent=1)
-        f.write("\n")
-    if any("failed" in r for r in results):
-        raise SystemExit(1)
-
-
 if __name__ == "__main__":
-    main()
+    main(__file__, STEPS, gpu_step, lambda B, T: cpu_lstm(B, T, backward=True), "eda_train_bench.json")

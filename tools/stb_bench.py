@@ -83,7 +83,7 @@ def session_step(B):
         setattr(mod, name, wrapper)
         return fn
 
-    saved = [(ops, n, timed(ops, n, l)) for n, l in (("stb_center", "center"), ("lstm", "lstm"), ("stb_track", "track"),
+    saved = [(ops, n, timed(ops, n, l)) for n, l in (("stb_center", "center"), ("lstm_train", "lstm"), ("stb_track", "track"),
                                                      ("eda_head", "head"), ("eda_count", "count"), ("linear_step_f32", "lstm_input_gemm"))]
     saved.append((m, "_encode", timed(m, "_encode", "encoder")))
     split = {}
