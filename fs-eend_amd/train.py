@@ -79,9 +79,14 @@ def drop_site_seed(base: int, site: int) -> int:
 
 
 def never_graded(name: str) -> bool:
-    """Parameters of the FS model that are not on the forward path: the decoder's dead input projection
-    and the fusion layers' norm12."""
+    """Parameters of the FS and LS models that are not on the forward path: the decoder's dead input
+    projection and the fusion layers' norm12 (merge_tfm_encoder.py / merge_retnet_layer.py:93)."""
     return name.startswith("dec.encoder.") or name.startswith("dec.encoder_norm.") or ".norm12." in name
+
+
+# dropout site ids: FS encoder layer i -> 16*i + k, decoder layer i of either model -> 4096 + 16*i + k, with k (SITE_ATT: FS only;
+# the LS Conformer blocks number their own six sites, train_ls.py):
+SITE_ATT, SITE_OUT1, SITE_SPK, SITE_OUT2, SITE_FF, SITE_FFOUT = 0, 1, 2, 3, 4, 5
 
 
 class FlatState:
@@ -143,22 +148,20 @@ class _AttnSave:
         self.ctx = torch.empty(nseq * Tp, D, dtype=F16, device=dev)
 
 
-class _Buffers:
-    """Device buffers of one (B, Tp, C) training shape."""
+class _StepBuffers:
+    """Device buffers of one (B, Tp, C) training shape that both steps have: the input slab, the embedding / attractor rows, the decoder
+    layers' saved tensors (`mixer(nseq)` builds those of a layer's time mixer) and the backward temporaries of the shared frame."""
 
-    def __init__(self, dev, B, Tp, C, n_enc, n_dec, F_enc, F_dec, Fin, Fin_pad):
-        e = lambda *s, dt: torch.empty(*s, dtype=dt, device=dev)
+    def __init__(self, dev, B, Tp, C, n_dec, F_dec, Fin_pad, mixer):
+        e = self._e = lambda *s, dt: torch.empty(*s, dtype=dt, device=dev)
         Me, Md = B * Tp, B * C * Tp
         Mx = max(Me, Md)
         self.xin16 = torch.zeros(Me, Fin_pad, dtype=F16, device=dev)
-        self.bn_mean, self.bn_var = e(Fin, dt=F32), e(Fin, dt=F32)
         self.h32 = e(Me, D, dt=F32)
         self.site0 = _Site(dev, Me)
-        self.enc = [dict(att=_AttnSave(dev, B, Tp), s1=_Site(dev, Me), hid=e(Me, F_enc, dt=F16), s2=_Site(dev, Me))
-                    for _ in range(n_enc)]
         self.emb32, self.emb16, self.inv_norm = e(Me, D, dt=F32), e(Me, D, dt=F16), e(Me, dt=F32)
         self.a32, self.a16 = e(Md, D, dt=F32), e(Md, D, dt=F16)
-        self.dec = [dict(att=_AttnSave(dev, B * C, Tp), s11=_Site(dev, Md), qkv=e(Md, 3 * D, dt=F16), o2=e(Md, D, dt=F16),
+        self.dec = [dict(mix=mixer(B * C), s11=_Site(dev, Md), qkv=e(Md, 3 * D, dt=F16), o2=e(Md, D, dt=F16),
                          s21=_Site(dev, Md), hid=e(Md, F_dec, dt=F16), s22=_Site(dev, Md)) for _ in range(n_dec)]
         # backward temporaries
         self.g32 = e(Md, D, dt=F32)
@@ -166,13 +169,8 @@ class _Buffers:
         self.de32 = e(Me, D, dt=F32)
         self.ds16 = e(Mx, D, dt=BF16)
         self.dctx16 = e(Mx, D, dt=BF16)
-        self.dh16 = e(Mx * max(F_enc, F_dec), dt=BF16)
-        self.dqkv16 = e(Mx, 3 * D, dt=BF16)
-        self.dot_ws = e(Mx * D, dt=BF16)
-        self.dh_ws = e(max(B, B * C) * H * Tp, dt=F32)
         self.gsum16 = e(Me, D, dt=BF16)
         self.demb16 = e(Me, D, dt=BF16)
-        self.dy_in = e(Me, Fin_pad, dt=BF16)
         self.conv_tmp = e(D * 19 * D, dt=F32)
         self.dpc = e(C, D, dt=F32)
         self.pc = e(C, D, dt=F32)
@@ -180,10 +178,58 @@ class _Buffers:
         self.loss = torch.zeros(4, dtype=F32, device=dev)         # [bce, emb, -, -]
 
 
+class _Buffers(_StepBuffers):
+    """... and what the FS step adds: the input BatchNorm statistics, the encoder layers, the causal attention's backward scratch."""
+
+    def __init__(self, dev, B, Tp, C, n_enc, n_dec, F_enc, F_dec, Fin, Fin_pad):
+        super().__init__(dev, B, Tp, C, n_dec, F_dec, Fin_pad, lambda nseq: _AttnSave(dev, nseq, Tp))
+        e = self._e
+        Me = B * Tp
+        Mx = max(Me, B * C * Tp)
+        self.bn_mean, self.bn_var = e(Fin, dt=F32), e(Fin, dt=F32)
+        self.enc = [dict(att=_AttnSave(dev, B, Tp), s1=_Site(dev, Me), hid=e(Me, F_enc, dt=F16), s2=_Site(dev, Me))
+                    for _ in range(n_enc)]
+        self.dh16 = e(Mx * max(F_enc, F_dec), dt=BF16)
+        self.dqkv16 = e(Mx, 3 * D, dt=BF16)
+        self.dot_ws = e(Mx * D, dt=BF16)
+        self.dh_ws = e(max(B, B * C) * H * Tp, dt=F32)
+        self.dy_in = e(Me, Fin_pad, dt=BF16)
+
+
+def _pack_ffn(W, key, w1, bufs):        # (W1, W2) f16 for the forward, (W2^T, W1^T) bf16 for the data gradient
+    pre, Fh = key[:-3], w1.shape[0]
+    _call("eend_ffn_train_stream_pack", w1, W[pre + ".w2"], bufs[0], Fh)
+    _call("eend_ffn_train_stream_pack", W[pre + ".w2T"], W[pre + ".w1T"], bufs[1], Fh)
+
+
+# The packed weight streams, re-packed from the operand copies after every parameter update.  One row per kind:
+#   kind, key predicate (key, operand copy, all copies), element-count entry, its arguments, dtype of each packed buffer, pack call
+_STREAM_KINDS = (
+    # post-norm ReLU FFN blocks (keys X.w1 / X.w2 / X.w1T / X.w2T): ffn_train_stream.hip
+    ("ffn", lambda k, w, W: k.endswith(".w1") and all(k[:-3] + sfx in W for sfx in (".w2", ".w1T", ".w2T")) and w.shape[1] == D,
+     "eend_ffn_train_stream_elems", lambda w: (w.shape[0],), (F16, BF16), _pack_ffn),
+    # K = 256 input projections with a packed-stream form (proj_stream.hip): the retention q / k / v / g operand copies (X.wqkvg)
+    ("proj", lambda k, w, W: k.endswith(".wqkvg") and w.dtype == F16 and w.dim() == 2 and w.shape[1] == D,
+     "eend_proj_stream_elems", lambda w: (w.shape[0],), (F16,),
+     lambda W, k, w, bufs: _call("eend_proj_stream_pack_f16", w, bufs[0], w.shape[0])),
+    # data gradients g += dY W of the K -> 256 projections with a large K (attention in-projections X.in_wT / X.in2_wT: K = 768, retention
+    # projections X.wqkvgT: K = 1024): gemm_acc_stream.hip, from the transposed bf16 operand copies [256][K]
+    ("gacc", lambda k, w, W: k.endswith((".in_wT", ".in2_wT", ".wqkvgT")) and w.dtype == BF16 and w.dim() == 2 and w.shape[0] == D,
+     "eend_gemm_acc_stream_elems", lambda w: (w.shape[1],), (BF16,),
+     lambda W, k, w, bufs: _call("eend_gemm_acc_stream_pack_bf16", w, w.stride(0), bufs[0], w.shape[1])),
+    # time-axis attention in-projections (X.in_w / X.in1_w, f16 [768][256]): packed for the one-launch training forward (attn_stream.hip)
+    ("attn", lambda k, w, W: k.endswith((".in_w", ".in1_w")) and w.dtype == F16 and tuple(w.shape) == (3 * D, D),
+     "eend_inproj_attn_packed_elems", lambda w: (), (F16,),
+     lambda W, k, w, bufs: _call("eend_inproj_attn_pack_f16", w, bufs[0])),
+)
+_PACK_ORDER = ("ffn", "proj", "attn", "gacc")       # the order prep_weights packs in (within a kind: the order of the operand copies)
+
+
 class TrainStepBase:
     """What the FS-EEND and LS-EEND training steps share: the flat parameter / gradient / Adam buffers, the weight
-    re-layout table, dropout site bookkeeping, the generic backward helpers (LayerNorm, ReLU FFN, bias / weight
-    gradients), the data-parallel gradient exchange and the optimiser."""
+    re-layout table and the packed weight streams, dropout site bookkeeping, the generic backward helpers (LayerNorm,
+    ReLU FFN, bias / weight gradients), the attractor decoder layer around its time mixer, the frame of `forward` and
+    `backward` (lengths, labels, loss tail, embedding block), the data-parallel gradient exchange and the optimiser."""
 
     def _init_common(self, model, warmup, lr, schedule_scale, grad_clip, betas, eps, bn_momentum, process_group, drop_seed):
         ps = set()
@@ -257,68 +303,75 @@ class TrainStepBase:
     def _vec(self, key, pname, n, nscale=0, scale=1.0):
         return self._add(key, pname, (n, 1, 1), (1, 0, 0), 2, nscale=nscale, scale=scale, alloc=(n,))
 
+    def _input_table(self, key, pname, Fin):
+        """The encoder's input projection (Fin -> 256), its K padded to the MFMA tile; `pname` also names its weight gradient."""
+        self.Fin, self.Fin_pad, self.in_weight = Fin, (Fin + 127) // 128 * 128, pname
+        self._plain(key, pname, D, Fin, kpad=self.Fin_pad)
+
+    def _embed_table(self):
+        """The look-ahead conv and the embedding half of dec.convert, forward and data-gradient layouts; the sinusoid rows."""
+        m = self.model
+        k = m.cnn.kernel_size[0]
+        self.ktaps, self.cpad = k, m.cnn.padding[0]
+        # forward: [co][tap*256 + ci]; data gradient: [ci][tap'*256 + co] = W[co][ci][k-1-tap']
+        self._add("cnn.w", "cnn.weight", (D, k, D), (D * k, 1, k), 0, alloc=(D, k * D))
+        self._add("cnn.wd", "cnn.weight", (D, k, D), (k, -1, D * k), 1, off=k - 1, alloc=(D, k * D))
+        self._add("convert.w1", "dec.convert.weight", (D, 1, D), (2 * D, 0, 1), 0)
+        self._add("convert.w1T", "dec.convert.weight", (D, 1, D), (1, 0, 2 * D), 1)
+        self.pe = m.dec.pos_enc.pe[0].to(device=self.dev, dtype=F32).contiguous()       # (5000, 256) sinusoid rows
+
+    def _dec_table(self, i):
+        """Decoder layer i after its time mixer: the mixer's out-projection, the speaker-axis attention, the FFN -- [N][K] f16 and
+        transposed bf16 copies (the mixer's own in-projection entries are the subclass's)."""
+        p_ = f"{self.DEC_PREFIX}{i}."
+        Fh = self.flat.shapes[p_ + "linear1.weight"][0]
+        for key, pname, N, K in (("out1_w", "self_attn1.out_proj.weight", D, D), ("in2_w", "self_attn2.in_proj_weight", 3 * D, D),
+                                 ("out2_w", "self_attn2.out_proj.weight", D, D), ("w1", "linear1.weight", Fh, D),
+                                 ("w2", "linear2.weight", D, Fh)):
+            self._plain(f"d{i}.{key}", p_ + pname, N, K)
+            self._transposed(f"d{i}.{key}T", p_ + pname, N, K)
+
     def _table_end(self):
         arr = (_lib.PrepEntry * len(self._entries))(*self._entries)
         raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
         self._table = raw.to(self.dev)
         self._n_entries = len(self._entries)
-        # post-norm ReLU FFN blocks (keys X.w1 / X.w2 / X.w1T / X.w2T): packed weight streams of ffn_train_stream.hip, re-packed from the
-        # operand copies after every parameter update -- (W1, W2) f16 for the forward, (W2^T, W1^T) bf16 for the data gradient
-        self._ffn_streams = {}
-        for key in list(self.W):
-            if key.endswith(".w1") and all(key[:-3] + sfx in self.W for sfx in (".w2", ".w1T", ".w2T")):
-                pre = key[:-3]
-                Fh = self.W[key].shape[0]
-                n = _lib.load().eend_ffn_train_stream_elems(Fh)
-                if n > 0 and self.W[key].shape[1] == D:
-                    self._ffn_streams[pre] = (torch.empty(n, dtype=F16, device=self.dev), torch.empty(n, dtype=BF16, device=self.dev), Fh)
-        self._stream_of_w1 = {self.W[pre + ".w1"].data_ptr(): pre for pre in self._ffn_streams}
-        # K = 256 input projections with a packed-stream form (proj_stream.hip): the retention q / k / v / g operand copies (X.wqkvg)
-        self._proj_streams = {}
-        for key in list(self.W):
-            w = self.W[key]
-            if key.endswith(".wqkvg") and w.dtype == F16 and w.dim() == 2 and w.shape[1] == D:
-                n = _lib.load().eend_proj_stream_elems(int(w.shape[0]))
-                if n > 0:
-                    self._proj_streams[key] = torch.empty(n, dtype=F16, device=self.dev)
-        # data gradients g += dY W of the K -> 256 projections with a large K (attention in-projections X.in_wT / X.in2_wT: K = 768, retention
-        # projections X.wqkvgT: K = 1024): packed streams of gemm_acc_stream.hip from the transposed bf16 operand copies [256][K]
-        self._gacc_streams = {}
-        for key in list(self.W):
-            w = self.W[key]
-            if (key.endswith(".in_wT") or key.endswith(".in2_wT") or key.endswith(".wqkvgT")) and w.dtype == BF16 and w.dim() == 2 and w.shape[0] == D:
-                n = _lib.load().eend_gemm_acc_stream_elems(int(w.shape[1]))
-                if n > 0:
-                    self._gacc_streams[key] = torch.empty(n, dtype=BF16, device=self.dev)
-        self._gacc_of_w = {self.W[k].data_ptr(): k for k in self._gacc_streams}
-        # time-axis attention in-projections (X.in_w / X.in1_w, f16 [768][256]): packed for the one-launch training forward (attn_stream.hip)
-        self._attn_packed = {}
-        for key in list(self.W):
-            w = self.W[key]
-            if (key.endswith(".in_w") or key.endswith(".in1_w")) and w.dtype == F16 and tuple(w.shape) == (3 * D, D):
-                self._attn_packed[key] = torch.empty(_lib.load().eend_inproj_attn_packed_elems(), dtype=F16, device=self.dev)
-        self._attn_packed_of_w = {self.W[k].data_ptr(): k for k in self._attn_packed}
+        # the packed weight streams (_STREAM_KINDS): one registry, data_ptr of the operand copy -> (kind, key, packed buffers)
+        L = _lib.load()
+        self._streams = {}
+        for kind, match, elems, arg, dtypes, _ in _STREAM_KINDS:
+            for key, w in list(self.W.items()):
+                if match(key, w, self.W):
+                    n = getattr(L, elems)(*arg(w))
+                    if n > 0:
+                        self._streams[w.data_ptr()] = (kind, key, tuple(torch.empty(n, dtype=dt, device=self.dev) for dt in dtypes))
+        pack = {row[0]: row[-1] for row in _STREAM_KINDS}
+        self._packs = [(pack[kind], key, bufs) for k in _PACK_ORDER for kind, key, bufs in self._streams.values() if kind == k]
 
     def prep_weights(self):
-        """f32 parameters -> MFMA operand copies (one launch), then the packed FFN streams."""
+        """f32 parameters -> MFMA operand copies (one launch), then the packed weight streams."""
         _call("eend_prep_weights", self._table, self._n_entries)
-        for pre, (fw, bw, Fh) in self._ffn_streams.items():
-            _call("eend_ffn_train_stream_pack", self.W[pre + ".w1"], self.W[pre + ".w2"], fw, Fh)
-            _call("eend_ffn_train_stream_pack", self.W[pre + ".w2T"], self.W[pre + ".w1T"], bw, Fh)
-        for key, buf in self._proj_streams.items():
-            _call("eend_proj_stream_pack_f16", self.W[key], buf, int(self.W[key].shape[0]))
-        for key, buf in self._attn_packed.items():
-            _call("eend_inproj_attn_pack_f16", self.W[key], buf)
-        for key, buf in self._gacc_streams.items():
-            w = self.W[key]
-            _call("eend_gemm_acc_stream_pack_bf16", w, w.stride(0), buf, int(w.shape[1]))
+        for pack, key, bufs in self._packs:
+            pack(self.W, key, self.W[key], bufs)
+
+    def _stream(self, kind, w):
+        """The packed buffers of kind `kind` built from the operand copy `w`, or None."""
+        s = self._streams.get(w.data_ptr())
+        return s[2] if s is not None and s[0] == kind else None
 
     def _ffn_stream_for(self, w1, M, F):
-        """Key of the packed streams serving this FFN at M rows, or None (the un-packed, row-major entries then)."""
-        pre = self._stream_of_w1.get(w1.data_ptr())
-        if pre is None or M % 16 != 0 or not _lib.load().eend_ffn_train_stream_ok(M, F, D):
+        """(forward, data-gradient) packed streams serving this FFN at M rows, or None (the un-packed, row-major entries then)."""
+        bufs = self._stream("ffn", w1)
+        if bufs is None or M % 16 != 0 or not _lib.load().eend_ffn_train_stream_ok(M, F, D):
             return None
-        return pre
+        return bufs
+
+    def _gacc_stream_for(self, wT, M, K):
+        """The packed stream of the data-gradient GEMM g += dY W where it pays (gacc_stream_min_rows), or None (gemm.hip's tiles then)."""
+        bufs = self._stream("gacc", wT)
+        if bufs is None or M < self.gacc_stream_min_rows or not _lib.load().eend_gemm_acc_stream_ok(M, K, K):
+            return None
+        return bufs[0]
 
     # ------------------------------------------------------------------ helpers
     def _table_for(self, srcs, T):
@@ -357,10 +410,10 @@ class TrainStepBase:
         """linear1 + ReLU + dropout + linear2 + dropout + residual + LayerNorm of a post-norm block.  One launch (ffn.hip MODE 3: the hidden
         activations are written once for the backward and never re-read) where the shape allows, else the two GEMM launches."""
         F = hid.shape[1]
-        pre = self._ffn_stream_for(w1, M, F) if x16.shape[1] == 256 and x16.stride(0) == 256 else None
-        if pre is not None:
+        streams = self._ffn_stream_for(w1, M, F) if x16.shape[1] == 256 and x16.stride(0) == 256 else None
+        if streams is not None:
             # packed weight stream (ffn_train_stream.hip): hid is written in the BLOCKED layout its two consumers read (_ffn_bwd)
-            _call("eend_ffn_train_stream_f16", x16, 256, self._ffn_streams[pre][0], b1, b2, res, 1.0, self._P(ln + ".weight"), self._P(ln + ".bias"),
+            _call("eend_ffn_train_stream_f16", x16, 256, streams[0], b1, b2, res, 1.0, self._P(ln + ".weight"), self._P(ln + ".bias"),
                   1e-5, out32, site.out16, hid, site.xhat, site.rstd, M, F, drop_hidden, drop_out)
             return
         if F % 64 == 0 and (M + 128) * F * 2 < (1 << 32) and x16.shape[1] == 256:
@@ -397,9 +450,9 @@ class TrainStepBase:
 
     def _gemm_acc(self, a16, K, wT, g32, M):
         """g32 += a16 wT^T in place: the packed-stream kernel where it pays (see _gemm_acc_ln_bwd), else gemm.hip's tiles."""
-        key = self._gacc_of_w.get(wT.data_ptr())
-        if key is not None and M >= self.gacc_stream_min_rows and _lib.load().eend_gemm_acc_stream_ok(M, K, K):
-            _call("eend_gemm_acc_stream_bf16", a16, K, self._gacc_streams[key], g32, M, K)
+        stream = self._gacc_stream_for(wT, M, K)
+        if stream is not None:
+            _call("eend_gemm_acc_stream_bf16", a16, K, stream, g32, M, K)
         else:
             _call("eend_gemm_acc_bf16", a16, K, wT, K, g32, 1.0, g32, None, M, K)
 
@@ -410,12 +463,12 @@ class TrainStepBase:
         """g32 += a16 wT^T (the data gradient of a K -> 256 linear joining the residual-gradient stream), then the LayerNorm backward of the
         post-norm site `site` that stream now stands in front of -- one launch (gemm.hip EPI_RES_LNBWD): `_ln_bwd`'s outputs, the f32 stream
         read and written once instead of twice."""
-        key = self._gacc_of_w.get(wT.data_ptr())
-        if key is not None and M >= self.gacc_stream_min_rows and _lib.load().eend_gemm_acc_stream_ok(M, K, K):
+        stream = self._gacc_stream_for(wT, M, K)
+        if stream is not None:
             # from about 100 k rows the packed-stream GEMM (wave-owned rows, no k-tile barriers) + the LayerNorm backward as its own pass beat
             # the tiled GEMM with the LayerNorm backward in its epilogue: [196608, 256, 768] 172 + 95 us against 314 us, [393216, 256, 1024]
             # 363 + 192 against 665 us (same box)
-            _call("eend_gemm_acc_stream_bf16", a16, K, self._gacc_streams[key], g32, M, K)
+            _call("eend_gemm_acc_stream_bf16", a16, K, stream, g32, M, K)
             self._ln_bwd(g32, site, ln, ds16, M, drop, bias)
             return
         _call("eend_gemm_acc_lnbwd_bf16", a16, K, wT, K, g32, site.xhat, site.rstd, self._P(ln + ".weight"), g32, ds16, self.ws, WS_FLOATS,
@@ -426,12 +479,12 @@ class TrainStepBase:
         W = self.W
         Fh = hid.shape[1]
         dh = dh16[:M * Fh].view(M, Fh)
-        pre = self._ffn_stream_for(W[wkey + ".w1"], M, Fh) if x_in16.stride(0) == 256 else None      # the same predicate as the forward's
-        if pre is not None:
+        streams = self._ffn_stream_for(W[wkey + ".w1"], M, Fh) if x_in16.stride(0) == 256 else None      # the same predicate as the forward's
+        if streams is not None:
             # hid and dH in the blocked layout: flags 2 (X blocked) / 4 (dY blocked) of the weight-gradient entries
             g2 = self._G(p_ + "linear2.weight").view(-1)
             _call("eend_wgrad_bf16", ds16, D, hid, Fh, 1 | 2, M, D, Fh, self.ws, WS_FLOATS, g2, Fh, Fh, 1.0, 0)
-            _call("eend_ffn_bwd_data_stream_bf16", ds16, D, self._ffn_streams[pre][1], hid, drop_scale, dh, g32, M, Fh)
+            _call("eend_ffn_bwd_data_stream_bf16", ds16, D, streams[1], hid, drop_scale, dh, g32, M, Fh)
             _call("eend_wgrad_bias_bf16", dh, Fh, x_in16, D, 1 | 4, M, Fh, D, self.ws, WS_FLOATS, self._G(p_ + "linear1.weight"), D, D,
                   self._G(p_ + "linear1.bias"), 1.0, 0)
             return
@@ -466,6 +519,158 @@ class TrainStepBase:
 
     def _pit_assign(self, P, ys, ts, n_spk):
         return P.batch_pit_n_speaker_loss(ys, ts, n_spk)[1]
+
+    # ------------------------------------------------------------------ the frame of forward / backward
+    def _buffers(self, B, Tp, C):
+        key = (B, Tp, C)
+        b = self._bufs.get(key)
+        if b is None:
+            if len(self._bufs) >= 2:
+                self._bufs.clear()
+            b = self._bufs[key] = self._new_buffers(B, Tp, C)
+        return b
+
+    def _begin_forward(self, src, labels, ilens, dropout, Tv=None):
+        """Features on the device, the buffers of this (B, Tp, C), the cached length tensors, the forward count and dropout base, the
+        (B, T, C) label tensor and the feature pointer table.  Tv: the length the model pads every sequence to (None: T) -> (bf, srcs)."""
+        dev = self.dev
+        srcs = [s.to(device=dev, dtype=F32).contiguous() for s in src]
+        B, T = len(srcs), max(int(s.shape[0]) for s in srcs)
+        ncols = [int(l.shape[1]) for l in labels]
+        C = max(ncols)
+        Tv = T if Tv is None else Tv
+        Tp = ops.frames_pad(Tv)
+        bf = self._buffers(B, Tp, C)
+        il = [min(int(l), T) for l in ilens]
+        key = (tuple(il), tuple(ncols), T)
+        if getattr(bf, "len_key", None) != key:              # cached: no H2D copies in the steady state
+            bf.il = torch.tensor(il, dtype=I32, device=dev)
+            bf.tl = torch.full((B,), Tv, dtype=I32, device=dev)
+            bf.nc = torch.tensor(ncols, dtype=I32, device=dev)
+            bf.len_key = key
+        bf.shape, bf.Tv = (B, T, Tp, C), Tv
+        self._fwd_count += 1
+        bf.drop_base = drop_step_seed(self.drop_seed, self._fwd_count) if (dropout and self.drop_p > 0.0) else None
+        bf.drop_specs = {}
+        bf.n_frames = sum(int(l.shape[0]) for l in labels)
+        if all(tuple(l.shape) == (T, C) for l in labels):    # equal-length chunks (the training set-up): one stack
+            lab = torch.stack([l.to(device=dev, dtype=F32) for l in labels]).contiguous()
+        else:
+            lab = torch.zeros(B, T, C, dtype=F32, device=dev)
+            for b_, l in enumerate(labels):
+                lab[b_, :l.shape[0], :l.shape[1]] = l.to(device=dev, dtype=F32)
+        bf.labels = lab
+        bf.ptrs, bf.lens = self._table_for(srcs, T)
+        return bf, srcs
+
+    def _embed_fwd(self, bf, enc_out16):
+        """Encoder output -> unit embeddings (truncate, look-ahead conv, L2 norm) -> the decoder's input rows convert(cat(emb, pe_c))."""
+        B, T, Tp, C = bf.shape
+        bf.enc_out16 = enc_out16
+        _call("eend_conv1d_l2norm_train_f16", enc_out16, self.W["cnn.w"], self._P("cnn.bias"), bf.il, bf.emb32, bf.emb16, bf.inv_norm, B, Tp,
+              D, self.ktaps, self.cpad)
+        _call("eend_convert_const_f32", 0, self._P("dec.convert.weight"), self._P("dec.convert.bias"), self.pe, bf.pc, None, None,
+              None, C)
+        ops.convert_fanout(bf.emb16, self.W["convert.w1"], bf.pc, bf.a32, bf.a16, B, Tp, C)
+        return bf.a16
+
+    def _dec_layer_fwd(self, bf, i, ctx16):
+        """Decoder layer i after its time mixer has written its context rows `ctx16`: out-projection -> norm11, attention over the
+        speaker slots -> norm21, FFN -> norm22 (merge_tfm_encoder.py:364-400, merge_retnet_layer.py:233-253) -> the layer's f16 output."""
+        W, sv, p_, so = self.W, bf.dec[i], f"{self.DEC_PREFIX}{i}.", 4096 + 16 * i
+        B, T, Tp, C = bf.shape
+        Md = B * C * Tp
+        self._linear_ln(ctx16, W[f"d{i}.out1_w"], self._P(p_ + "self_attn1.out_proj.bias"), bf.a32, p_ + "norm11", sv["s11"], bf.a32,
+                        Md, D, self._drop(bf, so + SITE_OUT1))
+        ops.linear(sv["s11"].out16, W[f"d{i}.in2_w"], self._P(p_ + "self_attn2.in_proj_bias"), sv["qkv"])
+        _call("eend_spk_attn_train_f16", sv["qkv"], sv["o2"], B, C, Tp, H, 0.125, self._drop(bf, so + SITE_SPK))
+        self._linear_ln(sv["o2"], W[f"d{i}.out2_w"], self._P(p_ + "self_attn2.out_proj.bias"), bf.a32, p_ + "norm21", sv["s21"], bf.a32,
+                        Md, D, self._drop(bf, so + SITE_OUT2))
+        self._ffn(sv["s21"].out16, W[f"d{i}.w1"], self._P(p_ + "linear1.bias"), sv["hid"], W[f"d{i}.w2"], self._P(p_ + "linear2.bias"),
+                  bf.a32, p_ + "norm22", sv["s22"], bf.a32, Md, self._drop(bf, so + SITE_FF), self._drop(bf, so + SITE_FFOUT))
+        return sv["s22"].out16
+
+    def _finish_forward(self, bf, pit, fused_loss):
+        """Head + BCE (+ PIT label choice) + emb-consistency loss and their gradients w.r.t. attractors / embeddings; with
+        fused_loss=False only the head's logits, the normalised attractors and the emb-consistency loss."""
+        B, T, Tp, C = bf.shape
+        lab = bf.labels
+        lens, inv_count = self._emb_loss_args(bf)
+        if not fused_loss:
+            bf.logits_full = torch.empty(B, T, C, dtype=F32, device=self.dev)
+            bf.attr_n = torch.empty(B, T, C, D, dtype=F32, device=self.dev)
+            ops.head_l2dot(bf.emb32, bf.a32, bf.attr_n, bf.logits_full, B, T, Tp, C, D)
+            bf.loss[1] = ops.emb_consistency(bf.emb32.view(B, Tp, D), lab, T, lens=lens, inv_count=inv_count)
+            return bf
+        if pit:
+            il, ncols, _ = bf.len_key
+            lab = bf.labels = self._pit_labels(bf, lab, il, ncols)
+        _call("eend_head_bce_f32", bf.emb32, bf.a32, lab, bf.il, bf.nc, 1.0 / float(bf.n_frames), None, bf.logits, bf.g32, bf.de32,
+              self.ws, WS_FLOATS, bf.loss[0:1], B, T, Tp, C)
+        bf.loss[1] = ops.emb_consistency(bf.emb32.view(B, Tp, D), lab, T, lens=lens, inv_count=inv_count)
+        _call("eend_emb_consistency_bwd_f16", bf.emb16, lab, lens, inv_count, bf.de32, B, T, Tp, D, C)
+        return bf
+
+    def _head_grad_from_dlogits(self, bf, dlogits, emb_loss_grad):
+        """After forward(fused_loss=False): the caller's d loss / d logits -> gradients w.r.t. attractors (bf.g32) / embeddings (bf.de32)."""
+        B, T, Tp, C = bf.shape
+        dl = dlogits.to(device=self.dev, dtype=F32).contiguous()
+        if tuple(dl.shape) != (B, T, C):
+            raise EendHipError(f"backward: dlogits must be ({B}, {T}, {C})")
+        _call("eend_head_bce_f32", bf.emb32, bf.a32, None, None, None, 0.0, dl, None, bf.g32, bf.de32, self.ws, WS_FLOATS,
+              bf.loss[2:3], B, T, Tp, C)
+        if emb_loss_grad != 0.0:
+            lens, scale = self._emb_loss_args(bf, emb_loss_grad)
+            _call("eend_emb_consistency_bwd_f16", bf.emb16, bf.labels, lens, scale, bf.de32, B, T, Tp, D, C)
+
+    def _dec_layer_bwd(self, bf, i, g32, ff_scale):
+        """Backward of `_dec_layer_fwd` up to and including norm11; g32 = gradient w.r.t. the layer output, in and out.  Returns what the
+        mixer's backward needs: the layer's input rows and `below`, the (site, LayerNorm name, dropout spec, bias name) of the
+        LayerNorm that input came out of (None for layer 0) -- its backward rides on the mixer's last data-gradient GEMM."""
+        W, sv, p_, so = self.W, bf.dec[i], f"{self.DEC_PREFIX}{i}.", 4096 + 16 * i
+        B, T, Tp, C = bf.shape
+        Md = B * C * Tp
+        dsd, dctx, dqkv = bf.ds16[:Md], bf.dctx16[:Md], bf.dqkv16[:Md]
+        if i == len(bf.dec) - 1:      # (the other layers' norm22 backward ran in the epilogue of the layer above's last data-gradient GEMM)
+            self._ln_bwd(g32, sv["s22"], p_ + "norm22", dsd, Md, self._drop(bf, so + SITE_FFOUT), p_ + "linear2.bias")
+        self._ffn_bwd(g32, dsd, bf.dh16, sv["hid"], sv["s21"].out16, Md, f"d{i}", p_, "norm22", ff_scale)
+        # speaker-axis attention block (merge_tfm_encoder.py:373, :388-394)
+        self._ln_bwd(g32, sv["s21"], p_ + "norm21", dsd, Md, self._drop(bf, so + SITE_OUT2), p_ + "self_attn2.out_proj.bias")
+        self._wgrad(dsd, sv["o2"], Md, D, D, p_ + "self_attn2.out_proj.weight")
+        _call("eend_gemm_bf16", dsd, D, W[f"d{i}.out2_wT"], D, None, dctx, D, Md, D, D)
+        _call("eend_spk_attn_bwd_bf16", sv["qkv"], dctx, dqkv, B, C, Tp, H, 0.125, self._drop(bf, so + SITE_SPK))
+        self._wgrad_bias(dqkv, sv["s11"].out16, Md, 3 * D, D, p_ + "self_attn2.in_proj_weight", p_ + "self_attn2.in_proj_bias")
+        # ... its in-projection's data gradient joins the stream, and norm11's backward runs in the same launch
+        self._gemm_acc_ln_bwd(dqkv, 3 * D, W[f"d{i}.in2_wT"], g32, sv["s11"], p_ + "norm11", dsd, Md, self._drop(bf, so + SITE_OUT1),
+                              p_ + "self_attn1.out_proj.bias")
+        if i == 0:
+            return bf.a16, None
+        pb = f"{self.DEC_PREFIX}{i - 1}."         # the layer below ends in norm22
+        return bf.dec[i - 1]["s22"].out16, (bf.dec[i - 1]["s22"], pb + "norm22", self._drop(bf, so - 16 + SITE_FFOUT), pb + "linear2.bias")
+
+    def _embed_bwd(self, bf, g32):
+        """Backward of `_embed_fwd`: g32 = gradient w.r.t. the decoder's input rows -> bf.ge32 = gradient w.r.t. the encoder output."""
+        W = self.W
+        B, T, Tp, C = bf.shape
+        Me = B * Tp
+        # ---- convert fan-out (factored): its constant part, its weight, and the embeddings' share into de32
+        _call("eend_convert_fanout_bwd_f32", g32, bf.gsum16, self.ws, WS_FLOATS, bf.dpc, B, Tp, C)
+        _call("eend_convert_const_f32", 1, None, None, self.pe, None, bf.dpc, self._G("dec.convert.weight"), self._G("dec.convert.bias"), C)
+        self._wgrad(bf.gsum16, bf.emb16, Me, D, D, "dec.convert.weight", ld_out=2 * D, k_out=D)
+        _call("eend_gemm_acc_bf16", bf.gsum16, D, W["convert.w1T"], D, bf.de32, 1.0, bf.de32, None, Me, D)
+        # ---- L2 norm + look-ahead conv; de32 = gradient w.r.t. the unit embeddings (head + emb loss + convert)
+        _call("eend_l2norm_bwd_bf16", bf.emb32, bf.de32, bf.inv_norm, bf.demb16, B, bf.Tv, Tp)
+        self._bias_grad(bf.demb16, Me, D, "cnn.bias")
+        _call("eend_conv1d_wgrad_bf16", bf.demb16, bf.enc_out16, bf.il, B, Tp, D, self.ktaps, self.cpad, self.ws, WS_FLOATS, bf.conv_tmp,
+              self._G("cnn.weight"))
+        _call("eend_conv1d_dgrad_bf16", bf.demb16, W["cnn.wd"], bf.tl, bf.il, bf.ge32, B, Tp, D, self.ktaps, self.ktaps - 1 - self.cpad)
+        return bf.ge32
+
+    def _input_weight_grad(self, bf, ds16):
+        """Weight gradient of the encoder's input projection from ds16 = gradient w.r.t. its output (bf16), the padded K cut off."""
+        B, T, Tp, C = bf.shape
+        _call("eend_wgrad_bf16", ds16, D, bf.xin16, self.Fin_pad, 1, B * Tp, D, self.Fin_pad, self.ws, WS_FLOATS, self._G(self.in_weight),
+              self.Fin, self.Fin, 1.0, 0)
 
     # ------------------------------------------------------------------ optimiser
     def accumulate_grads(self, index: int, count: int):
@@ -551,17 +756,15 @@ class FsTrainStep(TrainStepBase):
         self._build_weight_table()
 
     # ------------------------------------------------------------------ weight operand copies
-    def _build_weight_table(self):
-        m, fl, dev = self.model, self.flat, self.dev
-        self._table_begin()
-        W = self.W
-        add, plain, transposed, vec = self._add, self._plain, self._transposed, self._vec
+    DEC_PREFIX = "dec.attractor_decoder.layers."
 
-        Fin = m.enc.in_size
-        self.Fin, self.Fin_pad = Fin, (Fin + 127) // 128 * 128
+    def _build_weight_table(self):
+        m = self.model
+        self._table_begin()
+        plain, transposed, vec = self._plain, self._transposed, self._vec
         qs = ops.QSCALE_LOG2
-        plain("enc.in.w", "enc.encoder.weight", D, Fin, kpad=self.Fin_pad)
-        transposed("enc.in.wT", "enc.encoder.weight", D, Fin, rows_alloc=self.Fin_pad)
+        self._input_table("enc.in.w", "enc.encoder.weight", m.enc.in_size)
+        transposed("enc.in.wT", "enc.encoder.weight", D, self.Fin, rows_alloc=self.Fin_pad)
         for i, l in enumerate(m.enc.transformer_encoder.layers):
             p_ = f"enc.transformer_encoder.layers.{i}."
             Fh = l.linear1.out_features
@@ -574,65 +777,40 @@ class FsTrainStep(TrainStepBase):
             transposed(f"e{i}.w1T", p_ + "linear1.weight", Fh, D)
             plain(f"e{i}.w2", p_ + "linear2.weight", D, Fh)
             transposed(f"e{i}.w2T", p_ + "linear2.weight", D, Fh)
-        k = m.cnn.kernel_size[0]
-        self.ktaps, self.cpad = k, m.cnn.padding[0]
-        # forward: [co][tap*256 + ci]; data gradient: [ci][tap'*256 + co] = W[co][ci][k-1-tap']
-        add("cnn.w", "cnn.weight", (D, k, D), (D * k, 1, k), 0, alloc=(D, k * D))
-        add("cnn.wd", "cnn.weight", (D, k, D), (k, -1, D * k), 1, off=k - 1, alloc=(D, k * D))
-        add("convert.w1", "dec.convert.weight", (D, 1, D), (2 * D, 0, 1), 0)
-        add("convert.w1T", "dec.convert.weight", (D, 1, D), (1, 0, 2 * D), 1)
-        for i, l in enumerate(m.dec.attractor_decoder.layers):
-            p_ = f"dec.attractor_decoder.layers.{i}."
-            Fh = l.linear1.out_features
+        self._embed_table()
+        for i in range(len(m.dec.attractor_decoder.layers)):
+            p_ = f"{self.DEC_PREFIX}{i}."
             plain(f"d{i}.in1_w", p_ + "self_attn1.in_proj_weight", 3 * D, D, nscale=D, scale=qs)
             vec(f"d{i}.in1_b", p_ + "self_attn1.in_proj_bias", 3 * D, nscale=D, scale=qs)
             transposed(f"d{i}.in1_wT", p_ + "self_attn1.in_proj_weight", 3 * D, D)
-            plain(f"d{i}.out1_w", p_ + "self_attn1.out_proj.weight", D, D)
-            transposed(f"d{i}.out1_wT", p_ + "self_attn1.out_proj.weight", D, D)
-            plain(f"d{i}.in2_w", p_ + "self_attn2.in_proj_weight", 3 * D, D)
-            transposed(f"d{i}.in2_wT", p_ + "self_attn2.in_proj_weight", 3 * D, D)
-            plain(f"d{i}.out2_w", p_ + "self_attn2.out_proj.weight", D, D)
-            transposed(f"d{i}.out2_wT", p_ + "self_attn2.out_proj.weight", D, D)
-            plain(f"d{i}.w1", p_ + "linear1.weight", Fh, D)
-            transposed(f"d{i}.w1T", p_ + "linear1.weight", Fh, D)
-            plain(f"d{i}.w2", p_ + "linear2.weight", D, Fh)
-            transposed(f"d{i}.w2T", p_ + "linear2.weight", D, Fh)
+            self._dec_table(i)
         self._table_end()
-        self.pe = m.dec.pos_enc.pe[0].to(device=dev, dtype=F32).contiguous()       # (5000, 256) sinusoid rows
 
+    def _new_buffers(self, B, Tp, C) -> _Buffers:
+        m = self.model
+        Fe = m.enc.transformer_encoder.layers[0].linear1.out_features if len(m.enc.transformer_encoder.layers) else D
+        Fd = m.dec.attractor_decoder.layers[0].linear1.out_features if len(m.dec.attractor_decoder.layers) else D
+        return _Buffers(self.dev, B, Tp, C, len(m.enc.transformer_encoder.layers), len(m.dec.attractor_decoder.layers), Fe, Fd,
+                        self.Fin, self.Fin_pad)
 
-    def _buffers(self, B, Tp, C) -> _Buffers:
-        key = (B, Tp, C)
-        b = self._bufs.get(key)
-        if b is None:
-            if len(self._bufs) >= 2:
-                self._bufs.clear()
-            m = self.model
-            Fe = m.enc.transformer_encoder.layers[0].linear1.out_features if len(m.enc.transformer_encoder.layers) else D
-            Fd = m.dec.attractor_decoder.layers[0].linear1.out_features if len(m.dec.attractor_decoder.layers) else D
-            b = _Buffers(self.dev, B, Tp, C, len(m.enc.transformer_encoder.layers), len(m.dec.attractor_decoder.layers),
-                         Fe, Fd, self.Fin, self.Fin_pad)
-            self._bufs[key] = b
-        return b
-
-
-    # ------------------------------------------------------------------ dropout sites
-    # site ids: encoder layer i -> 16*i + k, decoder layer i -> 4096 + 16*i + k, with k:
-    SITE_ATT, SITE_OUT1, SITE_SPK, SITE_OUT2, SITE_FF, SITE_FFOUT = 0, 1, 2, 3, 4, 5
+    def _emb_loss_args(self, bf, grad=None):
+        """(lengths, normalisation) of the embedding-consistency loss and of its gradient scaled by `grad`: unmasked, over B T T
+        (0.0: the kernels' own 1 / (B T T))."""
+        B, T = bf.shape[:2]
+        return None, 0.0 if grad is None else float(grad) / (float(B) * T * T)
 
     def _attn_fwd(self, x16, w, bias, sv: _AttnSave, nseq, Tp, mask_delay, kv_len, drop=None):
-        key = self._attn_packed_of_w.get(w.data_ptr())
-        if key is not None and Tp <= 512 and H == 4 and self.attn_train_fused:
+        packed = self._stream("attn", w)
+        if packed is not None and Tp <= 512 and H == 4 and self.attn_train_fused:
             # in-projection + attention in one launch, Q / K / V^T on chip in between; bf16 head rows + lse saved for the backward
-            _call("eend_inproj_attn_train_bf16", x16, x16.stride(0), self._attn_packed[key], bias, sv.ctx, D, sv.q, sv.k, sv.v, sv.lse, nseq, H, Tp,
+            _call("eend_inproj_attn_train_bf16", x16, x16.stride(0), packed[0], bias, sv.ctx, D, sv.q, sv.k, sv.v, sv.lse, nseq, H, Tp,
                   mask_delay, kv_len, drop)
             return
         _call("eend_inproj_heads_train_bf16", x16, x16.stride(0), w, bias, sv.q, sv.qt, sv.k, sv.kt, sv.v, sv.vt, nseq, Tp, H)
         _call("eend_attn_causal_lse_bf16", sv.q, sv.k, sv.vt, sv.ctx, sv.lse, nseq, H, Tp, D, mask_delay, kv_len, ops.LN2, drop)
 
-
     # ------------------------------------------------------------------ forward (saves activations)
-    def forward(self, src: Sequence[Tensor], labels: Sequence[Tensor], ilens: Sequence[int], pit: bool = False,
+    def forward(self, src: Sequence[Tensor], labels: Sequence[Tensor], ilens: Sequence[int], pit: bool = False, *,
                 fused_loss: bool = True, dropout: bool = True):
         """Train-mode model.forward with every activation the backward needs saved.  labels: prepared (T_i, nspk_i+2)
         tensors (oln_tfm_enc_dec.py:53-75).
@@ -640,47 +818,20 @@ class FsTrainStep(TrainStepBase):
                           (bf.loss = [bce, emb_loss]); `backward(bf)` then completes the step.
         fused_loss=False: stop at the head (bf.logits_full (B,T,C), bf.attr_n (B,T,C,D), bf.loss[1] = emb_loss): the
                           caller computes its own loss on the logits and passes d loss / d logits to `backward`."""
-        m, W, dev = self.model, self.W, self.dev
-        srcs = [s.to(device=dev, dtype=F32).contiguous() for s in src]
-        B, T = len(srcs), max(int(s.shape[0]) for s in srcs)
-        ncols = [int(l.shape[1]) for l in labels]
-        C = max(ncols)
-        Tp = ops.frames_pad(T)
-        bf = self._buffers(B, Tp, C)
-        Me, Md = B * Tp, B * C * Tp
-        il = [min(int(l), T) for l in ilens]
-        key = (tuple(il), tuple(ncols), T)
-        if getattr(bf, "len_key", None) != key:              # cached: no H2D copies in the steady state
-            bf.il = torch.tensor(il, dtype=I32, device=dev)
-            bf.tl = torch.full((B,), T, dtype=I32, device=dev)
-            bf.nc = torch.tensor(ncols, dtype=I32, device=dev)
-            bf.len_key = key
-        bf.shape = (B, T, Tp, C)
-        bf.srcs = srcs
-        self._fwd_count += 1
-        bf.drop_base = drop_step_seed(self.drop_seed, self._fwd_count) if (dropout and self.drop_p > 0.0) else None
-        bf.drop_specs = {}
+        m, W = self.model, self.W
+        bf, srcs = self._begin_forward(src, labels, ilens, dropout)
+        bf.srcs = srcs                    # kept alive: the backward's BatchNorm reads the features again through bf.ptrs
+        B, T, Tp, C = bf.shape
+        Me = B * Tp
         dr = lambda site: self._drop(bf, site)
-        n_frames = sum(int(l.shape[0]) for l in labels)
-        if all(tuple(l.shape) == (T, C) for l in labels):    # equal-length chunks (the training set-up): one stack
-            lab = torch.stack([l.to(device=dev, dtype=F32) for l in labels]).contiguous()
-        else:
-            lab = torch.zeros(B, T, C, dtype=F32, device=dev)
-            for b_, l in enumerate(labels):
-                lab[b_, :l.shape[0], :l.shape[1]] = l.to(device=dev, dtype=F32)
-        bf.labels = lab
         enc = m.enc
-        delay_e = enc.mask_delay if enc.has_mask else Tp
-        kv_e = T
-        bf.delay_e, bf.kv_e = delay_e, kv_e
+        bf.delay_e, bf.kv_e = enc.mask_delay if enc.has_mask else Tp, T
 
         # ---- BatchNorm1d, train mode: batch statistics over all B*T padded frames, running-stat update (model :165-166)
-        ptrs, lens = self._table_for(srcs, T)
-        bf.ptrs, bf.lens = ptrs, lens
-        _call("eend_bn_train_stats_f32", ptrs, lens, -1.0, self.ws, WS_FLOATS, bf.bn_mean, bf.bn_var, enc.bn.running_mean,
+        _call("eend_bn_train_stats_f32", bf.ptrs, bf.lens, -1.0, self.ws, WS_FLOATS, bf.bn_mean, bf.bn_var, enc.bn.running_mean,
               enc.bn.running_var, self.bn_momentum, B, T, self.Fin)
         enc.bn.num_batches_tracked += 1
-        _call("eend_gather_bn_cast_pad_f16", ptrs, lens, -1.0, self._P("enc.bn.weight"), self._P("enc.bn.bias"), bf.bn_mean,
+        _call("eend_gather_bn_cast_pad_f16", bf.ptrs, bf.lens, -1.0, self._P("enc.bn.weight"), self._P("enc.bn.bias"), bf.bn_mean,
               bf.bn_var, enc.bn.eps, bf.xin16, B, T, Tp, self.Fin, self.Fin_pad, 1)
         self._linear_ln(bf.xin16, W["enc.in.w"], self._P("enc.encoder.bias"), None, "enc.encoder_norm", bf.site0, bf.h32, Me,
                         self.Fin_pad)
@@ -688,54 +839,19 @@ class FsTrainStep(TrainStepBase):
         for i, sv in enumerate(bf.enc):
             p_ = f"enc.transformer_encoder.layers.{i}."
             so = 16 * i
-            self._attn_fwd(x16, W[f"e{i}.in_w"], W[f"e{i}.in_b"], sv["att"], B, Tp, delay_e, kv_e, dr(so + self.SITE_ATT))
+            self._attn_fwd(x16, W[f"e{i}.in_w"], W[f"e{i}.in_b"], sv["att"], B, Tp, bf.delay_e, bf.kv_e, dr(so + SITE_ATT))
             self._linear_ln(sv["att"].ctx, W[f"e{i}.out_w"], self._P(p_ + "self_attn.out_proj.bias"), bf.h32, p_ + "norm1", sv["s1"],
-                            bf.h32, Me, D, dr(so + self.SITE_OUT1))
+                            bf.h32, Me, D, dr(so + SITE_OUT1))
             self._ffn(sv["s1"].out16, W[f"e{i}.w1"], self._P(p_ + "linear1.bias"), sv["hid"], W[f"e{i}.w2"], self._P(p_ + "linear2.bias"),
-                      bf.h32, p_ + "norm2", sv["s2"], bf.h32, Me, dr(so + self.SITE_FF), dr(so + self.SITE_FFOUT))
+                      bf.h32, p_ + "norm2", sv["s2"], bf.h32, Me, dr(so + SITE_FF), dr(so + SITE_FFOUT))
             x16 = sv["s2"].out16
-        bf.enc_out16 = x16
 
-        # ---- truncate / look-ahead conv / L2 norm (model :38-41)
-        _call("eend_conv1d_l2norm_train_f16", x16, W["cnn.w"], self._P("cnn.bias"), bf.il, bf.emb32, bf.emb16, bf.inv_norm, B, Tp, D,
-              self.ktaps, self.cpad)
-
-        # ---- attractor decoder (model :112-118)
-        _call("eend_convert_const_f32", 0, self._P("dec.convert.weight"), self._P("dec.convert.bias"), self.pe, bf.pc, None, None,
-              None, C)
-        ops.convert_fanout(bf.emb16, W["convert.w1"], bf.pc, bf.a32, bf.a16, B, Tp, C)
-        x16 = bf.a16
-        dm = m.dec.mask_delay
+        # ---- truncate / look-ahead conv / L2 norm (model :38-41), attractor decoder (model :112-118)
+        x16 = self._embed_fwd(bf, x16)
         for i, sv in enumerate(bf.dec):
-            p_ = f"dec.attractor_decoder.layers.{i}."
-            so = 4096 + 16 * i
-            self._attn_fwd(x16, W[f"d{i}.in1_w"], W[f"d{i}.in1_b"], sv["att"], B * C, Tp, dm, T, dr(so + self.SITE_ATT))
-            self._linear_ln(sv["att"].ctx, W[f"d{i}.out1_w"], self._P(p_ + "self_attn1.out_proj.bias"), bf.a32, p_ + "norm11",
-                            sv["s11"], bf.a32, Md, D, dr(so + self.SITE_OUT1))
-            ops.linear(sv["s11"].out16, W[f"d{i}.in2_w"], self._P(p_ + "self_attn2.in_proj_bias"), sv["qkv"])
-            _call("eend_spk_attn_train_f16", sv["qkv"], sv["o2"], B, C, Tp, H, 0.125, dr(so + self.SITE_SPK))
-            self._linear_ln(sv["o2"], W[f"d{i}.out2_w"], self._P(p_ + "self_attn2.out_proj.bias"), bf.a32, p_ + "norm21", sv["s21"],
-                            bf.a32, Md, D, dr(so + self.SITE_OUT2))
-            self._ffn(sv["s21"].out16, W[f"d{i}.w1"], self._P(p_ + "linear1.bias"), sv["hid"], W[f"d{i}.w2"], self._P(p_ + "linear2.bias"),
-                      bf.a32, p_ + "norm22", sv["s22"], bf.a32, Md, dr(so + self.SITE_FF), dr(so + self.SITE_FFOUT))
-            x16 = sv["s22"].out16
-
-        # ---- head + BCE (+ PIT label choice) + emb-consistency loss, and their gradients w.r.t. attractors / embeddings
-        if not fused_loss:
-            bf.logits_full = torch.empty(B, T, C, dtype=F32, device=dev)
-            bf.attr_n = torch.empty(B, T, C, D, dtype=F32, device=dev)
-            ops.head_l2dot(bf.emb32, bf.a32, bf.attr_n, bf.logits_full, B, T, Tp, C, D)
-            bf.loss[1] = ops.emb_consistency(bf.emb32.view(B, Tp, D), lab, T)
-            return bf
-        if pit:
-            lab = self._pit_labels(bf, lab, il, ncols)
-            bf.labels = lab
-        _call("eend_head_bce_f32", bf.emb32, bf.a32, lab, bf.il, bf.nc, 1.0 / float(n_frames), None, bf.logits, bf.g32, bf.de32,
-              self.ws, WS_FLOATS, bf.loss[0:1], B, T, Tp, C)
-        emb_loss = ops.emb_consistency(bf.emb32.view(B, Tp, D), lab, T)
-        bf.loss[1] = emb_loss
-        _call("eend_emb_consistency_bwd_f16", bf.emb16, lab, None, 0.0, bf.de32, B, T, Tp, D, C)
-        return bf
+            self._attn_fwd(x16, W[f"d{i}.in1_w"], W[f"d{i}.in1_b"], sv["mix"], B * C, Tp, m.dec.mask_delay, T, dr(4096 + 16 * i + SITE_ATT))
+            x16 = self._dec_layer_fwd(bf, i, sv["mix"].ctx)
+        return self._finish_forward(bf, pit, fused_loss)
 
     # ------------------------------------------------------------------ backward
     def _attn_bwd(self, g32, ds16, dctx16, dqkv16, sv: _AttnSave, x_in16, nseq, Tp, M, w_outT, w_inT, p_out, p_in, bf, delay,
@@ -760,65 +876,27 @@ class FsTrainStep(TrainStepBase):
         W = self.W
         B, T, Tp, C = bf.shape
         if dlogits is not None:
-            dl = dlogits.to(device=self.dev, dtype=F32).contiguous()
-            if tuple(dl.shape) != (B, T, C):
-                raise EendHipError(f"backward: dlogits must be ({B}, {T}, {C})")
-            _call("eend_head_bce_f32", bf.emb32, bf.a32, None, None, None, 0.0, dl, None, bf.g32, bf.de32, self.ws, WS_FLOATS,
-                  bf.loss[2:3], B, T, Tp, C)
-            if emb_loss_grad != 0.0:
-                _call("eend_emb_consistency_bwd_f16", bf.emb16, bf.labels, None, float(emb_loss_grad) / (float(B) * T * T), bf.de32,
-                      B, T, Tp, D, C)
+            self._head_grad_from_dlogits(bf, dlogits, emb_loss_grad)
         Me, Md = B * Tp, B * C * Tp
         m = self.model
-        dm = m.dec.mask_delay
         ds16, dctx16, dqkv16 = bf.ds16, bf.dctx16, bf.dqkv16
         dr = lambda site: self._drop(bf, site)
         ff_scale = 1.0 / (1.0 - self.drop_p) if bf.drop_base is not None else 1.0
 
-        # ---- decoder layers, last to first; bf.g32 = gradient w.r.t. the layer output
+        # ---- decoder layers, last to first; bf.g32 = gradient w.r.t. the layer output: the shared layer, then the time-axis
+        # attention block (merge_tfm_encoder.py:364, :379-385)
         g32 = bf.g32
         for i in reversed(range(len(bf.dec))):
-            sv = bf.dec[i]
-            p_ = f"dec.attractor_decoder.layers.{i}."
-            x_in16 = bf.dec[i - 1]["s22"].out16 if i > 0 else bf.a16
-            dsd = ds16[:Md]
-            so = 4096 + 16 * i
-            if i == len(bf.dec) - 1:      # (the other layers' norm22 backward ran in the epilogue of the layer above's last data-gradient GEMM)
-                self._ln_bwd(g32, sv["s22"], p_ + "norm22", dsd, Md, dr(so + self.SITE_FFOUT), p_ + "linear2.bias")
-            self._ffn_bwd(g32, dsd, bf.dh16, sv["hid"], sv["s21"].out16, Md, f"d{i}", p_, "norm22", ff_scale)
-            # speaker-axis attention block (merge_tfm_encoder.py:373, :388-394)
-            self._ln_bwd(g32, sv["s21"], p_ + "norm21", dsd, Md, dr(so + self.SITE_OUT2), p_ + "self_attn2.out_proj.bias")
-            self._wgrad(dsd, sv["o2"], Md, D, D, p_ + "self_attn2.out_proj.weight")
-            _call("eend_gemm_bf16", dsd, D, W[f"d{i}.out2_wT"], D, None, dctx16[:Md], D, Md, D, D)
-            _call("eend_spk_attn_bwd_bf16", sv["qkv"], dctx16[:Md], dqkv16[:Md], B, C, Tp, H, 0.125, dr(so + self.SITE_SPK))
-            self._wgrad_bias(dqkv16[:Md], sv["s11"].out16, Md, 3 * D, D, p_ + "self_attn2.in_proj_weight", p_ + "self_attn2.in_proj_bias")
-            # ... its in-projection's data gradient joins the stream, and norm11's backward runs in the same launch
-            # time-axis attention block (:364, :379-385)
-            self._gemm_acc_ln_bwd(dqkv16[:Md], 3 * D, W[f"d{i}.in2_wT"], g32, sv["s11"], p_ + "norm11", dsd, Md, dr(so + self.SITE_OUT1),
-                                  p_ + "self_attn1.out_proj.bias")
-            below = None
-            if i > 0:                     # the layer below ends in norm22: its backward rides on this block's last GEMM
-                pb = f"dec.attractor_decoder.layers.{i - 1}."
-                below = (bf.dec[i - 1]["s22"], pb + "norm22", dr(so - 16 + self.SITE_FFOUT), pb + "linear2.bias")
-            self._attn_bwd(g32, dsd, dctx16[:Md], dqkv16[:Md], sv["att"], x_in16, B * C, Tp, Md, W[f"d{i}.out1_wT"],
-                           W[f"d{i}.in1_wT"], p_ + "self_attn1.out_proj", p_ + "self_attn1.in_proj", bf, dm, T, T,
-                           dr(so + self.SITE_ATT), next_ln=below)
+            p_ = f"{self.DEC_PREFIX}{i}."
+            x_in16, below = self._dec_layer_bwd(bf, i, g32, ff_scale)
+            self._attn_bwd(g32, ds16[:Md], dctx16[:Md], dqkv16[:Md], bf.dec[i]["mix"], x_in16, B * C, Tp, Md, W[f"d{i}.out1_wT"],
+                           W[f"d{i}.in1_wT"], p_ + "self_attn1.out_proj", p_ + "self_attn1.in_proj", bf, m.dec.mask_delay, T, T,
+                           dr(4096 + 16 * i + SITE_ATT), next_ln=below)
 
-        # ---- convert fan-out (model :113-114, factored): g32 = gradient w.r.t. attr0
-        _call("eend_convert_fanout_bwd_f32", g32, bf.gsum16, self.ws, WS_FLOATS, bf.dpc, B, Tp, C)
-        _call("eend_convert_const_f32", 1, None, None, self.pe, None, bf.dpc, self._G("dec.convert.weight"), self._G("dec.convert.bias"), C)
-        self._wgrad(bf.gsum16, bf.emb16, Me, D, D, "dec.convert.weight", ld_out=2 * D, k_out=D)
-        _call("eend_gemm_acc_bf16", bf.gsum16, D, W["convert.w1T"], D, bf.de32, 1.0, bf.de32, None, Me, D)
-
-        # ---- L2 norm + look-ahead conv (model :40-41); de32 = gradient w.r.t. the unit embeddings (head + emb loss + convert)
-        _call("eend_l2norm_bwd_bf16", bf.emb32, bf.de32, bf.inv_norm, bf.demb16, B, T, Tp)
-        self._bias_grad(bf.demb16, Me, D, "cnn.bias")
-        _call("eend_conv1d_wgrad_bf16", bf.demb16, bf.enc_out16, bf.il, B, Tp, D, self.ktaps, self.cpad, self.ws, WS_FLOATS, bf.conv_tmp,
-              self._G("cnn.weight"))
-        _call("eend_conv1d_dgrad_bf16", bf.demb16, W["cnn.wd"], bf.tl, bf.il, bf.ge32, B, Tp, D, self.ktaps, self.ktaps - 1 - self.cpad)
+        # ---- convert fan-out, L2 norm, look-ahead conv (model :113-114, :40-41)
+        g32 = self._embed_bwd(bf, g32)
 
         # ---- encoder layers, last to first
-        g32 = bf.ge32
         dse = ds16[:Me]
         for i in reversed(range(len(bf.enc))):
             sv = bf.enc[i]
@@ -826,23 +904,21 @@ class FsTrainStep(TrainStepBase):
             x_in16 = bf.enc[i - 1]["s2"].out16 if i > 0 else bf.site0.out16
             so = 16 * i
             if i == len(bf.enc) - 1:      # (the other layers' norm2 backward ran in the epilogue of the layer above's last data-gradient GEMM)
-                self._ln_bwd(g32, sv["s2"], p_ + "norm2", dse, Me, dr(so + self.SITE_FFOUT), p_ + "linear2.bias")
+                self._ln_bwd(g32, sv["s2"], p_ + "norm2", dse, Me, dr(so + SITE_FFOUT), p_ + "linear2.bias")
             self._ffn_bwd(g32, dse, bf.dh16, sv["hid"], sv["s1"].out16, Me, f"e{i}", p_, "norm2", ff_scale)
-            self._ln_bwd(g32, sv["s1"], p_ + "norm1", dse, Me, dr(so + self.SITE_OUT1), p_ + "self_attn.out_proj.bias")
+            self._ln_bwd(g32, sv["s1"], p_ + "norm1", dse, Me, dr(so + SITE_OUT1), p_ + "self_attn.out_proj.bias")
             if i > 0:
                 pb = f"enc.transformer_encoder.layers.{i - 1}."
-                below = (bf.enc[i - 1]["s2"], pb + "norm2", dr(so - 16 + self.SITE_FFOUT), pb + "linear2.bias")
+                below = (bf.enc[i - 1]["s2"], pb + "norm2", dr(so - 16 + SITE_FFOUT), pb + "linear2.bias")
             else:                         # the encoder's input LayerNorm (model :166)
                 below = (bf.site0, "enc.encoder_norm", None, "enc.encoder.bias")
             self._attn_bwd(g32, dse, dctx16[:Me], dqkv16[:Me], sv["att"], x_in16, B, Tp, Me, W[f"e{i}.out_wT"], W[f"e{i}.in_wT"],
-                           p_ + "self_attn.out_proj", p_ + "self_attn.in_proj", bf, bf.delay_e, bf.kv_e, T, dr(so + self.SITE_ATT), next_ln=below)
+                           p_ + "self_attn.out_proj", p_ + "self_attn.in_proj", bf, bf.delay_e, bf.kv_e, T, dr(so + SITE_ATT), next_ln=below)
 
         # ---- input projection + LayerNorm + BatchNorm (model :166,:173-174)
         if len(bf.enc) == 0:
             self._ln_bwd(g32, bf.site0, "enc.encoder_norm", dse, Me, None, "enc.encoder.bias")
-        _call("eend_wgrad_bf16", dse, D, bf.xin16, self.Fin_pad, 1, Me, D, self.Fin_pad, self.ws, WS_FLOATS, self._G("enc.encoder.weight"),
-              self.Fin, self.Fin, 1.0, 0)
+        self._input_weight_grad(bf, dse)
         _call("eend_gemm_bf16", dse, D, W["enc.in.wT"], D, None, bf.dy_in, self.Fin_pad, Me, self.Fin_pad, D)
         _call("eend_bn_bwd_f32", bf.ptrs, bf.lens, -1.0, bf.bn_mean, bf.bn_var, m.enc.bn.eps, bf.dy_in, self.Fin_pad, self.ws, WS_FLOATS,
               self._G("enc.bn.weight"), self._G("enc.bn.bias"), B, T, Tp, self.Fin)
-

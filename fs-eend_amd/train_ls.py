@@ -32,7 +32,8 @@ from torch import Tensor
 from . import ops
 from .lib import EendHipError
 from .shard import all_reduce_bn_sums, gather_bn_stats
-from .train import (BF16, D, F16, F32, H, I32, WS_FLOATS, TrainStepBase, _Site, _call, drop_step_seed)
+from .train import (BF16, D, F16, F32, H, WS_FLOATS, TrainStepBase, _Site, _StepBuffers, _call,
+                    never_graded)   # noqa: F401  (never_graded: one definition for both models, importable from here too)
 
 # The Macaron half-step FFNs of the Conformer blocks as one training-forward launch each (eend_ffn_swish_train_f16): bit 0 = FFN_a,
 # bit 1 = FFN_b.  Built in round 5 and kept off there because it moved the gradient norms of two ill-conditioned tensors of golden
@@ -40,14 +41,7 @@ from .train import (BF16, D, F16, F32, H, I32, WS_FLOATS, TrainStepBase, _Site, 
 # fp32-vs-fp64 gap of each tensor (round 6, tests/test_train_step_ls.py) every golden is green with both fused: on.
 MACARON_FUSED = 3
 
-ENC_FFA_HID, ENC_FFA_OUT, ENC_RET, ENC_CONV, ENC_FFB_HID, ENC_FFB_OUT = 0, 1, 2, 3, 4, 5
-SITE_OUT1, SITE_SPK, SITE_OUT2, SITE_FF, SITE_FFOUT = 1, 2, 3, 4, 5
-
-
-def never_graded(name: str) -> bool:
-    """Parameters of the LS model that are not on the forward path: the decoder's dead input projection and the fusion
-    layers' norm12 (merge_retnet_layer.py:93)."""
-    return name.startswith("dec.encoder.") or name.startswith("dec.encoder_norm.") or ".norm12." in name
+ENC_FFA_HID, ENC_FFA_OUT, ENC_RET, ENC_CONV, ENC_FFB_HID, ENC_FFB_OUT = 0, 1, 2, 3, 4, 5      # (the decoder layers' ids: train.SITE_*)
 
 
 class _RetSave:
@@ -63,18 +57,16 @@ class _RetSave:
         self.ctx = torch.zeros(nseq * Tp, D, dtype=F16, device=dev)
 
 
-class _LsBuffers:
-    """Device buffers of one (B, Tp, C) training shape."""
+class _LsBuffers(_StepBuffers):
+    """... and what the LS step adds: the Conformer blocks, the retention kernels' forward transients and backward scratch."""
 
     def __init__(self, dev, B, Tp, C, n_enc, n_dec, F_enc, F_dec, Fin_pad, L):
-        e = lambda *s, dt: torch.empty(*s, dtype=dt, device=dev)
+        super().__init__(dev, B, Tp, C, n_dec, F_dec, Fin_pad, lambda nseq: _RetSave(dev, nseq, Tp))
+        e = self._e
         Me, Md = B * Tp, B * C * Tp
         Mx = max(Me, Md)
         nseq_max = max(B, B * C)
         nc = max(1, Tp // L)
-        self.xin16 = torch.zeros(Me, Fin_pad, dtype=F16, device=dev)
-        self.h32 = e(Me, D, dt=F32)
-        self.site0 = _Site(dev, Me)
         self.enc = []
         for _ in range(n_enc):
             self.enc.append(dict(
@@ -84,10 +76,6 @@ class _LsBuffers:
                 bn_mean=e(D, dt=F32), bn_var=e(D, dt=F32), bn_n=e(1, dt=F32),
                 lnD=_Site(dev, Me), zb=e(Me, F_enc, dt=F16), ab=e(Me, F_enc, dt=F16),
                 lnE=_Site(dev, Me)))
-        self.emb32, self.emb16, self.inv_norm = e(Me, D, dt=F32), e(Me, D, dt=F16), e(Me, dt=F32)
-        self.a32, self.a16 = e(Md, D, dt=F32), e(Md, D, dt=F16)
-        self.dec = [dict(ret=_RetSave(dev, B * C, Tp), s11=_Site(dev, Md), qkv=e(Md, 3 * D, dt=F16), o2=e(Md, D, dt=F16),
-                         s21=_Site(dev, Md), hid=e(Md, F_dec, dt=F16), s22=_Site(dev, Md)) for _ in range(n_dec)]
         # forward transients (f16 operands of the retention forward kernels)
         self.fq, self.fk, self.fkt, self.fvt = (e(Mx * D, dt=F16) for _ in range(4))
         self.st = e(nseq_max * H * nc * 2 * 4096, dt=F16)
@@ -95,11 +83,6 @@ class _LsBuffers:
         self.kv_ws = e(nseq_max * H * nc * 4096, dt=F32)
         self.bn_stats = e(2 * D + 1, dt=F32)
         # backward temporaries
-        self.g32 = e(Md, D, dt=F32)
-        self.ge32 = e(Me, D, dt=F32)
-        self.de32 = e(Me, D, dt=F32)
-        self.ds16 = e(Mx, D, dt=BF16)
-        self.dctx16 = e(Mx, D, dt=BF16)
         self.dctx32 = e(Mx, D, dt=F32)
         self.dy16 = e(Mx, D, dt=BF16)
         self.dh16 = e(max(Me * max(F_enc, 2 * D), Md * F_dec), dt=BF16)
@@ -109,13 +92,6 @@ class _LsBuffers:
         self.g_ws = e(nseq_max * H * nc * 4096, dt=F32)
         self.st_bwd = e(nseq_max * H * nc * 6 * 4096, dt=BF16)
         self.bn_sums = e(2 * D, dt=F32)
-        self.gsum16 = e(Me, D, dt=BF16)
-        self.demb16 = e(Me, D, dt=BF16)
-        self.conv_tmp = e(D * 19 * D, dt=F32)
-        self.dpc = e(C, D, dt=F32)
-        self.pc = e(C, D, dt=F32)
-        self.logits = e(B, Tp, C, dt=F32)
-        self.loss = torch.zeros(4, dtype=F32, device=dev)         # [bce, emb, -, -]
 
 
 class LsTrainStep(TrainStepBase):
@@ -162,14 +138,14 @@ class LsTrainStep(TrainStepBase):
         self._add_entry(wT, 0, qw, (D, 4, D), (1, stride, D), 1)           # wT[k][j*256 + n] = W_j[n][k]
         self.W[key + ".wqkvg"], self.W[key + ".bqkvg"], self.W[key + ".wqkvgT"] = w, b, wT
 
+    DEC_PREFIX = "dec.layers."
+
     def _build_weight_table(self):
-        m, dev = self.model, self.dev
+        m = self.model
         self._table_begin()
-        plain, transposed, add = self._plain, self._transposed, self._add
+        plain, transposed = self._plain, self._transposed
         e = m.enc.encoder
-        Fin = m._in_size
-        self.Fin, self.Fin_pad = Fin, (Fin + 127) // 128 * 128
-        plain("in.w", "enc.encoder.input_projection.linear.weight", D, Fin, kpad=self.Fin_pad)
+        self._input_table("in.w", "enc.encoder.input_projection.linear.weight", m._in_size)
         self.F_enc = e.layers[0].sequential[0].module.sequential[1].linear.out_features if len(e.layers) else D
         self.kdw = e._conv_kernel_size
         for i in range(len(e.layers)):
@@ -186,42 +162,22 @@ class LsTrainStep(TrainStepBase):
             transposed(f"e{i}.pw1T", s_ + "2.module.sequential.2.conv.weight", 2 * D, D)
             plain(f"e{i}.pw2", s_ + "2.module.sequential.7.conv.weight", D, D)
             transposed(f"e{i}.pw2T", s_ + "2.module.sequential.7.conv.weight", D, D)
-        k = m.cnn.kernel_size[0]
-        self.ktaps, self.cpad = k, m.cnn.padding[0]
-        add("cnn.w", "cnn.weight", (D, k, D), (D * k, 1, k), 0, alloc=(D, k * D))
-        add("cnn.wd", "cnn.weight", (D, k, D), (k, -1, D * k), 1, off=k - 1, alloc=(D, k * D))
-        add("convert.w1", "dec.convert.weight", (D, 1, D), (2 * D, 0, 1), 0)
-        add("convert.w1T", "dec.convert.weight", (D, 1, D), (1, 0, 2 * D), 1)
+        self._embed_table()
         self.F_dec = m.dec.layers[0].linear1.out_features if len(m.dec.layers) else D
-        for i, l in enumerate(m.dec.layers):
-            p_ = f"dec.layers.{i}."
-            Fh = l.linear1.out_features
-            self._ret_tables(f"d{i}", p_ + "self_attn1.")
-            plain(f"d{i}.out1_w", p_ + "self_attn1.out_proj.weight", D, D)
-            transposed(f"d{i}.out1_wT", p_ + "self_attn1.out_proj.weight", D, D)
-            plain(f"d{i}.in2_w", p_ + "self_attn2.in_proj_weight", 3 * D, D)
-            transposed(f"d{i}.in2_wT", p_ + "self_attn2.in_proj_weight", 3 * D, D)
-            plain(f"d{i}.out2_w", p_ + "self_attn2.out_proj.weight", D, D)
-            transposed(f"d{i}.out2_wT", p_ + "self_attn2.out_proj.weight", D, D)
-            plain(f"d{i}.w1", p_ + "linear1.weight", Fh, D)
-            transposed(f"d{i}.w1T", p_ + "linear1.weight", Fh, D)
-            plain(f"d{i}.w2", p_ + "linear2.weight", D, Fh)
-            transposed(f"d{i}.w2T", p_ + "linear2.weight", D, Fh)
+        for i in range(len(m.dec.layers)):
+            self._ret_tables(f"d{i}", f"{self.DEC_PREFIX}{i}.self_attn1.")
+            self._dec_table(i)
         self._table_end()
-        self.pe = m.dec.pos_enc.pe[0].to(device=dev, dtype=F32).contiguous()
 
     # ------------------------------------------------------------------ helpers
-    def _buffers(self, B, Tp, C) -> _LsBuffers:
-        key = (B, Tp, C)
-        b = self._bufs.get(key)
-        if b is None:
-            if len(self._bufs) >= 2:
-                self._bufs.clear()
-            m = self.model
-            b = _LsBuffers(self.dev, B, Tp, C, len(m.enc.encoder.layers), len(m.dec.layers), self.F_enc, self.F_dec, self.Fin_pad,
-                           self.L)
-            self._bufs[key] = b
-        return b
+    def _new_buffers(self, B, Tp, C) -> _LsBuffers:
+        m = self.model
+        return _LsBuffers(self.dev, B, Tp, C, len(m.enc.encoder.layers), len(m.dec.layers), self.F_enc, self.F_dec, self.Fin_pad, self.L)
+
+    def _emb_loss_args(self, bf, grad=None):
+        """(lengths, normalisation) of the embedding-consistency loss and of its gradient scaled by `grad`: masked by the lengths,
+        over sum(len^2) (LS model :92-113)."""
+        return bf.il, bf.inv_sq if grad is None else float(grad) * bf.inv_sq
 
     def _pit_assign(self, P, ys, ts, n_spk):
         return P.pit_loss_multispk(ys, ts, n_spk)           # train/oln_tfm_enc_dec_spk_pit_on_the_fly.py:92 (Hungarian)
@@ -237,14 +193,14 @@ class LsTrainStep(TrainStepBase):
         W = self.W
         n = nseq * Tp * D
         q, k, kt, vt = bf.fq[:n], bf.fk[:n], bf.fkt[:n], bf.fvt[:n]
-        ws = self._proj_streams.get(wkey + ".wqkvg")
+        ws = self._stream("proj", W[wkey + ".wqkvg"])
         groups = [dict(rows=q, kind=2, rows2=sv.q), dict(rows=k, kind=2, rows2=sv.k, heads_t=kt), dict(rows2=sv.v, heads_t=vt),
                   dict(rows=sv.g, kind=1, ld=D)]
         if ws is not None and nseq * Tp >= self.proj_stream_min_rows and ops.proj_stream_ok(x16.stride(0), nseq * Tp, 4 * D, Tp, H, groups):
             # one pass over the rows for the f16 operands of the forward kernel AND the bf16 head rows the backward keeps (proj_stream.hip:
             # [393216, 1024] 526 us against 803 us for the two projections below, [65536, 1024] 101 against 149 us; below about 48 k rows
             # the 256-row tiles leave CUs idle and the two launches win)
-            ops.proj_stream(x16, ws, W[wkey + ".bqkvg"], nseq * Tp, 4 * D, Tp, H, groups)
+            ops.proj_stream(x16, ws[0], W[wkey + ".bqkvg"], nseq * Tp, 4 * D, Tp, H, groups)
         else:
             ops.retention_proj(x16, W[wkey + ".wqkvg"], W[wkey + ".bqkvg"], q, k, kt, vt, sv.g, nseq, Tp, H)
             _call("eend_inproj_heads_train_bf16", x16, x16.stride(0), W[wkey + ".wqkvg"], W[wkey + ".bqkvg"], sv.q, None, sv.k, None,
@@ -253,54 +209,30 @@ class LsTrainStep(TrainStepBase):
               Tp, self.L, D, D, 1e-6, Tv)
 
     # ------------------------------------------------------------------ forward (saves activations)
-    def forward(self, src: Sequence[Tensor], labels: Sequence[Tensor], ilens: Sequence[int], pit: bool = False, dropout: bool = True,
-                fused_loss: bool = True):
+    def forward(self, src: Sequence[Tensor], labels: Sequence[Tensor], ilens: Sequence[int], pit: bool = False, *,
+                dropout: bool = True, fused_loss: bool = True):
         """Train-mode model.forward with every activation the backward needs saved.  labels: prepared (T_i, nspk_i+2)
         tensors (oln_tfm_enc_dec_on_the_fly.py:53-75).
         fused_loss=True : also standard_loss + masked emb-consistency loss and their gradients w.r.t. attractors /
                           embeddings (bf.loss = [bce, emb_loss]); `backward(bf)` then completes the step.
         fused_loss=False: stop at the head (bf.logits_full (B,T,C), bf.attr_n (B,T,C,D), bf.loss[1] = emb_loss): the
                           caller computes its own loss on the logits and passes d loss / d logits to `backward`."""
-        m, W, dev, L = self.model, self.W, self.dev, self.L
-        srcs = [s.to(device=dev, dtype=F32).contiguous() for s in src]
-        B, T = len(srcs), max(int(s.shape[0]) for s in srcs)
-        ncols = [int(l.shape[1]) for l in labels]
-        C = max(ncols)
-        Tv = math.ceil(T / L) * L                       # the reference's padded length (LS model :281-283)
-        Tp = ops.frames_pad(Tv)
-        bf = self._buffers(B, Tp, C)
-        Me, Md = B * Tp, B * C * Tp
-        il = [min(int(l), T) for l in ilens]
-        if any(int(l) != int(s.shape[0]) for l, s in zip(ilens, srcs)):
+        m, W, L = self.model, self.W, self.L
+        if any(int(l) != int(s.shape[0]) for l, s in zip(ilens, src)):
             # the reference pads the decoder and windows the emb-consistency loss by max(ilens) AFTER truncating the embeddings
             # (LS model :80-84, :100); this step derives both from the feature lengths, which is the same thing only when they agree
             # -- as they always do in the reference's training_step
             raise EendHipError("LsTrainStep.forward: ilens must equal the feature lengths (ilens shorter than the features are not supported)")
-        key = (tuple(il), tuple(ncols), T)
-        if getattr(bf, "len_key", None) != key:              # cached: no H2D copies in the steady state
-            bf.il = torch.tensor(il, dtype=I32, device=dev)
-            bf.tl = torch.full((B,), Tv, dtype=I32, device=dev)
-            bf.nc = torch.tensor(ncols, dtype=I32, device=dev)
-            bf.inv_sq = 1.0 / float(sum(l * l for l in il))
-            bf.len_key = key
-        bf.shape = (B, T, Tp, C)
-        bf.Tv = Tv
-        self._fwd_count += 1
-        bf.drop_base = drop_step_seed(self.drop_seed, self._fwd_count) if (dropout and self.drop_p > 0.0) else None
-        bf.drop_specs = {}
+        T = max(int(s.shape[0]) for s in src)
+        Tv = math.ceil(T / L) * L                       # the reference's padded length (LS model :281-283)
+        bf, srcs = self._begin_forward(src, labels, ilens, dropout, Tv)        # (srcs: held until the gather below has been queued)
+        bf.inv_sq = 1.0 / float(sum(l * l for l in bf.len_key[0]))
+        B, T, Tp, C = bf.shape
+        Me = B * Tp
         dr = lambda site: self._drop(bf, site)
-        n_frames = sum(int(l.shape[0]) for l in labels)
-        if all(tuple(l.shape) == (T, C) for l in labels):
-            lab = torch.stack([l.to(device=dev, dtype=F32) for l in labels]).contiguous()
-        else:
-            lab = torch.zeros(B, T, C, dtype=F32, device=dev)
-            for b_, l in enumerate(labels):
-                lab[b_, :l.shape[0], :l.shape[1]] = l.to(device=dev, dtype=F32)
-        bf.labels = lab
 
         # ---- input projection + LayerNorm (conformer/encoder.py:194-196); pad_sequence(0) + cast in one launch
-        ptrs, lens = self._table_for(srcs, T)
-        _call("eend_gather_bn_cast_pad_f16", ptrs, lens, 0.0, None, None, None, None, 0.0, bf.xin16, B, T, Tp, self.Fin, self.Fin_pad, 0)
+        _call("eend_gather_bn_cast_pad_f16", bf.ptrs, bf.lens, 0.0, None, None, None, None, 0.0, bf.xin16, B, T, Tp, self.Fin, self.Fin_pad, 0)
         self._linear_ln(bf.xin16, W["in.w"], self._P("enc.encoder.input_projection.linear.bias"), None, "enc.encoder.layer_norm",
                         bf.site0, bf.h32, Me, self.Fin_pad)
         h32 = bf.h32
@@ -354,47 +286,14 @@ class LsTrainStep(TrainStepBase):
                 _call("eend_swish_dropout_f16", sv["zb"], sv["ab"], Me, self.F_enc, dr(so + ENC_FFB_HID))
                 self._linear_ln(sv["ab"], W[f"e{i}.w2b"], self._P(ffb + "4.linear.bias"), h32, s_ + "4", sv["lnE"], h32, Me, self.F_enc,
                                 dr(so + ENC_FFB_OUT), alpha=0.5)
-        enc_out16 = bf.enc[-1]["lnE"].out16 if bf.enc else bf.site0.out16
-        bf.enc_out16 = enc_out16
 
-        # ---- truncate / zero re-pad, look-ahead conv, L2 norm (LS model :80-87)
-        _call("eend_conv1d_l2norm_train_f16", enc_out16, W["cnn.w"], self._P("cnn.bias"), bf.il, bf.emb32, bf.emb16, bf.inv_norm, B, Tp, D,
-              self.ktaps, self.cpad)
-
-        # ---- attractor decoder (LS model :215-220; merge_retnet_layer.py:233-253)
-        _call("eend_convert_const_f32", 0, self._P("dec.convert.weight"), self._P("dec.convert.bias"), self.pe, bf.pc, None, None,
-              None, C)
-        ops.convert_fanout(bf.emb16, W["convert.w1"], bf.pc, bf.a32, bf.a16, B, Tp, C)
-        x16 = bf.a16
+        # ---- truncate / zero re-pad, look-ahead conv, L2 norm (LS model :80-87); attractor decoder (LS model :215-220): retention over
+        # time, then the shared layer (merge_retnet_layer.py:233-253); head + losses, the emb-consistency loss masked (LS model :89-117)
+        x16 = self._embed_fwd(bf, bf.enc[-1]["lnE"].out16 if bf.enc else bf.site0.out16)
         for i, sv in enumerate(bf.dec):
-            p_ = f"dec.layers.{i}."
-            so = 4096 + 16 * i
-            self._ret_fwd(bf, x16, f"d{i}", sv["ret"], B * C, Tp, Tv)
-            self._linear_ln(sv["ret"].ctx, W[f"d{i}.out1_w"], self._P(p_ + "self_attn1.out_proj.bias"), bf.a32, p_ + "norm11", sv["s11"],
-                            bf.a32, Md, D, dr(so + SITE_OUT1))
-            ops.linear(sv["s11"].out16, W[f"d{i}.in2_w"], self._P(p_ + "self_attn2.in_proj_bias"), sv["qkv"])
-            _call("eend_spk_attn_train_f16", sv["qkv"], sv["o2"], B, C, Tp, H, 0.125, dr(so + SITE_SPK))
-            self._linear_ln(sv["o2"], W[f"d{i}.out2_w"], self._P(p_ + "self_attn2.out_proj.bias"), bf.a32, p_ + "norm21", sv["s21"],
-                            bf.a32, Md, D, dr(so + SITE_OUT2))
-            self._ffn(sv["s21"].out16, W[f"d{i}.w1"], self._P(p_ + "linear1.bias"), sv["hid"], W[f"d{i}.w2"], self._P(p_ + "linear2.bias"),
-                      bf.a32, p_ + "norm22", sv["s22"], bf.a32, Md, dr(so + SITE_FF), dr(so + SITE_FFOUT))
-            x16 = sv["s22"].out16
-
-        # ---- head + BCE (+ PIT label choice) + masked emb-consistency loss, and their gradients (LS model :89-117)
-        if not fused_loss:
-            bf.logits_full = torch.empty(B, T, C, dtype=F32, device=dev)
-            bf.attr_n = torch.empty(B, T, C, D, dtype=F32, device=dev)
-            ops.head_l2dot(bf.emb32, bf.a32, bf.attr_n, bf.logits_full, B, T, Tp, C, D)
-            bf.loss[1] = ops.emb_consistency(bf.emb32.view(B, Tp, D), lab, T, lens=bf.il, inv_count=bf.inv_sq)
-            return bf
-        if pit:
-            lab = self._pit_labels(bf, lab, il, ncols)
-            bf.labels = lab
-        _call("eend_head_bce_f32", bf.emb32, bf.a32, lab, bf.il, bf.nc, 1.0 / float(n_frames), None, bf.logits, bf.g32, bf.de32,
-              self.ws, WS_FLOATS, bf.loss[0:1], B, T, Tp, C)
-        bf.loss[1] = ops.emb_consistency(bf.emb32.view(B, Tp, D), lab, T, lens=bf.il, inv_count=bf.inv_sq)
-        _call("eend_emb_consistency_bwd_f16", bf.emb16, lab, bf.il, bf.inv_sq, bf.de32, B, T, Tp, D, C)
-        return bf
+            self._ret_fwd(bf, x16, f"d{i}", sv["mix"], B * C, Tp, Tv)
+            x16 = self._dec_layer_fwd(bf, i, sv["mix"].ctx)
+        return self._finish_forward(bf, pit, fused_loss)
 
     # ------------------------------------------------------------------ backward
     def _ln_bwd2(self, g, g_is_bf16, site: _Site, ln, ds32, accumulate, M, ds16=None, alpha16=1.0, drop=None, bias=None):
@@ -462,59 +361,23 @@ class LsTrainStep(TrainStepBase):
         B, T, Tp, C = bf.shape
         Tv = bf.Tv
         if dlogits is not None:
-            dl = dlogits.to(device=self.dev, dtype=F32).contiguous()
-            if tuple(dl.shape) != (B, T, C):
-                raise EendHipError(f"backward: dlogits must be ({B}, {T}, {C})")
-            _call("eend_head_bce_f32", bf.emb32, bf.a32, None, None, None, 0.0, dl, None, bf.g32, bf.de32, self.ws, WS_FLOATS,
-                  bf.loss[2:3], B, T, Tp, C)
-            if emb_loss_grad != 0.0:
-                _call("eend_emb_consistency_bwd_f16", bf.emb16, bf.labels, bf.il, float(emb_loss_grad) * bf.inv_sq, bf.de32, B, T, Tp, D, C)
+            self._head_grad_from_dlogits(bf, dlogits, emb_loss_grad)
         Me, Md = B * Tp, B * C * Tp
         m = self.model
-        ds16, dctx16, dqkv16 = bf.ds16, bf.dctx16, bf.dqkv16
+        ds16, dctx16 = bf.ds16, bf.dctx16
         dr = lambda site: self._drop(bf, site)
         ff_scale = 1.0 / (1.0 - self.drop_p) if bf.drop_base is not None else 1.0
 
-        # ---- decoder layers, last to first; bf.g32 = gradient w.r.t. the layer output
+        # ---- decoder layers, last to first; bf.g32 = gradient w.r.t. the layer output: the shared layer, then the retention block
         g32 = bf.g32
         for i in reversed(range(len(bf.dec))):
-            sv = bf.dec[i]
-            p_ = f"dec.layers.{i}."
-            x_in16 = bf.dec[i - 1]["s22"].out16 if i > 0 else bf.a16
-            dsd = ds16[:Md]
-            so = 4096 + 16 * i
-            if i == len(bf.dec) - 1:      # (the other layers' norm22 backward ran in the epilogue of the layer above's last data-gradient GEMM)
-                self._ln_bwd(g32, sv["s22"], p_ + "norm22", dsd, Md, dr(so + SITE_FFOUT), p_ + "linear2.bias")
-            self._ffn_bwd(g32, dsd, bf.dh16, sv["hid"], sv["s21"].out16, Md, f"d{i}", p_, "norm22", ff_scale)
-            self._ln_bwd(g32, sv["s21"], p_ + "norm21", dsd, Md, dr(so + SITE_OUT2), p_ + "self_attn2.out_proj.bias")
-            self._wgrad(dsd, sv["o2"], Md, D, D, p_ + "self_attn2.out_proj.weight")
-            _call("eend_gemm_bf16", dsd, D, W[f"d{i}.out2_wT"], D, None, dctx16[:Md], D, Md, D, D)
-            _call("eend_spk_attn_bwd_bf16", sv["qkv"], dctx16[:Md], dqkv16[:Md], B, C, Tp, H, 0.125, dr(so + SITE_SPK))
-            self._wgrad_bias(dqkv16[:Md], sv["s11"].out16, Md, 3 * D, D, p_ + "self_attn2.in_proj_weight", p_ + "self_attn2.in_proj_bias")
-            # the in-projection's data gradient joins the stream; norm11's backward in the same launch (train.TrainStepBase._gemm_acc_ln_bwd)
-            self._gemm_acc_ln_bwd(dqkv16[:Md], 3 * D, W[f"d{i}.in2_wT"], g32, sv["s11"], p_ + "norm11", dsd, Md, dr(so + SITE_OUT1),
-                                  p_ + "self_attn1.out_proj.bias")
-            below = None
-            if i > 0:                     # the layer below ends in norm22: its backward rides on this block's last GEMM
-                pb = f"dec.layers.{i - 1}."
-                below = (bf.dec[i - 1]["s22"], pb + "norm22", dr(so - 16 + SITE_FFOUT), pb + "linear2.bias")
-            self._ret_bwd(bf, g32, dsd, sv["ret"], x_in16, B * C, Md, f"d{i}", p_ + "self_attn1.", next_ln=below)
+            x_in16, below = self._dec_layer_bwd(bf, i, g32, ff_scale)
+            self._ret_bwd(bf, g32, ds16[:Md], bf.dec[i]["mix"], x_in16, B * C, Md, f"d{i}", f"{self.DEC_PREFIX}{i}.self_attn1.", next_ln=below)
 
-        # ---- convert fan-out (LS model :216-217, factored): g32 = gradient w.r.t. attr0
-        _call("eend_convert_fanout_bwd_f32", g32, bf.gsum16, self.ws, WS_FLOATS, bf.dpc, B, Tp, C)
-        _call("eend_convert_const_f32", 1, None, None, self.pe, None, bf.dpc, self._G("dec.convert.weight"), self._G("dec.convert.bias"), C)
-        self._wgrad(bf.gsum16, bf.emb16, Me, D, D, "dec.convert.weight", ld_out=2 * D, k_out=D)
-        _call("eend_gemm_acc_bf16", bf.gsum16, D, W["convert.w1T"], D, bf.de32, 1.0, bf.de32, None, Me, D)
-
-        # ---- L2 norm + look-ahead conv (LS model :86-87)
-        _call("eend_l2norm_bwd_bf16", bf.emb32, bf.de32, bf.inv_norm, bf.demb16, B, Tv, Tp)
-        self._bias_grad(bf.demb16, Me, D, "cnn.bias")
-        _call("eend_conv1d_wgrad_bf16", bf.demb16, bf.enc_out16, bf.il, B, Tp, D, self.ktaps, self.cpad, self.ws, WS_FLOATS, bf.conv_tmp,
-              self._G("cnn.weight"))
-        _call("eend_conv1d_dgrad_bf16", bf.demb16, W["cnn.wd"], bf.tl, bf.il, bf.ge32, B, Tp, D, self.ktaps, self.ktaps - 1 - self.cpad)
+        # ---- convert fan-out, L2 norm over the padded length, look-ahead conv (LS model :216-217, :86-87)
+        g32 = self._embed_bwd(bf, g32)
 
         # ---- Conformer blocks, last to first; g32 = gradient w.r.t. the block output
-        g32 = bf.ge32
         dse = ds16[:Me]
         for i in reversed(range(len(bf.enc))):
             sv = bf.enc[i]
@@ -554,5 +417,4 @@ class LsTrainStep(TrainStepBase):
 
         # ---- input projection + LayerNorm (conformer/encoder.py:195-196)
         self._ln_bwd(g32, bf.site0, "enc.encoder.layer_norm", dse, Me, None, "enc.encoder.input_projection.linear.bias")
-        _call("eend_wgrad_bf16", dse, D, bf.xin16, self.Fin_pad, 1, Me, D, self.Fin_pad, self.ws, WS_FLOATS,
-              self._G("enc.encoder.input_projection.linear.weight"), self.Fin, self.Fin, 1.0, 0)
+        self._input_weight_grad(bf, dse)

@@ -28,3 +28,14 @@ def test_constant_lr_without_scheduler_and_noam_with():
     assert [e.current_lr(t) for t in (1, 2, 1000)] == [3e-4] * 3
     e.warmup, e.base_lr = 25, 1.0
     assert e.current_lr(1) == noam_lr(1, 256, 25) and e.current_lr(30) == noam_lr(30, 256, 25)
+
+
+def test_training_steps_share_never_graded_and_dropout_site_ids():
+    """One definition of never_graded behind both modules, and the decoder-layer dropout site ids of the engines equal to those the
+    oracle's hash masks are driven with (oracle/dropout_ref.py): the same hash, so the two sets agree by construction."""
+    from fs_eend_amd import train, train_ls
+    from oracle.dropout_ref import HashDropout
+    assert train_ls.never_graded is train.never_graded
+    names = ("SITE_ATT", "SITE_OUT1", "SITE_SPK", "SITE_OUT2", "SITE_FF", "SITE_FFOUT")
+    assert [getattr(train, n) for n in names] == [getattr(HashDropout, n) for n in names] == [0, 1, 2, 3, 4, 5]
+    assert not any(hasattr(train_ls, n) or hasattr(train.FsTrainStep, n) for n in names)      # kept in one place
