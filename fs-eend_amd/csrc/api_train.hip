@@ -57,6 +57,65 @@ int plan_wgrad(long M, int N, int K, int conv_cin, long ws_floats, int* tile, in
     return EEND_OK;
 }
 
+// x_is_f16: bit 0 = X is f16 (else bf16), bit 1 = X in the blocked layout, bit 2 = dY in the blocked layout (include/eend_hip.h)
+WgradParams wgrad_params(const void* dY, int lda, const void* X, int ldb, int x_is_f16, long M, int N, int K, float* ws) {
+    WgradParams p;
+    memset(&p, 0, sizeof(p));
+    p.A = dY; p.B = X; p.partial = ws; p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb;
+    p.b_is_f16 = (x_is_f16 & 1) ? 1 : 0; p.b_blocked = (x_is_f16 & 2) ? 1 : 0; p.a_blocked = (x_is_f16 & 4) ? 1 : 0;
+    return p;
+}
+
+// plan -> main kernel -> tile reduction into out; with bias_out also the column sums of dY, written as N / bias_rows rows of bias_rows
+// (row stride bias_ld) and scaled / accumulated like the tiles.  The callers have checked what the two reductions would refuse.
+int wgrad_run(WgradParams& p, long ws_floats, float* out, int ld_out, int K_out, float* bias_out, int bias_rows, long bias_ld, float scale,
+              int accumulate, int group_rows, long group_gap, hipStream_t st) {
+    int rc = plan_wgrad(p.M, p.N, p.K, p.conv_cin, ws_floats, &p.tile, &p.nsplit, &p.m_per_split, bias_out != nullptr);
+    if (rc != EEND_OK) return rc;
+    if (bias_out) p.bias_partial = p.partial + (size_t)p.nsplit * p.N * p.K;
+    rc = eend_launch_wgrad(p, st);
+    if (rc != EEND_OK) return rc;
+    rc = eend_launch_wgrad_reduce_tiles(p.partial, p.tile, p.nsplit, p.N, p.K, K_out, out, ld_out, scale, accumulate, st, group_rows, group_gap);
+    if (rc != EEND_OK || !bias_out) return rc;
+    return eend_launch_wgrad_reduce(p.bias_partial, p.N, p.nsplit, p.N / bias_rows, bias_rows, bias_rows, bias_out, (int)bias_ld, scale,
+                                    accumulate, st);
+}
+
+// what the three fused-FFN entries set alike; everything else stays zero
+FfnParams ffn_base(const void* X, int ldx, const void* W1, const void* W2, const float* res, float alpha, float* out32, void* hid16,
+                   int M, int F) {
+    FfnParams p;
+    memset(&p, 0, sizeof(p));
+    p.X = X; p.ldx = ldx; p.W1 = W1; p.W2 = W2; p.res = res; p.alpha = alpha; p.out32 = out32; p.hid16 = hid16; p.M = M; p.F = F;
+    return p;
+}
+
+// number of row splits of the two FS BatchNorm passes over the B * T padded frames: 256 rows per split, at most 512 splits
+long bn_split_count(int B, int T) {
+    const long ns = ((long)B * T + 255) / 256;
+    return ns > 512 ? 512 : ns;
+}
+
+// number of blocks of the two LS BatchNorm statistics passes over the nseq * Tv valid slab rows: 32 rows per block (8 iterations of
+// four rows in flight per thread), at most 4096 blocks
+long slab_block_count(int nseq, int Tv) {
+    const long nb = ((long)nseq * Tv + 31) / 32;
+    return nb > 4096 ? 4096 : nb;
+}
+
+// LayerNorm backward over M rows of 256: the row pass, then d gamma | d beta | d bias -- the three column blocks of its partials --
+// in one reduction launch
+int layernorm_bwd(const void* g, int g_is_bf16, const void* xhat_f16, const float* rstd, const float* gamma, float* ds_f32, int accumulate,
+                  void* ds_bf16, float alpha16, float* ws, long ws_floats, float* dgamma, float* dbeta, float* dbias, long M,
+                  const eend_dropout* drop, void* stream) {
+    if (!ws || !dgamma || !dbeta || ws_floats < 1024L * 768 || (dbias && !ds_bf16)) return EEND_EINVAL;
+    int nb = 0;
+    int rc = eend_launch_ln_bwd2(g, g_is_bf16, xhat_f16, rstd, gamma, ds_f32, accumulate, ds_bf16, alpha16, ws, &nb, M, drop_spec(drop),
+                                 (hipStream_t)stream);
+    if (rc != EEND_OK) return rc;
+    return eend_launch_wgrad_reduce_multi(ws, 768, nb, 256, dgamma, dbeta, dbias, (hipStream_t)stream);
+}
+
 }  // namespace
 
 extern "C" {
@@ -85,10 +144,8 @@ int eend_ffn_train_f16(const void* X, int ldx, const void* W1, const float* b1, 
                        void* xhat_f16, float* rstd, int M, int F, const eend_dropout* drop_hidden, const eend_dropout* drop_out,
                        void* stream) {
     if (!X || !W1 || !b1 || !W2 || !b2 || !res || !gamma || !beta || !out_f32 || !out_f16 || !hid_f16 || !xhat_f16 || !rstd) return EEND_EINVAL;
-    FfnParams p;
-    memset(&p, 0, sizeof(p));
-    p.X = X; p.ldx = ldx; p.W1 = W1; p.b1 = b1; p.W2 = W2; p.b2 = b2; p.res = res; p.alpha = alpha; p.gamma = gamma; p.beta = beta;
-    p.eps = eps; p.out32 = out_f32; p.out16 = out_f16; p.M = M; p.F = F; p.hid16 = hid_f16; p.xhat16 = xhat_f16; p.rstat = rstd;
+    FfnParams p = ffn_base(X, ldx, W1, W2, res, alpha, out_f32, hid_f16, M, F);
+    p.b1 = b1; p.b2 = b2; p.gamma = gamma; p.beta = beta; p.eps = eps; p.out16 = out_f16; p.xhat16 = xhat_f16; p.rstat = rstd;
     p.drop1 = drop_spec(drop_hidden); p.drop2 = drop_spec(drop_out);
     return eend_launch_ffn_fused(p, 1, FFN_EPI_RES_LN, (hipStream_t)stream);
 }
@@ -98,10 +155,8 @@ int eend_ffn_swish_train_f16(const void* X, int ldx, const void* W1, const float
                              void* a_f16, void* xhat_f16, float* rstd, int M, int F, int residual_stream_unnormalised,
                              const eend_dropout* drop_hidden, const eend_dropout* drop_out, void* stream) {
     if (!X || !W1 || !b1 || !W2 || !b2 || !res || !gamma || !beta || !out_f32 || !out_f16 || !z_f16 || !a_f16 || !xhat_f16 || !rstd) return EEND_EINVAL;
-    FfnParams p;
-    memset(&p, 0, sizeof(p));
-    p.X = X; p.ldx = ldx; p.W1 = W1; p.b1 = b1; p.W2 = W2; p.b2 = b2; p.res = res; p.alpha = alpha; p.gamma = gamma; p.beta = beta;
-    p.eps = eps; p.out32 = out_f32; p.out16 = out_f16; p.M = M; p.F = F; p.hid16 = a_f16; p.z16 = z_f16; p.xhat16 = xhat_f16; p.rstat = rstd;
+    FfnParams p = ffn_base(X, ldx, W1, W2, res, alpha, out_f32, a_f16, M, F);
+    p.b1 = b1; p.b2 = b2; p.gamma = gamma; p.beta = beta; p.eps = eps; p.out16 = out_f16; p.z16 = z_f16; p.xhat16 = xhat_f16; p.rstat = rstd;
     p.drop1 = drop_spec(drop_hidden); p.drop2 = drop_spec(drop_out);
     return eend_launch_ffn_fused(p, 2, residual_stream_unnormalised ? FFN_EPI_RES_SCALE_LN16 : FFN_EPI_RES_LN, (hipStream_t)stream);
 }
@@ -109,10 +164,8 @@ int eend_ffn_swish_train_f16(const void* X, int ldx, const void* W1, const float
 int eend_ffn_bwd_data_bf16(const void* dY, int ldy, const void* W2T, const void* hid_f16, const void* W1T, float drop_scale,
                            void* dH_bf16, float* g_f32, int M, int F, void* stream) {
     if (!dY || !W2T || !hid_f16 || !W1T || !dH_bf16 || !g_f32) return EEND_EINVAL;
-    FfnParams p;
-    memset(&p, 0, sizeof(p));
-    p.X = dY; p.ldx = ldy; p.W1 = W2T; p.W2 = W1T; p.hidmask = hid_f16; p.hid16 = dH_bf16; p.res = g_f32; p.out32 = g_f32; p.alpha = 1.0f;
-    p.M = M; p.F = F; p.drop1 = DropSpec{0u, 0u, drop_scale};
+    FfnParams p = ffn_base(dY, ldy, W2T, W1T, g_f32, 1.0f, g_f32, dH_bf16, M, F);
+    p.hidmask = hid_f16; p.drop1 = DropSpec{0u, 0u, drop_scale};
     return eend_launch_ffn_fused(p, 0, FFN_EPI_RES_LN, (hipStream_t)stream);
 }
 
@@ -326,33 +379,16 @@ int eend_wgrad_bf16(const void* dY, int lda, const void* X, int ldb, int x_is_f1
                     long ws_floats, float* out, int ld_out, int K_out, float scale, int accumulate, void* stream) {
     if (!dY || !X || !ws || !out || M <= 0 || N <= 0 || K <= 0 || (N % 128) || (K % 128)) return EEND_EINVAL;
     if (K_out <= 0 || K_out > K || ld_out < K_out) return EEND_EINVAL;      // (before any launch: the reduction would refuse it after the main kernel ran)
-    WgradParams p;
-    memset(&p, 0, sizeof(p));
-    p.A = dY; p.B = X; p.partial = ws; p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb;
-    p.b_is_f16 = (x_is_f16 & 1) ? 1 : 0; p.b_blocked = (x_is_f16 & 2) ? 1 : 0; p.a_blocked = (x_is_f16 & 4) ? 1 : 0;
-    int rc = plan_wgrad(M, N, K, 0, ws_floats, &p.tile, &p.nsplit, &p.m_per_split);
-    if (rc != EEND_OK) return rc;
-    rc = eend_launch_wgrad(p, (hipStream_t)stream);
-    if (rc != EEND_OK) return rc;
-    return eend_launch_wgrad_reduce_tiles(ws, p.tile, p.nsplit, N, K, K_out, out, ld_out, scale, accumulate, (hipStream_t)stream);
+    WgradParams p = wgrad_params(dY, lda, X, ldb, x_is_f16, M, N, K, ws);
+    return wgrad_run(p, ws_floats, out, ld_out, K_out, nullptr, 0, 0, scale, accumulate, 0, 0, (hipStream_t)stream);
 }
 
 int eend_wgrad_bias_bf16(const void* dY, int lda, const void* X, int ldb, int x_is_f16, long M, int N, int K, float* ws,
                          long ws_floats, float* out, int ld_out, int K_out, float* bias_out, float scale, int accumulate, void* stream) {
     if (!dY || !X || !ws || !out || !bias_out || M <= 0 || N <= 0 || K <= 0 || (N % 128) || (K % 128)) return EEND_EINVAL;
     if (K_out <= 0 || K_out > K || ld_out < K_out) return EEND_EINVAL;
-    WgradParams p;
-    memset(&p, 0, sizeof(p));
-    p.A = dY; p.B = X; p.partial = ws; p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb;
-    p.b_is_f16 = (x_is_f16 & 1) ? 1 : 0; p.b_blocked = (x_is_f16 & 2) ? 1 : 0; p.a_blocked = (x_is_f16 & 4) ? 1 : 0;
-    int rc = plan_wgrad(M, N, K, 0, ws_floats, &p.tile, &p.nsplit, &p.m_per_split, true);
-    if (rc != EEND_OK) return rc;
-    p.bias_partial = ws + (size_t)p.nsplit * N * K;
-    rc = eend_launch_wgrad(p, (hipStream_t)stream);
-    if (rc != EEND_OK) return rc;
-    rc = eend_launch_wgrad_reduce_tiles(ws, p.tile, p.nsplit, N, K, K_out, out, ld_out, scale, accumulate, (hipStream_t)stream);
-    if (rc != EEND_OK) return rc;
-    return eend_launch_wgrad_reduce(p.bias_partial, N, p.nsplit, 1, N, N, bias_out, N, scale, accumulate, (hipStream_t)stream);
+    WgradParams p = wgrad_params(dY, lda, X, ldb, x_is_f16, M, N, K, ws);
+    return wgrad_run(p, ws_floats, out, ld_out, K_out, bias_out, N, N, scale, accumulate, 0, 0, (hipStream_t)stream);
 }
 
 int eend_wgrad_bias_grouped_bf16(const void* dY, int lda, const void* X, int ldb, int x_is_f16, long M, int N, int K, float* ws,
@@ -360,21 +396,10 @@ int eend_wgrad_bias_grouped_bf16(const void* dY, int lda, const void* X, int ldb
     if (!dY || !X || !ws || !out || !bias_out || M <= 0 || N <= 0 || K <= 0 || (N % 128) || (K % 128) || group_rows <= 0 || (N % group_rows) ||
         group_stride < (long)group_rows * K)
         return EEND_EINVAL;
-    WgradParams p;
-    memset(&p, 0, sizeof(p));
-    p.A = dY; p.B = X; p.partial = ws; p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb;
-    p.b_is_f16 = (x_is_f16 & 1) ? 1 : 0; p.b_blocked = (x_is_f16 & 2) ? 1 : 0; p.a_blocked = (x_is_f16 & 4) ? 1 : 0;
-    int rc = plan_wgrad(M, N, K, 0, ws_floats, &p.tile, &p.nsplit, &p.m_per_split, true);
-    if (rc != EEND_OK) return rc;
-    p.bias_partial = ws + (size_t)p.nsplit * N * K;
-    rc = eend_launch_wgrad(p, (hipStream_t)stream);
-    if (rc != EEND_OK) return rc;
-    rc = eend_launch_wgrad_reduce_tiles(ws, p.tile, p.nsplit, N, K, K, out, K, scale, 0, (hipStream_t)stream, group_rows,
-                                        group_stride - (long)group_rows * K);
-    if (rc != EEND_OK) return rc;
+    WgradParams p = wgrad_params(dY, lda, X, ldb, x_is_f16, M, N, K, ws);
     // bias_out[g * group_stride + r]: the column sums of dY as N / group_rows rows of group_rows
-    return eend_launch_wgrad_reduce(p.bias_partial, N, p.nsplit, N / group_rows, group_rows, group_rows, bias_out, (int)group_stride, scale, 0,
-                                    (hipStream_t)stream);
+    return wgrad_run(p, ws_floats, out, K, K, bias_out, group_rows, group_stride, scale, 0, group_rows, group_stride - (long)group_rows * K,
+                     (hipStream_t)stream);
 }
 
 int eend_conv1d_wgrad_bf16(const void* dY, const void* X_f16, const int* ilens, int nseq, int Tp, int cin, int ktaps,
@@ -382,15 +407,9 @@ int eend_conv1d_wgrad_bf16(const void* dY, const void* X_f16, const int* ilens, 
     if (!dY || !X_f16 || !ilens || !ws || !tmp || !out || nseq <= 0 || Tp <= 0 || cin != 256 || ktaps <= 0 || pad < 0 || pad >= ktaps)
         return EEND_EINVAL;
     const int N = 256, K = ktaps * cin;
-    WgradParams p;
-    memset(&p, 0, sizeof(p));
-    p.A = dY; p.B = X_f16; p.partial = ws; p.M = (long)nseq * Tp; p.N = N; p.K = K; p.lda = 256; p.ldb = cin; p.b_is_f16 = 1;
+    WgradParams p = wgrad_params(dY, 256, X_f16, cin, 1, (long)nseq * Tp, N, K, ws);
     p.conv = 1; p.conv_cin = cin; p.conv_pad = pad; p.Tp = Tp; p.ilens = ilens;
-    int rc = plan_wgrad(p.M, N, K, cin, ws_floats, &p.tile, &p.nsplit, &p.m_per_split);
-    if (rc != EEND_OK) return rc;
-    rc = eend_launch_wgrad(p, (hipStream_t)stream);
-    if (rc != EEND_OK) return rc;
-    rc = eend_launch_wgrad_reduce_tiles(ws, p.tile, p.nsplit, N, K, K, tmp, K, 1.0f, 0, (hipStream_t)stream);
+    const int rc = wgrad_run(p, ws_floats, tmp, K, K, nullptr, 0, 0, 1.0f, 0, 0, 0, (hipStream_t)stream);
     if (rc != EEND_OK) return rc;
     return eend_launch_conv_wgrad_unpermute(tmp, out, N, cin, ktaps, (hipStream_t)stream);
 }
@@ -409,12 +428,8 @@ int eend_colsum_f32(const void* Y, int ld, long M, int N, int is_bf16, float* ws
 int eend_layernorm_bwd_f32(const float* g, const void* xhat_f16, const float* rstd, const float* gamma, float* ds_f32,
                            void* ds_bf16, float* ws, long ws_floats, float* dgamma, float* dbeta, float* dbias, long M,
                            const eend_dropout* drop, void* stream) {
-    if (!ws || !dgamma || !dbeta || ws_floats < 1024L * 768 || (dbias && !ds_bf16)) return EEND_EINVAL;
-    int nb = 0;
-    int rc = eend_launch_ln_bwd(g, xhat_f16, rstd, gamma, ds_f32, ds_bf16, ws, &nb, M, drop_spec(drop), (hipStream_t)stream);
-    if (rc != EEND_OK) return rc;
-    // d gamma | d beta | d bias: the three column blocks of the row pass's partials, one reduction launch
-    return eend_launch_wgrad_reduce_multi(ws, 768, nb, 256, dgamma, dbeta, dbias, (hipStream_t)stream);
+    // f32 in, overwrite, un-scaled branch gradient; ds_f32 may be g itself
+    return layernorm_bwd(g, 0, xhat_f16, rstd, gamma, ds_f32, 0, ds_bf16, 1.0f, ws, ws_floats, dgamma, dbeta, dbias, M, drop, stream);
 }
 
 int eend_head_bce_f32(const float* emb, const float* attr, const float* labels, const int* ilens, const int* ncols,
@@ -458,8 +473,7 @@ int eend_bn_train_stats_f32(const void* const* x_ptrs, const int* lens, float pa
                             int F, void* stream) {
     if (!ws || !mean || !var || B <= 0 || T <= 0 || F <= 0) return EEND_EINVAL;
     if ((long)B * T < 2) return EEND_EINVAL;            // the unbiased running variance divides by n - 1: refused before any launch
-    long ns = ((long)B * T + 255) / 256;
-    if (ns > 512) ns = 512;
+    const long ns = bn_split_count(B, T);
     if (ws_floats < (ns + 1) * 2L * F) return EEND_EINVAL;
     float* sums = ws + ns * 2L * F;
     const float n = (float)((long)B * T);
@@ -479,8 +493,7 @@ int eend_bn_bwd_f32(const void* const* x_ptrs, const int* lens, float pad_value,
                     float eps, const void* dy_bf16, int ld, float* ws, long ws_floats, float* dgamma, float* dbeta,
                     int B, int T, int Tp, int F, void* stream) {
     if (!ws || !dgamma || !dbeta || B <= 0 || T <= 0 || F <= 0) return EEND_EINVAL;
-    long ns = ((long)B * T + 255) / 256;
-    if (ns > 512) ns = 512;
+    const long ns = bn_split_count(B, T);
     if (ws_floats < ns * 2L * F) return EEND_EINVAL;
     int rc = eend_launch_bn_bwd((const float* const*)x_ptrs, lens, pad_value, mean, var, eps, dy_bf16, ld, ws, B, T, Tp, F, (int)ns,
                                 (hipStream_t)stream);
@@ -533,13 +546,8 @@ int eend_layernorm_train_f16(const float* x, const float* gamma, const float* be
 int eend_layernorm_bwd2_f32(const void* g, int g_is_bf16, const void* xhat_f16, const float* rstd, const float* gamma,
                             float* ds_f32, int accumulate, void* ds_bf16, float alpha16, float* ws, long ws_floats,
                             float* dgamma, float* dbeta, float* dbias, long M, const eend_dropout* drop, void* stream) {
-    if (!ws || !dgamma || !dbeta || ws_floats < 1024L * 768 || (dbias && !ds_bf16)) return EEND_EINVAL;
-    int nb = 0;
-    int rc = eend_launch_ln_bwd2(g, g_is_bf16, xhat_f16, rstd, gamma, ds_f32, accumulate, ds_bf16, alpha16, ws, &nb, M, drop_spec(drop),
-                                 (hipStream_t)stream);
-    if (rc != EEND_OK) return rc;
-    // d gamma | d beta | d bias: the three column blocks of the row pass's partials, one reduction launch
-    return eend_launch_wgrad_reduce_multi(ws, 768, nb, 256, dgamma, dbeta, dbias, (hipStream_t)stream);
+    return layernorm_bwd(g, g_is_bf16, xhat_f16, rstd, gamma, ds_f32, accumulate, ds_bf16, alpha16, ws, ws_floats, dgamma, dbeta, dbias, M,
+                         drop, stream);
 }
 
 int eend_resgrad_cast_bf16(const float* g, void* ds_bf16, float alpha, float* ws, long ws_floats, float* dbias, long M,
@@ -569,8 +577,7 @@ int eend_glu_dwconv_f16(const void* P_f16, const float* w, void* c_f16, int nseq
 int eend_bn_batch_stats_f16(const void* c_f16, float* ws, long ws_floats, float* stats, int nseq, int Tp, int Tv,
                             void* stream) {
     if (!c_f16 || !ws || !stats || nseq <= 0 || Tv <= 0) return EEND_EINVAL;
-    long nb = ((long)nseq * Tv + 31) / 32;             // 32 rows per block: 8 iterations of four rows in flight per thread
-    if (nb > 4096) nb = 4096;
+    const long nb = slab_block_count(nseq, Tv);
     if (ws_floats < (nb + 1) * 256L) return EEND_EINVAL;
     float* sum = ws + nb * 256L;
     const float n = (float)((long)nseq * Tv);
@@ -600,8 +607,7 @@ int eend_bn_swish_bwd_stats_bf16(const void* ds_bf16, const void* c_f16, const f
                                  const float* gamma, const float* beta, float* ws, long ws_floats, float* sums,
                                  float* dgamma, float* dbeta, int nseq, int Tp, int Tv, void* stream) {
     if (!ws || !sums || !dgamma || !dbeta || nseq <= 0 || Tv <= 0) return EEND_EINVAL;
-    long nb = ((long)nseq * Tv + 31) / 32;             // 32 rows per block: 8 iterations of four rows in flight per thread
-    if (nb > 4096) nb = 4096;
+    const long nb = slab_block_count(nseq, Tv);
     if (ws_floats < nb * 512L) return EEND_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     int rc = eend_launch_bn_swish_bwd_stats(ds_bf16, c_f16, mean, var, eps, gamma, beta, ws, nseq, Tp, Tv, (int)nb, st);

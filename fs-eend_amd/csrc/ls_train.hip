@@ -17,6 +17,11 @@
 // and summed in fixed order by wgrad_reduce_kernel -- deterministic, no atomics.  Frames t >= Tv of a sequence slab
 // (Tv = the reference's chunk-padded length, Tp = Tv rounded up to 64) are not part of the reference's tensors: they
 // are excluded from every statistic and receive zero gradients.
+//
+// ln_bwd2 is the LayerNorm backward of BOTH training steps: the FS step's post-norm form (f32 in, overwrite, un-scaled
+// branch, in place over the residual gradient) is its <false, false> instance with alpha16 = 1, reached through
+// eend_layernorm_bwd_f32.  It lives here, not in train_rows.hip, because the general form is the LS step's.  The block tail
+// of the persistent row kernels is write_block_partials (train_common.h), shared with train_rows.hip's slot_sum.
 #include "train_common.h"
 #include "kernels.h"
 
@@ -45,11 +50,7 @@ void swish_drop_fwd_kernel(const unsigned short* __restrict__ z, unsigned short*
         float a0 = z0 * sigm(z0), a1 = z1 * sigm(z1);
         a0 = drop_apply(drop, a0, (unsigned)row, (unsigned)(col + 2 * j));
         a1 = drop_apply(drop, a1, (unsigned)row, (unsigned)(col + 2 * j + 1));
-        typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-        h2 p;
-        p[0] = to_f16_sat(a0);
-        p[1] = to_f16_sat(a1);
-        o[j] = __builtin_bit_cast(unsigned, p);
+        o[j] = pack_f16_sat(a0, a1);
     }
     *(u32x4*)(a + row * F + col) = o;
 }
@@ -98,20 +99,23 @@ void layernorm_train_kernel(const float* __restrict__ x, const float* __restrict
     if (lane == 0) rstd_out[row] = rs;
 }
 
-// LayerNorm backward, generalised (train_rows.hip ln_bwd_kernel is the f32-in / overwrite special case):
+// LayerNorm backward of both training steps.  y = x_hat * gamma + beta, x_hat = (s - mean) * rstd:
+//   ds = rstd * (dy*gamma - mean_j(dy*gamma) - x_hat * mean_j(dy*gamma*x_hat));  dgamma = sum_rows dy*x_hat;  dbeta = sum_rows dy
 //   G16: the gradient w.r.t. the LayerNorm output arrives as bf16 (from a data-gradient GEMM) instead of f32;
 //   ACC: ds32 += ds (pre-norm blocks: the LayerNorm sits on a branch, its input gradient joins the residual stream).
 // Optional ds16 = bf16(alpha16 * dropout(ds)) with its column sums (bias gradient of the linear in front of a
-// post-norm LayerNorm, scaled like the branch).  partial: [gridDim.x][3][256] = dgamma, dbeta, colsum(ds16).
+// post-norm LayerNorm, scaled like the branch; the forward dropped that linear's output with the same (row, column)
+// mask, the residual path ds32 is not masked).  partial: [gridDim.x][3][256] = dgamma, dbeta, colsum(ds16).
+// The FS step is <false, false> with alpha16 = 1 (exact in f32) and runs IN PLACE, ds32 == gin: a lane reads its four
+// gradients of a row before it writes the same four, and neither gin nor ds32 is __restrict__ -- keep it so.
 template <bool G16, bool ACC>
 __global__ __launch_bounds__(256)
-void ln_bwd2_kernel(const void* __restrict__ gin, const _Float16* __restrict__ xhat, const float* __restrict__ rstd,
+void ln_bwd2_kernel(const void* gin, const _Float16* __restrict__ xhat, const float* __restrict__ rstd,
                     const float* __restrict__ gamma, float* ds32, __bf16* __restrict__ ds16, float alpha16,
                     float* __restrict__ partial, long M, const DropSpec drop) {
-    __shared__ float red[4][3][D];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const float4 gm = *(const float4*)(gamma + lane * 4);
-    float dg[4] = {0.f, 0.f, 0.f, 0.f}, db[4] = {0.f, 0.f, 0.f, 0.f}, dbr[4] = {0.f, 0.f, 0.f, 0.f};
+    float acc[3][4] = {};                                    // dgamma, dbeta, colsum(ds16)
     for (long row = (long)blockIdx.x * 4 + wave; row < M; row += (long)gridDim.x * 4) {
         float4 gy;
         if constexpr (G16) {
@@ -144,18 +148,12 @@ void ln_bwd2_kernel(const void* __restrict__ gin, const _Float16* __restrict__ x
             pk.x = pack_bf16(m0, m1);
             pk.y = pack_bf16(m2, m3);
             *(uint2*)(ds16 + row * D + lane * 4) = pk;
-            dbr[0] += m0; dbr[1] += m1; dbr[2] += m2; dbr[3] += m3;
+            acc[2][0] += m0; acc[2][1] += m1; acc[2][2] += m2; acc[2][3] += m3;
         }
-        dg[0] += gy.x * x0; dg[1] += gy.y * x1; dg[2] += gy.z * x2; dg[3] += gy.w * x3;
-        db[0] += gy.x; db[1] += gy.y; db[2] += gy.z; db[3] += gy.w;
+        acc[0][0] += gy.x * x0; acc[0][1] += gy.y * x1; acc[0][2] += gy.z * x2; acc[0][3] += gy.w * x3;
+        acc[1][0] += gy.x; acc[1][1] += gy.y; acc[1][2] += gy.z; acc[1][3] += gy.w;
     }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { red[wave][0][lane * 4 + e] = dg[e]; red[wave][1][lane * 4 + e] = db[e]; red[wave][2][lane * 4 + e] = dbr[e]; }
-    __syncthreads();
-    const int c = threadIdx.x;
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-        partial[((size_t)blockIdx.x * 3 + k) * D + c] = (red[0][k][c] + red[1][k][c]) + (red[2][k][c] + red[3][k][c]);
+    write_block_partials<3>(acc, partial);
 }
 
 // Residual-stream gradient -> gradient of a pre-norm branch output: ds16 = bf16(alpha * dropout(g32)) and its column
@@ -163,9 +161,8 @@ void ln_bwd2_kernel(const void* __restrict__ gin, const _Float16* __restrict__ x
 __global__ __launch_bounds__(256)
 void resgrad_cast_kernel(const float* __restrict__ g, __bf16* __restrict__ ds16, float alpha, float* __restrict__ partial, long M,
                          const DropSpec drop) {
-    __shared__ float red[4][D];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    float acc[1][4] = {};
     for (long row = (long)blockIdx.x * 4 + wave; row < M; row += (long)gridDim.x * 4) {
         const float4 v = *(const float4*)(g + row * D + lane * 4);
         const unsigned n = (unsigned)(lane * 4);
@@ -175,13 +172,9 @@ void resgrad_cast_kernel(const float* __restrict__ g, __bf16* __restrict__ ds16,
         pk.x = pack_bf16(m0, m1);
         pk.y = pack_bf16(m2, m3);
         *(uint2*)(ds16 + row * D + lane * 4) = pk;
-        acc[0] += m0; acc[1] += m1; acc[2] += m2; acc[3] += m3;
+        acc[0][0] += m0; acc[0][1] += m1; acc[0][2] += m2; acc[0][3] += m3;
     }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) red[wave][lane * 4 + e] = acc[e];
-    __syncthreads();
-    const int c = threadIdx.x;
-    partial[(size_t)blockIdx.x * D + c] = (red[0][c] + red[1][c]) + (red[2][c] + red[3][c]);
+    write_block_partials<1>(acc, partial);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -222,27 +215,38 @@ void glu_dwconv_fwd_kernel(const _Float16* __restrict__ P, const float* __restri
     }
 }
 
+// Cursor of the walk both BatchNorm statistics kernels take over block blockIdx.x's contiguous range [r, r1) of the nseq * Tv valid
+// rows of a [nseq][Tp][256] slab, (sequence, frame) advanced incrementally (round 6).  The kernels take four rows in flight per
+// iteration, row k into the k-th of four accumulators; a row at or beyond r1 is not loaded and contributes nothing.
+struct SlabRows {
+    long r, r1, seq;
+    int t;
+    DEV SlabRows(int nseq, int Tv, long rows_per_block) {
+        const long nrows = (long)nseq * Tv;
+        r = (long)blockIdx.x * rows_per_block;
+        r1 = r + rows_per_block < nrows ? r + rows_per_block : nrows;
+        seq = r / Tv;
+        t = (int)(r - seq * Tv);
+    }
+    DEV size_t row(int Tp) const { return (size_t)seq * Tp + t; }      // slab row of the cursor
+    DEV void next(int Tv) { if (++t == Tv) { t = 0; ++seq; } }
+};
+
 // Column statistics of c16 over the valid frames (t < Tv of every sequence): shift == nullptr -> sums; else
 // sums of (c - shift)^2.  One thread per channel, a block per contiguous range of valid rows; partial [gridDim.x][256].
 __global__ __launch_bounds__(256)
 void bn_colstats16_kernel(const _Float16* __restrict__ c16, const float* __restrict__ shift, float* __restrict__ partial, int nseq,
                           int Tp, int Tv, long rows_per_block) {
     const int ch = threadIdx.x;
-    const long nrows = (long)nseq * Tv;
-    const long r0 = (long)blockIdx.x * rows_per_block;
-    long r1 = r0 + rows_per_block;
-    r1 = r1 < nrows ? r1 : nrows;
     const float mu = shift ? shift[ch] : 0.f;
     float a[4] = {0.f, 0.f, 0.f, 0.f};
-    long seq = r0 / Tv;
-    int t = (int)(r0 - seq * Tv);
-    for (long r = r0; r < r1; r += 4) {                       // four rows in flight, (sequence, frame) advanced incrementally (round 6)
+    for (SlabRows w(nseq, Tv, rows_per_block); w.r < w.r1; w.r += 4) {
         float v[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             v[k] = shift ? mu : 0.f;                          // (rows beyond the range contribute nothing)
-            if (r + k < r1) v[k] = (float)c16[((size_t)seq * Tp + t) * D + ch];
-            if (++t == Tv) { t = 0; ++seq; }
+            if (w.r + k < w.r1) v[k] = (float)c16[w.row(Tp) * D + ch];
+            w.next(Tv);
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) a[k] += shift ? (v[k] - mu) * (v[k] - mu) : v[k];
@@ -298,11 +302,7 @@ void bn_swish_fwd_kernel(const unsigned short* __restrict__ c16, const float* __
         const int c0 = col + 2 * j, c1 = c0 + 1;
         const float sc0 = gamma[c0] / __builtin_sqrtf(var[c0] + eps), sc1 = gamma[c1] / __builtin_sqrtf(var[c1] + eps);
         const float y0 = (f16_lo(x) - mean[c0]) * sc0 + beta[c0], y1 = (f16_hi(x) - mean[c1]) * sc1 + beta[c1];
-        typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-        h2 p;
-        p[0] = to_f16_sat(y0 * sigm(y0));
-        p[1] = to_f16_sat(y1 * sigm(y1));
-        o[j] = __builtin_bit_cast(unsigned, p);
+        o[j] = pack_f16_sat(y0 * sigm(y0), y1 * sigm(y1));
     }
     *(u32x4*)(s16 + row * D + col) = o;
 }
@@ -314,25 +314,19 @@ void bn_swish_bwd_stats_kernel(const __bf16* __restrict__ ds, const _Float16* __
                                const float* __restrict__ var, float eps, const float* __restrict__ gamma, const float* __restrict__ beta,
                                float* __restrict__ partial, int nseq, int Tp, int Tv, long rows_per_block) {
     const int ch = threadIdx.x;
-    const long nrows = (long)nseq * Tv;
-    const long r0 = (long)blockIdx.x * rows_per_block;
-    long r1 = r0 + rows_per_block;
-    r1 = r1 < nrows ? r1 : nrows;
     const float mu = mean[ch], rs = 1.0f / __builtin_sqrtf(var[ch] + eps), g = gamma[ch], b = beta[ch];
     float a1[4] = {0.f, 0.f, 0.f, 0.f}, a2[4] = {0.f, 0.f, 0.f, 0.f};
-    long seq = r0 / Tv;
-    int t = (int)(r0 - seq * Tv);
-    for (long r = r0; r < r1; r += 4) {                       // four rows in flight (see bn_colstats16_kernel)
+    for (SlabRows w(nseq, Tv, rows_per_block); w.r < w.r1; w.r += 4) {
         float cv[4], dv[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             cv[k] = mu; dv[k] = 0.f;
-            if (r + k < r1) {
-                const size_t off = ((size_t)seq * Tp + t) * D + ch;
+            if (w.r + k < w.r1) {
+                const size_t off = w.row(Tp) * D + ch;
                 cv[k] = (float)c16[off];
                 dv[k] = (float)ds[off];
             }
-            if (++t == Tv) { t = 0; ++seq; }
+            w.next(Tv);
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -455,10 +449,16 @@ void ret_gate_gn_bwd_kernel(const float* __restrict__ dctx, const _Float16* __re
     *(uint2*)(ot + row * D + lane * 4) = po;
 }
 
+// the grid of the persistent row kernels (LayerNorm backward, resgrad_cast): four rows per block and pass, at most 1024 blocks --
+// the row count of the partials their C entries size the workspace for
 int grid_rows(long M) {
     long nb = (M + 3) / 4;
     return (int)(nb < 1024 ? nb : 1024);
 }
+
+// the depthwise tap counts the two conv kernels are instantiated for
+template <class F>
+bool for_tap_count(int k, F&& f) { return dispatch_int<16, 7, 15, 31>(k, f); }
 
 }  // namespace
 
@@ -512,13 +512,10 @@ int eend_launch_resgrad_cast(const float* g, void* ds16, float alpha, float* par
 int eend_launch_glu_dwconv_fwd(const void* P16, const float* w, void* c16, int nseq, int Tp, int Tv, int k, hipStream_t stream) {
     if (!P16 || !w || !c16 || nseq <= 0 || nseq > 65535 || Tp <= 0 || Tv <= 0 || Tv > Tp) return EEND_EINVAL;
     const dim3 grid((Tp + 63) / 64, nseq);
-    switch (k) {
-        case 16: hipLaunchKernelGGL(glu_dwconv_fwd_kernel<16>, grid, dim3(256), 0, stream, (const _Float16*)P16, w, (_Float16*)c16, Tp, Tv); break;
-        case 7: hipLaunchKernelGGL(glu_dwconv_fwd_kernel<7>, grid, dim3(256), 0, stream, (const _Float16*)P16, w, (_Float16*)c16, Tp, Tv); break;
-        case 15: hipLaunchKernelGGL(glu_dwconv_fwd_kernel<15>, grid, dim3(256), 0, stream, (const _Float16*)P16, w, (_Float16*)c16, Tp, Tv); break;
-        case 31: hipLaunchKernelGGL(glu_dwconv_fwd_kernel<31>, grid, dim3(256), 0, stream, (const _Float16*)P16, w, (_Float16*)c16, Tp, Tv); break;
-        default: return EEND_EINVAL;
-    }
+    if (!for_tap_count(k, [&](auto kk) {
+            hipLaunchKernelGGL(glu_dwconv_fwd_kernel<decltype(kk)::value>, grid, dim3(256), 0, stream, (const _Float16*)P16, w, (_Float16*)c16, Tp, Tv);
+        }))
+        return EEND_EINVAL;
     return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
 }
 
@@ -574,16 +571,11 @@ int eend_launch_dwconv_glu_bwd(const void* dc16, const void* P16, const float* w
                                int k, hipStream_t stream) {
     if (!dc16 || !P16 || !w || !dP16 || !partial || nseq <= 0 || nseq > 65535 || Tp <= 0 || Tv <= 0 || Tv > Tp) return EEND_EINVAL;
     const dim3 grid((Tp + 63) / 64, nseq);
-#define DWB(KK) hipLaunchKernelGGL(dwconv_glu_bwd_kernel<KK>, grid, dim3(256), 0, stream, (const __bf16*)dc16, (const _Float16*)P16, w, \
-                                   (__bf16*)dP16, partial, Tp, Tv)
-    switch (k) {
-        case 16: DWB(16); break;
-        case 7: DWB(7); break;
-        case 15: DWB(15); break;
-        case 31: DWB(31); break;
-        default: return EEND_EINVAL;
-    }
-#undef DWB
+    if (!for_tap_count(k, [&](auto kk) {
+            hipLaunchKernelGGL(dwconv_glu_bwd_kernel<decltype(kk)::value>, grid, dim3(256), 0, stream, (const __bf16*)dc16, (const _Float16*)P16, w,
+                               (__bf16*)dP16, partial, Tp, Tv);
+        }))
+        return EEND_EINVAL;
     return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
 }
 

@@ -1,6 +1,9 @@
-// Device helpers shared by the training-step kernels (backward pass, optimiser).
+// Helpers shared by the training-step kernels (backward pass, optimiser): device code, and the launchers' dispatch over a
+// kernel's template parameter.
 #pragma once
 #include "common.h"
+#include <type_traits>
+#include <utility>
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
@@ -50,6 +53,13 @@ DEV unsigned pack_bf16(float lo, float hi) {
     o[1] = (__bf16)hi;
     return __builtin_bit_cast(unsigned, o);
 }
+DEV unsigned pack_f16_sat(float lo, float hi) {
+    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+    h2 o;
+    o[0] = to_f16_sat(lo);
+    o[1] = to_f16_sat(hi);
+    return __builtin_bit_cast(unsigned, o);
+}
 DEV float f16_lo(unsigned v) {
     typedef _Float16 h2 __attribute__((ext_vector_type(2)));
     return (float)__builtin_bit_cast(h2, v)[0];
@@ -63,4 +73,29 @@ DEV float wave_sum(float v) {
 #pragma unroll
     for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m, 64);
     return v;
+}
+
+// Tail of the persistent row kernels (256 threads = 4 waves over rows of 256 features, a lane owns columns 4*lane .. 4*lane + 3): each
+// wave hands in its K x 4 column sums, the block writes partial[(blockIdx.x * K + k) * 256 + c] = (wave0 + wave1) + (wave2 + wave3).
+// That addition order is part of the contract (the edge tests compare bit for bit).  EVERY thread of the block must get here, waves
+// whose row loop ran zero times included: there is a barrier inside.
+template <int K>
+DEV void write_block_partials(const float (&acc)[K][4], float* __restrict__ partial) {
+    __shared__ float red[4][K][256];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) red[wave][k][lane * 4 + e] = acc[k][e];
+    __syncthreads();
+    const int c = threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+        partial[((size_t)blockIdx.x * K + k) * 256 + c] = (red[0][k][c] + red[1][k][c]) + (red[2][k][c] + red[3][k][c]);
+}
+
+// Host: f(std::integral_constant<int, V>{}) for the V among Vs... that equals v -> true; none does -> false, f is not called.
+template <int... Vs, class F>
+bool dispatch_int(int v, F&& f) {
+    return ((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...);
 }

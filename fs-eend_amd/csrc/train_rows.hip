@@ -1,9 +1,11 @@
-// Row-local (HBM-bound) kernels of the training step: LayerNorm backward, the embedding.attractor head with its
-// BCE loss and gradient, L2-norm backward, the speaker-slot reductions of `convert`, speaker-axis attention
-// backward, train-mode BatchNorm statistics and its parameter gradients.  d_model = 256: one wave owns one row,
-// a lane 4 consecutive features (16-byte accesses), reductions are wave shuffles.  Parameter-gradient sums are
-// accumulated per wave over a persistent row loop, reduced per block through LDS and written as partials that
-// wgrad_reduce_kernel (wgrad.hip) sums in a fixed order -- deterministic, no atomics.
+// Row-local (HBM-bound) kernels of the training step: the embedding.attractor head with its BCE loss and gradient,
+// L2-norm backward, the speaker-slot reductions of `convert`, speaker-axis attention backward, train-mode BatchNorm
+// statistics and its parameter gradients.  d_model = 256: one wave owns one row, a lane 4 consecutive features
+// (16-byte accesses), reductions are wave shuffles.  Parameter-gradient sums are accumulated per wave over a
+// persistent row loop, reduced per block through LDS (write_block_partials, train_common.h) and written as partials
+// that wgrad_reduce_kernel (wgrad.hip) sums in a fixed order -- deterministic, no atomics.
+// The LayerNorm backward of this step is ls_train.hip's ln_bwd2_kernel<false, false> with alpha16 = 1: the LS step
+// needs the general form (bf16 input, accumulate, scaled branch), and the FS form was that kernel line for line.
 #include "train_common.h"
 #include "kernels.h"
 
@@ -11,54 +13,9 @@ namespace {
 
 constexpr int D = 256;
 
-// ---------------------------------------------------------------------------------------------------------------
-// LayerNorm backward.  y = x_hat * gamma + beta, x_hat = (s - mean) * rstd:
-//   ds = rstd * (dy*gamma - mean_j(dy*gamma) - x_hat * mean_j(dy*gamma*x_hat));  dgamma = sum_rows dy*x_hat;  dbeta = sum_rows dy
-// g: gradient w.r.t. the LayerNorm output (f32); ds32 may alias g.  partial: [gridDim.x][3][256]: dgamma, dbeta and the
-// column sums of the (dropout-masked) branch gradient = the bias gradient of the linear in front of the LayerNorm.
-// ---------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256)
-void ln_bwd_kernel(const float* g, const _Float16* __restrict__ xhat, const float* __restrict__ rstd,
-                   const float* __restrict__ gamma, float* ds32, __bf16* __restrict__ ds16, float* __restrict__ partial, long M,
-                   const DropSpec drop) {
-    __shared__ float red[4][3][D];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const float4 gm = *(const float4*)(gamma + lane * 4);
-    float dg[4] = {0.f, 0.f, 0.f, 0.f}, db[4] = {0.f, 0.f, 0.f, 0.f}, dbr[4] = {0.f, 0.f, 0.f, 0.f};
-    for (long row = (long)blockIdx.x * 4 + wave; row < M; row += (long)gridDim.x * 4) {
-        const float4 gy = *(const float4*)(g + row * D + lane * 4);
-        const f16x4 xh = *(const f16x4*)(xhat + row * D + lane * 4);
-        const float rs = rstd[row];
-        const float x0 = (float)xh[0], x1 = (float)xh[1], x2 = (float)xh[2], x3 = (float)xh[3];
-        const float d0 = gy.x * gm.x, d1 = gy.y * gm.y, d2 = gy.z * gm.z, d3 = gy.w * gm.w;
-        const float c1 = wave_sum(d0 + d1 + d2 + d3) * (1.0f / D);
-        const float c2 = wave_sum(d0 * x0 + d1 * x1 + d2 * x2 + d3 * x3) * (1.0f / D);
-        const float o0 = rs * (d0 - c1 - x0 * c2), o1 = rs * (d1 - c1 - x1 * c2);
-        const float o2 = rs * (d2 - c1 - x2 * c2), o3 = rs * (d3 - c1 - x3 * c2);
-        if (ds32) *(float4*)(ds32 + row * D + lane * 4) = make_float4(o0, o1, o2, o3);
-        if (ds16) {
-            // ds16 feeds the sub-layer branch (the linear in front of this LayerNorm): the forward dropped its output
-            // with the same (row, column) mask; the residual path (ds32) is not masked
-            const unsigned n = (unsigned)(lane * 4);
-            const float m0 = drop_apply(drop, o0, (unsigned)row, n), m1 = drop_apply(drop, o1, (unsigned)row, n + 1);
-            const float m2 = drop_apply(drop, o2, (unsigned)row, n + 2), m3 = drop_apply(drop, o3, (unsigned)row, n + 3);
-            uint2 pk;
-            pk.x = pack_bf16(m0, m1);
-            pk.y = pack_bf16(m2, m3);
-            *(uint2*)(ds16 + row * D + lane * 4) = pk;
-            dbr[0] += m0; dbr[1] += m1; dbr[2] += m2; dbr[3] += m3;
-        }
-        dg[0] += gy.x * x0; dg[1] += gy.y * x1; dg[2] += gy.z * x2; dg[3] += gy.w * x3;
-        db[0] += gy.x; db[1] += gy.y; db[2] += gy.z; db[3] += gy.w;
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { red[wave][0][lane * 4 + e] = dg[e]; red[wave][1][lane * 4 + e] = db[e]; red[wave][2][lane * 4 + e] = dbr[e]; }
-    __syncthreads();
-    const int c = threadIdx.x;
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-        partial[((size_t)blockIdx.x * 3 + k) * D + c] = (red[0][k][c] + red[1][k][c]) + (red[2][k][c] + red[3][k][c]);
-}
+// the speaker-slot counts the slot kernels are instantiated for
+template <class F>
+bool for_slot_count(int C, F&& f) { return dispatch_int<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12>(C, f); }
 
 // ---------------------------------------------------------------------------------------------------------------
 // Head forward + BCE loss + gradient, one wave per frame (b, t), t < Tp:
@@ -146,7 +103,6 @@ void l2norm_bwd_kernel(const float* __restrict__ y, const float* __restrict__ dy
 template <int C>
 __global__ __launch_bounds__(256)
 void slot_sum_kernel(const float* __restrict__ g0, __bf16* __restrict__ gsum, float* __restrict__ partial, int B, int Tp) {
-    __shared__ float red[4][C][D];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float acc[C][4];
 #pragma unroll
@@ -166,14 +122,7 @@ void slot_sum_kernel(const float* __restrict__ g0, __bf16* __restrict__ gsum, fl
         pk.y = pack_bf16(s.z, s.w);
         *(uint2*)(gsum + frame * D + lane * 4) = pk;
     }
-#pragma unroll
-    for (int c = 0; c < C; ++c)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) red[wave][c][lane * 4 + e] = acc[c][e];
-    __syncthreads();
-    for (int c = 0; c < C; ++c)
-        partial[((size_t)blockIdx.x * C + c) * D + threadIdx.x] =
-            (red[0][c][threadIdx.x] + red[1][c][threadIdx.x]) + (red[2][c][threadIdx.x] + red[3][c][threadIdx.x]);
+    write_block_partials<C>(acc, partial);
 }
 
 // convert.weight[:, D:] / convert.bias gradients and the forward constant, all (C, 256)-sized:
@@ -304,37 +253,48 @@ void spk_attn_bwd_kernel(const _Float16* __restrict__ qkv, const __bf16* __restr
 // Pass A: partial[s][0][c] = sum (x - shift_c), partial[s][1][c] = sum (x - shift_c)^2 over the split's rows.
 // Two passes (shift = 0, then shift = mean) give a cancellation-free variance.  Thread = feature column.
 // ---------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256)
-void bn_colstats_kernel(const float* const* __restrict__ x_ptrs, const int* __restrict__ lens, float pad_value,
-                        const float* __restrict__ shift, float* __restrict__ partial, int B, int T, int F, long rows_per_split) {
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= F) return;
+// The walk both BatchNorm channel kernels take over column c of split blockIdx.y's rows [r0, r1) of the padded (B, T) frames:
+// sixteen rows in flight per iteration, (utterance, frame) advanced incrementally, summed IN ROW ORDER (round 6: the one-row loop with
+// a division, a length and a pointer load per row was latency-bound -- 123 us per pass over 44 MB; same sums bit for bit).  The loads
+// are branch-free: a row beyond the split or the utterance reads `harmless` (any readable float of this thread's) and is replaced by
+// pad_value.  also(k, b, t) runs beside the load of row k (b = t = 0 beyond the split) for a second operand, sum(k, x) in row order
+// for the rows inside the split only.
+template <class Also, class Sum>
+DEV void bn_walk_split(const float* const* __restrict__ x_ptrs, const int* __restrict__ lens, float pad_value, const float* harmless,
+                       int B, int T, int F, int c, long rows_per_split, Also&& also, Sum&& sum) {
     const long r0 = (long)blockIdx.y * rows_per_split;
     long r1 = r0 + rows_per_split;
     if (r1 > (long)B * T) r1 = (long)B * T;
-    const float sh = shift ? shift[c] : 0.f;
-    // sixteen rows in flight per iteration, (utterance, frame) advanced incrementally, summed IN ROW ORDER (round 6: the one-row loop with a
-    // division, a length and a pointer load per row was latency-bound -- 123 us per pass over 44 MB; same sums bit for bit)
-    float s1 = 0.f, s2 = 0.f;
     int b = (int)(r0 / T), t = (int)(r0 - (long)b * T);
     for (long r = r0; r < r1; r += 16) {
         float x[16];
 #pragma unroll
         for (int k = 0; k < 16; ++k) {
-            // branch-free: a row beyond the split or the utterance loads from a harmless address (this thread's partial slot) and is replaced
             const bool in = r + k < r1;
-            const int bb = in ? b : 0;
+            const int bb = in ? b : 0, tt = in ? t : 0;
             const bool real = in && t < lens[bb];
-            const float* src = real ? x_ptrs[bb] + (size_t)t * F + c : partial + c;
+            const float* src = real ? x_ptrs[bb] + (size_t)t * F + c : harmless;
             const float v = *src;
             x[k] = real ? v : pad_value;
+            also(k, bb, tt);
             if (++t == T) { t = 0; ++b; }
         }
 #pragma unroll
         for (int k = 0; k < 16; ++k) {
-            if (r + k < r1) { const float d = x[k] - sh; s1 += d; s2 = __builtin_fmaf(d, d, s2); }
+            if (r + k < r1) sum(k, x[k]);
         }
     }
+}
+
+__global__ __launch_bounds__(256)
+void bn_colstats_kernel(const float* const* __restrict__ x_ptrs, const int* __restrict__ lens, float pad_value,
+                        const float* __restrict__ shift, float* __restrict__ partial, int B, int T, int F, long rows_per_split) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= F) return;
+    const float sh = shift ? shift[c] : 0.f;
+    float s1 = 0.f, s2 = 0.f;
+    bn_walk_split(x_ptrs, lens, pad_value, partial + c, B, T, F, c, rows_per_split, [](int, int, int) __attribute__((always_inline)) {},
+                  [&](int, float x) __attribute__((always_inline)) { const float d = x - sh; s1 += d; s2 = __builtin_fmaf(d, d, s2); });
     partial[((size_t)blockIdx.y * 2 + 0) * F + c] = s1;
     partial[((size_t)blockIdx.y * 2 + 1) * F + c] = s2;
 }
@@ -369,30 +329,11 @@ void bn_bwd_kernel(const float* const* __restrict__ x_ptrs, const int* __restric
                    float* __restrict__ partial, int B, int T, int Tp, int F, long rows_per_split) {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= F) return;
-    const long r0 = (long)blockIdx.y * rows_per_split;
-    long r1 = r0 + rows_per_split;
-    if (r1 > (long)B * T) r1 = (long)B * T;
     const float mu = mean[c], rs = 1.0f / __builtin_sqrtf(var[c] + eps);
-    float s1 = 0.f, s2 = 0.f;
-    int b = (int)(r0 / T), t = (int)(r0 - (long)b * T);
-    for (long r = r0; r < r1; r += 16) {                      // sixteen rows in flight, summed in row order (see bn_colstats_kernel)
-        float x[16], g[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            const bool in = r + k < r1;                       // branch-free, as in bn_colstats_kernel
-            const int bb = in ? b : 0, tt = in ? t : 0;
-            const bool real = in && t < lens[bb];
-            const float* src = real ? x_ptrs[bb] + (size_t)t * F + c : mean + c;
-            const float v = *src;
-            x[k] = real ? v : pad_value;
-            g[k] = (float)dy[((size_t)bb * Tp + tt) * ld + c];
-            if (++t == T) { t = 0; ++b; }
-        }
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            if (r + k < r1) { s1 = __builtin_fmaf(g[k], (x[k] - mu) * rs, s1); s2 += g[k]; }
-        }
-    }
+    float s1 = 0.f, s2 = 0.f, g[16];
+    bn_walk_split(x_ptrs, lens, pad_value, mean + c, B, T, F, c, rows_per_split,
+                  [&](int k, int b, int t) __attribute__((always_inline)) { g[k] = (float)dy[((size_t)b * Tp + t) * ld + c]; },
+                  [&](int k, float x) __attribute__((always_inline)) { s1 = __builtin_fmaf(g[k], (x - mu) * rs, s1); s2 += g[k]; });
     partial[((size_t)blockIdx.y * 2 + 0) * F + c] = s1;
     partial[((size_t)blockIdx.y * 2 + 1) * F + c] = s2;
 }
@@ -413,20 +354,6 @@ void attn_rowdot_kernel(const __bf16* __restrict__ dO, const _Float16* __restric
 }
 
 }  // namespace
-
-static int persistent_blocks(long rows) {
-    long nb = (rows + 3) / 4;
-    return (int)(nb < 1024 ? nb : 1024);
-}
-
-int eend_launch_ln_bwd(const float* g, const void* xhat16, const float* rstd, const float* gamma, float* ds32, void* ds16,
-                       float* partial, int* nblocks_out, long M, DropSpec drop, hipStream_t stream) {
-    if (!g || !xhat16 || !rstd || !gamma || !partial || M <= 0) return EEND_EINVAL;
-    const int nb = persistent_blocks(M);
-    if (nblocks_out) *nblocks_out = nb;
-    hipLaunchKernelGGL(ln_bwd_kernel, dim3(nb), dim3(256), 0, stream, g, (const _Float16*)xhat16, rstd, gamma, ds32, (__bf16*)ds16, partial, M, drop);
-    return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
-}
 
 int eend_launch_head_bce(const float* emb, const float* attr, const float* labels, const int* ilens, const int* ncols,
                          float inv_frames, const float* dlogits_in, float* logits, float* da, float* de, float* loss_partial, int B,
@@ -451,12 +378,10 @@ int eend_launch_slot_sum(const float* g0, void* gsum16, float* partial, int* nbl
     long nbl = ((long)B * Tp + 3) / 4;
     const int nb = (int)(nbl < 256 ? nbl : 256);
     if (nblocks_out) *nblocks_out = nb;
-    switch (C) {
-#define SS_CASE(n) case n: hipLaunchKernelGGL(slot_sum_kernel<n>, dim3(nb), dim3(256), 0, stream, g0, (__bf16*)gsum16, partial, B, Tp); break;
-        SS_CASE(1) SS_CASE(2) SS_CASE(3) SS_CASE(4) SS_CASE(5) SS_CASE(6) SS_CASE(7) SS_CASE(8) SS_CASE(9) SS_CASE(10) SS_CASE(11) SS_CASE(12)
-#undef SS_CASE
-        default: return EEND_EINVAL;
-    }
+    if (!for_slot_count(C, [&](auto c) {
+            hipLaunchKernelGGL(slot_sum_kernel<decltype(c)::value>, dim3(nb), dim3(256), 0, stream, g0, (__bf16*)gsum16, partial, B, Tp);
+        }))
+        return EEND_EINVAL;
     return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
 }
 
@@ -472,12 +397,11 @@ int eend_launch_spk_attn_bwd(const void* qkv16, const void* dO16, void* dqkv16, 
                              hipStream_t stream) {
     if (!qkv16 || !dO16 || !dqkv16 || B <= 0 || Tp <= 0) return EEND_EINVAL;
     const long nb = ((long)B * Tp + 3) / 4;
-    switch (C) {
-#define SB_CASE(n) case n: hipLaunchKernelGGL(spk_attn_bwd_kernel<n>, dim3((unsigned)nb), dim3(256), 0, stream, (const _Float16*)qkv16, (const __bf16*)dO16, (__bf16*)dqkv16, B, Tp, scale, drop); break;
-        SB_CASE(1) SB_CASE(2) SB_CASE(3) SB_CASE(4) SB_CASE(5) SB_CASE(6) SB_CASE(7) SB_CASE(8) SB_CASE(9) SB_CASE(10) SB_CASE(11) SB_CASE(12)
-#undef SB_CASE
-        default: return EEND_EINVAL;
-    }
+    if (!for_slot_count(C, [&](auto c) {
+            hipLaunchKernelGGL(spk_attn_bwd_kernel<decltype(c)::value>, dim3((unsigned)nb), dim3(256), 0, stream, (const _Float16*)qkv16,
+                               (const __bf16*)dO16, (__bf16*)dqkv16, B, Tp, scale, drop);
+        }))
+        return EEND_EINVAL;
     return hipGetLastError() == hipSuccess ? EEND_OK : EEND_ELAUNCH;
 }
 

@@ -328,6 +328,50 @@ void wgrad_tr_kernel(const WgradParams p) {
     }
 }
 
+// The two walks of the reduction kernels over the nsplit partials src[s * stride] of one output.  Their addition orders are part of
+// the contract: the gradients are reproducible bit for bit, and tests/test_wgrad_edges.py compares them so.
+//
+// One thread per output (V = float, or f32x4 for four adjacent ones): four accumulators over the splits 4i .. 4i + 3, the remainder
+// into the first, combined as (s0 + s1) + (s2 + s3).
+template <class V>
+DEV V sum_splits(const V* __restrict__ src, long stride, int nsplit) {
+    V s0 = V{}, s1 = s0, s2 = s0, s3 = s0;
+    int s = 0;
+    for (; s + 4 <= nsplit; s += 4) {
+        s0 += src[(size_t)(s + 0) * stride];
+        s1 += src[(size_t)(s + 1) * stride];
+        s2 += src[(size_t)(s + 2) * stride];
+        s3 += src[(size_t)(s + 3) * stride];
+    }
+    for (; s < nsplit; ++s) s0 += src[(size_t)s * stride];
+    return (s0 + s1) + (s2 + s3);
+}
+
+// Few outputs, many partials: a block of 256 threads serves 32 outputs (o = threadIdx.x & 31), its 8 lane groups g = threadIdx.x >> 5
+// walk the splits g, g + 8, ... with eight loads in flight per thread (the walk is latency-bound: 20 us per call with two) and are
+// combined through LDS in a fixed order.  EVERY thread of the block must call it (barrier inside; live = false: nothing is loaded);
+// the sum is returned to every lane group, group 0 stores it.
+DEV float sum_splits_8groups(const float* __restrict__ src, long stride, int nsplit, bool live) {
+    __shared__ float red[8][32];
+    const int o = threadIdx.x & 31, g = threadIdx.x >> 5;
+    float s = 0.f;
+    if (live) {
+        float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        int sp = g;
+        for (; sp + 56 < nsplit; sp += 64) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) a[j] += src[(size_t)(sp + 8 * j) * stride];
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (sp + 8 * j < nsplit) a[j] += src[(size_t)(sp + 8 * j) * stride];
+        s = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
+    }
+    red[g][o] = s;
+    __syncthreads();
+    return ((red[0][o] + red[1][o]) + (red[2][o] + red[3][o])) + ((red[4][o] + red[5][o]) + (red[6][o] + red[7][o]));
+}
+
 // out[n][k] (row stride ld_out, k < K_out) = scale * sum_s partial[s][...]   (+ out if accumulate), partial in the accumulator order
 // of wgrad_tr_kernel<BT>: one thread per f32x4, consecutive threads read consecutive 16 bytes of every split's partial.
 template <int BT>
@@ -347,18 +391,7 @@ void wgrad_reduce_tr_kernel(const float* __restrict__ partial, long split_stride
     const int wk = wave >> 1, wn = wave & 1;
     const int n = (tile / ntk) * BT + wn * (BT / 2) + j * 32 + (lane & 31);
     const int k = (tile % ntk) * BT + wk * 64 + i * 32 + 8 * r4 + (lane >> 5) * 4;
-    const f32x4* src = (const f32x4*)partial + idx;
-    const long ss4 = split_stride / 4;
-    f32x4 s0 = f32x4{0.f, 0.f, 0.f, 0.f}, s1 = s0, s2 = s0, s3 = s0;
-    int s = 0;
-    for (; s + 4 <= nsplit; s += 4) {
-        s0 += src[(size_t)(s + 0) * ss4];
-        s1 += src[(size_t)(s + 1) * ss4];
-        s2 += src[(size_t)(s + 2) * ss4];
-        s3 += src[(size_t)(s + 3) * ss4];
-    }
-    for (; s < nsplit; ++s) s0 += src[(size_t)s * ss4];
-    const f32x4 v = ((s0 + s1) + (s2 + s3)) * scale;
+    const f32x4 v = sum_splits((const f32x4*)partial + idx, split_stride / 4, nsplit) * scale;
     // (group_rows > 0: the rows belong to several equally spaced destination tensors -- the four projections of a retention module in the
     // flat gradient buffer: group g = n / group_rows starts group_gap floats further than contiguous rows would)
     float* o = out + (size_t)n * ld_out + k + (group_rows > 0 ? (long)(n / group_rows) * group_gap : 0L);
@@ -374,52 +407,22 @@ void wgrad_reduce_kernel(const float* __restrict__ partial, long split_stride, i
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (long)N * K_out) return;
     const int n = (int)(idx / K_out), k = (int)(idx - (long)n * K_out);
-    const float* src = partial + (size_t)n * K + k;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    int s = 0;
-    for (; s + 4 <= nsplit; s += 4) {
-        s0 += src[(size_t)(s + 0) * split_stride];
-        s1 += src[(size_t)(s + 1) * split_stride];
-        s2 += src[(size_t)(s + 2) * split_stride];
-        s3 += src[(size_t)(s + 3) * split_stride];
-    }
-    for (; s < nsplit; ++s) s0 += src[(size_t)s * split_stride];
-    float v = ((s0 + s1) + (s2 + s3)) * scale;
+    float v = sum_splits(partial + (size_t)n * K + k, split_stride, nsplit) * scale;
     float* o = out + (size_t)n * ld_out + k;
     if (accumulate) v += *o;
     *o = v;
 }
 
-// Few outputs, many partials (LayerNorm / bias gradients: <= a few thousand outputs, up to 1024 partials): 8 lane
-// groups walk the partials in parallel (coalesced over 32 consecutive outputs) and are combined in a fixed order.
+// Few outputs, many partials (LayerNorm / bias gradients: <= a few thousand outputs, up to 1024 partials), coalesced over 32
+// consecutive outputs: sum_splits_8groups.
 __global__ __launch_bounds__(256)
 void wgrad_reduce_small_kernel(const float* __restrict__ partial, long split_stride, int nsplit, int N, int K, int K_out,
                                float* __restrict__ out, int ld_out, float scale, int accumulate) {
-    __shared__ float red[8][32];
-    const int o = threadIdx.x & 31, g = threadIdx.x >> 5;
-    const long idx = (long)blockIdx.x * 32 + o;
+    const long idx = (long)blockIdx.x * 32 + (threadIdx.x & 31);
     const bool live = idx < (long)N * K_out;
-    float s = 0.f;
-    if (live) {
-        const int n = (int)(idx / K_out), k = (int)(idx - (long)n * K_out);
-        const float* src = partial + (size_t)n * K + k;
-        // eight loads in flight per thread (the walk is latency-bound: 20 us per call with two); fixed combination order
-        float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        int sp = g;
-        for (; sp + 56 < nsplit; sp += 64) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) a[j] += src[(size_t)(sp + 8 * j) * split_stride];
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            if (sp + 8 * j < nsplit) a[j] += src[(size_t)(sp + 8 * j) * split_stride];
-        s = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
-    }
-    red[g][o] = s;
-    __syncthreads();
-    if (g == 0 && live) {
-        const int n = (int)(idx / K_out), k = (int)(idx - (long)n * K_out);
-        float v = (((red[0][o] + red[1][o]) + (red[2][o] + red[3][o])) + ((red[4][o] + red[5][o]) + (red[6][o] + red[7][o]))) * scale;
+    const int n = (int)(idx / K_out), k = (int)(idx - (long)n * K_out);
+    float v = sum_splits_8groups(partial + (size_t)n * K + k, split_stride, nsplit, live) * scale;
+    if (threadIdx.x < 32 && live) {
         float* dst = out + (size_t)n * ld_out + k;
         if (accumulate) v += *dst;
         *dst = v;
@@ -432,30 +435,12 @@ void wgrad_reduce_small_kernel(const float* __restrict__ partial, long split_str
 __global__ __launch_bounds__(256)
 void wgrad_reduce_multi_kernel(const float* __restrict__ partial, long split_stride, int nsplit, int ncols, int W,
                                float* __restrict__ out0, float* __restrict__ out1, float* __restrict__ out2) {
-    __shared__ float red[8][32];
-    const int o = threadIdx.x & 31, g = threadIdx.x >> 5;
-    const int col = blockIdx.x * 32 + o;
+    const int col = blockIdx.x * 32 + (threadIdx.x & 31);
     const int seg = col / W;
     float* dst = seg == 0 ? out0 : (seg == 1 ? out1 : out2);
     const bool live = col < ncols && dst != nullptr;
-    float s = 0.f;
-    if (live) {
-        const float* src = partial + col;
-        float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        int sp = g;
-        for (; sp + 56 < nsplit; sp += 64) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) a[j] += src[(size_t)(sp + 8 * j) * split_stride];
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            if (sp + 8 * j < nsplit) a[j] += src[(size_t)(sp + 8 * j) * split_stride];
-        s = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
-    }
-    red[g][o] = s;
-    __syncthreads();
-    if (g == 0 && live)
-        dst[col - seg * W] = ((red[0][o] + red[1][o]) + (red[2][o] + red[3][o])) + ((red[4][o] + red[5][o]) + (red[6][o] + red[7][o]));
+    const float v = sum_splits_8groups(partial + col, split_stride, nsplit, live);
+    if (threadIdx.x < 32 && live) dst[col - seg * W] = v;
 }
 
 // Column sums of a 2-byte-float matrix [M][N] (bias gradients): partial[s][n] = sum over the split's rows.

@@ -193,6 +193,38 @@ def test_layernorm_bwd2(hip_lib, dev, M):
 
 
 @pytest.mark.parametrize("M", E.ROW_M)
+def test_layernorm_bwd_is_bwd2_with_unit_alpha(hip_lib, dev, M):
+    """eend_layernorm_bwd_f32 and eend_layernorm_bwd2_f32(g_is_bf16 = 0, accumulate = 0, alpha16 = 1.0) run one kernel: the same operands
+    give byte-identical ds32, ds16, dgamma, dbeta and dbias, with and without p = 0.5 dropout, with ds_f32 aliasing g and separate"""
+    L = hip_lib
+    _grid_line("eend_layernorm_bwd_f32 / eend_layernorm_bwd2_f32", M)
+    gd, xd, rd, gam, refs = _ln_inputs(dev, M)
+    raw = lambda t: t.contiguous().view(torch.uint8)
+    for thresh in (0, E.HALF):
+        spec = _spec(SEED, thresh)
+        dref = ctypes.byref(spec) if thresh else None
+        for in_place in (False, True):
+            outs = []
+            for entry in ("eend_layernorm_bwd_f32", "eend_layernorm_bwd2_f32"):
+                ws = _ws(dev, LN_WS)
+                dg, db, dbias = (_nan((2, D), F32, dev) for _ in range(3))
+                gin = gd.clone()
+                ds32 = gin if in_place else _nan((M + 4, D), F32, dev)
+                ds16 = _nan((M + 4, D), BF16, dev)
+                if entry == "eend_layernorm_bwd_f32":
+                    rc = _rc(L, entry, gin, xd, rd, gam, ds32, ds16, ws, LN_WS, dg, db, dbias, M, dref)
+                else:
+                    rc = _rc(L, entry, gin, 0, xd, rd, gam, ds32, 0, ds16, 1.0, ws, LN_WS, dg, db, dbias, M, dref)
+                assert rc == 0, (entry, thresh, in_place)
+                assert _ws_tail_untouched(ws, LN_WS)
+                assert in_place or torch.equal(raw(gin), raw(gd)), "g is an input"
+                _check_ln_outputs(refs[(1.0, thresh)], M, dg, db, dbias, ds32, ds16)
+                outs.append((ds32, ds16, dg, db, dbias))
+            for name, a, b in zip(("ds32", "ds16", "dgamma", "dbeta", "dbias"), *outs):
+                assert torch.equal(raw(a), raw(b)), (name, thresh, in_place)
+
+
+@pytest.mark.parametrize("M", E.ROW_M)
 def test_resgrad_cast(hip_lib, dev, M):
     L = hip_lib
     _grid_line("eend_resgrad_cast_bf16", M)
