@@ -7,7 +7,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["gemm.hip", "ffn.hip", "ffn_stream.hip", "convert_f32.hip", "convert_rows.hip", "encin.hip", "conv_stream.hip", "proj.hip", "attn.hip", "attn_full.hip", "attn_stream.hip", "spk_stream.hip", "dec_stream.hip", "embloss.hip", "postproc.hip", "der_collar.hip", "der_sweep.hip", "segtrack.hip", "feature.hip", "resample.hip", "simulate.hip", "room.hip", "lstm.hip", "stb.hip", "pit.hip", "misc.hip", "retention.hip", "retention_full.hip", "ret_stream.hip", "stream.hip", "stream_multi.hip", "stream_chunk.hip", "attn_prefill.hip", "copy_blocks.hip", "ls_multi.hip", "ls_chunk.hip", "ls_prefill.hip", "skinny.hip", "gemm_f32.hip", "api.hip",
+SOURCES = ["gemm.hip", "ffn.hip", "ffn_stream.hip", "convert_f32.hip", "convert_rows.hip", "encin.hip", "conv_stream.hip", "proj.hip", "attn.hip", "attn_full.hip", "attn_stream.hip", "spk_stream.hip", "dec_stream.hip", "embloss.hip", "postproc.hip", "der_collar.hip", "der_sweep.hip", "segraster.hip", "segtrack.hip", "feature.hip", "resample.hip", "simulate.hip", "room.hip", "lstm.hip", "stb.hip", "pit.hip", "misc.hip", "retention.hip", "retention_full.hip", "ret_stream.hip", "stream.hip", "stream_multi.hip", "stream_chunk.hip", "attn_prefill.hip", "copy_blocks.hip", "ls_multi.hip", "ls_chunk.hip", "ls_prefill.hip", "skinny.hip", "gemm_f32.hip", "api.hip",
            # training step: backward kernels, optimiser
            "wgrad.hip", "ffn_train_stream.hip", "proj_stream.hip", "gemm_acc_stream.hip", "attn_bwd.hip", "attn_bwd_fused.hip", "train_rows.hip", "embloss_bwd.hip", "optim.hip", "api_train.hip", "wgrad_f32.hip",
            # LS-EEND training step

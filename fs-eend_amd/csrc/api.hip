@@ -511,6 +511,35 @@ int eend_collar_der_sweep_u64(const unsigned char* ref, const int* ref_off, int 
                                         subsampling, half_collar, skip_overlap, counters, cooc, mapping, totals, (hipStream_t)stream);
 }
 
+int eend_collar_der_regions_u64(const unsigned char* ref, const int* ref_off, int Cr, const unsigned char* hyp, const int* hyp_off, int Ch,
+                                int B, int subsampling, int half_collar, int skip_overlap, const int* uem, const int* uem_off,
+                                unsigned long long* counters, unsigned long long* cooc, int* mapping, unsigned long long* ref_time,
+                                unsigned long long* hyp_time, void* stream) {
+    return eend_launch_collar_der_regions(ref, ref_off, Cr, hyp, hyp_off, Ch, B, subsampling, half_collar, skip_overlap, uem, uem_off,
+                                          counters, cooc, mapping, ref_time, hyp_time, (hipStream_t)stream);
+}
+
+int eend_collar_der_sweep_regions_u64(const unsigned char* ref, const int* ref_off, int Cr, const float* pred, const int* pred_off, int Ch,
+                                      const unsigned char* sad, int B, const float* thresholds, int n_thresholds, const int* medians,
+                                      int n_medians, int subsampling, int half_collar, int skip_overlap, const int* uem,
+                                      const int* uem_off, unsigned long long* counters, unsigned long long* cooc, int* mapping,
+                                      unsigned long long* totals, unsigned long long* ref_time, unsigned long long* hyp_time,
+                                      void* stream) {
+    return eend_launch_collar_der_sweep_regions(ref, ref_off, Cr, pred, pred_off, Ch, sad, B, thresholds, n_thresholds, medians, n_medians,
+                                                subsampling, half_collar, skip_overlap, uem, uem_off, counters, cooc, mapping, totals,
+                                                ref_time, hyp_time, (hipStream_t)stream);
+}
+
+int eend_jer_assign_f64(const unsigned long long* cooc, const unsigned long long* ref_time, const unsigned long long* hyp_time, int Cr,
+                        int Ch, long n, int* pairing, unsigned long long* speakers, void* stream) {
+    return eend_launch_jer_assign(cooc, ref_time, hyp_time, Cr, Ch, n, pairing, speakers, (hipStream_t)stream);
+}
+
+int eend_segments_raster_u8(const int* segments, long n_segments, const int* ref_off, int B, int C, unsigned char* rows, long n_rows,
+                            void* stream) {
+    return eend_launch_segments_raster(segments, n_segments, ref_off, B, C, rows, n_rows, (hipStream_t)stream);
+}
+
 int eend_der_sweep_limits(int* max_thresholds, int* max_medians, int* max_points, int* max_median) {
     if (!max_thresholds || !max_medians || !max_points || !max_median) return EEND_EINVAL;
     *max_thresholds = DER_SWEEP_NTHETA;

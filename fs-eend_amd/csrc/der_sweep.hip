@@ -55,16 +55,32 @@ constexpr int SCRATCH = FSTAGE * 4;
 static_assert(SCRATCH >= REF_BYTES && SCRATCH >= POINT_BYTES && SCRATCH % 16 == 0 && (EXT * 2) % 4 == 0, "der_sweep scratch block");
 static_assert(GMAX == NTH * 2 && NT / 64 == 4, "der_sweep layout");
 
+// <REG, MARG>, as for der_collar_pass_kernel: <false, false> is the kernel of eend_collar_der_sweep_u64, with that entry's
+// argument list and its code of before; eend_collar_der_sweep_regions_u64 runs <false, true> without a table and <true, true>
+// with one, both with one RegionArgs more.  The region term comes from
+// der_tile.h (region_clear, region_fill, region_bit), the same calls at the same place of step 1 as in ref_side.  The marginal
+// times: the reference's in a register per thread (one for all points), the hypothesis's, one per point, in LDS (hsum, 2 KB:
+// lane j of every wave adds popcount(H_j & keep) with an LDS atomic; a workgroup's sum is below 2^31 frames, so 32 bits do),
+// which keeps the LDS at the limits below 64 KB and adds no accumulator registers to the 64 of the co-occurrence counts.
+template <bool REG, bool MARG, typename... Extra>
 __global__ __launch_bounds__(NT)
 void der_sweep_pass_kernel(const unsigned char* __restrict__ ref, const int* __restrict__ roff, int Cr,
                            const float* __restrict__ pred, const int* __restrict__ poff, int Ch,
                            const unsigned char* __restrict__ sad, const float* __restrict__ thresholds, int nth,
                            const int* __restrict__ medians, int nmed, int sub, int h, int skip, int hcap, int B,
-                           unsigned long long* __restrict__ counters, unsigned long long* __restrict__ cooc) {
+                           unsigned long long* __restrict__ counters, unsigned long long* __restrict__ cooc, Extra... extra) {
+    const int *uem = nullptr, *uoff = nullptr;
+    unsigned long long *ref_time = nullptr, *hyp_time = nullptr;
+    if constexpr (MARG) {
+        const RegionArgs& x = region_args(extra...);
+        uem = x.uem, uoff = x.uoff, ref_time = x.ref_time, hyp_time = x.hyp_time;
+    }
     extern __shared__ unsigned short dmask[];                     // [nth][hcap]: decisions per threshold and staged frame
     __shared__ uint4 scratch4[SCRATCH / 16];
     __shared__ unsigned long long bits[NWORDS], planes_r[NGRP][CMAX], wsum[GMAX][NT / 64][2], sums[2];
     __shared__ unsigned before[NWORDS];
+    __shared__ unsigned long long regw[REG ? NGRP : 1], tsum[MARG ? CMAX : 1];
+    __shared__ unsigned hsum[MARG ? GMAX : 1][CMAX];
     unsigned char* const scratch = (unsigned char*)scratch4;
     unsigned short* const rmask = (unsigned short*)scratch;       // step 1
     unsigned* const stage = (unsigned*)(scratch + EXT * 2);
@@ -97,7 +113,11 @@ void der_sweep_pass_kernel(const unsigned char* __restrict__ ref, const int* __r
     int rot = tid % Ch;                                           // a thread starts its row at another column: LDS banks
 
     for (int k = tid; k < GMAX * (NT / 64) * 2; k += NT) (&wsum[0][0][0])[k] = 0;
-    unsigned long long total = 0, kept = 0, pair[GMAX];
+    if constexpr (MARG)
+        for (int k = tid; k < GMAX * CMAX; k += NT) (&hsum[0][0])[k] = 0;
+    Regions rg;
+    if constexpr (REG) rg = rec_regions(uem, uoff, rec);
+    unsigned long long total = 0, kept = 0, rtime = 0, pair[GMAX];
 #pragma unroll
     for (int q = 0; q < GMAX; ++q) pair[q] = 0;
 
@@ -110,7 +130,9 @@ void der_sweep_pass_kernel(const unsigned char* __restrict__ ref, const int* __r
         const int ng = ((tl + NT - 1) / NT) * (NT / 64);
 
         // ---- 1. the reference side, as ref_side of der_tile.h
+        if constexpr (REG) region_clear(regw);                   // the last tile's reads lie before the barrier above
         load_masks(ref, r0, Tr, Cr, t0 - h, n, rmask, stage);
+        if constexpr (REG) region_fill(rg, t0, tl, regw);        // after the barriers of load_masks, before those of the bits
         for (int e0 = 0; e0 <= n - 1; e0 += NT) {
             const int e = e0 + tid;
             const unsigned long long w = __ballot(e < n - 1 && rmask[e] != rmask[e + 1]);
@@ -146,6 +168,7 @@ void der_sweep_pass_kernel(const unsigned char* __restrict__ ref, const int* __r
             }
             const unsigned nr = __popc(rr);
             if (skip && nr >= 2) keep = false;
+            if constexpr (REG) keep = keep && region_bit(regw, r);
             if (keep) {
                 total += nr;
                 kept += 1;
@@ -158,6 +181,7 @@ void der_sweep_pass_kernel(const unsigned char* __restrict__ ref, const int* __r
                 if (lane == s) mine = pr;
             }
             if (lane < CMAX) planes_r[r * (NT / 64) + wave][lane] = mine;
+            if constexpr (MARG) rtime += __popcll(mine);
         }
         __syncthreads();                                          // rmask is done with: the block takes the float rows
 
@@ -263,7 +287,7 @@ void der_sweep_pass_kernel(const unsigned char* __restrict__ ref, const int* __r
                 }
                 __syncthreads();
                 // as score_point of der_tile.h: this thread's sum of min(nr, nh); this wave's sum of nh over kept frames
-                unsigned bt = 0, nhw = 0;
+                unsigned bt = 0, nhw = 0, ht = 0;
 #pragma unroll
                 for (int r = 0; r < ROUNDS; ++r)
                     if (r * NT < tl) {
@@ -277,7 +301,10 @@ void der_sweep_pass_kernel(const unsigned char* __restrict__ ref, const int* __r
                             nhw += __popcll(ph & kp[r]);
                         }
                         if (lane < CMAX) PH[(r * (NT / 64) + wave) * CMAX + lane] = mine;
+                        if constexpr (MARG) ht += __popcll(mine & kp[r]);
                     }
+                if constexpr (MARG)
+                    if (lane < CMAX && ht) atomicAdd(&hsum[g][lane], ht);
                 unsigned bw = 0;                                  // bt <= 4 * 16: 7 bits
 #pragma unroll
                 for (int b = 0; b < 7; ++b) bw += (unsigned)__popcll(__ballot(bt >> b & 1u)) << b;
@@ -298,10 +325,19 @@ void der_sweep_pass_kernel(const unsigned char* __restrict__ ref, const int* __r
 
     __syncthreads();
     if (tid < 2) sums[tid] = 0;
+    if constexpr (MARG)
+        if (tid < CMAX) tsum[tid] = 0;
     __syncthreads();
     if (total) atomicAdd(&sums[0], total);
     if (kept) atomicAdd(&sums[1], kept);
+    if constexpr (MARG) gather_times(tsum, rtime);
     __syncthreads();
+    if constexpr (MARG)                                           // thread (q, c): speaker c at the points q, q + 16
+        for (int q = ci; q < G; q += NT / CMAX) {
+            const size_t o = ((size_t)q * B + rec) * CMAX + cj;
+            if (tsum[cj]) atomicAdd(ref_time + o, tsum[cj]);
+            if (hsum[q][cj]) atomicAdd(hyp_time + o, (unsigned long long)hsum[q][cj]);
+        }
     if (tid < G) {                                                // total, miss, false alarm, frames kept, sum of min(nr, nh)
         unsigned long long nhs = 0, both = 0;
         for (int w = 0; w < NT / 64; ++w) {
@@ -339,8 +375,34 @@ int eend_launch_collar_der_sweep(const unsigned char* ref, const int* roff, int 
     const int G = nth * nmed;
     if (!der_clear(counters, cooc, (long)G * B, stream)) return EEND_ELAUNCH;
     const int hcap = sweep_staged_frames(sub);
-    hipLaunchKernelGGL(der_sweep_pass_kernel, dim3(der_tile_groups(B), B), dim3(NT), (size_t)nth * hcap * 2, stream, ref, roff, Cr,
-                       pred, poff, Ch, sad, thresholds, nth, medians, nmed, sub, h, skip ? 1 : 0, hcap, B, counters, cooc);
+    hipLaunchKernelGGL((der_sweep_pass_kernel<false, false>), dim3(der_tile_groups(B), B), dim3(NT), (size_t)nth * hcap * 2, stream, ref,
+                       roff, Cr, pred, poff, Ch, sad, thresholds, nth, medians, nmed, sub, h, skip ? 1 : 0, hcap, B, counters, cooc);
+    if (hipGetLastError() != hipSuccess) return EEND_ELAUNCH;
+    return eend_launch_collar_der_assign(roff, poff, Cr, Ch, B, G, sub, medians, nmed, counters, cooc, mapping, totals, stream);
+}
+
+int eend_launch_collar_der_sweep_regions(const unsigned char* ref, const int* roff, int Cr, const float* pred, const int* poff, int Ch,
+                                         const unsigned char* sad, int B, const float* thresholds, int nth, const int* medians, int nmed,
+                                         int sub, int h, int skip, const int* uem, const int* uoff, unsigned long long* counters,
+                                         unsigned long long* cooc, int* mapping, unsigned long long* totals, unsigned long long* ref_time,
+                                         unsigned long long* hyp_time, hipStream_t stream) {
+    if (!ref || !roff || !pred || !poff || !thresholds || !medians || !counters || !cooc || !mapping || !ref_time || !hyp_time)
+        return EEND_EINVAL;
+    if (!der_args_ok(Cr, Ch, B, sub, h) || !der_regions_ok(uem, uoff)) return EEND_EINVAL;
+    if (nth < 1 || nth > NTH || nmed < 1 || nmed > NMED || nth * nmed > GMAX) return EEND_EINVAL;
+    if (((uintptr_t)pred & 3) != 0) return EEND_EINVAL;
+    const int G = nth * nmed;
+    if (!der_clear_times(counters, cooc, ref_time, hyp_time, (long)G * B, stream)) return EEND_ELAUNCH;
+    const int hcap = sweep_staged_frames(sub);
+    const dim3 grid(der_tile_groups(B), B);
+    const size_t lds = (size_t)nth * hcap * 2;
+    const RegionArgs x{uem, uoff, ref_time, hyp_time};
+    if (uem)
+        hipLaunchKernelGGL((der_sweep_pass_kernel<true, true, RegionArgs>), grid, dim3(NT), lds, stream, ref, roff, Cr, pred, poff, Ch, sad,
+                           thresholds, nth, medians, nmed, sub, h, skip ? 1 : 0, hcap, B, counters, cooc, x);
+    else
+        hipLaunchKernelGGL((der_sweep_pass_kernel<false, true, RegionArgs>), grid, dim3(NT), lds, stream, ref, roff, Cr, pred, poff, Ch, sad,
+                           thresholds, nth, medians, nmed, sub, h, skip ? 1 : 0, hcap, B, counters, cooc, x);
     if (hipGetLastError() != hipSuccess) return EEND_ELAUNCH;
     return eend_launch_collar_der_assign(roff, poff, Cr, Ch, B, G, sub, medians, nmed, counters, cooc, mapping, totals, stream);
 }

@@ -4,6 +4,9 @@
 // median_ok, median_of).  Also here, what der_collar.hip's two kernels are made of: the recording header (Rec), the tile's
 // extents (Tile), the reference side of a tile (boundary_words, boundaries_below, ref_side) and the hypothesis side of one
 // operating point (score_point, add_counter); der_sweep_pass_kernel holds the same in its own text (der_sweep.hip says why).
+// The scoring regions of eend_collar_der_regions_u64 (Regions, region_clear, region_fill, region_bit) are one more term of keep:
+// both kernels take it from here, as template instances of their own (REG), and the marginal times with it (MARG); the
+// instances <false, false> are the kernels of the entries without regions, instruction for instruction.
 #pragma once
 #include "common.h"
 #include "kernels.h"
@@ -99,6 +102,66 @@ DEV void load_masks(const unsigned char* __restrict__ rows, long row0, int len, 
     }
 }
 
+// ---- the scoring regions of a recording (a UEM): sorted, disjoint, half-open intervals [s, e) of reference frames
+
+// Recording `rec` of the table uem i32 [.][2] under the offsets uoff i32 [B + 1]: its n intervals from iv.
+struct Regions {
+    const int2* iv;
+    int n;
+};
+DEV Regions rec_regions(const int* __restrict__ uem, const int* __restrict__ uoff, int rec) {
+    Regions g;
+    const int a = uoff[rec], n = uoff[rec + 1] - a;
+    g.iv = (const int2*)uem + a;
+    g.n = n > 0 ? n : 0;
+    return g;
+}
+
+// What the kernels with regions take beyond the arguments of those without, as one argument: the table and the marginal times.
+struct RegionArgs {
+    const int *uem, *uoff;
+    unsigned long long *ref_time, *hyp_time;
+};
+DEV const RegionArgs& region_args(const RegionArgs& x) { return x; }
+
+// regw [NGRP]: bit j of the words = frame t0 + j of the tile lies in some interval.  region_clear, a barrier, region_fill, a
+// barrier, then region_bit.  The fill: a binary search on the starts finds the first interval that reaches the tile; from there
+// thread k takes every NT-th interval up to the first that starts beyond the tile, so a tile of hundreds of one-frame regions
+// is a few rounds of the loop, not a fixed stage.  An interval ORs its bits into each word it meets (LDS atomics: two intervals
+// may share a word).  The frames of a tile lie in [0, T), which clips the intervals; an unsorted table ends the loop early or
+// late but writes nowhere else.
+DEV void region_clear(unsigned long long* regw) {
+    if (threadIdx.x < NGRP) regw[threadIdx.x] = 0;
+}
+DEV void region_fill(const Regions& g, int t0, int tl, unsigned long long* regw) {
+    const int tend = t0 + tl;
+    int lo = 0, hi = g.n;                                         // -> the intervals that start at or before t0
+#pragma unroll 1
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (g.iv[mid].x <= t0) lo = mid + 1;
+        else hi = mid;
+    }
+    const int first = lo > 0 && g.iv[lo - 1].y > t0 ? lo - 1 : lo;
+#pragma unroll 1
+    for (long k = (long)first + threadIdx.x; k < g.n; k += NT) {
+        const int2 se = g.iv[k];
+        if (se.x >= tend) break;
+        const int a = (se.x > t0 ? se.x : t0) - t0, b = (se.y < tend ? se.y : tend) - t0;   // bits [a, b) of the tile
+        if (a >= b) continue;
+#pragma unroll 1
+        for (int w = a >> 6; w <= (b - 1) >> 6; ++w) {
+            const int x = a > w * 64 ? a - w * 64 : 0, y = b < w * 64 + 64 ? b - w * 64 : 64;
+            const unsigned long long upto = y == 64 ? ~0ull : (1ull << y) - 1;
+            atomicOr(regw + w, upto & ~((1ull << x) - 1));
+        }
+    }
+}
+// frame r NT + tid of the tile: word r NT / 64 + wave, bit lane
+DEV bool region_bit(const unsigned long long* regw, int r) {
+    return regw[r * (NT / 64) + (threadIdx.x >> 6)] >> (threadIdx.x & 63) & 1ull;
+}
+
 // ---- the reference side of a tile
 
 // What the reference side leaves in LDS: the boundary bits, the boundaries in the words before each, the planes R_i & keep.
@@ -139,9 +202,12 @@ DEV unsigned boundaries_below(const RefLds& L, int w, unsigned long long below) 
 }
 
 // From rmask (the tile's masks with the halo): keep and nr of every frame, total and frames kept added up per thread, the planes
-// R_i & keep.  The caller's barrier comes before the planes are read or rmask is written.
+// R_i & keep.  The caller's barrier comes before the planes are read or rmask is written.  REG: a kept frame also has its bit in
+// regw (region_fill, a barrier since).  MARG: lane i < Cr of a wave adds the kept frames of speaker i in its groups to rtime.
+template <bool REG = false, bool MARG = false>
 DEV void ref_side(const Tile& t, const unsigned short* rmask, int Cr, int sub, int h, int skip, RefLds& L, RefRegs& f,
-                  unsigned long long& total, unsigned long long& kept) {
+                  unsigned long long& total, unsigned long long& kept, const unsigned long long* regw = nullptr,
+                  unsigned long long* rtime = nullptr) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     boundary_words(rmask, t.n, L);
     // frame j = r NT + tid asks about bits j and j + 2 h: the same bit of a word in every round, NT / 64 words on per round
@@ -165,6 +231,7 @@ DEV void ref_side(const Tile& t, const unsigned short* rmask, int Cr, int sub, i
         }
         const unsigned nr = __popc(rr);
         if (skip && nr >= 2) keep = false;
+        if constexpr (REG) keep = keep && region_bit(regw, r);
         if (keep) {
             total += nr;
             kept += 1;
@@ -177,6 +244,7 @@ DEV void ref_side(const Tile& t, const unsigned short* rmask, int Cr, int sub, i
             if (lane == s) mine = pr;
         }
         if (lane < CMAX) L.planes[r * (NT / 64) + wave][lane] = mine;
+        if constexpr (MARG) *rtime += __popcll(mine);
     }
 }
 
@@ -186,9 +254,11 @@ DEV void ref_side(const Tile& t, const unsigned short* rmask, int Cr, int sub, i
 // planes H_j go to PH [NGRP][CMAX].  wsum [NT / 64][2], the point's sums per wave, in LDS and 0 at first: this wave's sum of nh
 // over its kept frames (popcount(H_j & keep)) and of min(nr, nh) (ballots over the 7 bits of a thread's sum, <= 4 * 16) are
 // added by lane 0, before the barrier that would otherwise expose the round trip.  Returns thread (i, j)'s
-// popcount(R_i & keep & H_j) over the tile.  The next write to PH or L.planes must follow a barrier.
+// popcount(R_i & keep & H_j) over the tile.  The next write to PH or L.planes must follow a barrier.  MARG: lane j < Ch of a wave
+// adds the kept frames under hypothesis speaker j in its groups to htime.
+template <bool MARG = false>
 DEV unsigned score_point(const Tile& t, const RefLds& L, const RefRegs& f, const unsigned short* hm, int Cr, int Ch,
-                         unsigned long long* PH, unsigned long long (*wsum)[2]) {
+                         unsigned long long* PH, unsigned long long (*wsum)[2], unsigned long long* htime = nullptr) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, ci = tid >> 4, cj = tid & 15;
     unsigned bt = 0, nhw = 0, bw = 0;
 #pragma unroll
@@ -204,6 +274,7 @@ DEV unsigned score_point(const Tile& t, const RefLds& L, const RefRegs& f, const
                 nhw += __popcll(ph & f.kp[r]);
             }
             if (lane < CMAX) PH[(r * (NT / 64) + wave) * CMAX + lane] = mine;
+            if constexpr (MARG) *htime += __popcll(mine & f.kp[r]);
         }
 #pragma unroll
     for (int b = 0; b < 7; ++b) bw += (unsigned)__popcll(__ballot(bt >> b & 1u)) << b;
@@ -260,6 +331,37 @@ void der_clear_kernel(unsigned long long* __restrict__ counters, unsigned long l
 inline bool der_clear(unsigned long long* counters, unsigned long long* cooc, long n, hipStream_t stream) {
     hipLaunchKernelGGL(der_clear_kernel, dim3((unsigned)n), dim3(NT), 0, stream, counters, cooc, n);   // n x NT = n x 16 x 16 counts
     return hipGetLastError() == hipSuccess;
+}
+// ... and with them the marginal times of the entries with regions, 2 x 16 per matrix
+static __global__ __launch_bounds__(NT)
+void der_clear_times_kernel(unsigned long long* __restrict__ counters, unsigned long long* __restrict__ cooc,
+                            unsigned long long* __restrict__ ref_time, unsigned long long* __restrict__ hyp_time, long n) {
+    const size_t i = (size_t)blockIdx.x * NT + threadIdx.x;
+    if (i < (size_t)n * 8) counters[i] = 0;
+    if (i < (size_t)n * CMAX * CMAX) cooc[i] = 0;
+    if (i < (size_t)n * CMAX) {
+        ref_time[i] = 0;
+        hyp_time[i] = 0;
+    }
+}
+inline bool der_clear_times(unsigned long long* counters, unsigned long long* cooc, unsigned long long* ref_time,
+                            unsigned long long* hyp_time, long n, hipStream_t stream) {
+    hipLaunchKernelGGL(der_clear_times_kernel, dim3((unsigned)n), dim3(NT), 0, stream, counters, cooc, ref_time, hyp_time, n);
+    return hipGetLastError() == hipSuccess;
+}
+
+// The marginal times of a workgroup: the lanes i < 16 of its waves hold their sums for speaker i; added up in LDS (tsum [CMAX],
+// 0 and a barrier before), then, after a barrier, one integer atomic per speaker by flush_times.
+DEV void gather_times(unsigned long long* tsum, unsigned long long mine) {
+    if ((threadIdx.x & 63) < CMAX && mine) atomicAdd(tsum + (threadIdx.x & 63), mine);
+}
+DEV void flush_times(unsigned long long* out, const unsigned long long* tsum) {
+    if (threadIdx.x < CMAX && tsum[threadIdx.x]) atomicAdd(out + threadIdx.x, tsum[threadIdx.x]);
+}
+
+// the table of the entries with regions: both pointers or neither, pairs loaded as int2
+inline bool der_regions_ok(const int* uem, const int* uoff) {
+    return (uem == nullptr) == (uoff == nullptr) && ((uintptr_t)uem & 7) == 0;
 }
 
 }  // namespace der

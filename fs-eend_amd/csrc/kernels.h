@@ -130,6 +130,22 @@ int eend_launch_collar_der_sweep(const unsigned char* ref, const int* roff, int 
                                  const unsigned char* sad, int B, const float* thresholds, int nth, const int* medians, int nmed, int sub,
                                  int h, int skip, unsigned long long* counters, unsigned long long* cooc, int* mapping,
                                  unsigned long long* totals, hipStream_t stream);
+// both with scoring regions (uem i32 [.][2] under uoff i32 [B + 1]; both null: none anywhere) and the marginal times u64 [.][16]
+int eend_launch_collar_der_regions(const unsigned char* ref, const int* roff, int Cr, const unsigned char* hyp, const int* hoff, int Ch,
+                                   int B, int sub, int h, int skip, const int* uem, const int* uoff, unsigned long long* counters,
+                                   unsigned long long* cooc, int* mapping, unsigned long long* ref_time, unsigned long long* hyp_time,
+                                   hipStream_t stream);
+int eend_launch_collar_der_sweep_regions(const unsigned char* ref, const int* roff, int Cr, const float* pred, const int* poff, int Ch,
+                                         const unsigned char* sad, int B, const float* thresholds, int nth, const int* medians, int nmed,
+                                         int sub, int h, int skip, const int* uem, const int* uoff, unsigned long long* counters,
+                                         unsigned long long* cooc, int* mapping, unsigned long long* totals, unsigned long long* ref_time,
+                                         unsigned long long* hyp_time, hipStream_t stream);
+// the Jaccard assignment on n matrices (der_collar.hip at jer_assign_kernel)
+int eend_launch_jer_assign(const unsigned long long* cooc, const unsigned long long* ref_time, const unsigned long long* hyp_time, int Cr,
+                           int Ch, long n, int* pairing, unsigned long long* speakers, hipStream_t stream);
+// segment tables -> packed uint8 reference rows (segraster.hip)
+int eend_launch_segments_raster(const int* seg, long nseg, const int* roff, int B, int C, unsigned char* rows, long nrows,
+                                hipStream_t stream);
 
 int eend_launch_stft_logmel(const float* y, long len, long first, int n_frames, const float* dft, const float* melT, float* out,
                             hipStream_t stream);

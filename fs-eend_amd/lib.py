@@ -77,6 +77,11 @@ PROTOTYPES = {
     "eend_collar_der_limits": [_vp, _vp],
     "eend_collar_der_sweep_u64": [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "eend_der_sweep_limits": [_vp, _vp, _vp, _vp],
+    "eend_collar_der_regions_u64": [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "eend_collar_der_sweep_regions_u64": [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp,
+                                          _vp, _vp, _vp, _vp],
+    "eend_jer_assign_f64": [_vp, _vp, _vp, _i, _i, _l, _vp, _vp, _vp],
+    "eend_segments_raster_u8": [_vp, _l, _vp, _i, _i, _vp, _l, _vp],
     "eend_stft_logmel23_f32": [_vp, _l, _l, _i, _vp, _vp, _vp, _vp],
     "eend_feature_meannorm_f32": [_vp, _vp, _i, _i, _i, _vp],
     "eend_splice_subsample_f32": [_vp, _i, _i, _i, _i, _vp, _vp],

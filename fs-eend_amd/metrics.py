@@ -20,6 +20,21 @@ ties between equally good mappings are broken.
 
 One quirk of the reference's script is not reproduced: `reference[Segment(s, e)] = str(spkid)` lets a second speaker with an
 identical run (s, e) overwrite the first; here both speakers count.
+
+Real corpora (AMI, DIHARD II / III) are scored inside the regions of a UEM file, also by the Jaccard error rate, and against
+references that come as RTTM text:
+
+    uem=                       on every scoring call: per recording None (all of [0, T)), a list of half-open (start, end) pairs
+                               in reference frames, or an (n, 2) integer tensor.  A frame is scored iff it lies in an interval,
+                               is clear of the collars of the *uncropped* reference and (skip_overlap) has < 2 reference
+                               speakers; an interval's edge is not a boundary (include/eend_hip.h eend_collar_der_regions_u64)
+    jaccard_error / JaccardER  per-speaker Jaccard error with its own min-cost pairing (eend_jer_assign_f64), over the same
+                               kept frames; collar=0 is the usual DIHARD figure
+    read_rttm / read_uem / pack_rttm   text -> frame tables on the host -> label rows rasterised on the device
+
+These follow what pyannote's `uemify` and dscore's JER are documented to do, restated in integers in tests/der_region_ref.py
+with scipy's linear_sum_assignment as the reference; neither tool is a dependency or was available to compare against, so no
+equality with them is claimed.
 """
 import ctypes
 import math
@@ -129,6 +144,7 @@ def _check_packed(ref, roff, rows, off, dtype, *, side, what):
 
 
 _OUT = (((8,), _I64), ((CMAX, CMAX), _I64), ((CMAX,), _I32))   # counters, cooc, mapping behind the leading dimensions
+_OUT_TIMES = _OUT + (((CMAX,), _I64), ((CMAX,), _I64))         # ... and ref_time, hyp_time of the entries with regions
 
 
 def _check_out(out, lead, name, device):
@@ -144,9 +160,125 @@ def _check_out(out, lead, name, device):
     return out
 
 
-def collar_der_packed(batch, collar=50, subsampling=10, skip_overlap=False, out=None):
+def _check_out_times(out, lead, name, device):
+    """As _check_out for the entries with regions: `out` may be None, the three tensors of _check_out (the two marginal times
+    are made here) or all five (counters, cooc, mapping, ref_time int64 (*lead, 16), hyp_time int64 (*lead, 16))."""
+    out = tuple(out) if out is not None else ()
+    if len(out) not in (0, 3, 5):
+        raise _lib.EendHipError(f"{name}: out = (counters, cooc, mapping) or (counters, cooc, mapping, ref_time, hyp_time)")
+    first = _check_out(out[:3] if out else None, lead, name, device)
+    times = out[3:] or tuple(torch.empty(lead + s, dtype=dt, device=device) for s, dt in _OUT_TIMES[3:])
+    for t, (s, dt) in zip(times, _OUT_TIMES[3:]):
+        if t.shape != lead + s or t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+            raise _lib.EendHipError(f"{name}: ref_time and hyp_time = int64 {lead + s} on the GPU")
+    return tuple(first) + tuple(times)
+
+
+# ---- scoring regions (UEM)
+
+_I32_MAX = 2 ** 31 - 1
+
+
+def _check_uem_one(u, name):
+    """One recording's regions -> None, or the sorted, merged list of (start, end) pairs.  ValueError for a shape that is not
+    (n, 2), a value that is not an integer, start < 0 and end <= start."""
+    if u is None:
+        return None
+    if isinstance(u, torch.Tensor):
+        if u.is_floating_point() or u.is_complex() or u.dtype == torch.bool:
+            raise ValueError(f"{name}: expected integer frames, got {u.dtype}")
+        if not (u.dim() == 2 and u.shape[1] == 2) and u.numel():
+            raise ValueError(f"{name}: expected (n, 2) intervals, got shape {tuple(u.shape)}")
+        u = u.cpu().tolist() if u.numel() else []
+    if not isinstance(u, (list, tuple)):
+        raise ValueError(f"{name}: expected None, (start, end) pairs or an (n, 2) integer tensor, got {u!r}")
+    pairs = []
+    for iv in list(u):
+        iv = tuple(iv) if isinstance(iv, (list, tuple)) else (iv,)
+        if len(iv) != 2:
+            raise ValueError(f"{name}: expected (start, end) pairs, got {iv!r}")
+        s, e = iv
+        for v in (s, e):
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise ValueError(f"{name}: expected integer frames, got {v!r}")
+        if s < 0 or e <= s:
+            raise ValueError(f"{name}: expected 0 <= start < end, got ({s}, {e})")
+        pairs.append((s, min(e, _I32_MAX)))
+    out = []
+    for s, e in sorted(pairs):
+        if out and s <= out[-1][1]:
+            out[-1] = (out[-1][0], max(out[-1][1], e))
+        elif s < _I32_MAX:
+            out.append((s, e))
+    return out
+
+
+def _check_uems(uem, B, single=False):
+    """The `uem=` of a call on B recordings -> None (no regions anywhere) or a list of B checked entries.  `single`: the call got
+    one pair of tensors, not lists, and `uem` is that recording's."""
+    if uem is None:
+        return None
+    if single:
+        uem = [uem]
+    if not isinstance(uem, (list, tuple)) or len(uem) != B:
+        raise ValueError(f"uem: expected one entry per recording ({B}): None, (start, end) pairs or an (n, 2) integer tensor")
+    out = [_check_uem_one(u, f"uem[{b}]") for b, u in enumerate(uem)]
+    return None if all(u is None for u in out) else out
+
+
+def pack_uem(uems, device=None):
+    """Checked or raw per-recording regions (a list with None, pair lists or (n, 2) tensors) -> the device table the kernels read:
+    (int32 (max(n_total, 1), 2) intervals, recording after recording; int32 (B + 1,) offsets).  None becomes the one interval
+    [0, 2^31 - 1), which the kernels clip to [0, T)."""
+    uems = [_check_uem_one(u, f"uem[{b}]") for b, u in enumerate(uems)]
+    if device is None:
+        if not torch.cuda.is_available():
+            raise _lib.EendHipError("pack_uem: no GPU available (the HIP path has no CPU fallback)")
+        device = torch.device("cuda", torch.cuda.current_device())
+    rows, off = [], [0]
+    for u in uems:
+        rows += [(0, _I32_MAX)] if u is None else u
+        off.append(len(rows))
+    table = torch.tensor(rows or [(0, 0)], dtype=_I32).reshape(-1, 2)
+    return table.to(device), torch.tensor(off, dtype=_I32).to(device)
+
+
+def _check_uem_table(uem, B, name):
+    if uem is None:
+        return None, None
+    table, off = uem
+    for t, what in ((table, "intervals"), (off, "offsets")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != _I32 or not t.is_contiguous():
+            raise _lib.EendHipError(f"{name}: uem {what}: expected a contiguous int32 GPU tensor (see pack_uem)")
+    if table.dim() != 2 or table.shape[1] != 2 or off.numel() != B + 1:
+        raise _lib.EendHipError(f"{name}: uem = (int32 (n, 2) intervals, int32 (B + 1,) offsets) as pack_uem makes them")
+    return table, off
+
+
+def collar_der_regions_packed(batch, uem=None, collar=50, subsampling=10, skip_overlap=False, out=None):
+    """`collar_der_packed` through eend_collar_der_regions_u64: `uem` = the device table of `pack_uem` (None: no regions
+    anywhere) -> (counters, cooc, mapping, ref_time int64 (B, 16), hyp_time int64 (B, 16)); the two marginal times are the kept
+    frames in which a reference speaker, and the kept reference frames under which a hypothesis speaker, is active.  Three
+    launches, no host sync, capturable; `out`: the first three or all five tensors to write into."""
+    _check_numbers(collar, subsampling)
+    ref, roff, hyp, hoff = batch
+    B = _check_packed(ref, roff, hyp, hoff, _U8, side="hyp", what="collar_der_regions_packed: not a batch made by pack()")
+    table, uoff = _check_uem_table(uem, B, "collar_der_regions_packed")
+    out = counters, cooc, mapping, ref_time, hyp_time = _check_out_times(out, (B,), "collar_der_regions_packed", ref.device)
+    _lib.check(_lib.load().eend_collar_der_regions_u64(
+        ref.data_ptr(), roff.data_ptr(), ref.shape[1], hyp.data_ptr(), hoff.data_ptr(), hyp.shape[1], B, int(subsampling),
+        int(collar) // 2, int(bool(skip_overlap)), table.data_ptr() if table is not None else None,
+        uoff.data_ptr() if uoff is not None else None, counters.data_ptr(), cooc.data_ptr(), mapping.data_ptr(), ref_time.data_ptr(),
+        hyp_time.data_ptr(), _post._stream()), "eend_collar_der_regions_u64")
+    return out
+
+
+def collar_der_packed(batch, collar=50, subsampling=10, skip_overlap=False, out=None, uem=None):
     """Score a packed batch (see `pack`): three launches on the current stream, no host sync, so the call can be
-    captured in a graph.  `out` = (counters int64 (B, 8), cooc int64 (B, 16, 16), mapping int32 (B, 16)) to write into."""
+    captured in a graph.  `out` = (counters int64 (B, 8), cooc int64 (B, 16, 16), mapping int32 (B, 16)) to write into.
+    `uem`: the device table of `pack_uem`; only the frames inside a recording's intervals are scored."""
+    if uem is not None:
+        return collar_der_regions_packed(batch, uem, collar, subsampling, skip_overlap, out)[:3]
     _check_numbers(collar, subsampling)
     ref, roff, hyp, hoff = batch
     B = _check_packed(ref, roff, hyp, hoff, _U8, side="hyp", what="collar_der_packed: not a batch made by pack()")
@@ -158,14 +290,18 @@ def collar_der_packed(batch, collar=50, subsampling=10, skip_overlap=False, out=
     return out
 
 
-def collar_der_counters(refs, hyps, collar=50, subsampling=10, skip_overlap=False):
+def collar_der_counters(refs, hyps, collar=50, subsampling=10, skip_overlap=False, uem=None):
     """Lists of activity tensors, or a single pair -> (counters int64 (B, 8), cooc int64 (B, 16, 16), mapping int32 (B, 16)),
     all still on the device, no host sync.  counters[b] = total, missed detection, false alarm, confusion, correct, frames kept,
     frames removed within [0, T), sum of min(nr, nh); cooc[b][i][j] = kept frames with reference i and hypothesis j both active;
-    mapping[b][j] = the reference speaker of hypothesis j, -1 = unmapped."""
+    mapping[b][j] = the reference speaker of hypothesis j, -1 = unmapped.  `uem`: per recording None, (start, end) pairs or an
+    (n, 2) integer tensor (for a single pair: that recording's), sorted and merged here."""
+    single = not isinstance(refs, (list, tuple))
     refs, hyps = _as_list(refs), _as_list(hyps)
     _check_args(refs, hyps, collar, subsampling)
-    return collar_der_packed(pack(refs, hyps, subsampling), collar, subsampling, skip_overlap)
+    uems = _check_uems(uem, len(refs), single)
+    batch = pack(refs, hyps, subsampling)
+    return collar_der_packed(batch, collar, subsampling, skip_overlap, uem=pack_uem(uems, batch[0].device) if uems else None)
 
 
 def rate(total, errors):
@@ -184,23 +320,30 @@ def _detail(c, mapping):
     return {**_components(c), "mapping": {j: i for j, i in enumerate(mapping) if i >= 0}, "frames kept": c[5], "frames removed": c[6]}
 
 
-def _details(refs, hyps, collar, subsampling, skip_overlap):
-    counters, _, mapping = collar_der_counters(refs, hyps, collar, subsampling, skip_overlap)
+def _details(refs, hyps, collar, subsampling, skip_overlap, uems=None):
+    counters, _, mapping = collar_der_counters(refs, hyps, collar, subsampling, skip_overlap, uems)
     return [_detail(c, m) for c, m in zip(counters.cpu().tolist(), mapping.cpu().tolist())]
 
 
-def collar_der(ref, hyp, collar=50, subsampling=10, skip_overlap=False):
+def collar_der(ref, hyp, collar=50, subsampling=10, skip_overlap=False, uem=None):
     """One recording -> pyannote's detailed components ('total', 'correct', 'confusion', 'false alarm', 'missed detection',
-    'diarization error rate'), plus 'mapping' {hyp: ref}, 'frames kept' and 'frames removed'."""
-    return _details([ref], [hyp], collar, subsampling, skip_overlap)[0]
+    'diarization error rate'), plus 'mapping' {hyp: ref}, 'frames kept' and 'frames removed'.  `uem`: the recording's scoring
+    regions, (start, end) pairs or an (n, 2) integer tensor in reference frames."""
+    return _details([ref], [hyp], collar, subsampling, skip_overlap, None if uem is None else [uem])[0]
 
 
-def score_predictions(ref, pred, threshold=0.5, median=11, sad=None, collar=50, subsampling=10, skip_overlap=False):
+def score_predictions(ref, pred, threshold=0.5, median=11, sad=None, collar=50, subsampling=10, skip_overlap=False, uem=None,
+                      jaccard=False):
     """(Tr, Cr) labels and (Th, Ch) probabilities -> collar_der of postproc.activity(pred, threshold, median, sad): probabilities
-    to DER without leaving the device."""
+    to DER without leaving the device.  `jaccard`: also 'jaccard error rate' and 'pairing' {ref: hyp} over the same kept frames."""
     _check_args(_as_list(ref), _as_list(pred), collar, subsampling)
+    _check_uems(uem, 1, True)
     hyp = _post.activity(_post._to_device(pred, "pred"), threshold, median, sad)
-    return collar_der(ref, hyp, collar, subsampling, skip_overlap)
+    res = collar_der(ref, hyp, collar, subsampling, skip_overlap, uem)
+    if jaccard:
+        j = jaccard_error(ref, hyp, uem, collar, subsampling, skip_overlap)
+        res["jaccard error rate"], res["pairing"] = j["jaccard error rate"], j["pairing"]
+    return res
 
 
 class CollarDER:
@@ -223,13 +366,13 @@ class CollarDER:
         self.recordings += 1
         return res
 
-    def __call__(self, ref, hyp, detailed=False):
-        res = self._add(collar_der(ref, hyp, self.collar, self.subsampling, self.skip_overlap))
+    def __call__(self, ref, hyp, detailed=False, uem=None):
+        res = self._add(collar_der(ref, hyp, self.collar, self.subsampling, self.skip_overlap, uem))
         return res if detailed else res["diarization error rate"]
 
-    def score_batch(self, refs, hyps):
+    def score_batch(self, refs, hyps, uems=None):
         """Many recordings in one launch -> their detailed results, in order; all are accumulated."""
-        return [self._add(r) for r in _details(refs, hyps, self.collar, self.subsampling, self.skip_overlap)]
+        return [self._add(r) for r in _details(refs, hyps, self.collar, self.subsampling, self.skip_overlap, uems)]
 
     def report(self):
         """The aggregate components, with 'diarization error rate' = abs(self) and the number of recordings."""
@@ -331,13 +474,15 @@ def pack_predictions(preds, sads=None):
 
 
 def collar_der_sweep_packed(ref_batch, pred_batch, thresholds, medians, collar=50, subsampling=10, skip_overlap=False, out=None,
-                            totals=None):
+                            totals=None, uem=None, times=False):
     """Score every point of thresholds x medians on a packed batch (`pack_references`, `pack_predictions`) in one pass: three
     launches on the current stream and no host sync.  Point g = i_threshold * len(medians) + i_median.  `thresholds` / `medians`:
     sequences (checked, rounded to float32 and copied to the device here) or float32 / int32 device tensors (used as they are;
     a median that is not odd in 1 .. 127 marks its points with counters of -1).  `out` = (counters int64 (G, B, 8), cooc int64
     (G, B, 16, 16), mapping int32 (G, B, 16)) to write into; `totals` int64 (G, 8), not cleared: every (g, b)'s counters are added
-    to row g.  With `out` and device-tensor grids nothing is allocated or copied, so the call can be captured in a graph."""
+    to row g.  With `out` and device-tensor grids nothing is allocated or copied, so the call can be captured in a graph.
+    `uem`: the device table of `pack_uem`; `times`: return (and take in `out`) ref_time and hyp_time int64 (G, B, 16) as well.
+    Either goes through eend_collar_der_sweep_regions_u64."""
     _check_numbers(collar, subsampling)
     th, med = _check_grid(thresholds, medians)
     ref, roff = ref_batch[:2]
@@ -351,9 +496,21 @@ def collar_der_sweep_packed(ref_batch, pred_batch, thresholds, medians, collar=5
     medians = medians if med is None else torch.tensor(med, dtype=_I32).to(dev)
     nth, nmed = thresholds.numel(), medians.numel()
     G = nth * nmed
-    out = counters, cooc, mapping = _check_out(out, (G, B), "collar_der_sweep_packed", dev)
+    regions = uem is not None or times
+    table, uoff = _check_uem_table(uem, B, "collar_der_sweep_packed")
+    out = (_check_out_times if regions else _check_out)(out, (G, B), "collar_der_sweep_packed", dev)
+    counters, cooc, mapping = out[:3]
     if totals is not None and (totals.shape != (G, 8) or totals.dtype != _I64 or not totals.is_cuda or not totals.is_contiguous()):
         raise _lib.EendHipError("collar_der_sweep_packed: totals = int64 (G, 8) on the GPU")
+    if regions:
+        _lib.check(_lib.load().eend_collar_der_sweep_regions_u64(
+            ref.data_ptr(), roff.data_ptr(), ref.shape[1], rows.data_ptr(), poff.data_ptr(), rows.shape[1],
+            flags.data_ptr() if flags is not None else None, B, thresholds.data_ptr(), nth, medians.data_ptr(), nmed, int(subsampling),
+            int(collar) // 2, int(bool(skip_overlap)), table.data_ptr() if table is not None else None,
+            uoff.data_ptr() if uoff is not None else None, counters.data_ptr(), cooc.data_ptr(), mapping.data_ptr(),
+            totals.data_ptr() if totals is not None else None, out[3].data_ptr(), out[4].data_ptr(), _post._stream()),
+            "eend_collar_der_sweep_regions_u64")
+        return out if times else out[:3]
     _lib.check(_lib.load().eend_collar_der_sweep_u64(
         ref.data_ptr(), roff.data_ptr(), ref.shape[1], rows.data_ptr(), poff.data_ptr(), rows.shape[1],
         flags.data_ptr() if flags is not None else None, B, thresholds.data_ptr(), nth, medians.data_ptr(), nmed, int(subsampling),
@@ -362,16 +519,21 @@ def collar_der_sweep_packed(ref_batch, pred_batch, thresholds, medians, collar=5
     return out
 
 
-def sweep_counters(refs, preds, thresholds, medians, sads=None, collar=50, subsampling=10, skip_overlap=False, totals=None):
+def sweep_counters(refs, preds, thresholds, medians, sads=None, collar=50, subsampling=10, skip_overlap=False, totals=None, uem=None,
+                   times=False):
     """Lists of (Tr, Cr) labels and (Th, Ch) posteriors, or a single pair -> (counters int64 (G, B, 8), cooc int64 (G, B, 16, 16),
     mapping int32 (G, B, 16)) of the grid, still on the device, no host sync: row g of each is what
-    `collar_der_counters(refs, [postproc.activity(p, threshold, median, sad) ...])` returns at point g."""
+    `collar_der_counters(refs, [postproc.activity(p, threshold, median, sad) ...], uem=uem)` returns at point g.  `uem` as for
+    `collar_der_counters`; `times`: ref_time and hyp_time int64 (G, B, 16) as well."""
+    single = not isinstance(refs, (list, tuple))
     refs, preds = _as_list(refs), _as_list(preds)
     _check_args(refs, preds, collar, subsampling)
     _check_grid(thresholds, medians)
     _check_sads(preds, sads)
-    return collar_der_sweep_packed(pack_references(refs), pack_predictions(preds, sads), thresholds, medians, collar, subsampling,
-                                   skip_overlap, totals=totals)
+    uems = _check_uems(uem, len(refs), single)
+    ref_batch = pack_references(refs)
+    return collar_der_sweep_packed(ref_batch, pack_predictions(preds, sads), thresholds, medians, collar, subsampling,
+                                   skip_overlap, totals=totals, uem=pack_uem(uems, ref_batch[0].device) if uems else None, times=times)
 
 
 def _grid_values(th, med, thresholds, medians):
@@ -383,12 +545,19 @@ class SweepResult:
     """What a grid gave.  `thresholds` (as rounded to float32) and `medians`; `table[g]`: the aggregate components of point g =
     i_threshold * len(medians) + i_median over the recordings (sums, and 'diarization error rate' = sum of errors / sum of total),
     with its 'threshold' and 'median'; `details[g][b]`: recording b at point g in `collar_der`'s form (None where there are
-    only totals); `best` = (threshold, median, rate) of the lowest rate, the lowest g on ties."""
+    only totals); `best` = (threshold, median, rate) of the lowest rate, the lowest g on ties.  `jaccard` (None unless asked
+    for): per point the aggregate Jaccard error rate, also in `table[g]['jaccard error rate']`, and `jaccard_details[g][b]` in
+    `jaccard_error`'s form."""
 
-    def __init__(self, thresholds, medians, sums, details=None, recordings=0):
+    def __init__(self, thresholds, medians, sums, details=None, recordings=0, jaccard_details=None):
         self.thresholds, self.medians, self.details, self.recordings = list(thresholds), list(medians), details, recordings
+        self.jaccard_details, self.jaccard = jaccard_details, None
         self.table = [{"threshold": self.thresholds[g // len(self.medians)], "median": self.medians[g % len(self.medians)],
                        **_components(c)} for g, c in enumerate(sums)]
+        if jaccard_details is not None:
+            self.jaccard = [_jer_aggregate(point) for point in jaccard_details]
+            for row, j in zip(self.table, self.jaccard):
+                row["jaccard error rate"] = j
         g = min(range(len(self.table)), key=lambda i: (self.table[i]["diarization error rate"], i))
         self.best = (self.table[g]["threshold"], self.table[g]["median"], self.table[g]["diarization error rate"])
 
@@ -399,15 +568,24 @@ class SweepResult:
 
 
 def sweep_predictions(refs, preds, thresholds=(0.3, 0.4, 0.5, 0.6, 0.7), medians=(1, 11), sads=None, collar=50, subsampling=10,
-                      skip_overlap=False):
-    """Labels and posteriors (lists or one pair) -> SweepResult over the grid: one device pass, one copy to the host."""
+                      skip_overlap=False, uem=None, jaccard=False):
+    """Labels and posteriors (lists or one pair) -> SweepResult over the grid: one device pass, one copy to the host.  `uem` as
+    for `collar_der_counters`; `jaccard`: the Jaccard error rate of every point as well (one more launch, on G * B matrices)."""
     th, med = _check_grid(thresholds, medians)
-    counters, _, mapping = sweep_counters(refs, preds, thresholds, medians, sads, collar, subsampling, skip_overlap)
-    both = torch.cat([counters, mapping.to(_I64)], dim=2).cpu().tolist()           # (G, B, 8 + 16): the one copy
+    out = sweep_counters(refs, preds, thresholds, medians, sads, collar, subsampling, skip_overlap, uem=uem, times=jaccard)
+    counters, cooc, mapping = out[:3]
+    parts = [counters, mapping.to(_I64)]
+    if jaccard:
+        G, B = counters.shape[:2]
+        Cr, Ch = _widths(_as_list(refs), _as_list(preds))
+        pairing, speakers = jer_assign(cooc.view(G * B, CMAX, CMAX), out[3].view(G * B, CMAX), out[4].view(G * B, CMAX), Cr, Ch)
+        parts += [pairing.view(G, B, CMAX).to(_I64), speakers.view(G, B, 3 * CMAX), out[4]]
+    both = torch.cat(parts, dim=2).cpu().tolist()                                  # (G, B, 8 + 16 [+ 16 + 48 + 16]): the one copy
     th, med = _grid_values(th, med, thresholds, medians)
-    details = [[_detail(row[:8], row[8:]) for row in point] for point in both]
+    details = [[_detail(row[:8], row[8:24]) for row in point] for point in both]
     sums = [[sum(row[k] for row in point) for k in range(8)] for point in both]
-    return SweepResult(th, med, sums, details, len(both[0]))
+    jd = [[_jer_detail(row[24:40], row[40:88], row[88:104]) for row in point] for point in both] if jaccard else None
+    return SweepResult(th, med, sums, details, len(both[0]), jd)
 
 
 class DerSweep:
@@ -428,11 +606,14 @@ class DerSweep:
         self.totals = self._grid = None
         self.recordings = 0
 
-    def add(self, refs, preds, sads=None):
-        """Score a batch and add it to the totals; returns the batch's device tensors (counters, cooc, mapping)."""
+    def add(self, refs, preds, sads=None, uem=None):
+        """Score a batch and add it to the totals; returns the batch's device tensors (counters, cooc, mapping).  `uem` as for
+        `collar_der_counters`."""
+        single = not isinstance(refs, (list, tuple))
         refs, preds = _as_list(refs), _as_list(preds)
         _check_args(refs, preds, self.collar, self.subsampling)
         _check_sads(preds, sads)
+        uems = _check_uems(uem, len(refs), single)
         ref_batch, pred_batch = pack_references(refs), pack_predictions(preds, sads)
         dev = ref_batch[0].device
         if self.totals is None:
@@ -440,9 +621,266 @@ class DerSweep:
             self._grid = (torch.tensor(self.thresholds, dtype=_F32).to(dev), torch.tensor(self.medians, dtype=_I32).to(dev))
         self.recordings += len(refs)
         return collar_der_sweep_packed(ref_batch, pred_batch, self._grid[0], self._grid[1], self.collar, self.subsampling,
-                                       self.skip_overlap, totals=self.totals)
+                                       self.skip_overlap, totals=self.totals, uem=pack_uem(uems, dev) if uems else None)
 
     def report(self):
         n = len(self.thresholds) * len(self.medians)
         sums = self.totals.cpu().tolist() if self.totals is not None else [[0] * 8 for _ in range(n)]
         return SweepResult(self.thresholds, self.medians, sums, None, self.recordings)
+
+
+# ---- Jaccard error rate (csrc/der_collar.hip jer_assign_kernel, eend_jer_assign_f64)
+
+def _widths(refs, hyps):
+    return max(1, max(t.shape[1] for t in refs)), max(1, max(t.shape[1] for t in hyps))
+
+
+def jer_assign(cooc, ref_time, hyp_time, Cr=CMAX, Ch=CMAX, out=None):
+    """int64 (n, 16, 16), (n, 16), (n, 16) on the device, as the entries with regions write them -> (pairing int32 (n, 16),
+    reference -> hypothesis, -1 = unpaired; speakers int64 (n, 16, 3) = ref_time, paired hyp_time or 0, intersection).  One
+    launch, no host sync.  The pairing minimises the sum of 1 - intersection / union; it is not the mapping of the DER."""
+    n = cooc.shape[0]
+    for t, shape in ((cooc, (n, CMAX, CMAX)), (ref_time, (n, CMAX)), (hyp_time, (n, CMAX))):
+        if not t.is_cuda or t.dtype != _I64 or not t.is_contiguous() or tuple(t.shape) != shape or n < 1:
+            raise _lib.EendHipError("jer_assign: cooc (n, 16, 16), ref_time (n, 16), hyp_time (n, 16): contiguous int64 on the GPU")
+    if out is None:
+        out = (torch.empty(n, CMAX, dtype=_I32, device=cooc.device), torch.empty(n, CMAX, 3, dtype=_I64, device=cooc.device))
+    pairing, speakers = out
+    if (pairing.shape != (n, CMAX) or pairing.dtype != _I32 or speakers.shape != (n, CMAX, 3) or speakers.dtype != _I64
+            or not pairing.is_cuda or not speakers.is_cuda or not pairing.is_contiguous() or not speakers.is_contiguous()):
+        raise _lib.EendHipError("jer_assign: out = (int32 (n, 16), int64 (n, 16, 3)) on the GPU")
+    _lib.check(_lib.load().eend_jer_assign_f64(cooc.data_ptr(), ref_time.data_ptr(), hyp_time.data_ptr(), int(Cr), int(Ch), n,
+                                               pairing.data_ptr(), speakers.data_ptr(), _post._stream()), "eend_jer_assign_f64")
+    return out
+
+
+def jaccard_error_counters(refs, hyps=None, uem=None, collar=0, subsampling=10, skip_overlap=False, out=None):
+    """Lists of activity tensors or one pair -- or, with hyps=None, a batch made by `pack` with `uem` the device table of
+    `pack_uem` -- -> (pairing int32 (B, 16), speakers int64 (B, 16, 3), hyp_time int64 (B, 16)) on the device.  On a packed
+    batch nothing is copied or synchronised (four launches), so the call can be captured in a graph; `out` = (the five tensors
+    of collar_der_regions_packed, (pairing, speakers)) to write into."""
+    if hyps is None:
+        batch, table = refs, uem
+    else:
+        single = not isinstance(refs, (list, tuple))
+        refs, hyps = _as_list(refs), _as_list(hyps)
+        _check_args(refs, hyps, collar, subsampling)
+        uems = _check_uems(uem, len(refs), single)
+        batch = pack(refs, hyps, subsampling)
+        table = pack_uem(uems, batch[0].device) if uems else None
+    der_out, jer_out = out if out is not None else (None, None)
+    _, cooc, _, ref_time, hyp_time = collar_der_regions_packed(batch, table, collar, subsampling, skip_overlap, der_out)
+    pairing, speakers = jer_assign(cooc, ref_time, hyp_time, batch[0].shape[1], batch[2].shape[1], jer_out)
+    return pairing, speakers, hyp_time
+
+
+def _jer_detail(pairing, speakers, hyp_time):
+    """One recording's rows from the device (lists; speakers flat, 3 per speaker) -> the dict of `jaccard_error`."""
+    per = {}
+    for i in range(CMAX):
+        rt, ht, inter = speakers[3 * i:3 * i + 3]
+        if rt > 0:
+            union = rt + ht - inter
+            per[i] = {"ref time": rt, "hyp time": ht, "intersection": inter, "jaccard error rate": (union - inter) / union}
+    if per:
+        jer = sum(v["jaccard error rate"] for v in per.values()) / len(per)
+    else:
+        jer = 0.0 if not any(hyp_time) else 1.0
+    return {"jaccard error rate": jer, "speakers": per, "pairing": {i: j for i, j in enumerate(pairing) if j >= 0 and i in per},
+            "spurious": not per and any(hyp_time)}
+
+
+def _jer_aggregate(details):
+    """Sum of the per-speaker errors over the number of reference speakers; with none, 0.0 unless some hypothesis spoke."""
+    n = sum(len(d["speakers"]) for d in details)
+    errors = sum(v["jaccard error rate"] for d in details for v in d["speakers"].values())
+    return errors / n if n else (1.0 if any(d["spurious"] for d in details) else 0.0)
+
+
+def _jer_details(refs, hyps, uems, collar, subsampling, skip_overlap):
+    pairing, speakers, hyp_time = jaccard_error_counters(_as_list(refs), _as_list(hyps), uems, collar, subsampling, skip_overlap)
+    rows = torch.cat([pairing.to(_I64), speakers.view(-1, 3 * CMAX), hyp_time], dim=1).cpu().tolist()
+    return [_jer_detail(r[:16], r[16:64], r[64:80]) for r in rows]
+
+
+def jaccard_error(ref, hyp, uem=None, collar=0, subsampling=10, skip_overlap=False):
+    """One recording -> {'jaccard error rate': the mean over the reference speakers with kept time of (union - intersection) /
+    union (1.0 for a speaker left unpaired; with no reference speaker 0.0, or 1.0 if a hypothesis speaker has kept time),
+    'speakers': {ref: {'ref time', 'hyp time', 'intersection', 'jaccard error rate'}} in kept frames, 'pairing': {ref: hyp},
+    'spurious': hypothesis activity without any reference speaker}.  All counts are over the frames `collar_der` keeps with
+    the same arguments; collar=0 gives the usual DIHARD figure."""
+    return _jer_details([ref], [hyp], None if uem is None else [uem], collar, subsampling, skip_overlap)[0]
+
+
+class JaccardER:
+    """`CollarDER` for the Jaccard error rate: `metric(ref, hyp, detailed=True, uem=...)` per recording, `abs(metric)` = the sum
+    of the per-speaker errors over the number of reference speakers of the recordings scored so far."""
+
+    def __init__(self, collar=0, subsampling=10, skip_overlap=False):
+        _check_numbers(collar, subsampling)
+        self.collar, self.subsampling, self.skip_overlap = int(collar), int(subsampling), bool(skip_overlap)
+        self.reset()
+
+    def reset(self):
+        self.errors, self.speakers, self.recordings, self.spurious = 0.0, 0, 0, 0
+
+    def _add(self, res):
+        self.errors += sum(v["jaccard error rate"] for v in res["speakers"].values())
+        self.speakers += len(res["speakers"])
+        self.spurious += int(res["spurious"])
+        self.recordings += 1
+        return res
+
+    def __call__(self, ref, hyp, detailed=False, uem=None):
+        res = self._add(jaccard_error(ref, hyp, uem, self.collar, self.subsampling, self.skip_overlap))
+        return res if detailed else res["jaccard error rate"]
+
+    def score_batch(self, refs, hyps, uems=None):
+        """Many recordings in one launch -> their detailed results, in order; all are accumulated."""
+        return [self._add(r) for r in _jer_details(refs, hyps, uems, self.collar, self.subsampling, self.skip_overlap)]
+
+    def report(self):
+        return {"jaccard error rate": abs(self), "speakers": self.speakers, "recordings": self.recordings,
+                "errors": self.errors}
+
+    def __abs__(self):
+        return self.errors / self.speakers if self.speakers else (1.0 if self.spurious else 0.0)
+
+
+# ---- references as RTTM + UEM text (host parse; csrc/segraster.hip rasterises on the device)
+
+def _lines(source):
+    if isinstance(source, (str, bytes)) or hasattr(source, "__fspath__"):
+        with open(source, "r") as f:
+            return f.read().splitlines()
+    return [ln.decode() if isinstance(ln, bytes) else ln for ln in source]
+
+
+def _frame(t, frame_rate, where):
+    """np.rint(t * frame_rate) on float64, the reference's rule (datasets/feature.py get_labeledSTFT): half to even."""
+    f = round(t * frame_rate)                                     # Python's round on a float is rint: exact, half to even
+    if f > MAX_FRAMES:
+        raise ValueError(f"{where}: frame {f} is beyond {MAX_FRAMES}")
+    return f
+
+
+def _number(text, where):
+    try:
+        v = float(text)
+    except ValueError:
+        raise ValueError(f"{where}: {text!r} is not a number") from None
+    if not math.isfinite(v):
+        raise ValueError(f"{where}: {text!r} is not finite")
+    return v
+
+
+def read_rttm(source, frame_rate=100.0):
+    """RTTM text (a path, an open file or an iterable of lines) -> {recording: {'speakers': [names in order of first
+    appearance], 'segments': [(speaker index, start frame, end frame), ...] in file order}}.  SPEAKER records only, other
+    types are skipped.  start -> rint(start * frame_rate), end -> rint((start + duration) * frame_rate): the label matrix the
+    reference's datasets make of the same segments.  ValueError naming the line for a malformed line, a negative start or
+    duration, a 17th speaker in a recording, and a frame beyond MAX_FRAMES."""
+    out = {}
+    for no, line in enumerate(_lines(source), 1):
+        f = line.split()
+        if not f or f[0].startswith(("#", ";")) or (f[0] != "SPEAKER" and f[0].isupper() and len(f) >= 8):
+            continue
+        where = f"RTTM line {no}"
+        if f[0] != "SPEAKER" or len(f) < 8:
+            raise ValueError(f"{where}: expected 'SPEAKER file chan start duration <NA> <NA> name ...', got {line!r}")
+        start, dur = _number(f[3], where), _number(f[4], where)
+        if start < 0 or dur < 0:
+            raise ValueError(f"{where}: negative start or duration in {line!r}")
+        rec = out.setdefault(f[1], {"speakers": [], "segments": []})
+        if f[7] not in rec["speakers"]:
+            if len(rec["speakers"]) == CMAX:
+                raise ValueError(f"{where}: more than {CMAX} speakers in recording {f[1]!r}")
+            rec["speakers"].append(f[7])
+        rec["segments"].append((rec["speakers"].index(f[7]), _frame(start, frame_rate, where), _frame(start + dur, frame_rate, where)))
+    return out
+
+
+def read_uem(source, frame_rate=100.0):
+    """UEM text ('file chan start end' per line) -> {recording: sorted, merged [(start frame, end frame), ...]}, frames by the
+    rule of `read_rttm`; an interval that is empty after rounding is dropped.  ValueError naming the line for a malformed line,
+    a negative time, end < start, and a frame beyond MAX_FRAMES."""
+    out = {}
+    for no, line in enumerate(_lines(source), 1):
+        f = line.split()
+        if not f or f[0].startswith(("#", ";")):
+            continue
+        where = f"UEM line {no}"
+        if len(f) != 4:
+            raise ValueError(f"{where}: expected 'file chan start end', got {line!r}")
+        start, end = _number(f[2], where), _number(f[3], where)
+        if start < 0 or end < 0:
+            raise ValueError(f"{where}: negative time in {line!r}")
+        if end < start:
+            raise ValueError(f"{where}: end before start in {line!r}")
+        s, e = _frame(start, frame_rate, where), _frame(end, frame_rate, where)
+        out.setdefault(f[0], [])
+        if s < e:
+            out[f[0]].append((s, e))
+    return {rec: _check_uem_one(ivs, rec) for rec, ivs in out.items()}
+
+
+def segments_raster(tables, lengths, n_speakers=None, device=None):
+    """Per recording a list of (speaker, start, end) and a length in frames -> (uint8 rows, int32 offsets) on the device, equal to
+    `pack_references` of the label matrices, which are never built on the host: the segment table is copied and
+    eend_segments_raster_u8 writes the rows (zeroed, then one store per segment and frame)."""
+    if len(tables) != len(lengths) or not tables:
+        raise ValueError(f"{len(tables)} segment tables for {len(lengths)} lengths")
+    if len(tables) > 65535:
+        raise ValueError("more than 65535 recordings in one batch")
+    C = max([1] + [s[0] + 1 for t in tables for s in t]) if n_speakers is None else int(n_speakers)
+    off, segs = [0], []
+    for b, (t, n) in enumerate(zip(tables, lengths)):
+        if isinstance(n, bool) or not isinstance(n, int) or n < 0:
+            raise ValueError(f"lengths[{b}]: expected a number of frames >= 0, got {n!r}")
+        off.append(off[-1] + n)
+        for spk, s, e in t:
+            if not 0 <= spk < C or C > CMAX:
+                raise ValueError(f"recording {b}: speaker {spk} of {C}, at most {CMAX} are scored")
+            if s < 0 or e > n:
+                raise ValueError(f"recording {b}: segment ({s}, {e}) outside its {n} frames")
+            if s < e:
+                segs.append((b, spk, s, e))
+    if off[-1] > MAX_FRAMES:
+        raise ValueError("row offsets beyond 2^31 are out of scope")
+    if device is None:
+        if not torch.cuda.is_available():
+            raise _lib.EendHipError("segments_raster: no GPU available (the HIP path has no CPU fallback)")
+        device = torch.device("cuda", torch.cuda.current_device())
+    rows = torch.empty(max(off[-1], 1), C, dtype=_U8, device=device)
+    offsets = torch.tensor(off, dtype=_I32).to(device)
+    seg = torch.tensor(segs or [(0, 0, 0, 0)], dtype=_I32).reshape(-1, 4).to(device)
+    _lib.check(_lib.load().eend_segments_raster_u8(seg.data_ptr(), len(segs), offsets.data_ptr(), len(tables), C, rows.data_ptr(),
+                                                   rows.shape[0], _post._stream()), "eend_segments_raster_u8")
+    return rows, offsets
+
+
+def rttm_lengths(recs, rttm, uem=None, lengths=None):
+    """A recording's length in frames: the largest of its last segment end, its last UEM end and the caller's length."""
+    out = []
+    for b, rec in enumerate(recs):
+        n = max([0] + [e for _, _, e in rttm.get(rec, {"segments": []})["segments"]])
+        if uem is not None and uem.get(rec):
+            n = max(n, uem[rec][-1][1])
+        if lengths is not None:
+            given = lengths[rec] if isinstance(lengths, dict) else lengths[b]
+            n = max(n, int(given))
+        out.append(n)
+    return out
+
+
+def pack_rttm(recs, rttm, uem=None, lengths=None):
+    """Recording ids in batch order, `read_rttm`'s and (optionally) `read_uem`'s dicts, and optional lengths in frames (a list
+    in that order, or a dict) -> ((uint8 rows, int32 offsets), the device UEM table or None): the reference half of a batch,
+    rasterised on the device, and what `uem=` of the packed calls takes.  A recording absent from `rttm` has no segments; one
+    absent from `uem` is scored everywhere."""
+    recs = list(recs)
+    lens = rttm_lengths(recs, rttm, uem, lengths)
+    C = max([1] + [len(rttm[r]["speakers"]) for r in recs if r in rttm])
+    ref = segments_raster([rttm.get(r, {"segments": []})["segments"] for r in recs], lens, C)
+    table = pack_uem([uem.get(r) for r in recs], ref[0].device) if uem is not None else None
+    return ref, table

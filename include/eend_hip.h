@@ -410,6 +410,67 @@ int eend_collar_der_sweep_u64(const unsigned char* ref, const int* ref_off, int 
  * only); the speaker, frame and collar limits are those of eend_collar_der_u64. */
 int eend_der_sweep_limits(int* max_thresholds, int* max_medians, int* max_points, int* max_median);
 
+/* eend_collar_der_u64 with scoring regions (the UEM files of AMI and DIHARD: pyannote's metric(reference, hypothesis, uem=uem))
+ * and with the marginal times the Jaccard error rate needs; additive to ABI version 5.  Everything eend_collar_der_u64 states
+ * holds; what is new, in reference frames:
+ *   Regions.  uem i32 [.][2] (8-byte aligned) holds half-open intervals [s, e), 0 <= s < e, recording after recording; recording
+ * b has the intervals uem_off[b] .. uem_off[b + 1] - 1 (uem_off i32 [B + 1], on the device, not decreasing), sorted and disjoint.
+ * A frame t of [0, T) is kept iff (a) it lies in some interval of its recording, (b) no reference boundary b has
+ * t - h < b <= t + h (rule 1 of eend_collar_der_u64), and (c) with skip_overlap it has fewer than two reference speakers.  The
+ * boundaries are those of the uncropped reference: a boundary outside every interval still removes the frames of an interval
+ * that its collar reaches, and an interval's edge is not a boundary.  This is the order of pyannote's uemify (the collars are
+ * cut out of the UEM, then both sides are cropped to what is left), and it is why zeroing the activity outside the regions is
+ * no substitute: that turns every edge into a boundary and still counts the frames outside as kept.  Intervals are clipped to
+ * [0, T); a recording with no interval scores nothing (total = 0, frames kept = 0); one interval [0, e) with e >= T gives
+ * the counters of eend_collar_der_u64.  frames kept + frames removed = T as before: the frames outside the regions are removed.
+ * uem = uem_off = NULL: no regions anywhere, every frame of [0, T) passes (a); one of the two NULL is EEND_EINVAL.  The host
+ * does not read the table: an interval with e <= s adds nothing, an unsorted table may lose intervals but is read within its
+ * offsets only.
+ *   Marginal times.  ref_time u64 [B][16]: the kept frames in which reference speaker i is active; hyp_time u64 [B][16]: the
+ * kept reference frames under an active frame of hypothesis speaker j (a hypothesis frame counts once per kept reference
+ * frame under it, as in cooc).  Entries beyond Cr and Ch are 0.
+ *   counters, cooc and mapping are those of eend_collar_der_u64 over the kept frames.  Three launches (clear, one pass, the
+ * assignment); per tile of reference frames the region term is built from the intervals that meet the tile (a binary search on
+ * the starts, then a loop over as many intervals as there are) and is one more term of the bit that says a frame is kept;
+ * integer atomics only, the same bits on every run, nothing allocated, the host not waited for. */
+int eend_collar_der_regions_u64(const unsigned char* ref, const int* ref_off, int Cr, const unsigned char* hyp, const int* hyp_off, int Ch,
+                                int B, int subsampling, int half_collar, int skip_overlap, const int* uem, const int* uem_off,
+                                unsigned long long* counters, unsigned long long* cooc, int* mapping, unsigned long long* ref_time,
+                                unsigned long long* hyp_time, void* stream);
+
+/* eend_collar_der_sweep_u64 with the regions and marginal times of eend_collar_der_regions_u64: the kept frames are the same at
+ * every point.  ref_time, hyp_time u64 [G][B][16]; ref_time is equal for all g.  Everything else as the two entries state. */
+int eend_collar_der_sweep_regions_u64(const unsigned char* ref, const int* ref_off, int Cr, const float* pred, const int* pred_off, int Ch,
+                                      const unsigned char* sad, int B, const float* thresholds, int n_thresholds, const int* medians,
+                                      int n_medians, int subsampling, int half_collar, int skip_overlap, const int* uem,
+                                      const int* uem_off, unsigned long long* counters, unsigned long long* cooc, int* mapping,
+                                      unsigned long long* totals, unsigned long long* ref_time, unsigned long long* hyp_time,
+                                      void* stream);
+
+/* Jaccard error rate (DIHARD's second metric) from the outputs of the two entries above, n matrices (B, or G * B of the sweep):
+ * cooc u64 [n][16][16], ref_time and hyp_time u64 [n][16]; Cr, Ch in 1 .. 16 as there.  All counts are over the kept frames, so
+ * the usual figure is scored with half_collar = 0.  Reference speaker i is a speaker of the recording iff ref_time[i] > 0,
+ * hypothesis speaker j iff hyp_time[j] > 0.  For a pair of both, inter = cooc[i][j], union = ref_time[i] + hyp_time[j] - inter,
+ * cost = 1 - inter / union in float64.  The pairing is the one-to-one assignment of minimal total cost (not the mapping of the
+ * DER, which maximises the overlap); a reference speaker left alone costs 1, and a pair with inter = 0, which costs the same,
+ * is reported as unpaired.  Where several pairings are optimal any one is returned.
+ *   Outputs: pairing i32 [n][16], reference -> hypothesis, -1 = unpaired or no such speaker; speakers u64 [n][16][3] = ref_time,
+ * the paired speaker's hyp_time or 0, inter.  The caller forms the ratios: a speaker's error is (union - inter) / union (1 when
+ * unpaired), a recording's the mean over its reference speakers.  One launch, one wave per matrix, the float64
+ * shortest-augmenting-path solver on a cost matrix in LDS; the host is not waited for.  EEND_EINVAL: a NULL pointer, Cr or Ch
+ * outside 1 .. 16, n < 1. */
+int eend_jer_assign_f64(const unsigned long long* cooc, const unsigned long long* ref_time, const unsigned long long* hyp_time, int Cr,
+                        int Ch, long n, int* pairing, unsigned long long* speakers, void* stream);
+
+/* Reference segments -> the packed label rows eend_collar_der_u64 reads.  segments i32 [n_segments][4] (16-byte aligned) =
+ * recording, speaker, start frame, end frame (half-open); ref_off i32 [B + 1] on the device, the rows of recording b being
+ * ref_off[b] .. ref_off[b + 1] - 1 of rows u8 [n_rows][C] (16-byte aligned; n_rows >= ref_off[B], C in 1 .. 16).  All n_rows rows
+ * are zeroed, then every frame of every segment gets a 1 in its speaker's column; frames outside the recording's rows, and
+ * segments whose recording or speaker is outside the table, write nothing, and a segment with end <= start is empty.  Two
+ * launches (clear, one workgroup per segment); overlapping segments store the same value, so the bytes do not depend on order. */
+int eend_segments_raster_u8(const int* segments, long n_segments, const int* ref_off, int B, int C, unsigned char* rows, long n_rows,
+                            void* stream);
+
 /* ---- feature front-end ({LS,FS}-EEND/datasets/feature.py: stft :166-191, transform :43-131, splice :141-163,
  * subsample :133-138, extract_fbank :324-336); fp32 throughout.  ---- */
 
